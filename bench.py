@@ -1,17 +1,27 @@
 #!/usr/bin/env python
 """bench.py — ZSGNet training-step throughput on MI355X (BASELINE.json metric: train images/sec).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, one rank per GPU)
 
 A "step" is the reference's hot loop body, utils.py:407-414: zero_grad -> ZSGNet.forward -> ZSGLoss -> backward
 (-> bucketed RCCL all-reduce) -> Adam -> Evaluator, on a synthetic batch already resident in HBM (SURVEY.md §8d:
-img ~ U[0,1) 300x300, 20-token queries, per-GPU batch 16 = BASELINE configs[1]).  W warm-up steps, then exactly K timed
-steps between barrier + torch.cuda.synchronize(); MAX over ranks; rank 0 prints ONE JSON line.
+img ~ U[0,1) 300x300, 20-token queries, per-GPU batch 16 = BASELINE configs[1]).  W warm-up steps, a fixed number of untimed
+settle steps (--settle), then exactly K timed steps between barrier + torch.cuda.synchronize(); MAX over ranks; rank 0 prints ONE
+JSON line.  `ms_per_step` is the wall time of the K timed steps / K.
 
 `median_ms_per_step` comes from HIP events recorded at the step boundaries INSIDE the timed region (no extra sync).
 
-Extra legs (rank 0, outside the timed region):
+--dump-outputs DIR: rank 0 writes what the LAST timed step computed as DIR/<name>.npy (float32, or float64 for integer / float64
+values): the forward's outputs (out_*), the loss dict (loss_*), the evaluator's dict (eval_*), and a fixed seeded sample of the flat
+parameter and gradient buffers after the step (param_sample, grad_sample).  An array above 4M elements is written as a fixed seeded
+sample of at most 4M.  The last timed step of such a run starts from the seeded initial state (weights, Adam moments, LSTM-state
+RNG; restored by device copies enqueued in front of it), so the same arguments give the same inputs in every run and build.
+
+A plain run does only what the headline needs.  The extra legs below run only with --full (the --no-* / --other-configs /
+--ddp-variants / --forward-leg / --prof-out options select among them).
+
+Extra legs (--full; rank 0, outside the timed region):
   roofline     — per-launch HIP-event timing of every kernel (zsg_prof_*, entries named as rocprofv3 names them); the
                  kernel with the largest share is reported as achieved TFLOP/s = ALGORITHMIC 2*MAC (direct convolution) /
                  event time against the 157.3 TFLOP/s fp32-MFMA peak: with every launch alone on the GPU (primary) and as
@@ -22,6 +32,8 @@ Extra legs (rank 0, outside the timed region):
                  produced from the same kernel sources (sha256 stamp), else null.
   forward      — train-mode forward only (the north_star's ">= 70 % on the ResNet-50+FPN forward"): HIP-event median.
   cpu_baseline — the CPU oracle's same step (torch-CPU fp32, B=4) on the host cores ("port"); N=1 only.
+  other_configs — BASELINE configs[3] / [4]'s per-GPU shapes timed in this process (N=1).
+  rccl         — data-parallel runs: the exposed all-reduce time and the priority / transport variant legs.
 """
 import argparse
 import ctypes as C
@@ -171,8 +183,12 @@ def parse():
     ap.add_argument("--no-bx", action="store_true", help="(accepted and ignored: the bf16x6 leg was removed in round 4)")
     ap.add_argument("--prof-out", default="")
     ap.add_argument("--force-ddp", action="store_true", help="wrap in the RCCL data-parallel reducer even at world size 1 (smoke test)")
-    ap.add_argument("--settle", type=int, default=-1, help="untimed settle steps AFTER the requested warm-up (default: until the step time is "
-                    "stable, between 25 and 60 steps; 0 = none)")
+    ap.add_argument("--settle", type=int, default=None, help="untimed settle steps AFTER the requested warm-up (default: 60, 30 when N > 1 — "
+                    "a fixed count, so that the timed steps see the same inputs in every run; -1 = until the step time is stable, between "
+                    "25 and 60 steps; 0 = none)")
+    ap.add_argument("--full", action="store_true", help="also run the extra legs (forward, roofline, cpu_baseline, other_configs, the "
+                    "data-parallel exposed all-reduce and variant legs) after the timed steps; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--other-configs", default="auto", choices=["auto", "on", "off"], help="after the headline legs, time BASELINE configs[3] / [4]'s "
                     "per-GPU shapes (SSD-VGG16 300^2 B=32, ResNet-101 FPN 600^2 B=32) in this process; auto = only for the default headline "
                     "configuration at N=1 with a stamp-matched shipped tuning table (otherwise they would be autotuned for minutes)")
@@ -184,7 +200,13 @@ def parse():
                     "tuner's near-ties inside the real step before the timed region (ZSGNet.refine_tuning; untimed, N = 1 only)")
     ap.add_argument("--launch-check", action="store_true", help="only bring up the N-rank process group (backend ZSG_DIST_BACKEND, default "
                     "nccl), all-reduce one tensor and print a JSON line: tests the launcher without a GPU (gloo)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:
+        asked = [f for f, on in (("--forward-leg", a.forward_leg), ("--prof-out", a.prof_out), ("--other-configs on", a.other_configs == "on"),
+                                 ("--ddp-variants on", a.ddp_variants == "on")) if on]
+        if asked:
+            ap.error(f"{', '.join(asked)}: extra legs run only with --full")
+    return a
 
 
 def self_launch(a) -> int:
@@ -274,6 +296,36 @@ def time_config(arch: str, backbone: str, img: int, bs: int, tokens: int, warm: 
     return res
 
 
+DUMP_CAP = 1 << 22                 # elements per dumped array (16 MB in float32); larger arrays are written as a fixed seeded sample
+DUMP_SAMPLE = 1 << 20              # flat parameter / gradient buffer: elements drawn (before de-duplication)
+
+
+def dump_outputs(path: str, last: dict, store) -> dict:
+    """--dump-outputs: the last timed step's forward outputs, loss dict and evaluator dict, and a seeded sample of the flat parameter and
+    gradient buffers after it, as <path>/<name>.npy.  Returns {name: shape}."""
+    import numpy as np
+
+    def host(t):
+        a_ = t.detach().cpu()
+        a_ = a_.numpy() if a_.dtype in (torch.float32, torch.float64) else (a_.float().numpy() if a_.is_floating_point() else a_.double().numpy())
+        if a_.size > DUMP_CAP:
+            a_ = a_.reshape(-1)[np.unique(np.random.default_rng(0).integers(0, a_.size, DUMP_CAP))]
+        return a_
+    arrays = {}
+    for prefix in ("out", "loss", "eval"):
+        for k, v in last[prefix].items():
+            if torch.is_tensor(v) and not (prefix == "out" and k == "att_bbx_out"):      # (att_bbx_out = att_out and bbx_out side by side)
+                arrays[f"{prefix}_{k}"] = host(v)
+    idx = torch.from_numpy(np.unique(np.random.default_rng(1).integers(0, store.flat.numel(), DUMP_SAMPLE))).to(store.flat.device)
+    arrays["param_sample"], arrays["grad_sample"] = host(store.flat[idx]), host(store.grad[idx])
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 def main():
     a = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -322,18 +374,33 @@ def main():
     lf, ev = loss.get_default_loss(r, s, cfg), evaluator.get_default_eval(r, s, cfg)
     opt = optim.FusedAdam(net, lr=cfg["lr"], betas=(0.9, 0.99))
 
+    w0 = net.store.flat.clone() if a.dump_outputs else None     # (--dump-outputs: the seeded initial weights, see restart())
+
     from zsgnet_pytorch_amd.synth import synthetic_batch
     bt = synthetic_batch(a.bs, a.img, a.img, T=a.tokens, seed=1234 + rank)
     batch = {k: v.cuda() for k, v in bt.items()}
     torch.manual_seed(99 + rank)                  # LSTM initial states (mdl.py:279-294) are drawn on the host each step
 
-    def step():
+    def step(keep=None):
         opt.zero_grad()
         out = model(batch)
         ls = lf(out, batch)
         ls["loss"].mean().backward()
         opt.step()
-        return ls, ev(out, batch)
+        em = ev(out, batch)
+        if keep is not None:                      # (--dump-outputs: the last timed step's results)
+            keep.update(out=out, loss=ls, eval=em)
+        return ls, em
+
+    def restart():
+        """--dump-outputs, every rank: the seeded initial state in front of the last timed step — weights, Adam moments and step count
+        (stream-ordered device copies behind the previous step's update, ~0.2 ms), the LSTM states' host RNG.  Fp32 atomics make a long
+        training trajectory differ from run to run; one step from the seeded state is the same computation in every run and build."""
+        net.store.flat.copy_(w0)
+        opt.m.zero_()
+        opt.v.zero_()
+        opt.step_count.zero_()
+        torch.manual_seed(99 + rank)
 
     for _ in range(a.warmup):
         ls, em = step()
@@ -342,14 +409,19 @@ def main():
     # Untimed; single-GPU runs only (under DDP rank 0's table is broadcast before the other ranks lower).
     if model is net and a.refine != "off" and tuning_info()["tuned_now"] > 0:
         net.refine_tuning(batch, log=(lambda m: print(m, file=sys.stderr, flush=True)) if os.environ.get("ZSG_REFINE_LOG") else None)
+        torch.manual_seed(99 + rank)              # (the refinement drew a timing-dependent number of LSTM states)
         for _ in range(3):
             ls, em = step()
 
     # Untimed settle phase AFTER the requested warm-up: the shader clock leaves its idle state and the launch queues
     # fill over the first few dozen steps (a 5-step warm-up is 70 ms of GPU work), which put the driver's 20-step mean 1.7 % above its
-    # median in round 4.  Steps run until the last 8 event-timed steps lie within 0.5 % of their median (at least 25, at most 60 steps;
-    # --settle N fixes the count).  Nothing here is timed or reported as throughput.
+    # median in round 4.  By default a fixed count (60 steps — where the adaptive rule below ended in most runs —, 30 when N > 1), so that
+    # the timed steps start from the same weights and LSTM states in every run (--dump-outputs compares builds output for output);
+    # --settle -1: steps run until the last 8 event-timed steps lie within 0.5 % of their median (at least 25, at most 60 steps).
+    # Nothing here is timed or reported as throughput.
     settle_n = 0
+    if a.settle is None:
+        a.settle = 60 if world == 1 else 30
     if a.settle != 0:
         lo, hi = (a.settle, a.settle) if a.settle > 0 else ((25, 60) if world == 1 else (30, 30))     # (N > 1: the same count on every rank)
         sev = [torch.cuda.Event(enable_timing=True)]
@@ -380,14 +452,18 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     host_t = [t0]
+    last = {} if (a.dump_outputs and rank == 0) else None
     for i in range(a.steps):
-        ls, em = step()
+        if w0 is not None and i == a.steps - 1:
+            restart()
+        ls, em = step(last if i == a.steps - 1 else None)
         marks[i + 1].record()               # (an event record is ~1 us of host time and no synchronisation)
         host_t.append(time.perf_counter())
     t_host = host_t[-1] - t0                # when the host had enqueued everything
     fence()
     dt = time.perf_counter() - t0
     gpu_clock = clk.stop()
+    dumped = dump_outputs(a.dump_outputs, last, net.store) if last is not None else None      # (before any extra leg changes the weights)
     host = {"enqueue_ms_per_step": round(1e3 * t_host / a.steps, 3), "lead_ms_at_end": round(1e3 * (dt - t_host), 3),
             "first_steps_ms": [round(1e3 * (host_t[i + 1] - host_t[i]), 3) for i in range(min(4, a.steps))],
             "what": "host time to enqueue one step (mean; the first steps after the fence, before the launch queues fill and throttle "
@@ -395,7 +471,7 @@ def main():
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps))
     median_ms = per_step[len(per_step) // 2]
     exposed_ms = None
-    if red0 is not None:
+    if red0 is not None and a.full:
         # the exposed all-reduce time is measured in its OWN short leg behind the timed region (every rank, same count): its two event
         # records per step no longer sit in the headline number
         red0.time_wait = True
@@ -408,7 +484,7 @@ def main():
     # wave priority starves or helps the collectives that run beside it and (b) which transport is faster.  Every
     # rank runs the same legs in the same order; untimed warm-up + 20 timed steps each, max over ranks; not part of `value`.
     variants = None
-    if model is not net and a.ddp_variants != "off":
+    if model is not net and a.full and a.ddp_variants != "off":
         def short_leg(n_warm=8, n=20):
             for _ in range(n_warm):
                 step()
@@ -475,7 +551,7 @@ def main():
     # (the forward-only leg runs BEFORE the per-kernel profiled legs: bracketing every launch with timing events leaves the
     # process ~3 % slower afterwards)
     fwd = None
-    if not a.no_roofline or a.forward_leg:          # every rank (the training forward of a DDP model broadcasts the BatchNorm buffers)
+    if a.full and (not a.no_roofline or a.forward_leg):          # every rank (the training forward of a DDP model broadcasts the BatchNorm buffers)
         # grad mode ON, as in a training step: the forward then also co-schedules the backward's weight preparation on the side
         # stream (mdl._Plan.run_forward), which a no_grad forward would leave out.  (The 21 forwards advance the BatchNorm running
         # statistics; nothing below depends on them.)
@@ -494,7 +570,7 @@ def main():
                "what": "train-mode ZSGNet.forward only, grad mode on (batch-statistics BatchNorm; the backward's weight preparation "
                        "co-runs on the side stream as in a step), algorithmic conv FLOPs / fp32-MFMA peak"}
     roof, prof_rows = None, []
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         # EVERY rank runs the profiled steps (they contain the data-parallel collectives); rank 0 reports its own kernels
         from zsgnet_pytorch_amd import ops as zops
 
@@ -587,13 +663,14 @@ def main():
             with open(a.prof_out, "w") as f:
                 json.dump({"as_timed": prof_rows, "isolated": iso_rows}, f, indent=1)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(a.arch, a.img, a.tokens)
 
     others = None
     headline_default = (a.arch, a.backbone, a.img, a.bs, a.tokens) == ("resnet50", "retina", 300, 16, 20)
-    if rank == 0 and world == 1 and not a.force_ddp and (a.other_configs == "on" or (a.other_configs == "auto" and headline_default and tuning_info()["stamp_match"]
-                                                                                    and os.environ.get("ZSG_SHIPPED_TUNE", "1") != "0")):
+    if a.full and rank == 0 and world == 1 and not a.force_ddp and (a.other_configs == "on" or (a.other_configs == "auto" and headline_default
+                                                                                               and tuning_info()["stamp_match"]
+                                                                                               and os.environ.get("ZSG_SHIPPED_TUNE", "1") != "0")):
         # BASELINE.json configs[3] and configs[4]'s per-GPU shape, on the shipped table, OUTSIDE the headline's timed region (VERDICT r04
         # item 4: the driver's one command now sees them); ~12 s together
         others = {"what": "the other single-GPU-sized BASELINE.json configurations, timed in this process after the headline legs (same step, "
@@ -634,7 +711,7 @@ def main():
             "rccl": rccl,
             "final_loss": round(loss_val, 4), "final_acc": acc,
             "forward": fwd, "source_stamp": source_stamp(), "tuning": tuning_info(),
-            "roofline": roof, "cpu_baseline": cpu, "other_configs": others,
+            "roofline": roof, "cpu_baseline": cpu, "other_configs": others, "full": a.full, "dumped_outputs": dumped,
         }
     if world > 1:
         dist.barrier()

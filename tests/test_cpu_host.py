@@ -414,6 +414,58 @@ def test_bench_self_launches_n_ranks_gloo():
     assert out == {"launch_check": True, "n_gpus": 2, "backend": "gloo"}
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("zsg_bench", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_bench_extra_legs_need_full(monkeypatch):
+    """A plain bench run measures the headline only: asking for one of the extra legs without --full is refused, with --full it parses."""
+    b = _bench_module()
+    for extra in (["--forward-leg"], ["--prof-out", "p.json"], ["--other-configs", "on"], ["--ddp-variants", "on"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"] + extra)
+        with pytest.raises(SystemExit):
+            b.parse()
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full"] + extra)
+        a = b.parse()
+        assert a.full and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", "d"])
+    a = b.parse()
+    assert not a.full and a.dump_outputs == "d" and a.settle is None
+
+
+def test_bench_dump_outputs_float_files_under_64mb(tmp_path):
+    """bench.py --dump-outputs on host tensors of the shapes of a large step (ResNet-101 600^2, B=32 outputs; a 40M-element flat
+    buffer): every file is float32 / float64, integer values are exact, big arrays and the flat buffers become the same seeded sample
+    in every call, and the whole dump stays under 64 MB."""
+    import types
+    b = _bench_module()
+    g = torch.Generator().manual_seed(0)
+    store = types.SimpleNamespace(flat=torch.randn(40_000_000, generator=g), grad=torch.randn(40_000_000, generator=g))
+    bbx = torch.randn(32, 68000, 4, generator=g)
+    last = dict(out=dict(att_out=torch.randn(32, 68000, 1, generator=g, requires_grad=True), bbx_out=bbx, att_bbx_out=torch.zeros(3),
+                         feat_sizes=torch.tensor([[75, 75], [38, 38]]), num_f_out=torch.tensor([5])),
+                loss=dict(loss=torch.tensor(1.5), cls_ls=torch.tensor(1.0), box_ls=torch.tensor(0.5)),
+                eval=dict(Acc=torch.tensor(0.25), MaxPos=torch.tensor(3), idxs=torch.arange(32), pred_boxes=torch.randn(32, 4).half(),
+                          pred_scores=torch.randn(32), note="not an array"))
+    shapes = b.dump_outputs(str(tmp_path / "a"), last, store)
+    b.dump_outputs(str(tmp_path / "b"), last, store)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in shapes) and "out_att_bbx_out.npy" not in files
+    assert {"out_att_out.npy", "out_bbx_out.npy", "loss_loss.npy", "eval_Acc.npy", "param_sample.npy", "grad_sample.npy"} <= set(files)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+        assert x.size <= b.DUMP_CAP
+    assert np.load(tmp_path / "a" / "eval_MaxPos.npy") == 3 and np.load(tmp_path / "a" / "eval_idxs.npy").tolist() == list(range(32))
+    assert np.array_equal(np.load(tmp_path / "a" / "out_att_out.npy"), last["out"]["att_out"].detach().numpy())
+    assert np.isin(np.load(tmp_path / "a" / "out_bbx_out.npy"), bbx.numpy()).all()          # a sample of the values, not new ones
+
+
 @pytest.mark.parametrize("name,defer", [("fwd", 0), ("bwd", 1)])
 def test_lane_schedule_orders_every_cross_stream_edge(name, defer, monkeypatch):
     """ops.Program._schedule (the dry run behind the completion-event launcher): on random lane patterns every side-stream launch is

@@ -11,5 +11,5 @@ for i in $(seq $N); do
   $B 2>/dev/null | grep "^{" | python -c "$P" new
 done
 K='import sys,json; d=json.loads(sys.stdin.read()); print(sys.argv[1], [(k["kernel"], k["ms_per_step"], k.get("gbps")) for k in d["roofline"]["top_kernels"] if k.get("tflops_executed") is None])'
-ZSG_LIB_PATH=$OLD python $R/bench.py --no-cpu-baseline --steps 30 --warmup 10 ${AB_ARGS:-} 2>/dev/null | grep "^{" | python -c "$K" old
-python $R/bench.py --no-cpu-baseline --steps 30 --warmup 10 ${AB_ARGS:-} 2>/dev/null | grep "^{" | python -c "$K" new
+ZSG_LIB_PATH=$OLD python $R/bench.py --full --no-cpu-baseline --steps 30 --warmup 10 ${AB_ARGS:-} 2>/dev/null | grep "^{" | python -c "$K" old
+python $R/bench.py --full --no-cpu-baseline --steps 30 --warmup 10 ${AB_ARGS:-} 2>/dev/null | grep "^{" | python -c "$K" new
