@@ -34,7 +34,7 @@ for step in range(4):
     ls = lf(out, bt)
     ls["loss"].backward()
     if step < 2:                  # (the last two steps run without any host synchronisation between backward and the optimizer:
-        torch.cuda.synchronize()  #  with ZSG_ADAM_OVERLAP=1 FusedAdam updates most parameters UNDER the backward's last weight gradients)
+        torch.cuda.synchronize()  #  the optimizer's update is ordered behind the backward's side stream by the streams alone)
         res[f"out{{step}}"] = out["att_bbx_out"].detach().cpu()
         res[f"loss{{step}}"] = ls["loss"].detach().cpu()
         res[f"grad{{step}}"] = net.store.grad.clone().cpu()
@@ -50,12 +50,12 @@ def test_two_processes_bit_identical(tmp_path):
     script = tmp_path / "run.py"
     script.write_text(SCRIPT.format(root=ROOT))
     env = dict(os.environ, ZSG_DETERMINISTIC="1", ZSG_TUNE_CACHE=str(tmp_path / "tune.json"))
-    # process 2: the optimizer update split around the backward's tail (ZSG_ADAM_OVERLAP=1); 3: every launch on ONE stream (no
-    # cross-stream edge can be missing there); 4: round-2 scheduling (event-record markers instead of completion signals, the
-    # backward's weight images / the query encoder released at the head of the forward, P3 before the P6 chain).  Scheduling decides
-    # WHEN a launch runs, never what it computes: all five must agree to the bit.
-    variants = [{}, {}, {"ZSG_ADAM_OVERLAP": "1"}, {"ZSG_SIDE_STREAM": "0"},
-                {"ZSG_COMPLETION_EVENTS": "0", "ZSG_PREP_AT": "top", "ZSG_LANG_AT": "head", "ZSG_FPN_P6_FIRST": "0", "ZSG_PREP_RELEASE_TOP": "0"}]
+    # process 2: every weight gradient released at once, beside its own layer's data gradient (ZSG_SIDE_DEFER=0, ZSG_SIDE_BATCH=1);
+    # 3: every launch on ONE stream (no cross-stream edge can be missing there); 4: weight gradients released later and in larger
+    # groups (ZSG_SIDE_DEFER=2, ZSG_SIDE_BATCH=4).  Scheduling decides WHEN a launch runs, never what it computes: all five must agree
+    # to the bit.
+    variants = [{}, {}, {"ZSG_SIDE_DEFER": "0", "ZSG_SIDE_BATCH": "1"}, {"ZSG_SIDE_STREAM": "0"},
+                {"ZSG_SIDE_DEFER": "2", "ZSG_SIDE_BATCH": "4"}]
     outs = []
     for i, extra in enumerate(variants):
         out = tmp_path / f"r{i}.pt"
@@ -63,7 +63,7 @@ def test_two_processes_bit_identical(tmp_path):
         outs.append(torch.load(out))
     assert (tmp_path / "tune.json").exists(), "the first process must persist its tile choices"
     a = outs[0]
-    what = ["a second deterministic run", "the overlapped optimizer update", "the single-stream run", "the round-2 scheduling"]
+    what = ["a second deterministic run", "the immediate weight-gradient release", "the single-stream run", "the late batched release"]
     for o, w in zip(outs[1:], what):
         for k in a:
             assert torch.equal(a[k], o[k]), f"{k}: {w} differs (max |d| {float((a[k] - o[k]).abs().max()):.3g})"

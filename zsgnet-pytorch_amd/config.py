@@ -22,7 +22,6 @@ DEFAULTS: Dict[str, Any] = {
     "pretrained_path": "",          # local checkpoint instead of the torchvision download
     "synthetic": True,              # synthetic batches instead of the CSV datasets
     "steps_per_epoch": 50,
-    "use_hip_graph": False,
     "word_vectors": "",             # .npz word-vector table (`words`, `vectors`) used when spaCy is not installed
     "gpu_img_normalise": True,      # images travel as uint8 HWC; /255 + NHWC4 on the GPU (bit-identical to the host path)
     # configs/ds_info.json: where each dataset's images and csv files live (override with --ds_info.<name>.<key>=...)

@@ -68,39 +68,11 @@ class BnL:
 
 
 BNB_FUSE = os.environ.get("ZSG_BNB_FUSE", "1") != "0"     # BatchNorm-backward sums in the epilogue of the data gradient that completes dout
-# BatchNorm statistics / backward sums FINALISED by the last-arriving tile of the producing convolution (csrc/bn_tail.h, round 5): no
-# finalize launch, no re-reduction in the apply pass, wherever the launch has <= 128 partial rows per column block ("0": rounds 1-4's
-# separate finalize / inline apply; "fwd" / "bwd": one direction only — A/B switches)
-FPN_ORDER_DEFAULT = "p6m"
 # bn3 + residual + ReLU of a bottleneck applied by the NEXT block's conv1 (zsg_conv_igemm_bnpre) instead of a zsg_bn_apply launch, where the
-# activation is at least this large (MB; 0 = never): the apply pass is HBM-bound there and the consumer would read its output again
-BN_PRE_MIN_MB = float(os.environ.get("ZSG_BN_PRE_MIN_MB", "40"))
-STAGE_INPUTS = os.environ.get("ZSG_STAGE_INPUTS", "1") != "0"      # (A/B: 0 = the separate torch copies of rounds 1-4)
-BN_TAIL = os.environ.get("ZSG_BN_TAIL", "1")
-MASKED_DOUT = os.environ.get("ZSG_MASKED_DOUT", "1") != "0"      # the completing data gradient stores the ReLU-masked dout = the residual's gradient (bn(): back)
+# activation is at least this large (MB): the apply pass is HBM-bound there and the consumer would read its output again
+BN_PRE_MIN_MB = 40
+STAGE_INPUTS = True      # run_forward stages its inputs in one launch (tests/test_gpu_net.py compares it with the torch copies)
 WG_BATCH = os.environ.get("ZSG_WG_BATCH", "1") != "0"      # identical-shape Winograd weight gradients of a stage in ONE launch (_Plan._batch_wgrads)
-SK_BWD = os.environ.get("ZSG_SK_BWD", "0") != "0"      # stream-K candidates also for the backward's data gradients (measured slower: ops.autotune_conv)
-BN_TAIL_MIN_ROWS = int(os.environ.get("ZSG_BN_TAIL_MIN_ROWS", "0"))      # (A/B: only launches with more partial rows than this finalise in-kernel)
-def prep_at() -> str:
-    """ZSG_PREP_AT: where the backward's weight images are enqueued on the side stream during the forward (see _Plan._prep_index)."""
-    return os.environ.get("ZSG_PREP_AT", "j2")
-
-
-def lang_at() -> str:
-    """ZSG_LANG_AT: where the forward program releases the query encoder + language maps on the side stream: "head" = first (they
-    co-run with the stem), "stem" = behind the stem, "j<n>" = behind the n-th join (see _Plan._lower)."""
-    return os.environ.get("ZSG_LANG_AT", "j3")
-
-
-def adam_overlap() -> bool:
-    """ZSG_ADAM_OVERLAP=1 (default OFF): with FusedAdam attached the backward does not join the side stream at its end; FusedAdam.step
-    updates every parameter behind the stem / first block under the side stream's last weight gradients and the rest after the join
-    (bit-identical: tests/test_gpu_determinism.py).  Measured in round 3: 14.30 vs 14.28 ms; off by default."""
-    return os.environ.get("ZSG_ADAM_OVERLAP", "0") == "1"
-
-
-def prep_release_top() -> bool:
-    return os.environ.get("ZSG_PREP_RELEASE_TOP", "1") == "1"
 
 
 class Act(TView):
@@ -137,9 +109,6 @@ class ZSGNet(nn.Module):
         self.use_lang = bool(cfg["use_lang"])
         self.use_img = bool(cfg["use_img"])
         self.same_atb = bool(cfg["use_same_atb"])
-        if "use_hip_graph" in cfg and cfg["use_hip_graph"]:
-            from . import ops as _ops          # opt-in: replay launch ranges as hipGraphs (measured slower on ROCm 7.2)
-            _ops.HIP_GRAPH = True
         if backbone_kind not in ("retina", "ssd_vgg"):
             raise ValueError(f"mdl_to_use={backbone_kind!r}: expected 'retina' or 'ssd_vgg' (mdl.py:410-414)")
         self.do_norm = bool(cfg["do_norm"])
@@ -367,20 +336,10 @@ class ZSGNet(nn.Module):
             self.store.view("att_box.5.bias").fill_(-4.0)
             self.store.view("reg_box.5.bias").zero_()
 
-    def join_grads(self):
-        """After a backward with FusedAdam attached the main stream has not yet joined the side stream's last weight gradients
-        (FusedAdam.step does, after updating everything else under them): anything ELSE that reads or writes gradients on the
-        current stream joins here."""
-        ov = getattr(self, "_adam_overlap", None)
-        if ov is not None:
-            torch.cuda.current_stream().wait_stream(ov[1])
-            self._adam_overlap = None
-
     def join_weight_readers(self):
         """Called before anything WRITES the flat weight buffer on the current stream (optimizer step, load_state_dict):
         a training forward that was never back-propagated (metrics-only forward, discarded loss) leaves its backward weight
         preparation running on the side stream, reading the weights — make the current stream wait for it."""
-        self.join_grads()
         for plan in self._plans.values():
             if plan._prep_pending:
                 torch.cuda.current_stream().wait_event(plan._prep_ev)
@@ -524,7 +483,6 @@ class _Plan:
         self._hc_pin, self._hc_ev = None, None      # pinned ring of host-drawn LSTM states (run_forward)
         self._prep_idx_v = False
         self._out_slots_v = False
-        self._adam_ev, self._adam_cut_v = None, False
         self.expect_backward = False
         self._tunables = []              # convolution descriptors of this plan, as lowered (ops.refine_in_step)
         self._wg_log = []                # (launch index, descriptor, src, dy, gradient view, parameter, name) of every convolution weight gradient
@@ -548,7 +506,7 @@ class _Plan:
         # forward (Winograd filter transforms, zero-fills of split-K outputs); the main stream waits for it right before the first
         # launch that needs any of it (_wait_idx): an event WAIT, no marker of its own
         self.prep_u, self._u_ev, self._wait_idx = Program("fwd-prep"), None, 1 << 30
-        self._side_prep = training and os.environ.get("ZSG_U_ON_SIDE", "1") != "0"
+        self._side_prep = training
         self._zero_calls = []
         self._lower()
         for i, c in enumerate(self.fwd.calls):          # (positions after the hoisting of the language maps)
@@ -725,7 +683,9 @@ class _Plan:
             self.prep_u.add(lib.zsg_memset_f32, out.buf[lv0.off:], out.B * lv0.bstride, 0.0, what="zero:" + L.name)
             pre_zero = out.buf
         tail_n = -1
-        if partials is not None and BN_TAIL in ("1", "fwd") and out.bn_chunks > BN_TAIL_MIN_ROWS:
+        if partials is not None:
+            # BatchNorm statistics FINALISED by the last-arriving tile of the convolution (csrc/bn_tail.h, round 5): no finalize launch, no
+            # re-reduction in the apply pass, wherever the launch has <= 128 partial rows per column block (tail_n > 0)
             tail_n = int(lib.zsg_conv_bn_tail_tickets(_ct.byref(d), 1 if d.use_wino else 0))
         out.bn_inline = None
         if tail_n > 0:
@@ -785,9 +745,7 @@ class _Plan:
         chunks = igemm_partial_rows(d)
         assert chunks * 2 * L.cout * 4 <= self.ws_bytes
         partials, out.bn_chunks = self._ws_now(), chunks
-        tail_n = -1
-        if BN_TAIL in ("1", "fwd") and chunks > BN_TAIL_MIN_ROWS:
-            tail_n = int(lib.zsg_conv_bn_tail_tickets(_ct.byref(d), 0))
+        tail_n = int(lib.zsg_conv_bn_tail_tickets(_ct.byref(d), 0))
         Lb = bn_fuse
         rm, rv = self.net._rm[Lb.index:Lb.index + Lb.c], self.net._rv[Lb.index:Lb.index + Lb.c]
         out.bn_inline = None
@@ -936,7 +894,7 @@ class _Plan:
             wargs = (dy.buf, U) + args[2:]
         # a split-K choice would cost the BatchNorm below its fused backward sums: a pass over dout and x plus a launch
         pen = (0.006 + 2 * dx.rows() * n * 4 / 4e9) if (completes_bn and BNB_FUSE and not d.zero_fill and mask is None) else 0.0
-        self._tune("igemm", lib.zsg_conv_igemm, d, args, stream_ptr(), split_penalty_ms=pen, wino_args=wargs, allow_sk=SK_BWD)
+        self._tune("igemm", lib.zsg_conv_igemm, d, args, stream_ptr(), split_penalty_ms=pen, wino_args=wargs, allow_sk=False)
         if self._side_prep and ((d.tile_hint >> 16) & 0xff) > 1 and args[4] is None and len(dx.levels) == 1:
             # split-K into a gradient buffer nothing has written yet: its zero-fill moves to the side-stream preparation (see conv())
             lv0 = dx.levels[0]
@@ -1013,7 +971,7 @@ class _Plan:
                 # ReLU-masked gradient (zsg_conv_desc.epi_flags bit 0) — which IS the residual branch's gradient (out = relu(bn(x) +
                 # residual)): the residual's gradient buffer becomes an alias of dout, and the apply pass below neither reads the mask nor
                 # writes a second output (16 -> 12 bytes per element on the step's sixteen bn3 passes, 645 MB per step at configs[1]).
-                alias = (fuse and MASKED_DOUT and relu and rmask is not None and residual.grad is None and len(residual.levels) == 1
+                alias = (fuse and relu and rmask is not None and residual.grad is None and len(residual.levels) == 1
                          and residual.levels[0].off == 0 and residual.ld == L.c and residual.C == L.c and residual.buf.numel() == out.grad.buf.numel())
                 if alias:
                     residual.grad = out.grad
@@ -1028,7 +986,7 @@ class _Plan:
                 part = self.ws[2 * L.c:]              # (the first 2C floats of the workspace: the finalize launch's coefficients)
                 # a = (src, wt|U, out, bias=None, add_src, mask=None, partials=None)
                 assert a[3] is None and a[5] is None and a[6] is None
-                tail_n = int(lib.zsg_conv_bn_tail_tickets(_ct.byref(d), 1 if d.use_wino else 0)) if (BN_TAIL in ("1", "bwd") and chunks > BN_TAIL_MIN_ROWS) else -1
+                tail_n = int(lib.zsg_conv_bn_tail_tickets(_ct.byref(d), 1 if d.use_wino else 0))
                 if tail_n > 0:
                     # the data gradient's last tile per column block finalises the coefficients and d(gamma) / d(beta): the apply pass
                     # is all that is left of this BatchNorm's backward
@@ -1099,7 +1057,7 @@ class _Plan:
             feats = self._lower_ssd(x0)
         else:
             H2, W2 = conv_out(H1, 3, 2, 1), conv_out(W1, 3, 2, 1)
-            if self.training and os.environ.get("ZSG_STEM_FUSE", "1") != "0":
+            if self.training:
                 x = self._lower_stem_fused(C[e + "conv1"], BN[e + "bn1"], x0, H1, W1, H2, W2)
             else:
                 a = self.conv_bn(C[e + "conv1"], BN[e + "bn1"], x0, True, name="stem.a", yname="stem.y")
@@ -1116,15 +1074,14 @@ class _Plan:
                     dx.gfilled = True
                 self.tape.append(pool_back)
             taps, lat = {}, {}
-            early = self.training and os.environ.get("ZSG_FPN_LATERAL_EARLY", "1") != "0"
             for blk in net.blocks:
                 # (a block that is not the last of its stage has ONE first reader, the next block's conv1: that convolution applies this block's
                 # closing BatchNorm + residual + ReLU itself where the activation is large, see BN_PRE_MIN_MB)
-                big = BN_PRE_MIN_MB > 0 and net.block_kind == "bottleneck" and self.training and not blk["last"]
+                big = net.block_kind == "bottleneck" and self.training and not blk["last"]
                 x = self._lower_block(blk, x, defer_out=big)
                 if blk["last"]:
                     taps[blk["layer"]] = x
-                    if early and blk["layer"] in (2, 3):
+                    if self.training and blk["layer"] in (2, 3):
                         # the pyramid's lateral 1x1 convolutions P3_1 / P4_1 only read C3 / C4: on the side stream as soon as their
                         # input exists, under layer3 / layer4 (whose 19^2 / 10^2 launches leave a quarter of the CUs idle), instead
                         # of in the main stream's chain between layer4 and the head
@@ -1147,25 +1104,16 @@ class _Plan:
             del self.fwd.calls[i0:i1], self.fwd.lanes[i0:i1]
         self.fwd.calls[hoist_to:hoist_to] = moved_c      # ... and re-insert in their original order
         self.fwd.lanes[hoist_to:hoist_to] = moved_l
-        where = lang_at()
-        if self.training and where != "head":
+        if self.training:
             # the head-of-program side-stream block (query encoder, language maps; ~0.25 ms, read by the head ~4 ms later) is released
-            # further into the program: behind the stem ("stem") or behind the n-th join of the main stream with the side stream
-            # ("j<n>": a join waits for the WHOLE side stream, so in front of the first one the block delays layer1.0's residual add)
+            # behind the 3rd join of the main stream with the side stream (a join waits for the WHOLE side stream, so in front of the
+            # first one the block delays layer1.0's residual add)
             ln = self.fwd.lanes
             j = next((i for i in range(1, len(ln)) if ln[i] == 0), None)
             if j is not None and j > 1 and all(l == 1 for l in ln[1:j]):
-                k = None
-                if where == "stem":
-                    k = j
-                    while k < len(ln) and ln[k] == 0:
-                        k += 1
-                elif where.startswith("j") and where[1:].isdigit():
-                    joins = [i for i in range(j, len(ln)) if ln[i] == 2]
-                    n = int(where[1:])
-                    if 1 <= n <= len(joins) - 2:          # (never behind the joins in front of the head itself; a network without
-                        k = joins[n - 1] + 1              #  residual joins — SSD-VGG — keeps the block at the head of the program)
-                if k is not None:
+                joins = [i for i in range(j, len(ln)) if ln[i] == 2]
+                if len(joins) >= 5:          # (never behind the joins in front of the head itself; a network without residual
+                    k = joins[2] + 1         #  joins — SSD-VGG — keeps the block at the head of the program)
                     blk_c, blk_l = self.fwd.calls[1:j], ln[1:j]
                     self.fwd.calls[1:k] = self.fwd.calls[j:k] + blk_c
                     self.fwd.lanes[1:k] = ln[j:k] + blk_l
@@ -1184,7 +1132,7 @@ class _Plan:
         are leaves of the backward graph and every activation / gradient buffer of a plan lives until the next forward, so holding the
         earlier ones back changes nothing but the order in which the side stream does its work: a job batch has njobs x the (n, c)
         blocks, i.e. a fraction of the split-K slabs and a longer stage loop per block (l3_conv2 x 5: 268 -> 205 us,
-        profiles/r06_wgrad_batching.txt).  The launch indices recorded for DDP's buckets / the Adam split (grad_ready) are re-based."""
+        profiles/r06_wgrad_batching.txt).  The launch indices recorded for DDP's buckets (grad_ready) are re-based."""
         import ctypes as C_
         groups = {}
         for rec in self._wg_log:
@@ -1420,7 +1368,7 @@ class _Plan:
         s7 = tuple(conv_out(v, 3, 2, 1) for v in s6)
         if net.six_hundred:
             fl = self._pyramid([hw(c4), hw(c5), s6, s7])
-            o3, (o4, o5, o6, o7) = None, fl
+            o3, o8, (o4, o5, o6, o7) = None, None, fl
         else:
             fl = self._pyramid([hw(c3), hw(c4), hw(c5), s6, s7, (1, 1)])
             o3, o4, o5, o6, o7, o8 = fl
@@ -1430,11 +1378,12 @@ class _Plan:
             # the laterals lowered early on the side stream (P3_1 under layer3, P4_1 under layer4) are joined HERE, in front of the pyramid's
             # own side-stream launches: a join waits for the whole side stream
             self._join_side()
-        # ZSG_FPN_ORDER (round 5; rocprofv3 showed the head's first convolution waiting 56 us for the side stream's chain P5_2 -> P4_2 -> P6 ->
-        # ReLU -> P7 -> pool, which only started behind P5_1): "p6" = the P6 chain (it reads C5 only) is released BEFORE P5_1; "p6m" = also
-        # P4_2 on the main stream; "0" = round 3's order.
-        order = os.environ.get("ZSG_FPN_ORDER", FPN_ORDER_DEFAULT)
-        p6_early = order in ("p6", "p6m") and not net.six_hundred and self.training
+        # Training (round 5; rocprofv3 showed the head's first convolution waiting 56 us for the side stream's chain P5_2 -> P4_2 -> P6 ->
+        # ReLU -> P7 -> pool, which only started behind P5_1): the P6 chain (it reads C5 only) is released BEFORE P5_1, and P4_2 runs on
+        # the main stream.  Eval and 600^2: the chain is lowered behind P4_2 and in front of P3_1 / the top-down add / the large P3_2 — a
+        # side-stream launch waits for the main-stream work enqueued before it, so in program order behind P3_2 the chain only started when
+        # P3_2 had finished and the head's first convolution waited ~90 us for it; here it runs under P3_1 / P3_2.
+        p6_early = self.training and not net.six_hundred
         if p6_early:
             # (P5_1 stays the consumer whose data gradient completes layer4's last BatchNorm dout — it carries that BatchNorm's backward
             # sums, which the strided P6 cannot — so the chain's backward entries go BEHIND P5_1's on the tape: the tape is replayed in reverse)
@@ -1452,69 +1401,24 @@ class _Plan:
         if t4 is None:
             t4 = self.conv(C[f + "P4_1"], c4, name="t4")
         p41 = self._upsample_add(t4, p51, "p41")
-        if order == "p6m" and p6_early:
+        if p6_early:
             p4 = self.conv(C[f + "P4_2"], p41, out=o4)
         else:
             with self.on_side_stream():
                 p4 = self.conv(C[f + "P4_2"], p41, out=o4)
-        if p6_early:
-            t3 = t3 if t3 is not None else self.conv(C[f + "P3_1"], c3, name="t3")
-            p31 = self._upsample_add(t3, p41, "p31")
-            p3 = self.conv(C[f + "P3_2"], p31, out=o3, name="p3")
-            self._join_side()
-            return [p3, p4, p5, p6, p7, p8]
-        # (P3_1 / top-down add / the large P3_2 are lowered BEHIND the P6 -> P7 -> P8 chain: a side-stream launch waits for the main-stream
-        # work enqueued before it, so in program order behind P3_2 the chain only started when P3_2 had finished and the head's first
-        # convolution waited ~90 us for it; here it runs under P3_1 / P3_2)
-        t3_in = t3
-
-        def lower_p3():
-            t3 = t3_in if t3_in is not None else self.conv(C[f + "P3_1"], c3, name="t3")
-            p31 = self._upsample_add(t3, p41, "p31")
-            return self.conv(C[f + "P3_2"], p31, out=o3, name="p3")
-        p6_first = os.environ.get("ZSG_FPN_P6_FIRST", "1") != "0"
-        if not p6_first:
-            p3 = lower_p3()
-        side = self.on_side_stream()
-        side.__enter__()
-        p6 = self.conv(C[f + "P6"], c5, out=o6)
-        r6 = self.act("r6", B, p6.levels[0].H, p6.levels[0].W, 256)
-        n6 = r6.buf.numel()
-        self.fwd.add(lib.zsg_relu_fwd, self.base(p6), n6, r6.buf, what="relu(p6)", lane=self._lane)
-
-        def relu_back():
-            if r6.grad is None:
-                return
-            g = self.grad_of(p6)
-            self.bwd.add(lib.zsg_relu_bwd, self.base(r6.grad), self.base(p6), n6, self.base(g), int(g.gfilled), what="relu_bwd(p6)")
-            g.gfilled = True
-        self.tape.append(relu_back)
-        p7 = self.conv(C[f + "P7_2"], r6, out=o7)
-        if net.six_hundred:
-            side.__exit__(None, None, None)
-            if p6_first:
-                p3 = lower_p3()
-            self._join_side()
-            return [p4, p5, p6, p7]           # p3 is computed and dropped, as the reference does (fpn_resnet.py:173-174)
-        l7 = p7.levels[0]
-        p8 = o8
-        self.fwd.add(lib.zsg_avgpool_fwd, self.base(p7), B, l7.H * l7.W, 256, self.base(p8), what="avgpool", lane=self._lane)
-        side.__exit__(None, None, None)
-
-        def avg_back():
-            if p8.grad is None:
-                return
-            g = self.grad_of(p7)
-            self.bwd.add(lib.zsg_avgpool_bwd, self.base(p8.grad), B, l7.H * l7.W, 256, self.base(g), int(g.gfilled), what="avgpool_bwd")
-            g.gfilled = True
-        self.tape.append(avg_back)
-        if p6_first:
-            p3 = lower_p3()
+            p6, p7, p8 = self._lower_p6_chain(c5, o6, o7, o8)
+        if t3 is None:
+            t3 = self.conv(C[f + "P3_1"], c3, name="t3")
+        p31 = self._upsample_add(t3, p41, "p31")
+        p3 = self.conv(C[f + "P3_2"], p31, out=o3, name="p3")
         self._join_side()
+        if net.six_hundred:
+            return [p4, p5, p6, p7]           # p3 is computed and dropped, as the reference does (fpn_resnet.py:173-174)
         return [p3, p4, p5, p6, p7, p8]
 
-    def _lower_p6_chain(self, c5: Act, o6: Act, o7: Act, o8: Act):
-        """P6 -> ReLU -> P7_2 -> global average pool (fpn_resnet.py:175-178 + mdl.py's P8) on the side stream"""
+    def _lower_p6_chain(self, c5: Act, o6: Act, o7: Act, o8: Optional[Act]):
+        """P6 -> ReLU -> P7_2 (-> global average pool: fpn_resnet.py:175-178 + mdl.py's P8; o8=None at 600^2, which stops at P7)
+        on the side stream"""
         net, B = self.net, self.B
         C = net.convs
         f = "backbone.fpn."
@@ -1532,6 +1436,8 @@ class _Plan:
                 g.gfilled = True
             self.tape.append(relu_back)
             p7 = self.conv(C[f + "P7_2"], r6, out=o7)
+            if o8 is None:
+                return p6, p7, None
             l7 = p7.levels[0]
             p8 = o8
             self.fwd.add(lib.zsg_avgpool_fwd, self.base(p7), B, l7.H * l7.W, 256, self.base(p8), what="avgpool", lane=self._lane)
@@ -1752,9 +1658,9 @@ class _Plan:
                 self.dgrad(L0, dy, Fp, n=Cf, row0=0, dx=self.grad_of(Fp))
             # The language / grid columns of dW0, the bias gradient and d(we) hang off dy only and feed nothing but the query encoder's
             # backward (itself on the side stream): with features present they are leaves of the main chain and go to the side stream,
-            # so that the pyramid's backward starts right behind conv0's data gradient (ZSG_LANG_BWD_SIDE=0: on the main stream, as before).
+            # so that the pyramid's backward starts right behind conv0's data gradient.
             # (not with do_norm: the language vector's normalisation has its backward on the main stream, right behind d(we))
-            ln = 1 if (Cf and not (net.do_norm and Cw) and os.environ.get("ZSG_LANG_BWD_SIDE", "1") != "0") else 0
+            ln = 1 if (Cf and not (net.do_norm and Cw)) else 0
             hws_bytes = 16 << 20           # (a workspace of their own: on the main stream they ran concurrently with the side stream's slabs)
             hws = self._buf(hws_bytes // 4) if (Cw or Cg) else None
             if Cw:
@@ -1818,12 +1724,12 @@ class _Plan:
         net = self.net
         B = self.B
         ensure_stream_scratch(stream_ptr())      # (stream-K launches take their scratch from the stream they run on)
-        net.join_grads()
-        rel = None
-        if prep_release_top() and self._prep_stream is not None:
+        do_prep = self.training and self.expect_backward and len(self.prep)
+        if do_prep or len(self.prep_u):
             # the side stream's weight preparation may start now (behind the optimizer step), not behind the input copies below
-            rel = self._rel_ev
-            rel.record(torch.cuda.current_stream())
+            if self._prep_stream is None:
+                self._prep_stream, self._prep_ev, self._u_ev = shared_side_stream(), torch.cuda.Event(), torch.cuda.Event()
+            self._rel_ev.record(torch.cuda.current_stream())
         img = img.contiguous()
         u8 = img.dtype == torch.uint8
         if not u8 and img.dtype != torch.float32:
@@ -1880,17 +1786,11 @@ class _Plan:
         if u8:
             check(lib.zsg_u8hwc_to_nhwc4(img.data_ptr(), B * self.H * self.W, self.fwd.calls[self.img_slot][1][5], stream_ptr()), "u8hwc_to_nhwc4")
         else:
-            self.fwd.run(stream_ptr(), 0, 1, graph=False)          # the one launch with a per-call pointer (the caller's image)
-        do_prep = self.training and self.expect_backward and len(self.prep)
+            self.fwd.run(stream_ptr(), 0, 1)          # the one launch with a per-call pointer (the caller's image)
         if do_prep or len(self.prep_u):
             # the forward's Winograd filter transforms and the backward's weight images (transposed filters of the data gradients,
             # their Winograd transforms) depend on the weights only: produced here on the side stream, under the forward
-            if self._prep_stream is None:
-                self._prep_stream, self._prep_ev, self._u_ev = shared_side_stream(), torch.cuda.Event(), torch.cuda.Event()
-            if rel is None:
-                self._prep_stream.wait_stream(torch.cuda.current_stream())     # after the optimizer step that wrote the weights
-            else:
-                self._prep_stream.wait_event(rel)
+            self._prep_stream.wait_event(self._rel_ev)
             if len(self.prep_u):
                 self.prep_u.run(self._prep_stream.cuda_stream)
                 self._u_ev.record(self._prep_stream)
@@ -1932,12 +1832,11 @@ class _Plan:
 
     def _out_slots(self):
         """The pointer arguments of the forward program that hold the address of the [B, A, 5] output buffer (the last head convolution, or
-        the two interleave launches of separate heads) — None when the address is also baked into another program of the plan or when
-        launch ranges are replayed as hipGraphs (captured addresses): run_forward then copies out of the static buffer."""
+        the two interleave launches of separate heads) — None when the address is also baked into another program of the plan: run_forward
+        then copies out of the static buffer."""
         if self._out_slots_v is not False:
             return self._out_slots_v
         import ctypes as C_
-        from .ops import HIP_GRAPH
         ptr, nbytes = self.out5.buf.data_ptr(), self.out5.buf.numel() * 4
 
         def holders(prog):
@@ -1945,28 +1844,19 @@ class _Plan:
             return [a for _, args, _ in prog.calls for a in args if isinstance(a, C_.c_void_p) and a.value is not None and ptr <= a.value < ptr + nbytes]
         mine = holders(self.fwd)
         others = sum(len(holders(pr)) for pr in (self.bwd, self.prep, self.prep_u) if pr is not None)
-        ok = (bool(mine) and all(a.value == ptr for a in mine) and not others and not HIP_GRAPH and os.environ.get("ZSG_FRESH_OUT", "1") != "0")
+        ok = (bool(mine) and all(a.value == ptr for a in mine) and not others and os.environ.get("ZSG_FRESH_OUT", "1") != "0")
         self._out_slots_v = mine if ok else None
         return self._out_slots_v
 
     def _prep_index(self):
         """Where in the forward program the backward's weight images (transposed / Winograd-transformed filters: ~0.2 ms of HBM-bound
-        launches the backward needs, nothing in the forward does) are enqueued on the side stream: None = in front of everything
-        (ZSG_PREP_AT=top), else the launch index they go in front of — `late` = the first launch that waits for the forward's own
-        preparation, `j<n>` = behind the n-th join of the main stream with the side stream (the residual blocks' downsample branches),
-        so that they do not sit in front of side-stream work the main stream waits for sooner."""
+        launches the backward needs, nothing in the forward does) are enqueued on the side stream: the launch index behind the 2nd join
+        of the main stream with the side stream (the residual blocks' downsample branches), so that they do not sit in front of
+        side-stream work the main stream waits for sooner; None = in front of everything (a network with too few joins: SSD-VGG)."""
         if self._prep_idx_v is not False:
             return self._prep_idx_v
-        mode = prep_at()
-        v = None
         joins = [i for i, l in enumerate(self.fwd.lanes) if l == 2]
-        if mode == "late" and len(self.prep_u):
-            v = self._wait_idx
-        elif mode.startswith("j") and mode[1:].isdigit() and len(joins) - 2 >= int(mode[1:]) >= 1:
-            v = joins[int(mode[1:]) - 1] + 1       # (never behind the joins in front of the head: SSD-VGG has no others -> top)
-        elif mode.isdigit():
-            v = min(int(mode), len(self.fwd.calls))
-        self._prep_idx_v = v if (v is None or v > 1) else None
+        self._prep_idx_v = joins[1] + 1 if len(joins) >= 4 else None       # (never behind the joins in front of the head)
         return self._prep_idx_v
 
     def run_backward(self, g5: torch.Tensor):
@@ -2019,48 +1909,7 @@ class _Plan:
             self.reducer.run(nb, lambda i, j: self.bwd.run(st, i, j, join=(j == nb)), side_stream=lambda: self.bwd._side)
             self.reducer.wait()
         else:
-            cut = self._adam_cut() if (getattr(net, "_fused_opt", None) is not None and adam_overlap()) else None
-            if cut is None:
-                self.bwd.run(st)
-            else:
-                # FusedAdam is attached: the range up to i_cut completes every gradient behind flat offset `off` (all but the stem /
-                # first block, whose weight gradients are the tail of the side stream with nothing left to overlap them); the main
-                # stream does NOT join the side stream here — FusedAdam.step updates [off, end) behind an event recorded now, and
-                # [0, off) after the join (ZSGNet.join_grads is the join for anyone else)
-                i_cut, off = cut
-                self.bwd.run(st, 0, i_cut, graph=False, join=False)
-                if self.bwd._side is None:
-                    self.bwd.run(st, i_cut, len(self.bwd.calls), graph=False)
-                else:
-                    if self._adam_ev is None:
-                        self._adam_ev = torch.cuda.Event()
-                    self._adam_ev.record(self.bwd._side)
-                    self.bwd.run(st, i_cut, len(self.bwd.calls), graph=False, join=False)
-                    net._adam_overlap = (self._adam_ev, self.bwd._side, off)
-
-    def _adam_cut(self):
-        """(launch index, flat offset): the backward launches [0, index) complete the gradient of every parameter stored at or behind
-        `offset`; the parameters in front of it (the stem and the first block: first in the flat buffer, last in the backward) are what
-        the final ~dozen launches write.  None when the split is not worth it."""
-        if self._adam_cut_v is not False:
-            return self._adam_cut_v
-        from . import ops as _ops
-        self._adam_cut_v = None
-        ents, n = self.net.store.entries, len(self.bwd.calls)
-        if not _ops.SIDE_STREAM or _ops.HIP_GRAPH or n < 40:
-            return None
-        tail = [nm for nm in self.net._param_names if self.grad_ready.get(nm, -1) >= n - 12]
-        if not tail:
-            return None
-        off = max(ents[nm].offset + (ents[nm].size + 3) // 4 * 4 for nm in tail)
-        rest = [nm for nm in self.net._param_names if ents[nm].offset >= off]
-        if off > self.net.store.total // 4 or not rest:
-            return None
-        i_cut = max(self.grad_ready.get(nm, -1) for nm in rest) + 1
-        if i_cut > n - 4:
-            return None
-        self._adam_cut_v = (i_cut, off)
-        return self._adam_cut_v
+            self.bwd.run(st)
 
 
 def map_pretrained_keys(net: "ZSGNet", sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:

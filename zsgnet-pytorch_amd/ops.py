@@ -2,7 +2,7 @@
 
 A `Program` is a flat list of (C function, pre-marshalled ctypes arguments): buffers are allocated once per input
 geometry, so one training step is just a loop of foreign calls on torch's current stream — no Python tensor ops, no
-host<->device synchronisation — and the whole list can be captured into a hipGraph.
+host<->device synchronisation.
 """
 import ctypes as C
 import os
@@ -195,10 +195,8 @@ def wino_ok(k: int, stride: int, pad: int, dil: int) -> bool:
     return k == 3 and stride == 1 and pad == 1 and dil == 1
 
 
-SIDE_STREAM = os.environ.get("ZSG_SIDE_STREAM", "1") != "0"
-HIP_GRAPH = os.environ.get("ZSG_HIP_GRAPH", "0")     # replay launch ranges as hipGraphs once they are warm ("0", "1", or program names "fwd,bwd")
-HIP_GRAPH = False if HIP_GRAPH == "0" else (True if HIP_GRAPH == "1" else tuple(HIP_GRAPH.split(",")))
-GRAPH_WARMUP = 2                                             # eager replays of a range before it is captured
+SIDE_STREAM = os.environ.get("ZSG_SIDE_STREAM", "1") != "0"          # read by Program.run on every call (bench.py toggles it)
+HIP_GRAPH = False       # hipGraph replay was removed (measured slower); bench.py still saves and restores this name
 
 
 # Backward: a side-stream (weight-gradient) launch is released only after this many further main-stream convolutions have
@@ -211,17 +209,13 @@ GRAPH_WARMUP = 2                                             # eager replays of 
 # 1x1 weight gradients, 1 wins again on configs[1] (two boxes: 13.32 -> 13.24, 13.46 -> 13.40 ms; 2 = 1, 3 slower;
 # profiles/r05_release_policy_prio.txt), so every plan uses 1 (Program.side_defer) unless ZSG_SIDE_DEFER says otherwise.
 SIDE_DEFER = int(os.environ.get("ZSG_SIDE_DEFER", "-1"))
-# ... and only at every n-th main-stream convolution: every release costs the main stream an event record, i.e. a marker packet
-# the next kernel has to wait for (~4 us each: doubling the ~70 records of a ResNet-50 backward costs 0.28 ms).  Measured on
+# ... and only at every n-th main-stream convolution: every release cost the main stream an event record, i.e. a marker packet
+# the next kernel had to wait for (~4 us each: doubling the ~70 records of a ResNet-50 backward cost 0.28 ms; the releases ride on
+# completion events now, Program._run_lanes, and the batching stays at the values measured then).  Measured on
 # configs[1]: n = 1 / 2 / 3 / 4 / 5 / 6 -> 14.59 / 14.66 / 14.40 / 14.56 / 14.41 / 14.51 ms; SSD-VGG B=32 39.49 -> 39.15 ms;
 # ResNet-18 neutral; ResNet-101 @600^2 B=32 (launches of several hundred us: overlap matters, markers do not) 110.4 -> 111.9 ms,
 # hence the plan picks 3 for small launches and 1 for large ones unless ZSG_SIDE_BATCH says otherwise (Program.side_batch).
 SIDE_BATCH = int(os.environ.get("ZSG_SIDE_BATCH", "0"))
-
-
-# Cross-stream edges ride on the producing launch's own completion signal (zsg_set_completion_event / zsg_stream_wait_event, zsg.h)
-# instead of an event-record marker in the producing stream's queue; ZSG_COMPLETION_EVENTS=0 restores the marker path.
-COMPLETION_EVENTS = os.environ.get("ZSG_COMPLETION_EVENTS", "1") != "0"
 
 
 _MAIN_CONVS = (lib.zsg_conv_igemm, lib.zsg_conv_wino, lib.zsg_conv_igemm_bnb, lib.zsg_conv_wino_bnb, lib.zsg_conv_igemm_bnstat,
@@ -291,7 +285,6 @@ class Program:
         self.side_batch = 1     # deferred side launches are released at every side_batch-th main-stream convolution
         self.side_defer = 1     # ... and only after this many further main-stream convolutions (backward program; SIDE_DEFER above)
         self._side_busy = False
-        self._graphs = {}       # (start, stop, side-stream mode) -> [eager replays so far, captured graph | None]
         self._sched = {}        # (start, stop, join, side stream busy at entry, release policy) -> compiled lane schedule
         self._ce_pool = []      # completion events (hipEvent_t behind the C ABI)
 
@@ -299,81 +292,21 @@ class Program:
         self.calls.append((fn, marshal(fn, args, self.keep), what or fn.__name__))
         self.lanes.append(lane)
 
-    def _run_lanes(self, stream: int, start: int, stop: int, join: bool = True):
-        """Replay with lane-1 launches on the side HIP stream: each one waits for everything enqueued on the main stream
-        before its release (its inputs), and the main stream re-joins the side stream at lane-2 launches and — unless
-        join=False (a DDP bucket boundary: the collective waits for both streams instead) — at the end of the range.
-        Weight-gradient kernels are leaves of the backward graph, so they fill the CUs the critical chain's small launches
-        leave idle; in the backward program their release is deferred (SIDE_DEFER) and batched (side_batch): every release
-        costs the main stream one event record."""
-        main = torch.cuda.current_stream()
-        assert main.cuda_stream == stream, "Program.run expects torch's current stream"
-        if self._side is None:
-            self._side = shared_side_stream()
-            self._ev_pool = []
-        side = self._side
-        st0, st1 = C.c_void_p(stream), C.c_void_p(side.cuda_stream)
-        dirty, nev = True, 0
-        defer = (SIDE_DEFER if SIDE_DEFER >= 0 else self.side_defer) if self.name == "bwd" else 0
-        pending = []            # deferred lane-1 launches: [index, main-stream convolutions still to enqueue before it]
-        nconv, batch = 0, max(1, SIDE_BATCH or self.side_batch)
-
-        def side_launch(i):
-            nonlocal dirty, nev
-            fn, args, what = self.calls[i]
-            if dirty:
-                if nev == len(self._ev_pool):
-                    self._ev_pool.append(torch.cuda.Event())
-                ev = self._ev_pool[nev]
-                nev += 1
-                ev.record(main)
-                side.wait_event(ev)
-                dirty = False
-            self._side_busy = True              # (survives the call: a later range may have to join what this one started)
-            rc = fn(*args, st1)
-            if rc:
-                raise ZsgError(f"{self.name}/{what} failed ({rc}): {lib.zsg_last_error().decode()}")
-
-        for i in range(start, stop):
-            fn, args, what = self.calls[i]
-            if self.lanes[i] == 2 and (self._side_busy or pending):
-                for j, _ in pending:
-                    side_launch(j)
-                pending.clear()
-                main.wait_stream(side)
-                self._side_busy = False
-            if self.lanes[i] == 1:
-                if defer:
-                    pending.append([i, defer])
-                else:
-                    side_launch(i)
-                continue
-            dirty = True
-            rc = fn(*args, st0)
-            if rc:
-                raise ZsgError(f"{self.name}/{what} failed ({rc}): {lib.zsg_last_error().decode()}")
-            if pending and fn in _MAIN_CONVS:
-                for e in pending:
-                    e[1] -= 1
-                nconv += 1
-                if nconv % batch == 0:
-                    while pending and pending[0][1] <= 0:
-                        side_launch(pending.pop(0)[0])
-        for j, _ in pending:
-            side_launch(j)
-        if join and self._side_busy:
-            main.wait_stream(side)
-            self._side_busy = False
+    def _error(self, what: str, rc: int) -> ZsgError:
+        return ZsgError(f"{self.name}/{what} failed ({rc}): {lib.zsg_last_error().decode()}")
 
     def _schedule(self, start: int, stop: int, join: bool, side_busy: bool):
-        """The lane scheduler of _run_lanes as a dry run: a flat list of operations for [start, stop) —
+        """The release policy of the lanes, compiled for [start, stop): lane-1 launches go to the side stream, each behind everything
+        enqueued on the main stream before its release (its inputs); the main stream re-joins the side stream at lane-2 launches and —
+        unless join=False (a DDP bucket boundary: the collective waits for both streams instead) — at the end of the range.  Weight-
+        gradient kernels are leaves of the backward graph, so they fill the CUs the critical chain's small launches leave idle; in the
+        backward program their release is deferred (SIDE_DEFER) and batched (side_batch).  A flat list of operations —
              ('m', i, k)  launch i on the main stream  (k >= 0: the launch carries completion event k)
              ('s', i, k)  launch i on the side stream  (      "      )
              ('ws', k) / ('wm', k)   the side / main stream waits for event k
              ('rm', k) / ('rs', k)   event k recorded on the main / side stream (a marker: only where no launch of this range precedes
                                      the edge)
-        Same release policy as _run_lanes (deferral, batching); a release is attached to the last main-stream launch in front of it, a
-        join to the last side-stream launch."""
+        A release is attached to the last main-stream launch in front of it, a join to the last side-stream launch."""
         ops, nev = [], 0
         dirty, last_main, last_side = True, None, None
         defer = (SIDE_DEFER if SIDE_DEFER >= 0 else self.side_defer) if self.name == "bwd" else 0
@@ -431,14 +364,14 @@ class Program:
             join_side()
         return ops, nev, side_busy
 
-    def _run_lanes_ce(self, stream: int, start: int, stop: int, join: bool = True):
-        """_run_lanes with the cross-stream edges on completion events of the producing launches (no marker packet in the producing
-        stream's queue: ~4.3 us of main-stream time per release, ~35 releases per step)."""
+    def _run_lanes(self, stream: int, start: int, stop: int, join: bool = True):
+        """Replay the _schedule of [start, stop) with the cross-stream edges on completion events of the producing launches
+        (zsg_set_completion_event / zsg_stream_wait_event, zsg.h): no marker packet in the producing stream's queue, ~4.3 us of
+        main-stream time per release, ~35 releases per step."""
         main = torch.cuda.current_stream()
         assert main.cuda_stream == stream, "Program.run expects torch's current stream"
         if self._side is None:
             self._side = shared_side_stream()
-            self._ev_pool = []
         key = (start, stop, join, self._side_busy, SIDE_DEFER, self.side_defer, SIDE_BATCH or self.side_batch)
         sched = self._sched.get(key)
         if sched is None:
@@ -447,7 +380,7 @@ class Program:
         while len(self._ce_pool) < nev:
             e = lib.zsg_event_create()
             if not e:
-                raise ZsgError(f"event_create failed: {lib.zsg_last_error().decode()}")
+                raise self._error("event_create", 0)
             self._ce_pool.append(C.c_void_p(e))
         evs = self._ce_pool
         st0, st1 = C.c_void_p(stream), C.c_void_p(self._side.cuda_stream)
@@ -468,7 +401,7 @@ class Program:
                         rec(evs[k], st)
                 if rc:
                     arm(None)
-                    raise ZsgError(f"{self.name}/{what} failed ({rc}): {lib.zsg_last_error().decode()}")
+                    raise self._error(what, rc)
             elif t == "ws":
                 wait(st1, evs[op[1]])
             elif t == "wm":
@@ -479,11 +412,9 @@ class Program:
                 rec(evs[op[1]], st1)
         self._side_busy = busy_out
 
-    def run(self, stream: int, start: int = 0, stop: Optional[int] = None, graph: bool = True, join: bool = True):
-        """Replay calls[start:stop] on `stream` (torch's current stream), eagerly by default (3.4-3.9 us of host time per
-        launch: the host stays ahead of the GPU).  With HIP_GRAPH on, a range that has been replayed GRAPH_WARMUP times is
-        captured into a hipGraph (both lanes, with their event edges) and launched as ONE graph from then on — measured
-        slower than eager replay on ROCm 7.2, hence opt-in."""
+    def run(self, stream: int, start: int = 0, stop: Optional[int] = None, join: bool = True):
+        """Replay calls[start:stop] on `stream` (torch's current stream), eagerly (3.4-3.9 us of host time per launch: the host
+        stays ahead of the GPU); with SIDE_STREAM on, lane-1 launches go to the side stream (_run_lanes)."""
         stop = len(self.calls) if stop is None else stop
         if os.environ.get("ZSG_DEBUG_SYNC"):          # locate a faulting launch: name it, run it, synchronise
             st = C.c_void_p(stream)
@@ -491,36 +422,16 @@ class Program:
                 print(f"[zsg] {self.name}/{what}", flush=True)
                 rc = fn(*args, st)
                 if rc:
-                    raise ZsgError(f"{self.name}/{what} failed ({rc}): {lib.zsg_last_error().decode()}")
+                    raise self._error(what, rc)
                 torch.cuda.synchronize()
             return
-        if not (HIP_GRAPH and graph) or stop - start < 8 or (isinstance(HIP_GRAPH, tuple) and self.name not in HIP_GRAPH):
-            return self._run_eager(stream, start, stop, join)
-        key = (start, stop, SIDE_STREAM)
-        ent = self._graphs.setdefault(key, [0, None])
-        if ent[1] is not None:
-            ent[1].replay()
-            return
-        if ent[0] < GRAPH_WARMUP:
-            ent[0] += 1
-            return self._run_eager(stream, start, stop)
-        g = torch.cuda.CUDAGraph()
-        torch.cuda.synchronize()
-        with torch.cuda.graph(g):
-            self._run_eager(torch.cuda.current_stream().cuda_stream, start, stop)
-        ent[1] = g
-        g.replay()
-
-    def _run_eager(self, stream: int, start: int, stop: int, join: bool = True):
         if SIDE_STREAM and any(self.lanes[start:stop]):
-            if COMPLETION_EVENTS and not torch.cuda.is_current_stream_capturing():
-                return self._run_lanes_ce(stream, start, stop, join)
             return self._run_lanes(stream, start, stop, join)
         st = C.c_void_p(stream)
         for fn, args, what in self.calls[start:stop]:
             rc = fn(*args, st)
             if rc:
-                raise ZsgError(f"{self.name}/{what} failed ({rc}): {lib.zsg_last_error().decode()}")
+                raise self._error(what, rc)
 
     def profile(self, stream: int):
         """[(what, ms)] per launch, timed with HIP events on the launch stream (developer tool, bench --per-op)."""
@@ -532,7 +443,7 @@ class Program:
             rc = fn(*args, st)
             b.record()
             if rc:
-                raise ZsgError(f"{self.name}/{what} failed ({rc}): {lib.zsg_last_error().decode()}")
+                raise self._error(what, rc)
             evs.append((what, fn.__name__, a, b))
         torch.cuda.synchronize()
         return [(w, f, a.elapsed_time(b)) for w, f, a, b in evs]
@@ -781,8 +692,8 @@ def sk_cands(d: ConvDesc, rows: int) -> list:
     """Stream-K candidates of an implicit-GEMM launch whose tile grid is below one round of (256 x workgroups-per-CU) workgroups —
     layer3 / layer4's 1x1 convolutions, the strided 3x3 ones, the small pyramid levels.  The library refuses what it cannot run
     (more tiles than workgroups, several segments): a refused candidate is simply not timed."""
-    if d.nseg != 1 or d.merge_x or os.environ.get("ZSG_SK", "1") == "0" or os.environ.get("ZSG_SK_IGEMM", "1") == "0" or HIP_GRAPH:
-        return []          # (hipGraph replay, opt-in: a captured range runs on the capture stream, which has no registered scratch)
+    if d.nseg != 1 or d.merge_x or os.environ.get("ZSG_SK", "1") == "0" or os.environ.get("ZSG_SK_IGEMM", "1") == "0":
+        return []
     out = []
     for bm, bn, w8, k64 in ((64, 64, 0, 0), (64, 64, 1, 0), (64, 64, 1, 1), (128, 64, 1, 0), (128, 128, 1, 0), (128, 128, 0, 0)):
         if (bn == 128 and d.N <= 64) or (k64 and d.C % 64):
@@ -805,7 +716,7 @@ def _wino_cands(d: ConvDesc, allow_sk: bool = True) -> list:
     # (tiles per block, channels per block, split-K, four position groups instead of two = twice the waves per SIMD)
     cands = [tile_hint(64, 64, 1), tile_hint(32, 64, 1), tile_hint(64, 64, 1, 1), tile_hint(32, 64, 1, 1), tile_hint(32, 32, 1, 1)]
     # stream-K (csrc/wino.hip, template flag SK): the 32 x 64 four-group tile over 256 workgroups, for grids below one round
-    if allow_sk and d.nseg == 1 and ((tiles + 31) // 32) * ((d.N + 63) // 64) <= 256 and os.environ.get("ZSG_SK", "1") != "0" and os.environ.get("ZSG_SK_WINO", "1") != "0" and not HIP_GRAPH:
+    if allow_sk and d.nseg == 1 and ((tiles + 31) // 32) * ((d.N + 63) // 64) <= 256 and os.environ.get("ZSG_SK", "1") != "0" and os.environ.get("ZSG_SK_WINO", "1") != "0":
         cands.append(tile_hint(32, 64, 1, 1) | (1 << SK_SHIFT))
     s0 = d.seg[0]
     dense = (d.nseg == 1 and not d.relu and d.out_ld == d.N and s0.out_bstride == s0.rows_y * s0.rows_x * d.N)
