@@ -425,6 +425,32 @@ int zsg_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float
 int zsg_adam_step_range(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                         float weight_decay, float grad_scale, int32_t* step_count, int32_t publish, void* stream);
 
+/* Adam over listed segments of the flat buffer (fine-tuning: frozen parameters are not listed; parameter groups).  segs: a DEVICE
+ * table of nseg segments in increasing chunk0 order, one per stepped parameter; the kernel reads and writes p, m, v inside the
+ * listed ranges only.  Every segment is cut into work chunks of at most ZSG_ADAM_CHUNK elements (a chunk never straddles two
+ * segments); chunk0 = the sum of ceil(len / ZSG_ADAM_CHUNK) over the segments before it, nchunks = that sum over all of them.
+ * groups: a HOST table of ngroups <= ZSG_ADAM_MAX_GROUPS hyperparameter sets, passed to the kernel by value (an lr change costs
+ * no copy).  counters: device int32, one per segment (distinct indices) = the steps its parameter has taken (torch's
+ * state['step']); a segment computes with t = counters[counter] + 1 and the block that finishes last advances every listed
+ * counter.  ticket: a device int32, 0 between launches, owned by the caller's optimizer.  A one-segment, one-group launch is
+ * bit-identical to zsg_adam_step over the same range. */
+#define ZSG_ADAM_MAX_GROUPS 8
+#define ZSG_ADAM_CHUNK 16384
+typedef struct zsg_adam_seg {
+    int64_t off;          /* first element (a multiple of 4: 16-byte aligned) */
+    int64_t len;          /* elements (any count; the parameter store pads to multiples of 4) */
+    int32_t group;        /* index into groups[] */
+    int32_t counter;      /* index into counters[] */
+    int32_t chunk0;       /* index of the segment's first work chunk */
+    int32_t reserved;
+} zsg_adam_seg;
+typedef struct zsg_adam_group {
+    float lr, beta1, beta2, eps, weight_decay;
+} zsg_adam_group;
+int zsg_adam_step_segments(float* p, const float* g, float* m, float* v, const zsg_adam_seg* segs, int32_t nseg, int32_t nchunks,
+                           const zsg_adam_group* groups, int32_t ngroups, float grad_scale, int32_t* counters, int32_t* ticket,
+                           void* stream);
+
 int zsg_memset_f32(float* p, int64_t n, float value, void* stream);
 
 /* Wave priority of the kernels of the step's dependent chain (convolutions forward / data gradient, BatchNorm passes, the small

@@ -1,0 +1,94 @@
+"""Developer tool: ms per training step at BASELINE configs[1] (ResNet-50 + FPN, 300x300, B = 16) with parts of the network frozen
+(requires_grad=False), timed with device events in ONE process, the variants alternating round by round so that clock and thermal drift
+fall on all of them alike.  Each variant has its own network (a change of the trainable set re-lowers the plan), the same weights and
+batch.  Prints one JSON object: per variant the median ms per step over the rounds, all round medians, the backward program's launch
+count and the number of stepped parameters.
+
+    python tools/finetune_step.py [--rounds 5] [--steps 10] [--warmup 3] [--out profiles/finetune_step.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from zsgnet_pytorch_amd import config, loss, mdl, ops, optim  # noqa: E402
+from zsgnet_pytorch_amd.synth import synthetic_batch  # noqa: E402
+
+ENC = "backbone.encoder."
+VARIANTS = {
+    "all_trainable": (),
+    "stem_layer1_frozen": (ENC + "conv1.", ENC + "bn1.", ENC + "layer1."),
+    "encoder_frozen": (ENC,),
+    "encoder_lstm_frozen": (ENC, "lstm."),
+}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--bs", type=int, default=16)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    torch.cuda.set_device(0)
+    cfg = config.get_cfg()
+    r, s = config.ratios_scales(cfg)
+    lf = loss.get_default_loss(r, s, cfg)
+    bt = {k: v.cuda() for k, v in synthetic_batch(a.bs, 300, 300, seed=1).items()}
+    bt["h0"], bt["c0"] = torch.zeros(2, a.bs, 128), torch.zeros(2, a.bs, 128)
+    sd = None
+    runs = {}
+    for name, prefixes in VARIANTS.items():
+        net = mdl.get_default_net(9, cfg)
+        if sd is None:
+            sd = {k: v.clone() for k, v in net.state_dict().items()}
+        net.load_state_dict(sd)
+        net.to("cuda").train()
+        for n, p in net.named_parameters():
+            p.requires_grad_(not (prefixes and n.startswith(prefixes)))
+        runs[name] = dict(net=net, opt=optim.FusedAdam(net, lr=1e-4, betas=(0.9, 0.99)), ms=[])
+
+    def step(v):
+        v["opt"].zero_grad()
+        lf(v["net"](bt), bt)["loss"].backward()
+        v["opt"].step()
+    for v in runs.values():              # lowering (and any tuning) outside the timed rounds
+        for _ in range(a.warmup):
+            step(v)
+    torch.cuda.synchronize()
+    for _ in range(a.rounds):
+        for name, v in runs.items():
+            for _ in range(a.warmup):
+                step(v)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
+            ev[0].record()
+            for i in range(a.steps):
+                step(v)
+                ev[i + 1].record()
+            torch.cuda.synchronize()
+            v["ms"].append(statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(a.steps)))
+    res = dict(config="BASELINE configs[1] shape (ResNet-50 + FPN, 300x300, B=%d, 1 GPU)" % a.bs, rounds=a.rounds, steps=a.steps,
+               tune_loaded=ops.TUNE_INFO.get("loaded", 0), stamp_match=ops.TUNE_INFO.get("table_stamp") == ops.TUNE_INFO.get("stamp"),
+               variants={})
+    for name, v in runs.items():
+        net = v["net"]
+        plan = [p for k, p in net._plans.items() if k[-1]][0]
+        res["variants"][name] = dict(ms_per_step=round(statistics.median(v["ms"]), 4), round_medians=[round(x, 4) for x in v["ms"]],
+                                     bwd_launches=len(plan.bwd.calls), prep_launches=len(plan.prep.calls),
+                                     stepped_params=sum(p.numel() for p in net.parameters() if p.grad is not None),
+                                     frozen_tensors=sum(1 for p in net.parameters() if not p.requires_grad))
+    js = json.dumps(res, indent=1)
+    print(js)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(js + "\n")
+
+
+if __name__ == "__main__":
+    main()

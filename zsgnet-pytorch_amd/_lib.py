@@ -33,6 +33,19 @@ class ConvDesc(C.Structure):
                 ("epi_flags", C.c_int32), ("seg", Seg * ZSG_MAX_SEG)]
 
 
+ADAM_MAX_GROUPS = 8          # ZSG_ADAM_MAX_GROUPS
+ADAM_CHUNK = 16384           # ZSG_ADAM_CHUNK: elements per work chunk of zsg_adam_step_segments
+
+
+class AdamSeg(C.Structure):
+    _fields_ = [("off", C.c_int64), ("len", C.c_int64), ("group", C.c_int32), ("counter", C.c_int32), ("chunk0", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class AdamGroup(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -120,6 +133,7 @@ SIGNATURES = {
     "zsg_iou": (I32, [P, P, I32, I32, P, P]),
     "zsg_adam_step": (I32, [P, P, P, P, I64, F32, F32, F32, F32, F32, F32, P, P]),
     "zsg_adam_step_range": (I32, [P, P, P, P, I64, F32, F32, F32, F32, F32, F32, P, I32, P]),
+    "zsg_adam_step_segments": (I32, [P, P, P, P, P, I32, I32, P, I32, F32, P, P, P]),
     "zsg_memset_f32": (I32, [P, I64, F32, P]),
     "zsg_set_stream_workspace": (I32, [P, P, SZ]),
     "zsg_set_main_priority": (I32, [I32]),

@@ -75,3 +75,95 @@ extern "C" int zsg_adam_step_range(float* p, const float* g, float* m, float* v,
                                    float weight_decay, float grad_scale, int32_t* step_count, int32_t publish, void* stream) {
     return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, grad_scale, step_count, publish ? 1 : 0, stream);
 }
+
+// ---- Adam over listed segments (fine-tuning: frozen parameters, parameter groups) -----------------------------------------------------
+// One block per work chunk of <= ZSG_ADAM_CHUNK elements of one segment (the segment table gives each segment's first chunk), so the
+// loop body is adam_kernel's, vectorised, with the segment's own hyperparameters and bias correction.  Nothing outside the listed
+// ranges is read or written.  The counters follow adam_kernel's ticket scheme: every block reads the counter of its segment when it
+// starts; the block that finishes last (by then every block has read) advances the counters of all listed segments.
+
+struct AdamGroups {
+    zsg_adam_group g[ZSG_ADAM_MAX_GROUPS];
+};
+
+__global__ __launch_bounds__(256) void adam_segments_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, const zsg_adam_seg* __restrict__ segs, int nseg,
+                                                            AdamGroups hp, float gs, int* counters, int* ticket) {
+    // the segment of this chunk: the last one whose chunk0 <= blockIdx.x (block-uniform binary search)
+    const int c = blockIdx.x;
+    int lo = 0, hi = nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (segs[mid].chunk0 <= c) lo = mid;
+        else hi = mid - 1;
+    }
+    const zsg_adam_seg sg = segs[lo];
+    const zsg_adam_group h = hp.g[sg.group];
+    const float lr = h.lr, b1 = h.beta1, b2 = h.beta2, eps = h.eps, wd = h.weight_decay;
+    const int t = __hip_atomic_load(counters + sg.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+    const float bc1 = 1.f - powf(b1, (float)t);
+    const float bc2s = sqrtf(1.f - powf(b2, (float)t));
+    const float step_size = lr / bc1;
+    const int64_t start = (int64_t)(c - sg.chunk0) * ZSG_ADAM_CHUNK;
+    const int64_t rem = sg.len - start;
+    const int cnt = rem < ZSG_ADAM_CHUNK ? (int)rem : ZSG_ADAM_CHUNK;
+    const int n4 = cnt >> 2;
+    float* pb = p + sg.off + start;
+    const float* gb = g + sg.off + start;
+    float* mb = m + sg.off + start;
+    float* vb = v + sg.off + start;
+    for (int i = threadIdx.x; i < n4; i += blockDim.x) {
+        f32x4 pp = *(const f32x4*)(pb + 4 * i);
+        f32x4 gg = *(const f32x4*)(gb + 4 * i) * gs;
+        f32x4 mm = *(const f32x4*)(mb + 4 * i);
+        f32x4 vv = *(const f32x4*)(vb + 4 * i);
+        if (wd != 0.f) gg += pp * wd;
+        mm = mm * b1 + gg * (1.f - b1);
+        vv = vv * b2 + gg * gg * (1.f - b2);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pp[e] -= step_size * (mm[e] / (sqrtf(vv[e]) / bc2s + eps));
+        *(f32x4*)(pb + 4 * i) = pp;
+        *(f32x4*)(mb + 4 * i) = mm;
+        *(f32x4*)(vb + 4 * i) = vv;
+    }
+    // tail of a segment whose length is not a multiple of 4 (its last chunk only)
+    if ((int)threadIdx.x < cnt - 4 * n4) {
+        const int i = 4 * n4 + threadIdx.x;
+        float gg = gb[i] * gs;
+        if (wd != 0.f) gg += pb[i] * wd;
+        const float mm = mb[i] * b1 + gg * (1.f - b1);
+        const float vv = vb[i] * b2 + gg * gg * (1.f - b2);
+        pb[i] -= step_size * (mm / (sqrtf(vv) / bc2s + eps));
+        mb[i] = mm;
+        vb[i] = vv;
+    }
+    __shared__ int last;
+    __syncthreads();
+    if (threadIdx.x == 0) last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+    __syncthreads();
+    if (!last) return;
+    for (int s = threadIdx.x; s < nseg; s += blockDim.x) {
+        const int k = segs[s].counter;
+        const int old = __hip_atomic_load(counters + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(counters + k, old + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (threadIdx.x == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+extern "C" int zsg_adam_step_segments(float* p, const float* g, float* m, float* v, const zsg_adam_seg* segs, int32_t nseg,
+                                      int32_t nchunks, const zsg_adam_group* groups, int32_t ngroups, float grad_scale,
+                                      int32_t* counters, int32_t* ticket, void* stream) {
+    ZSG_REQUIRE(p && g && m && v && segs && groups && counters && ticket, "adam_step_segments: null pointer");
+    ZSG_REQUIRE(ngroups >= 1 && ngroups <= ZSG_ADAM_MAX_GROUPS, "adam_step_segments: %d parameter groups (1..%d supported)", ngroups,
+                ZSG_ADAM_MAX_GROUPS);
+    ZSG_REQUIRE(nseg >= 0 && nchunks >= nseg, "adam_step_segments: %d segments in %d chunks", nseg, nchunks);
+    ZSG_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_step_segments: buffers must be 16-byte aligned");
+    if (nseg == 0) return 0;          // nothing is stepped: no launch, no counter moves
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("adam_step_segments", st, 0, (double)nchunks * ZSG_ADAM_CHUNK * 28);      // (bytes: an upper bound)
+    AdamGroups hp = {};
+    for (int i = 0; i < ngroups; ++i) hp.g[i] = groups[i];
+    ZSG_LAUNCH(adam_segments_kernel, dim3(nchunks), dim3(256), 0, st, p, g, m, v, segs, (int)nseg, hp, grad_scale, counters, ticket);
+    ZSG_CHECK_LAUNCH("adam_step_segments");
+    return 0;
+}

@@ -67,7 +67,7 @@ def plan_buckets(spans: Sequence[Tuple[int, int, int]], target_elems: int, tail_
             groups[-1].append(sp)
         else:
             groups.append([sp])
-    if tail_elems:
+    if tail_elems and groups:
         gi = max(range(len(groups)), key=lambda i: max(x[2] for x in groups[i]))
         g = groups[gi]
         if sum(x[1] for x in g) > 2 * tail_elems and len(g) > 1:
@@ -80,6 +80,13 @@ def plan_buckets(spans: Sequence[Tuple[int, int, int]], target_elems: int, tail_
             groups[gi:gi + 1] = pieces
     buckets = [Bucket(g[0][0], g[-1][0] + g[-1][1], max(x[2] for x in g)) for g in groups]
     return sorted(buckets, key=lambda b: (b.ready, b.start))
+
+
+def grad_spans(entries, names: Sequence[str], grad_ready, frozen=()) -> List[Tuple[int, int, int]]:
+    """(offset, padded size, ready index) of every parameter whose gradient the reducer all-reduces, in flat order: the trainable
+    ones only — no bucket covers a frozen span (torch DDP skips requires_grad=False parameters).  entries: ParamStore.entries;
+    grad_ready: the last backward launch that writes each gradient (-1 / missing: none)."""
+    return [(entries[n].offset, (entries[n].size + 3) // 4 * 4, grad_ready.get(n, -1)) for n in names if n not in frozen]
 
 
 class NativeComm:

@@ -415,10 +415,25 @@ class ZSGNet(nn.Module):
         T = inp["qvec"].shape[1]
         return B, H, W, (20 if T <= 20 else (50 if T <= 50 else T))
 
+    def _frozen_key(self) -> Tuple[int, ...]:
+        """flat-order indices of the parameters with requires_grad=False (the training plans are lowered for one trainable set)"""
+        return tuple(i for i, p in enumerate(self._ordered_params()) if not p.requires_grad)
+
     def _plan_for(self, B, H, W, T) -> "_Plan":
-        key = (B, H, W, T, self.training)
+        if not self.training:
+            key = (B, H, W, T, False)
+            if key not in self._plans:
+                self._plans[key] = _Plan(self, B, H, W, T, False)
+            return self._plans[key]
+        fz = self._frozen_key()
+        key = (B, H, W, T, fz, True)
         if key not in self._plans:
-            self._plans[key] = _Plan(self, B, H, W, T, self.training)
+            # a new trainable set: the training plans of the old one go (gradual unfreezing must not pile up activation buffers)
+            for k in [k for k in self._plans if k[-1] and k[4] != fz]:
+                old = self._plans.pop(k)
+                if old._prep_pending:           # (its side-stream weight preparation may still be reading the weights)
+                    torch.cuda.current_stream().wait_event(old._prep_ev)
+            self._plans[key] = _Plan(self, B, H, W, T, True, frozen={self._param_names[i] for i in fz})
         return self._plans[key]
 
     def forward(self, inp: Dict[str, Any]) -> Dict[str, Any]:
@@ -471,8 +486,11 @@ class _NetFn(torch.autograd.Function):
 class _Plan:
     """Static lowering of ZSGNet for one (B, H, W, T, training) geometry."""
 
-    def __init__(self, net: ZSGNet, B: int, H: int, W: int, T: int, training: bool):
+    def __init__(self, net: ZSGNet, B: int, H: int, W: int, T: int, training: bool, frozen=frozenset()):
         self.net, self.B, self.H, self.W, self.T, self.training = net, B, H, W, T, training
+        # parameters with requires_grad=False when the plan was lowered: no weight / bias gradient, no data gradient into an activation
+        # that no trainable parameter lies upstream of (Act.requires_grad), no p.grad view, no DDP bucket
+        self.frozen = frozenset(frozen) if training else frozenset()
         self.dev = net.device
         apply_main_priority_env()
         self.fwd = Program("fwd")
@@ -573,6 +591,10 @@ class _Plan:
     def base(a: Act) -> torch.Tensor:
         """flat tensor starting at the first element of a (single-level or packed) activation"""
         return a.buf[a.levels[0].off:]
+
+    def trains(self, name) -> bool:
+        """the parameter `name` gets a gradient (it is not frozen)"""
+        return name not in self.frozen
 
     def P(self, name):      # raw parameter storage
         return self.net.store.raw(name)
@@ -716,6 +738,7 @@ class _Plan:
             self.fwd.add(lib.zsg_bn_stats_from_partials, partials, out.bn_chunks, rows, Lb.c, out.bn_mean, out.bn_invstd, rm, rv, 0.1, 1e-5,
                          what="stats:" + Lb.name, lane=self._lane)
         out.needs_mask = relu
+        out.requires_grad = self._conv_rg(L, src)
         # the first consumer lowered is the LAST to add to src's gradient in the backward: if src is a train-mode BatchNorm's
         # output, that data gradient completes the BatchNorm's dout and can carry its backward sums (see bn())
         completes = self.training and getattr(src, "bn_out", False) and not getattr(src, "_consumed", False)
@@ -765,6 +788,7 @@ class _Plan:
                              what="stats:" + Lb.name, lane=self._lane)
         src.pending = None
         out.needs_mask = False
+        out.requires_grad = self._conv_rg(L, src)
         completes = self.training and getattr(src, "bn_out", False) and not getattr(src, "_consumed", False)
         src._consumed = True
         self.tape.append(lambda: self._conv_bwd(L, src, out, completes_bn=completes))
@@ -838,13 +862,18 @@ class _Plan:
         if wj.jobs:          # rotated filter transforms of the Winograd data gradients, from the transposed images
             self.prep.add(lib.zsg_wino_weights, wj.finish(self.dev), len(wj.jobs), wj.blocks, what="wino dgrad filter transforms")
 
+    def _conv_rg(self, L: ConvL, src: Act) -> bool:
+        """a convolution's output needs a gradient when its input does or one of its own parameters trains"""
+        return src.requires_grad or self.trains(L.name + ".weight") or (L.bias and self.trains(L.name + ".bias"))
+
     def _conv_bwd(self, L: ConvL, src: Act, out: Act, dy: Optional[Act] = None, completes_bn: bool = False):
         dy = dy or out.grad
         if dy is None:
             return
-        dw = fwd_desc(src, dy, L.cpad, L.cout, L.k, L.stride, L.pad, L.dil, wC=L.cpad)
-        self.wgrad(dw, src, dy, L.name + ".weight", "wgrad:" + L.name)
-        if L.bias:
+        if self.trains(L.name + ".weight"):
+            dw = fwd_desc(src, dy, L.cpad, L.cout, L.k, L.stride, L.pad, L.dil, wC=L.cpad)
+            self.wgrad(dw, src, dy, L.name + ".weight", "wgrad:" + L.name)
+        if L.bias and self.trains(L.name + ".bias"):
             base = dy.levels[0].off
             self.bwd.add(lib.zsg_colsum, dy.buf[base:], 1, 0, dy.rows(), dy.ld, 0, L.cout, self.G(L.name + ".bias"), 1,
                          what="bgrad:" + L.name, lane=1)
@@ -920,6 +949,10 @@ class _Plan:
         net = self.net
         lv = x.levels[0]
         out = self.act(name or L.name, x.B, lv.H, lv.W, L.c)
+        # (frozen gamma / beta with an input that needs a gradient: the backward still writes d(gamma) / d(beta) into the flat gradient
+        # buffer as a by-product of the fused kernels; those ranges are never exposed as p.grad, reduced or stepped)
+        out.requires_grad = (x.requires_grad or self.trains(L.name + ".weight") or self.trains(L.name + ".bias")
+                             or (residual is not None and residual.requires_grad))
         rows = x.B * lv.H * lv.W
         fused = self.training and getattr(x, "bn_chunks", 0) > 0
         mean, invstd = (x.bn_mean, x.bn_invstd) if fused else (self._buf(L.c), self._buf(L.c))
@@ -1124,6 +1157,8 @@ class _Plan:
                 emit()
             if WG_BATCH:
                 self._batch_wgrads()
+            # (a frozen BatchNorm's d(gamma) / d(beta) written as a by-product is not a gradient anyone waits for)
+            self.grad_ready = {k: v for k, v in self.grad_ready.items() if k not in self.frozen}
         self.tape = []
 
     def _batch_wgrads(self):
@@ -1215,6 +1250,7 @@ class _Plan:
             mean, invstd = self._buf(Lb.c), self._buf(Lb.c)
             self.fwd.add(lib.zsg_bn_stats, y.buf, rows, Lb.c, mean, invstd, rm, rv, 0.1, 1e-5, self.ws, self.ws_bytes, what=Lb.name)
         x = self.act("pool", B, H2, W2, Lb.c)
+        x.requires_grad = y.requires_grad or self.trains(Lb.name + ".weight") or self.trains(Lb.name + ".bias")
         idx = self._buf((B * H2 * W2 * Lb.c + 3) // 4)      # uint8 indices, stored in a float-sized buffer
         self.fwd.add(lib.zsg_bn_relu_maxpool_fwd, y.buf, B, H1, W1, Lb.c, mean, invstd, gam, bet, 3, 2, 1, H2, W2, x.buf, idx, what="bn1+relu+maxpool")
 
@@ -1256,6 +1292,7 @@ class _Plan:
             return o
         Ho, Wo = osz(l.H), osz(l.W)
         out = self.act(name, x.B, Ho, Wo, x.C)
+        out.requires_grad = x.requires_grad
         idx = self._buf((x.B * Ho * Wo * x.C + 3) // 4)
         self.fwd.add(lib.zsg_maxpool_fwd, x.buf, x.B, l.H, l.W, x.C, k, s, p, Ho, Wo, out.buf, idx, what=name)
 
@@ -1274,6 +1311,7 @@ class _Plan:
         rows = x.B * l.H * l.W
         if out is None:
             out = self.act(name, x.B, l.H, l.W, x.C)
+        out.requires_grad = x.requires_grad
         nrm = self._buf(rows)
         self.fwd.add(lib.zsg_l2norm_fwd, self.base(x), rows, x.C, self.base(out), nrm, what=name, lane=lane)
 
@@ -1425,6 +1463,7 @@ class _Plan:
         with self.on_side_stream():
             p6 = self.conv(C[f + "P6"], c5, out=o6)
             r6 = self.act("r6", B, p6.levels[0].H, p6.levels[0].W, 256)
+            r6.requires_grad = p6.requires_grad
             n6 = r6.buf.numel()
             self.fwd.add(lib.zsg_relu_fwd, self.base(p6), n6, r6.buf, what="relu(p6)", lane=self._lane)
 
@@ -1440,6 +1479,7 @@ class _Plan:
                 return p6, p7, None
             l7 = p7.levels[0]
             p8 = o8
+            p8.requires_grad = p7.requires_grad
             self.fwd.add(lib.zsg_avgpool_fwd, self.base(p7), B, l7.H * l7.W, 256, self.base(p8), what="avgpool", lane=self._lane)
 
             def avg_back():
@@ -1454,6 +1494,7 @@ class _Plan:
     def _upsample_add(self, a: Act, p: Act, name: str, join: bool = False) -> Act:
         la, lp = a.levels[0], p.levels[0]
         out = self.act(name, a.B, la.H, la.W, a.C)
+        out.requires_grad = a.requires_grad or p.requires_grad
         self.fwd.add(lib.zsg_upsample_add_fwd, a.buf, p.buf, a.B, lp.H, lp.W, la.H, la.W, a.C, out.buf, what=name,
                      lane=2 if (join and self.training) else 0)
 
@@ -1476,6 +1517,7 @@ class _Plan:
         H4 = 4 * Hd
         we = self.act("we", B, 1, 1, net.lstm_out_dim)
         dirs = [("", 0)] + ([("_reverse", 1)] if net.bid else [])
+        we.requires_grad = any(self.trains(f"lstm.{k}_l0{suf}") for suf, _ in dirs for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
         x_all = Act(self.in_qvec, B, E, E, [Level(0, 1, T, T * E)], "qvec")
         x_all.requires_grad = False
         xlast = self.act("xlast", B, 1, 1, E, requires_grad=False)
@@ -1501,14 +1543,18 @@ class _Plan:
                 dg = Act(self._buf(B * Tn * H4), B, H4, H4, [Level(0, 1, Tn, Tn * H4)], "dgates" + suf)
                 self.bwd.add(lib.zsg_lstm_bwd, we.grad.buf, net.lstm_out_dim, di * Hd, self.P("lstm.weight_hh_l0" + suf), gates, cst, c0,
                              self.in_qlens, lens, B, Tn, Hd, dg.buf, what="lstm_bwd" + suf, lane=1)
-                d_ih = fwd_desc(xin, dg, E, H4, 1, 1, 0, 1, wC=E)
-                self.bwd.add(lib.zsg_conv_wgrad, d_ih, xin.buf, dg.buf, self.G("lstm.weight_ih_l0" + suf), 1, self.wg_ws, self.wg_ws_bytes,
-                             what="wgrad:w_ih" + suf, lane=1)
-                hp = Act(hprev, B, Hd, Hd, [Level(0, 1, Tn, Tn * Hd)], "hprev" + suf)
-                d_hh = fwd_desc(hp, dg, Hd, H4, 1, 1, 0, 1, wC=Hd)
-                self.bwd.add(lib.zsg_conv_wgrad, d_hh, hp.buf, dg.buf, self.G("lstm.weight_hh_l0" + suf), 1, self.wg_ws, self.wg_ws_bytes,
-                             what="wgrad:w_hh" + suf, lane=1)
+                if self.trains("lstm.weight_ih_l0" + suf):
+                    d_ih = fwd_desc(xin, dg, E, H4, 1, 1, 0, 1, wC=E)
+                    self.bwd.add(lib.zsg_conv_wgrad, d_ih, xin.buf, dg.buf, self.G("lstm.weight_ih_l0" + suf), 1, self.wg_ws, self.wg_ws_bytes,
+                                 what="wgrad:w_ih" + suf, lane=1)
+                if self.trains("lstm.weight_hh_l0" + suf):
+                    hp = Act(hprev, B, Hd, Hd, [Level(0, 1, Tn, Tn * Hd)], "hprev" + suf)
+                    d_hh = fwd_desc(hp, dg, Hd, H4, 1, 1, 0, 1, wC=Hd)
+                    self.bwd.add(lib.zsg_conv_wgrad, d_hh, hp.buf, dg.buf, self.G("lstm.weight_hh_l0" + suf), 1, self.wg_ws, self.wg_ws_bytes,
+                                 what="wgrad:w_hh" + suf, lane=1)
                 for bname in ("lstm.bias_ih_l0", "lstm.bias_hh_l0"):
+                    if not self.trains(bname + suf):
+                        continue
                     self.bwd.add(lib.zsg_colsum, dg.buf, 1, 0, B * Tn, H4, 0, H4, self.G(bname + suf), 1, what="bgrad:" + bname + suf, lane=1)
             self.tape.append(back)
         return we
@@ -1523,9 +1569,13 @@ class _Plan:
         hc = types.SimpleNamespace(Cf=Cf, Cw=Cw, Cg=Cg, we=we, gridmap=None)
         # do_norm: per-pixel channel L2 normalisation of the maps and of the language vector
         hc.Fp = self.Fpack if Cf else None
+        feat_rg = any(f.requires_grad for f in feats)
+        if Cf:
+            self.Fpack.requires_grad = feat_rg
         heads_in = feats                         # the Acts whose .grad conv0's data gradient fills
         if net.do_norm and Cf:
             hc.Fp = self.packed("head.feat", B, sizes, 256)
+            hc.Fp.requires_grad = feat_rg
             heads_in = [self.l2norm(f, f"featnorm{i}", out=hc.Fp.lvl(i)) for i, f in enumerate(feats)]
         if net.do_norm and Cw:
             # (side stream, behind the query encoder that produces `we`; hoisted together with the language maps that read it)
@@ -1582,7 +1632,7 @@ class _Plan:
         self._head_stack("reg_box", 4 * nA, hc, o_reg, g_reg)
         self.fwd.add(lib.zsg_interleave, o_reg.buf, B * P, nA, 4, self.out5.buf, 5, 0, 0, what="out5<-reg")
         self.fwd.add(lib.zsg_interleave, o_att.buf, B * P, nA, 1, self.out5.buf, 5, 4, 0, what="out5<-att")
-        if self.training:
+        if self.training and (self._head_rg["att_box"] or self._head_rg["reg_box"]):
             def split_back():
                 self.bwd.add(lib.zsg_interleave, g_reg, B * P, nA, 4, self.g5_in, 5, 0, 1, what="g5->reg")
                 self.bwd.add(lib.zsg_interleave, g_att, B * P, nA, 1, self.g5_in, 5, 4, 1, what="g5->att")
@@ -1644,18 +1694,23 @@ class _Plan:
             self.fwd.add(lib.zsg_bn_apply, lmap.buf, h1.rows(), 256, zero, one, one, self.P(L0.name + ".bias"), None, 1, h1.buf, None,
                          what=L0.name)
         h1.needs_mask = True
+        w0t, b0t = self.trains(W0n), self.trains(L0.name + ".bias")
+        we_rg = bool(Cw) and we.requires_grad
+        h1.requires_grad = bool(Cf and Fp.requires_grad) or we_rg or w0t or b0t
 
         def head0_back():
             dy = h1.grad
             if dy is None:
                 return
-            gW0 = self.G(W0n)
-            if not Cw:       # (with language the bias gradient falls out of the border sums below)
+            gW0 = self.G(W0n) if w0t else None
+            if not Cw and b0t:       # (with language the bias gradient falls out of the border sums below)
                 self.bwd.add(lib.zsg_colsum, dy.buf, 1, 0, dy.rows(), 256, 0, 256, self.G(L0.name + ".bias"), 1, what="bgrad:" + L0.name, lane=1)
             if Cf:
-                dwf = fwd_desc(Fp, dy, Cf, 256, 3, 1, 1, 1, wC=cp, wc0=0)
-                self.wgrad(dwf, Fp, dy, W0n, "wgrad:" + L0.name)
-                self.dgrad(L0, dy, Fp, n=Cf, row0=0, dx=self.grad_of(Fp))
+                if w0t:
+                    dwf = fwd_desc(Fp, dy, Cf, 256, 3, 1, 1, 1, wC=cp, wc0=0)
+                    self.wgrad(dwf, Fp, dy, W0n, "wgrad:" + L0.name)
+                if Fp.requires_grad:
+                    self.dgrad(L0, dy, Fp, n=Cf, row0=0, dx=self.grad_of(Fp))
             # The language / grid columns of dW0, the bias gradient and d(we) hang off dy only and feed nothing but the query encoder's
             # backward (itself on the side stream): with features present they are leaves of the main chain and go to the side stream,
             # so that the pyramid's backward starts right behind conv0's data gradient.
@@ -1663,7 +1718,8 @@ class _Plan:
             ln = 1 if (Cf and not (net.do_norm and Cw)) else 0
             hws_bytes = 16 << 20           # (a workspace of their own: on the main stream they ran concurrently with the side stream's slabs)
             hws = self._buf(hws_bytes // 4) if (Cw or Cg) else None
-            if Cw:
+            if Cw and (w0t or b0t or we_rg):
+                # (a frozen bias still receives the border sums' column total: a by-product in the flat gradient buffer, never exposed)
                 # language columns of dW0 and d(we) from validity-masked sums of dy, themselves nine plain per-image sums
                 S = self._buf(2 * B * 9 * 256)
                 Q = self._buf(9 * B * 256)
@@ -1673,21 +1729,24 @@ class _Plan:
                 for i, (h, w) in enumerate(sizes):
                     self.bwd.add(lib.zsg_head_border_sums, self.base(dy.lvl(i)), B, h, w, 256, Q, what=f"bsum{i}", lane=ln)
                 self.bwd.add(lib.zsg_head_border_finalize, Q, B, 256, S, self.base(S2), self.G(L0.name + ".bias"), what="bsum.finalize", lane=ln)
-                dwl = fwd_desc(we, S1, Cw, 9 * 256, 1, 1, 0, 1, wC=cp, wt_ld=cp, wc0=Cf)
-                self.bwd.add(lib.zsg_conv_wgrad, dwl, we.buf, S, gW0, 1, hws, hws_bytes, what="wgrad:" + L0.name + ".lang", lane=ln)
-                ent = net.store.entries[W0n]
-                Wrows = Act(net.store.flat, 1, Cw, cp, [Level(ent.offset + Cf, 1, 9 * 256, 9 * 256 * cp)], "head.W0rows")
-                gwe = self.grad_of(we)
-                dwe = fwd_desc(Wrows, S2, Cw, B, 1, 1, 0, 1, wC=Cw, wt_ld=Cw)
-                self.bwd.add(lib.zsg_conv_wgrad, dwe, Wrows.buf, S, self.base(gwe), int(gwe.gfilled), hws, hws_bytes, what="dwe:" + prefix, lane=ln)
-                gwe.gfilled = True
-            if Cg:
+                if w0t:
+                    dwl = fwd_desc(we, S1, Cw, 9 * 256, 1, 1, 0, 1, wC=cp, wt_ld=cp, wc0=Cf)
+                    self.bwd.add(lib.zsg_conv_wgrad, dwl, we.buf, S, gW0, 1, hws, hws_bytes, what="wgrad:" + L0.name + ".lang", lane=ln)
+                if we_rg:
+                    ent = net.store.entries[W0n]
+                    Wrows = Act(net.store.flat, 1, Cw, cp, [Level(ent.offset + Cf, 1, 9 * 256, 9 * 256 * cp)], "head.W0rows")
+                    gwe = self.grad_of(we)
+                    dwe = fwd_desc(Wrows, S2, Cw, B, 1, 1, 0, 1, wC=Cw, wt_ld=Cw)
+                    self.bwd.add(lib.zsg_conv_wgrad, dwe, Wrows.buf, S, self.base(gwe), int(gwe.gfilled), hws, hws_bytes, what="dwe:" + prefix, lane=ln)
+                    gwe.gfilled = True
+            if Cg and w0t:
                 dys = self.packed(prefix + ".dysum", 1, sizes, 256)
                 for i, (h, w) in enumerate(sizes):
                     self.bwd.add(lib.zsg_batch_sum, self.base(dy.lvl(i)), B, h * w * 256, self.base(dys.lvl(i)), what=f"dysum{i}", lane=ln)
                 dwg = fwd_desc(gridmap, dys, 4, 256, 3, 1, 1, 1, wC=cp, wc0=Cf + Cw)
                 self.bwd.add(lib.zsg_conv_wgrad, dwg, gridmap.buf, dys.buf, gW0, 1, hws, hws_bytes, what="wgrad:" + L0.name + ".grid", lane=ln)
-            self.grad_ready[W0n] = len(self.bwd.calls)
+            if w0t:
+                self.grad_ready[W0n] = len(self.bwd.calls)
         self.tape.append(head0_back)
         hs = [h1]
         for i in range(1, 5):
@@ -1709,14 +1768,22 @@ class _Plan:
             off += hh * ww
         g5p = Act(self._buf(B * P * npad), B, npad, npad, lvp, prefix + ".g5p")
         h5 = hs[-1]
+        w5t, b5t = self.trains(L5.name + ".weight"), self.trains(L5.name + ".bias")
+        self._head_rg = getattr(self, "_head_rg", {})
+        self._head_rg[prefix] = w5t or b5t or h5.requires_grad
 
         def head5_back():
+            if not self._head_rg[prefix]:
+                return                   # (everything of this head and upstream of it is frozen)
             self.bwd.add(lib.zsg_pad_rows, g_in, B * P, nout, nout, g5p.buf, npad, what="pad g5")
-            # column sums of the PADDED copy (16-byte loads; its pad columns are zero and land in the 4-float storage padding)
-            self.bwd.add(lib.zsg_colsum, g5p.buf, 1, 0, B * P, npad, 0, npad, self.G(L5.name + ".bias"), 1, what="bgrad:" + L5.name, lane=1)
-            dw = fwd_desc(h5, g5p, L5.cpad, nout, 3, 1, 1, 1, wC=L5.cpad)
-            self.wgrad(dw, h5, g5p, L5.name + ".weight", "wgrad:" + L5.name)
-            self.dgrad(L5, g5p, h5, n=256)
+            if b5t:
+                # column sums of the PADDED copy (16-byte loads; its pad columns are zero and land in the 4-float storage padding)
+                self.bwd.add(lib.zsg_colsum, g5p.buf, 1, 0, B * P, npad, 0, npad, self.G(L5.name + ".bias"), 1, what="bgrad:" + L5.name, lane=1)
+            if w5t:
+                dw = fwd_desc(h5, g5p, L5.cpad, nout, 3, 1, 1, 1, wC=L5.cpad)
+                self.wgrad(dw, h5, g5p, L5.name + ".weight", "wgrad:" + L5.name)
+            if h5.requires_grad:
+                self.dgrad(L5, g5p, h5, n=256)
         self.tape.append(head5_back)
 
     # ---- execution -------------------------------------------------------------------------------------------------------
@@ -1868,11 +1935,20 @@ class _Plan:
         # FusedAdam.zero_grad() (one memset, the p.grad views stay), or here when the p.grad were set to None.
         params = net._ordered_params()
         st = stream_ptr()
+        if self.frozen:
+            # p.grad views for the trainable parameters only: a frozen one keeps p.grad None (as autograd leaves it), so the
+            # optimizer does not step it
+            names = net._param_names
+            params = [p for n, p in zip(names, params) if n not in self.frozen]
+            for n, p in zip(names, net._ordered_params()):
+                if n in self.frozen:
+                    p.grad = None
         if any(p.grad is None for p in params):
             net._grad_reduced = False
             lib.zsg_memset_f32(net.store.grad.data_ptr(), net.store.grad.numel(), 0.0, st)
-            for n, p in zip(net._param_names, params):
-                p.grad = net.store.view(n, net.store.grad)
+            for n, p in zip(net._param_names, net._ordered_params()):
+                if n not in self.frozen:
+                    p.grad = net.store.view(n, net.store.grad)
         if g5.data_ptr() != self.g5_in.data_ptr():        # (the loss wrote it in place: see ZSGNet.forward)
             self.g5_in.view_as(g5).copy_(g5)
         ddp = getattr(net, "_ddp", None)
@@ -1900,9 +1976,8 @@ class _Plan:
                 self.g5_in.mul_(1.0 / ddp.world)       # (the loss kernel writes the gradient pre-scaled when it can: loss._LossFn.forward)
             self.g5_from_loss = None
             if self.reducer is None:
-                ents = net.store.entries
-                spans = [(ents[n].offset, (ents[n].size + 3) // 4 * 4, self.grad_ready.get(n, -1)) for n in net._param_names]
-                self.reducer = ddp.make_reducer(spans)
+                from .dist import grad_spans
+                self.reducer = ddp.make_reducer(grad_spans(net.store.entries, net._param_names, self.grad_ready, self.frozen))
             # (join=False: a range that ends at a bucket boundary leaves the side stream's weight gradients running; the
             # bucket's collective waits for both streams, the main stream only joins at the very end)
             nb = len(self.bwd.calls)

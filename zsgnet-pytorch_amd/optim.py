@@ -1,23 +1,52 @@
 """Fused Adam over the model's flat parameter buffer (reference: torch.optim.Adam(betas=(0.9,0.99)), main_dist.py:50,
 stepped at utils.py:413).  One HIP launch updates all 37.6 M parameters (28 B/param of HBM traffic) instead of ~170
-per-tensor updates; the step counter lives on the device."""
+per-tensor updates; the step counter lives on the device.
+
+Fine-tuning (torch.optim semantics): `params=` takes the model's parameters or a list of group dicts with their own lr / betas /
+eps / weight_decay (add_param_group too).  A parameter is stepped only when it is in some group AND its p.grad is not None — a
+frozen parameter (requires_grad=False: the backward leaves its p.grad at None) keeps its value and moments bit for bit.  With one
+group and every parameter stepped, the step is the single zsg_adam_step launch; otherwise zsg_adam_step_segments updates the
+listed parameters only, with per-group hyperparameters and per-parameter step counters (torch's state['step'])."""
+import ctypes as C
+
 import torch
 
-from ._lib import lib, check, stream_ptr
+from ._lib import ADAM_CHUNK, ADAM_MAX_GROUPS, AdamGroup, AdamSeg, check, lib, stream_ptr
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, model, lr=1e-4, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, grad_scale=1.0, params=None):
         net = model.module if hasattr(model, "module") else model
         self.net = net
-        params = net._ordered_params()
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        plist = net._ordered_params()
+        self._index = {id(p): i for i, p in enumerate(plist)}
+        super().__init__(plist if params is None else params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         flat = net.store.flat
         self.m = torch.zeros_like(flat)
         self.v = torch.zeros_like(flat)
         self._step2 = torch.zeros(2, dtype=torch.int32, device=flat.device)      # [steps taken, the update kernel's completion ticket]
         self.step_count = self._step2[:1]
         self.grad_scale = grad_scale
+        # per-parameter step counters of the segmented path [n params | its completion ticket].  While _seg is False every parameter has
+        # taken step_count steps (the single-launch path counts for all); once a step leaves some parameter out, the counts move here.
+        self._pcount = torch.zeros(len(plist) + 1, dtype=torch.int32, device=flat.device)
+        self._seg, self._uniform = False, True
+        self._seg_key, self._seg_tab, self._nchunks = None, None, 0
+
+    def add_param_group(self, param_group):
+        """torch's add_param_group, restricted to parameters of the model's flat store (the kernels address them by offset)."""
+        ps = param_group["params"]
+        ps = [ps] if isinstance(ps, torch.Tensor) else list(ps)
+        param_group = dict(param_group, params=ps)          # (an iterator is consumed here once)
+        index = self.__dict__.get("_index", {})
+        for p in ps:
+            if id(p) not in index:
+                shape = tuple(p.shape) if isinstance(p, torch.Tensor) else type(p).__name__
+                raise ValueError(f"FusedAdam: a tensor of shape {shape} is not a parameter of the model's flat parameter store; "
+                                 "only the model's own parameters (model.parameters() or a subset) can be optimised")
+        if len(self.param_groups) >= ADAM_MAX_GROUPS:
+            raise ValueError(f"FusedAdam: at most {ADAM_MAX_GROUPS} parameter groups are supported")
+        super().add_param_group(param_group)
 
     def zero_grad(self, set_to_none: bool = False):
         """One memset of the flat gradient buffer; the p.grad views stay (backward accumulates into them).  With
@@ -31,22 +60,82 @@ class FusedAdam(torch.optim.Optimizer):
         if st.grad is not None and st.grad.is_cuda:
             check(lib.zsg_memset_f32(st.grad.data_ptr(), st.grad.numel(), 0.0, stream_ptr()), "zero_grad")
 
+    # ---- which parameters a step updates ------------------------------------------------------------------------------
+    def _stepped(self):
+        """(parameter index, group index) of every parameter this step updates, in flat order, or None when that is ALL of them in one
+        group (the single-launch path)."""
+        groups = self.param_groups
+        if len(groups) == 1 and len(groups[0]["params"]) == len(self._index):
+            if all(p.grad is not None for p in groups[0]["params"]):
+                return None
+        idx = self._index
+        return tuple(sorted((idx[id(p)], gi) for gi, g in enumerate(groups) for p in g["params"] if p.grad is not None))
+
+    def _segment_table(self, key):
+        """device segment table of zsg_adam_step_segments for `key` (rebuilt only when the stepped set or the groups change)"""
+        if key == self._seg_key:
+            return
+        ents, names = self.net.store.entries, self.net._param_names
+        segs = (AdamSeg * max(1, len(key)))()
+        chunk = 0
+        for k, (i, gi) in enumerate(key):
+            e = ents[names[i]]
+            n = (e.size + 3) // 4 * 4                   # the store pads every parameter to 4 floats: step the padding as the full launch does
+            assert e.offset % 4 == 0 and e.offset + n <= self.net.store.flat.numel()
+            segs[k] = AdamSeg(e.offset, n, gi, i, chunk, 0)
+            chunk += (n + ADAM_CHUNK - 1) // ADAM_CHUNK
+        blob = bytes(segs)[:C.sizeof(AdamSeg) * len(key)]
+        self._seg_tab = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(self.net.store.flat.device) if key else None
+        self._seg_key, self._nchunks = key, chunk
+
     @torch.no_grad()
     def step(self, closure=None):
-        g = self.param_groups[0]
         st = self.net.store
         self.net.join_weight_readers()          # (a forward without backward may still be reading the weights on the side stream)
-        hp = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(self.grad_scale))
-        check(lib.zsg_adam_step(st.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), st.flat.numel(), *hp,
-                                self.step_count.data_ptr(), stream_ptr()), "zsg_adam_step")
+        sel = self._stepped()
+        if sel is None and self._seg and self._uniform:
+            # every parameter has taken the same number of steps again: back to the single counter
+            self._step2[0].copy_(self._pcount[0])
+            self._pcount.zero_()
+            self._seg = False
+        if sel is None and not self._seg:
+            g = self.param_groups[0]
+            hp = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(self.grad_scale))
+            check(lib.zsg_adam_step(st.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), st.flat.numel(), *hp,
+                                    self.step_count.data_ptr(), stream_ptr()), "zsg_adam_step")
+            return
+        if sel is None:
+            sel = tuple((i, 0) for i in range(len(self._index)))
+        if not self._seg:                        # the counts move to the per-parameter counters
+            n = len(self._index)
+            self._pcount[:n].copy_(self._step2[:1].expand(n))
+            self._step2[0].zero_()
+            self._seg, self._uniform = True, True
+        if len(sel) < len(self._index):
+            self._uniform = False
+        self._segment_table(sel)
+        if not sel:
+            return
+        gt = (AdamGroup * len(self.param_groups))(*[AdamGroup(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                                                              float(g["weight_decay"])) for g in self.param_groups])
+        n = len(self._index)
+        check(lib.zsg_adam_step_segments(st.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self._seg_tab.data_ptr(),
+                                         len(sel), self._nchunks, gt, len(self.param_groups), float(self.grad_scale),
+                                         self._pcount.data_ptr(), self._pcount[n:].data_ptr(), stream_ptr()), "zsg_adam_step_segments")
+
+    def param_steps(self) -> torch.Tensor:
+        """steps taken by every parameter, in flat order (torch.optim.Adam's state[p]['step'])"""
+        n = len(self._index)
+        return (self._pcount[:n] if self._seg else self._step2[:1].expand(n)).clone()
 
     def state_dict(self):
         d = super().state_dict()
-        d["zsg"] = dict(m=self.m, v=self.v, step=self.step_count)
+        d["zsg"] = dict(m=self.m, v=self.v, step=self.step_count, steps=self.param_steps())
         return d
 
     def load_state_dict(self, sd):
-        """Restores the moments / step counter AND the param_groups (lr as left by the scheduler, betas, eps, weight decay).
+        """Restores the moments / step counters AND the param_groups (lr as left by the scheduler, betas, eps, weight decay).
+        A state saved before per-parameter counters existed (one 'step') gives its count to every parameter.
         A plain torch.optim.Adam state dict (a reference checkpoint) has per-parameter OIHW moments that do not map onto
         the flat OHWI buffer: refuse it loudly instead of silently restarting the moments."""
         z = sd.get("zsg")
@@ -55,8 +144,19 @@ class FusedAdam(torch.optim.Optimizer):
                              "state of the reference cannot be mapped onto the flat parameter buffer); resume with load_opt=False")
         self.m.copy_(z["m"])
         self.v.copy_(z["v"])
-        self.step_count.copy_(z["step"].to(self.step_count.dtype))
-        for g, gs in zip(self.param_groups, sd.get("param_groups", [])):
+        steps = z.get("steps")
+        n = len(self._index)
+        self._pcount.zero_()
+        if steps is not None and steps.numel() == n and bool((steps != steps.reshape(-1)[0]).any()):
+            self._pcount[:n].copy_(steps.to(self._pcount.dtype))
+            self._step2.zero_()
+            self._seg, self._uniform = True, False
+        else:
+            cnt = z["step"] if steps is None or steps.numel() != n else steps.reshape(-1)[:1]
+            self.step_count.copy_(cnt.to(self.step_count.dtype))
+            self._seg, self._uniform = False, True
+        saved = sd.get("param_groups", [])
+        for g, gs in zip(self.param_groups, saved):
             for k in ("lr", "betas", "eps", "weight_decay"):
                 if k in gs:
                     g[k] = gs[k]

@@ -47,8 +47,13 @@ class Learner:
             self.load_model_dict(cfg["resume_path"] or str(self.model_file), cfg["load_opt"])
 
     # ---- optimizer / scheduler (utils.py:667-691) ----------------------------------------------------------------
-    def prepare_optimizer(self, lr: float):
-        self.optimizer = self.opt_fn(self.mdl, lr=lr)
+    def prepare_optimizer(self, lr: float, params=None):
+        """params (utils.py:666-671): the parameters to optimise — an iterable of the model's parameters or torch.optim group dicts —
+        handed to opt_fn as params=; None optimises every parameter (opt_fn is called as before)."""
+        if params is None:
+            self.optimizer = self.opt_fn(self.mdl, lr=lr)
+        else:
+            self.optimizer = self.opt_fn(self.mdl, lr=lr, params=params)
         if self.cfg["use_reduce_lr_plateau"]:     # reference steps it with val accuracy in the default mode='min'
             self.lr_scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, factor=self.cfg["reduce_factor"],
                                                                            patience=self.cfg["patience"])
