@@ -285,6 +285,24 @@ int zsg_bn_backward(const float* dout, const float* relu_out, const uint8_t* rel
  * as finalised by zsg_conv_igemm_bnb_tail / zsg_conv_wino_bnb_tail (native_batch_norm_backward's input-gradient formula). */
 int zsg_bn_bwd_apply(const float* dout, const uint8_t* relu_mask, const float* x, int64_t rows, int32_t C, const float* mean,
                      const float* invstd, const float* gamma, const float* coef, float* dx, float* g_out, void* stream);
+/* Frozen (eval-mode) BatchNorm inside a training network: the backward of F.batch_norm(training=False) with mean = running_mean and
+ * invstd = rsqrt(running_var + eps) (zsg_bn_eval_stats).  g = dout * relu-bit (relu_mask, or NULL: g = dout);  dx = gamma*invstd*g
+ * (no mean-subtraction terms; NULL: the input needs no gradient);  optional g_out = g (gradient of the residual branch);
+ * dgamma = sum g*xhat, dbeta = sum g (each NULL to skip: frozen affine), ACCUMULATED (+=) when accumulate != 0, else overwritten.
+ * partials (optional): the [chunks][2][C] (sum g, sum g*xhat) rows a *_bnb data gradient wrote for the same mean / invstd; then x is
+ * not read and ws >= 2*C floats.  Without partials the one pass over dout / x also reduces the sums: ws >= zsg_bn_workspace_bytes(rows, C).
+ * The sums are reduced in a fixed order (fp64 finalize): deterministic.  With dgamma and dbeta both NULL the launch is a pure
+ * per-channel scale that never reads x or mean (ws unused). */
+int zsg_bn_frozen_backward(const float* dout, const uint8_t* relu_mask, const float* x, int64_t rows, int32_t C, const float* mean,
+                           const float* invstd, const float* gamma, float* dx, float* g_out, float* dgamma, float* dbeta,
+                           int32_t accumulate, const float* partials, int32_t chunks, void* ws, size_t ws_bytes, void* stream);
+/* Frozen counterpart of zsg_bn_relu_maxpool_bwd (forward: zsg_bn_relu_maxpool_fwd fed the eval statistics): one pass per INPUT
+ * pixel gathers d(out) at the window positions idx selected, masks it by relu(bn(x)) > 0 and writes dx = gamma*invstd*g (NULL: no
+ * input gradient); dgamma / dbeta as zsg_bn_frozen_backward (NULL to skip; then ws is unused), else ws >= zsg_bn_workspace_bytes(B*H*W, C). */
+int zsg_bn_frozen_relu_maxpool_bwd(const float* dout, const uint8_t* idx, const float* x, int32_t B, int32_t H, int32_t W, int32_t C,
+                                   const float* mean, const float* invstd, const float* gamma, const float* beta, int32_t k, int32_t s,
+                                   int32_t p, int32_t Ho, int32_t Wo, float* dx, float* dgamma, float* dbeta, int32_t accumulate,
+                                   void* ws, size_t ws_bytes, void* stream);
 /* The same from the partial rows [chunks][2][C] of zsg_conv_igemm_bnb / zsg_conv_wino_bnb (finalize + apply: one pass over
  * dout and x instead of two).  ws: >= 2*C floats. */
 int zsg_bn_backward_from_partials(const float* dout, const uint8_t* relu_mask, const float* x, int64_t rows, int32_t C,

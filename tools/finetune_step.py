@@ -5,6 +5,10 @@ batch.  Prints one JSON object: per variant the median ms per step over the roun
 count and the number of stepped parameters.
 
     python tools/finetune_step.py [--rounds 5] [--steps 10] [--warmup 3] [--out profiles/finetune_step.json]
+    python tools/finetune_step.py --frozen-bn [--out profiles/finetune_step_frozen_bn.json]
+
+--frozen-bn measures every BatchNorm layer frozen (ZSGNet.freeze_batchnorm) against train-mode BatchNorm, with everything trainable
+and with the encoder's parameters frozen.
 """
 import argparse
 import json
@@ -25,6 +29,13 @@ VARIANTS = {
     "encoder_frozen": (ENC,),
     "encoder_lstm_frozen": (ENC, "lstm."),
 }
+# (frozen parameter prefixes, every BatchNorm layer in eval mode)
+BN_VARIANTS = {
+    "all_trainable": ((), False),
+    "all_trainable_bn_frozen": ((), True),
+    "encoder_frozen": ((ENC,), False),
+    "encoder_frozen_bn_frozen": ((ENC,), True),
+}
 
 
 def main():
@@ -34,6 +45,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--bs", type=int, default=16)
     ap.add_argument("--out", default="")
+    ap.add_argument("--frozen-bn", action="store_true")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     cfg = config.get_cfg()
@@ -43,7 +55,8 @@ def main():
     bt["h0"], bt["c0"] = torch.zeros(2, a.bs, 128), torch.zeros(2, a.bs, 128)
     sd = None
     runs = {}
-    for name, prefixes in VARIANTS.items():
+    variants = BN_VARIANTS if a.frozen_bn else {k: (v, False) for k, v in VARIANTS.items()}
+    for name, (prefixes, bn_frozen) in variants.items():
         net = mdl.get_default_net(9, cfg)
         if sd is None:
             sd = {k: v.clone() for k, v in net.state_dict().items()}
@@ -51,6 +64,8 @@ def main():
         net.to("cuda").train()
         for n, p in net.named_parameters():
             p.requires_grad_(not (prefixes and n.startswith(prefixes)))
+        if bn_frozen:
+            net.freeze_batchnorm()
         runs[name] = dict(net=net, opt=optim.FusedAdam(net, lr=1e-4, betas=(0.9, 0.99)), ms=[])
 
     def step(v):
@@ -81,7 +96,8 @@ def main():
         res["variants"][name] = dict(ms_per_step=round(statistics.median(v["ms"]), 4), round_medians=[round(x, 4) for x in v["ms"]],
                                      bwd_launches=len(plan.bwd.calls), prep_launches=len(plan.prep.calls),
                                      stepped_params=sum(p.numel() for p in net.parameters() if p.grad is not None),
-                                     frozen_tensors=sum(1 for p in net.parameters() if not p.requires_grad))
+                                     frozen_tensors=sum(1 for p in net.parameters() if not p.requires_grad),
+                                     frozen_bn_layers=len(net._frozen_bn_key()))
     js = json.dumps(res, indent=1)
     print(js)
     if a.out:

@@ -82,6 +82,8 @@ SIGNATURES = {
     "zsg_bn_bwd_apply": (I32, [P, P, P, I64, I32, P, P, P, P, P, P, P]),
     "zsg_conv_wino_bnb": (I32, [DP, P, P, P, P, P, P, P, P, P, P]),
     "zsg_bn_backward_from_partials": (I32, [P, P, P, I64, I32, P, P, P, P, P, P, P, I32, P, I32, P, SZ, P]),
+    "zsg_bn_frozen_backward": (I32, [P, P, P, I64, I32, P, P, P, P, P, P, P, I32, P, I32, P, SZ, P]),
+    "zsg_bn_frozen_relu_maxpool_bwd": (I32, [P, P, P, I32, I32, I32, I32, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, I32, P, SZ, P]),
     "zsg_wino_u_elems": (I64, [I32, I32]),
     "zsg_wino_weights": (I32, [P, I32, I32, P]),
     "zsg_conv_wgrad_workspace_bytes": (SZ, [DP]),

@@ -787,3 +787,202 @@ extern "C" int zsg_bn_backward(const float* dout, const float* relu_out, const u
     ZSG_CHECK_LAUNCH("bn_backward");
     return 0;
 }
+
+// ---- frozen (eval-mode) BatchNorm inside a training network -----------------------------------------------------------------
+// F.batch_norm(training=False) with mean = running_mean, invstd = rsqrt(running_var + eps) (zsg_bn_eval_stats): the input gradient
+// has no mean-subtraction terms, dx = gamma * invstd * g, so it needs none of the per-channel sums and ONE pass writes dx / g_out.
+// d(gamma) = sum g * xhat and d(beta) = sum g, when wanted, come from the same pass as partial rows [chunks][2][C] (fixed per-block
+// order) reduced by bn_bwd_finalize_kernel (fp64, fixed order: deterministic), or from a data gradient's *_bnb epilogue.
+// SUMS: this pass also reduces (sum g, sum g * xhat) per block (reads x); else x is never read.
+template <bool SUMS>
+__global__ __launch_bounds__(256) void bn_frozen_bwd_kernel(const float* __restrict__ dout, const uint8_t* __restrict__ relu_mask,
+                                                            const float* __restrict__ x, int64_t rows, int C, const float* __restrict__ mean,
+                                                            const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                            float* __restrict__ dx, float* __restrict__ g_out, int lanes, int rpb,
+                                                            float* __restrict__ part) {
+    ZSG_SET_MAIN_PRIO();
+    __shared__ f32x4 red[SUMS ? 2 : 1][SUMS ? 256 : 1];
+    const int rowlanes = 256 / lanes;
+    const int l = threadIdx.x % lanes, rl = threadIdx.x / lanes;
+    const int c = (blockIdx.y * lanes + l) * 4;
+    const bool cok = c < C;
+    if (!SUMS && !cok) return;
+    const int64_t r_begin = (int64_t)blockIdx.x * rpb;
+    const int64_t r_end = min(rows, r_begin + (int64_t)rpb);
+    f32x4 s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0};
+    if (cok) {
+        const f32x4 is = *(const f32x4*)(invstd + c);
+        const f32x4 sc = is * *(const f32x4*)(gamma + c);
+        f32x4 mu = {0, 0, 0, 0};
+        if (SUMS) mu = *(const f32x4*)(mean + c);
+        for (int64_t r = r_begin + rl; r < r_end; r += rowlanes) {
+            f32x4 g = *(const f32x4*)(dout + r * C + c);
+            if (relu_mask) {
+                const unsigned m = relu_mask[(r * C + c) >> 2];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) g[e] = ((m >> e) & 1u) ? g[e] : 0.f;
+            }
+            if (g_out) *(f32x4*)(g_out + r * C + c) = g;
+            if (dx) *(f32x4*)(dx + r * C + c) = sc * g;
+            if (SUMS) {
+                s0 += g;
+                s1 += g * ((*(const f32x4*)(x + r * C + c) - mu) * is);
+            }
+        }
+    }
+    if (SUMS) {
+        red[0][threadIdx.x] = s0;
+        red[1][threadIdx.x] = s1;
+        __syncthreads();
+        if (rl == 0 && cok) {
+            for (int k = 1; k < rowlanes; ++k) {
+                s0 += red[0][k * lanes + l];
+                s1 += red[1][k * lanes + l];
+            }
+            float* o = part + (size_t)blockIdx.x * 2 * C;
+            *(f32x4*)(o + c) = s0;
+            *(f32x4*)(o + C + c) = s1;
+        }
+    }
+}
+
+extern "C" int zsg_bn_frozen_backward(const float* dout, const uint8_t* relu_mask, const float* x, int64_t rows, int32_t C, const float* mean,
+                                      const float* invstd, const float* gamma, float* dx, float* g_out, float* dgamma, float* dbeta,
+                                      int32_t accumulate, const float* partials, int32_t chunks, void* ws, size_t ws_bytes, void* stream) {
+    const bool sums = dgamma || dbeta;
+    ZSG_REQUIRE(dout && invstd && gamma && rows > 0 && C > 0 && (C % 4) == 0 && (!partials || chunks > 0) &&
+                    (!sums || (ws && (partials || (x && mean)))),
+                "bn_frozen_backward: bad argument");
+    BnGeom g = bn_geom(rows, C);
+    hipStream_t st = (hipStream_t)stream;
+    const bool own = sums && !partials;         // this pass reduces the sums itself (reads x)
+    if (sums && ws_bytes < (own ? zsg_bn_workspace_bytes(rows, C) : 2 * (size_t)C * sizeof(float)))
+        ZSG_FAIL(-2, "bn_frozen_backward: workspace too small");
+    ZSG_PROF("bn_backward", st, 0, (double)rows * C * (4 * (1 + (own ? 1 : 0) + (dx ? 1 : 0) + (g_out ? 1 : 0)) + (relu_mask ? 0.25 : 0)));
+    float* part = (float*)ws;
+    if (own) {
+        ZSG_LAUNCH(bn_frozen_bwd_kernel<true>, dim3(g.chunks, g.slabs), dim3(256), 0, st, dout, relu_mask, x, rows, C, mean, invstd, gamma, dx,
+                           g_out, g.lanes, g.rpb, part);
+        ZSG_LAUNCH(bn_bwd_finalize_kernel, dim3(C / 4), dim3(64 * BN_FW), 0, st, part, g.chunks, C, rows, part + (size_t)g.chunks * 2 * C,
+                           dgamma, dbeta, accumulate);
+    } else {
+        if (dx || g_out)
+            ZSG_LAUNCH(bn_frozen_bwd_kernel<false>, dim3(g.chunks, g.slabs), dim3(256), 0, st, dout, relu_mask, x, rows, C, mean, invstd, gamma,
+                               dx, g_out, g.lanes, g.rpb, (float*)nullptr);
+        if (sums)      // (coefficients into ws[0, 2C): unused, the finalize kernel writes them)
+            ZSG_LAUNCH(bn_bwd_finalize_kernel, dim3(C / 4), dim3(64 * BN_FW), 0, st, partials, chunks, C, rows, (float*)ws, dgamma, dbeta,
+                               accumulate);
+    }
+    ZSG_CHECK_LAUNCH("bn_frozen_backward");
+    return 0;
+}
+
+// Stem, frozen: d(x) of maxpool(relu(bn_eval(x))) per INPUT pixel in one pass — g gathered from the windows that contain the pixel (the
+// order of bn_pool_bwd_apply_kernel), masked by relu(bn(x)) > 0 (bn_pool_val: the forward's bits), dx = gamma * invstd * g;
+// SUMS: the block's (sum g, sum g * xhat) partial row, as bn_frozen_bwd_kernel.
+template <bool SUMS>
+__global__ __launch_bounds__(256) void bn_frozen_pool_bwd_kernel(const float* __restrict__ dout, const uint8_t* __restrict__ idx,
+                                                                 const float* __restrict__ x, int H, int W, int C, int k, int s, int p, int Ho,
+                                                                 int Wo, const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta, int64_t rows,
+                                                                 float* __restrict__ dx, int lanes, int rpb, float* __restrict__ part) {
+    ZSG_SET_MAIN_PRIO();
+    __shared__ f32x4 red[SUMS ? 2 : 1][SUMS ? 256 : 1];
+    const int rowlanes = 256 / lanes;
+    const int l = threadIdx.x % lanes, rl = threadIdx.x / lanes;
+    const int c = (blockIdx.y * lanes + l) * 4;
+    const bool cok = c < C;
+    if (!SUMS && !cok) return;
+    const int64_t r_begin = (int64_t)blockIdx.x * rpb;
+    const int64_t r_end = min(rows, r_begin + (int64_t)rpb);
+    f32x4 s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0};
+    if (cok) {
+        const f32x4 mu = *(const f32x4*)(mean + c), is = *(const f32x4*)(invstd + c);
+        const f32x4 sc = is * *(const f32x4*)(gamma + c), be = *(const f32x4*)(beta + c);
+        int64_t r = r_begin + rl;
+        int wi = (int)(r % W);
+        int64_t t0 = r / W;
+        int hi = (int)(t0 % H);
+        int64_t b = t0 / H;
+        const bool s2 = s == 2;
+        for (; r < r_end; r += rowlanes) {
+            const f32x4 xv = *(const f32x4*)(x + r * C + c);
+            const f32x4 v = bn_pool_val(xv, mu, sc, be);
+            f32x4 g = {0, 0, 0, 0};
+            const int hn0 = hi + p, wn0 = wi + p;
+            const int ho_hi = min(s2 ? (hn0 >> 1) : hn0 / s, Ho - 1), wo_hi = min(s2 ? (wn0 >> 1) : wn0 / s, Wo - 1);
+            const int hlo = hn0 - k + s, wlo = wn0 - k + s;
+            const int ho_lo = (hn0 - k + 1 <= 0) ? 0 : (s2 ? (hlo >> 1) : hlo / s), wo_lo = (wn0 - k + 1 <= 0) ? 0 : (s2 ? (wlo >> 1) : wlo / s);
+            for (int ho = ho_hi; ho >= ho_lo; --ho) {
+                const int rr = hn0 - ho * s;
+                for (int wo = wo_hi; wo >= wo_lo; --wo) {
+                    const int64_t o = ((b * Ho + ho) * Wo + wo) * C + c;
+                    const uchar4 u = *(const uchar4*)(idx + o);
+                    const f32x4 d = *(const f32x4*)(dout + o);
+                    const unsigned code = rr * k + (wn0 - wo * s);
+                    g[0] += (u.x == code) ? d[0] : 0.f;
+                    g[1] += (u.y == code) ? d[1] : 0.f;
+                    g[2] += (u.z == code) ? d[2] : 0.f;
+                    g[3] += (u.w == code) ? d[3] : 0.f;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) g[e] = v[e] > 0.f ? g[e] : 0.f;
+            if (dx) *(f32x4*)(dx + r * C + c) = sc * g;
+            if (SUMS) {
+                s0 += g;
+                s1 += g * ((xv - mu) * is);
+            }
+            wi += rowlanes;
+            while (wi >= W) {
+                wi -= W;
+                if (++hi == H) {
+                    hi = 0;
+                    ++b;
+                }
+            }
+        }
+    }
+    if (SUMS) {
+        red[0][threadIdx.x] = s0;
+        red[1][threadIdx.x] = s1;
+        __syncthreads();
+        if (rl == 0 && cok) {
+            for (int kk = 1; kk < rowlanes; ++kk) {
+                s0 += red[0][kk * lanes + l];
+                s1 += red[1][kk * lanes + l];
+            }
+            float* o = part + (size_t)blockIdx.x * 2 * C;
+            *(f32x4*)(o + c) = s0;
+            *(f32x4*)(o + C + c) = s1;
+        }
+    }
+}
+
+// ws: >= zsg_bn_workspace_bytes(B * H * W, C) when dgamma or dbeta is given (unused otherwise)
+extern "C" int zsg_bn_frozen_relu_maxpool_bwd(const float* dout, const uint8_t* idx, const float* x, int32_t B, int32_t H, int32_t W, int32_t C,
+                                              const float* mean, const float* invstd, const float* gamma, const float* beta, int32_t k,
+                                              int32_t s, int32_t p, int32_t Ho, int32_t Wo, float* dx, float* dgamma, float* dbeta,
+                                              int32_t accumulate, void* ws, size_t ws_bytes, void* stream) {
+    const bool sums = dgamma || dbeta;
+    ZSG_REQUIRE(dout && idx && x && mean && invstd && gamma && beta && (dx || sums) && (!sums || ws) && B > 0 && H > 0 && W > 0 && Ho > 0 &&
+                    Wo > 0 && C > 0 && (C % 4) == 0 && k > 0 && k <= 15 && s > 0,
+                "bn_frozen_relu_maxpool_bwd: bad argument");
+    const int64_t prow = (int64_t)B * Ho * Wo, rows = (int64_t)B * H * W;
+    if (sums && ws_bytes < zsg_bn_workspace_bytes(rows, C)) ZSG_FAIL(-2, "bn_frozen_relu_maxpool_bwd: workspace too small");
+    const BnGeom g = bn_geom(rows, C);
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("bn_backward", st, 0, ((double)prow * 1.25 + (double)rows * (dx ? 2 : 1)) * C * 4);
+    float* part = (float*)ws;
+    if (sums) {
+        ZSG_LAUNCH(bn_frozen_pool_bwd_kernel<true>, dim3(g.chunks, g.slabs), dim3(256), 0, st, dout, idx, x, H, W, C, k, s, p, Ho, Wo, mean,
+                           invstd, gamma, beta, rows, dx, g.lanes, g.rpb, part);
+        ZSG_LAUNCH(bn_bwd_finalize_kernel, dim3(C / 4), dim3(64 * BN_FW), 0, st, part, g.chunks, C, rows, part + (size_t)g.chunks * 2 * C,
+                           dgamma, dbeta, accumulate);
+    } else {
+        ZSG_LAUNCH(bn_frozen_pool_bwd_kernel<false>, dim3(g.chunks, g.slabs), dim3(256), 0, st, dout, idx, x, H, W, C, k, s, p, Ho, Wo, mean,
+                           invstd, gamma, beta, rows, dx, g.lanes, g.rpb, (float*)nullptr);
+    }
+    ZSG_CHECK_LAUNCH("bn_frozen_relu_maxpool_bwd");
+    return 0;
+}

@@ -261,6 +261,8 @@ class DistributedDataParallel(nn.Module):
         from . import ops
         geo = self.module.plan_geometry(inp)
         key = tuple(geo[:3]) + (self.module.training,)
+        if self.module.training and hasattr(self.module, "_frozen_bn_key"):
+            key += (self.module._frozen_bn_key(),)       # (frozen BatchNorm layers lower other launches: tuned anew, broadcast anew)
         if key in self._tuned:
             return
         self._tuned.add(key)

@@ -133,6 +133,7 @@ class ZSGNet(nn.Module):
         self.reset_parameters()
         self._plans: Dict[Tuple, "_Plan"] = {}
         self._anchor = None
+        self._bn_eval = set()          # BatchNorm layers freeze_batchnorm() keeps in eval mode across train()
         self.debug = False
 
     # ------------------------------------------------------------------------------------------------------
@@ -419,21 +420,64 @@ class ZSGNet(nn.Module):
         """flat-order indices of the parameters with requires_grad=False (the training plans are lowered for one trainable set)"""
         return tuple(i for i, p in enumerate(self._ordered_params()) if not p.requires_grad)
 
+    def batchnorm_modules(self):
+        """(name, module) of every BatchNorm layer, in running-statistics order.  The layers are plain NamedTree nodes that carry the
+        reference's names and parameters (isinstance(m, nn.BatchNorm2d) does not find them); their `.training` flag decides, inside a
+        training network, whether the layer normalises with batch statistics or is frozen (see _frozen_bn_key)."""
+        if getattr(self, "_bn_mods", None) is None:
+            mods = dict(self.named_modules())
+            self._bn_mods = [(name, mods[name]) for name in self.bns]
+        return iter(self._bn_mods)
+
+    def freeze_batchnorm(self, prefixes=("",), freeze: bool = True) -> List[str]:
+        """Puts the BatchNorm layers whose names start with one of `prefixes` in eval mode (freeze=True) and remembers them, so that
+        train() keeps them there (mmdet's norm_eval); freeze=False returns them to the root's mode and forgets them.  A frozen layer of a
+        training network normalises with its running statistics, leaves them and num_batches_tracked unchanged and back-propagates
+        F.batch_norm(training=False)'s gradient.  Returns the names that matched."""
+        if isinstance(prefixes, str):
+            prefixes = (prefixes,)
+        names = []
+        for name, m in self.batchnorm_modules():
+            if any(name.startswith(p) for p in prefixes):
+                names.append(name)
+                if freeze:
+                    self._bn_eval.add(name)
+                    m.train(False)
+                else:
+                    self._bn_eval.discard(name)
+                    m.train(self.training)
+        return names
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        if mode and self._bn_eval:
+            for name, m in self.batchnorm_modules():
+                if name in self._bn_eval:
+                    m.train(False)
+        return self
+
+    def _frozen_bn_key(self) -> Tuple[int, ...]:
+        """running-statistics order indices of the BatchNorm layers in eval mode (frozen inside a training network)"""
+        return tuple(i for i, (_, m) in enumerate(self.batchnorm_modules()) if not m.training)
+
     def _plan_for(self, B, H, W, T) -> "_Plan":
         if not self.training:
             key = (B, H, W, T, False)
             if key not in self._plans:
                 self._plans[key] = _Plan(self, B, H, W, T, False)
             return self._plans[key]
-        fz = self._frozen_key()
-        key = (B, H, W, T, fz, True)
+        fz, fb = self._frozen_key(), self._frozen_bn_key()
+        key = (B, H, W, T, fz, fb, True)
         if key not in self._plans:
-            # a new trainable set: the training plans of the old one go (gradual unfreezing must not pile up activation buffers)
-            for k in [k for k in self._plans if k[-1] and k[4] != fz]:
+            # a new trainable set or frozen-BatchNorm set: the training plans of the old one go (gradual unfreezing must not pile up
+            # activation buffers)
+            for k in [k for k in self._plans if k[-1] and (k[4], k[5]) != (fz, fb)]:
                 old = self._plans.pop(k)
                 if old._prep_pending:           # (its side-stream weight preparation may still be reading the weights)
                     torch.cuda.current_stream().wait_event(old._prep_ev)
-            self._plans[key] = _Plan(self, B, H, W, T, True, frozen={self._param_names[i] for i in fz})
+            bn_names = list(self.bns)
+            self._plans[key] = _Plan(self, B, H, W, T, True, frozen={self._param_names[i] for i in fz},
+                                     frozen_bn={bn_names[i] for i in fb})
         return self._plans[key]
 
     def forward(self, inp: Dict[str, Any]) -> Dict[str, Any]:
@@ -486,8 +530,16 @@ class _NetFn(torch.autograd.Function):
 class _Plan:
     """Static lowering of ZSGNet for one (B, H, W, T, training) geometry."""
 
-    def __init__(self, net: ZSGNet, B: int, H: int, W: int, T: int, training: bool, frozen=frozenset()):
+    def __init__(self, net: ZSGNet, B: int, H: int, W: int, T: int, training: bool, frozen=frozenset(), frozen_bn=frozenset()):
         self.net, self.B, self.H, self.W, self.T, self.training = net, B, H, W, T, training
+        # BatchNorm layers in eval mode inside this training network: running statistics in the forward (one zsg_bn_eval_stats launch),
+        # no statistics update, F.batch_norm(training=False)'s backward (zsg_bn_frozen_backward / zsg_bn_frozen_relu_maxpool_bwd)
+        self.frozen_bn = frozenset(frozen_bn) if training else frozenset()
+        self._ev_stats = None
+        # which backward form each frozen layer got (_bn_frozen_back): 'bnb+fin' / 'bnb' (sums from the data gradient's epilogue, with or
+        # without its in-kernel finalize), 'onepass' (zsg_bn_frozen_backward reduces them), 'scale' (no sums: frozen affine); '+alias' when
+        # the residual's gradient aliases dout
+        self.frozen_bn_paths: Dict[str, str] = {}
         # parameters with requires_grad=False when the plan was lowered: no weight / bias gradient, no data gradient into an activation
         # that no trainable parameter lies upstream of (Act.requires_grad), no p.grad view, no DDP bucket
         self.frozen = frozenset(frozen) if training else frozenset()
@@ -596,6 +648,25 @@ class _Plan:
         """the parameter `name` gets a gradient (it is not frozen)"""
         return name not in self.frozen
 
+    def bn_frozen(self, L: Optional[BnL]) -> bool:
+        """the BatchNorm layer L is in eval mode inside this training plan"""
+        return L is not None and L.name in self.frozen_bn
+
+    def _eval_stats(self, L: BnL):
+        """(mean, invstd) of a frozen BatchNorm layer from its running statistics.  ONE zsg_bn_eval_stats launch over the span of every
+        frozen layer's slots, issued on the main stream where the first frozen layer needs it (a side-stream user waits for it: lane 1
+        waits for everything enqueued on the main stream before it).  The span may include train-mode layers' slots, whose running
+        statistics another launch of this forward may be updating at the same time: the values computed for those slots are never read."""
+        if self._ev_stats is None:
+            bns = [self.net.bns[n] for n in self.frozen_bn]
+            lo, hi = min(b.index for b in bns), max(b.index + b.c for b in bns)
+            self._ev_stats = (self._buf(self.net._rm.numel()), self._buf(self.net._rm.numel()))
+            m, s = self._ev_stats
+            self.fwd.add(lib.zsg_bn_eval_stats, self.net._rm[lo:hi], self.net._rv[lo:hi], hi - lo, 1e-5, m[lo:hi], s[lo:hi],
+                         what="eval stats: frozen BatchNorm", lane=0)
+        m, s = self._ev_stats
+        return m[L.index:L.index + L.c], s[L.index:L.index + L.c]
+
     def P(self, name):      # raw parameter storage
         return self.net.store.raw(name)
 
@@ -668,13 +739,15 @@ class _Plan:
         bias = self.P(L.name + ".bias") if L.bias else None
         rd = src
         ig_fn, wn_fn = lib.zsg_conv_igemm, lib.zsg_conv_wino
+        pend = getattr(src, "pending", None)
+        if self.bn_frozen(bn_fuse) and pend is None:
+            bn_fuse = None                 # a frozen BatchNorm normalises with its running statistics: no fused batch statistics
         # a split-K choice would cost this layer its fused BatchNorm statistics: a statistics pass over the output at
         # ~4 TB/s plus two more dependent launches
         pen = 0.0
         if bn_fuse is not None and self.training and not L.bias and not relu:
             pen = 0.008 + out.rows() * L.cout * 4 / 4e9
         wt = self.P(L.name + ".weight")
-        pend = getattr(src, "pending", None)
         if pend is not None:
             return self._conv_bnpre(L, src, out, d, wt, pend, bn_fuse)
         wargs = None
@@ -765,14 +838,25 @@ class _Plan:
             # lowering must not crash on a table it did not make
             d.tile_hint = tile_hint(64, 64, 1)
         lane = 2 if pend["join"] else self._lane
+        Lb = bn_fuse
+        out.bn_inline = None
+        what = L.name + "+bnpre(" + pend["name"] + ")"
+        if self.bn_frozen(Lb):
+            # (the BatchNorm behind this convolution is frozen: no statistics of the output, the loader still applies the pending one)
+            out.bn_chunks = 0
+            self.fwd.add(fn, d, x.buf, wt, out.buf, None, None, None, None, None, None, 0.1, 1e-5, *pre, what=what, lane=lane)
+            src.pending = None
+            out.needs_mask = False
+            out.requires_grad = self._conv_rg(L, src)
+            completes = self.training and getattr(src, "bn_out", False) and not getattr(src, "_consumed", False)
+            src._consumed = True
+            self.tape.append(lambda: self._conv_bwd(L, src, out, completes_bn=completes))
+            return out
         chunks = igemm_partial_rows(d)
         assert chunks * 2 * L.cout * 4 <= self.ws_bytes
         partials, out.bn_chunks = self._ws_now(), chunks
         tail_n = int(lib.zsg_conv_bn_tail_tickets(_ct.byref(d), 0))
-        Lb = bn_fuse
         rm, rv = self.net._rm[Lb.index:Lb.index + Lb.c], self.net._rv[Lb.index:Lb.index + Lb.c]
-        out.bn_inline = None
-        what = L.name + "+bnpre(" + pend["name"] + ")"
         if tail_n > 0:
             tk = self._buf(tail_n, dtype=torch.int32)
             out.bn_mean, out.bn_invstd = self._buf(Lb.c), self._buf(Lb.c)
@@ -954,13 +1038,18 @@ class _Plan:
         out.requires_grad = (x.requires_grad or self.trains(L.name + ".weight") or self.trains(L.name + ".bias")
                              or (residual is not None and residual.requires_grad))
         rows = x.B * lv.H * lv.W
+        frozen = self.bn_frozen(L)
         fused = self.training and getattr(x, "bn_chunks", 0) > 0
-        mean, invstd = (x.bn_mean, x.bn_invstd) if fused else (self._buf(L.c), self._buf(L.c))
+        assert not (frozen and fused), "a frozen BatchNorm's producer must not compute batch statistics"
+        if frozen:
+            mean, invstd = self._eval_stats(L)
+        else:
+            mean, invstd = (x.bn_mean, x.bn_invstd) if fused else (self._buf(L.c), self._buf(L.c))
         rm, rv = net._rm[L.index:L.index + L.c], net._rv[L.index:L.index + L.c]
         self.ws_need = max(getattr(self, "ws_need", 0), lib.zsg_bn_workspace_bytes(rows, L.c))
         gam, bet = self.P(L.name + ".weight"), self.P(L.name + ".bias")
-        if fused:
-            pass                          # statistics were finalized right after the producing convolution
+        if fused or frozen:
+            pass                          # statistics were finalized right after the producing convolution / are the running ones
         elif self.training:
             self.fwd.add(lib.zsg_bn_stats, x.buf, rows, L.c, mean, invstd, rm, rv, 0.1, 1e-5, self._ws_now(), self.ws_bytes, what=L.name, lane=self._lane)
         else:
@@ -984,6 +1073,9 @@ class _Plan:
 
         def back():
             if out.grad is None:
+                return
+            if frozen:
+                self._bn_frozen_back(L, x, out, residual, relu, rmask, rows, mean, invstd, gam)
                 return
             dx = self.grad_of(x)
             lw = getattr(out.grad, "last_writer", None)
@@ -1043,6 +1135,64 @@ class _Plan:
             dx.gfilled = True
         self.tape.append(back)
         return out
+
+    def _bn_frozen_back(self, L: BnL, x: Act, out: Act, residual: Optional[Act], relu: bool, rmask, rows: int, mean, invstd, gam):
+        """Backward of a frozen BatchNorm [+ residual] [+ ReLU]: dx = gamma * invstd * g with g = dout * relu-bit, d(gamma) / d(beta) for
+        the trainable ones only.  Where they are wanted and the data gradient that completed dout can carry the sums in its epilogue (as in
+        bn()'s back), it does so for the eval statistics, and the residual gradient may alias dout exactly as there."""
+        dx = self.grad_of(x) if x.requires_grad else None
+        dg = self.G(L.name + ".weight") if self.trains(L.name + ".weight") else None
+        db = self.G(L.name + ".bias") if self.trains(L.name + ".bias") else None
+        lw = getattr(out.grad, "last_writer", None)
+        fuse = (BNB_FUSE and (dg is not None or db is not None) and lw is not None and lw[0] == len(self.bwd.calls) - 1
+                and self.bwd.lanes[lw[0]] == 0 and len(out.grad.levels) == 1 and out.grad.levels[0].off == 0 and x.levels[0].off == 0
+                and out.grad.ld == L.c and x.ld == L.c)
+        if fuse:
+            idx, d, a, what = lw
+            chunks = self._wino_chunks(d, x.B) if d.use_wino else igemm_partial_rows(d)
+            fuse = chunks * 2 * L.c * 4 + 2 * L.c * 4 <= self.ws_bytes
+        g_out, bits = None, rmask
+        if residual is not None and residual.requires_grad:
+            alias = (fuse and relu and rmask is not None and residual.grad is None and len(residual.levels) == 1
+                     and residual.levels[0].off == 0 and residual.ld == L.c and residual.C == L.c and residual.buf.numel() == out.grad.buf.numel())
+            if alias:
+                residual.grad = out.grad
+                lw[1].epi_flags |= 1
+                bits = None
+            else:
+                rg = self.grad_of(residual)
+                assert not rg.gfilled, "residual gradient must be produced first (tape order)"
+                g_out = rg.buf
+                rg.gfilled = True
+        dout = self.base(out.grad)
+        dxb = dx.buf if dx is not None else None
+        what_b = "bnbwd(frozen):" + L.name
+        path = "onepass" if (dg is not None or db is not None) else "scale"
+        if fuse:
+            part = self.ws[2 * L.c:]
+            assert a[3] is None and a[5] is None and a[6] is None
+            tail_n = int(lib.zsg_conv_bn_tail_tickets(_ct.byref(d), 1 if d.use_wino else 0))
+            path = "bnb+fin" if tail_n > 0 else "bnb"
+            if tail_n > 0:
+                # the data gradient's last tile per column block writes d(gamma) / d(beta) for the eval statistics: a pure scale is left
+                fn = lib.zsg_conv_wino_bnb_tail if d.use_wino else lib.zsg_conv_igemm_bnb_tail
+                tk, coef = self._buf(tail_n, dtype=torch.int32), self._buf(2 * L.c)
+                self.bwd.calls[idx] = (fn, marshal(fn, (d, a[0], a[1], a[2], a[4], x.buf, mean, invstd, rmask, part, tk, coef, dg, db, 1),
+                                                   self.bwd.keep), what + "+bnb+fin")
+                if dxb is not None or g_out is not None:
+                    self.bwd.add(lib.zsg_bn_frozen_backward, dout, bits, None, rows, L.c, None, invstd, gam, dxb, g_out, None, None, 0,
+                                 None, 0, None, 0, what=what_b)
+            else:
+                fn = lib.zsg_conv_wino_bnb if d.use_wino else lib.zsg_conv_igemm_bnb
+                self.bwd.calls[idx] = (fn, marshal(fn, (d, a[0], a[1], a[2], a[4], x.buf, mean, invstd, rmask, part), self.bwd.keep), what + "+bnb")
+                self.bwd.add(lib.zsg_bn_frozen_backward, dout, bits, x.buf, rows, L.c, mean, invstd, gam, dxb, g_out, dg, db, 1, part, chunks,
+                             self.ws, self.ws_bytes, what=what_b)
+        elif dxb is not None or g_out is not None or dg is not None or db is not None:
+            self.bwd.add(lib.zsg_bn_frozen_backward, dout, rmask, x.buf, rows, L.c, mean, invstd, gam, dxb, g_out, dg, db, 1, None, 0,
+                         self.ws, self.ws_bytes, what=what_b)
+        self.frozen_bn_paths[L.name] = path + ("+alias" if bits is None and rmask is not None else "")
+        if dx is not None:
+            dx.gfilled = True
 
     # ---- the network ---------------------------------------------------------------------------------------------------
     def _lower(self):
@@ -1242,7 +1392,10 @@ class _Plan:
         rm, rv = net._rm[Lb.index:Lb.index + Lb.c], net._rv[Lb.index:Lb.index + Lb.c]
         gam, bet = self.P(Lb.name + ".weight"), self.P(Lb.name + ".bias")
         self.ws_need = max(getattr(self, "ws_need", 0), lib.zsg_bn_workspace_bytes(rows, Lb.c))
-        if getattr(y, "bn_chunks", 0) > 0:
+        frozen = self.bn_frozen(Lb)
+        if frozen:
+            mean, invstd = self._eval_stats(Lb)         # (conv() computed no statistics: the forward pass runs on the running ones)
+        elif getattr(y, "bn_chunks", 0) > 0:
             mean, invstd = y.bn_mean, y.bn_invstd
             if y.bn_inline is not None:          # few partial rows (small inputs): nobody else will finalize them
                 self.fwd.add(lib.zsg_bn_stats_from_partials, y.bn_inline, y.bn_chunks, rows, Lb.c, mean, invstd, rm, rv, 0.1, 1e-5, what="stats:" + Lb.name)
@@ -1256,6 +1409,18 @@ class _Plan:
 
         def back():
             if x.grad is None:
+                return
+            if frozen:
+                dy = self.grad_of(y) if y.requires_grad else None
+                dg = self.G(Lb.name + ".weight") if self.trains(Lb.name + ".weight") else None
+                db = self.G(Lb.name + ".bias") if self.trains(Lb.name + ".bias") else None
+                if dy is None and dg is None and db is None:
+                    return
+                self.bwd.add(lib.zsg_bn_frozen_relu_maxpool_bwd, self.base(x.grad), idx, y.buf, B, H1, W1, Lb.c, mean, invstd, gam, bet, 3, 2, 1,
+                             H2, W2, dy.buf if dy is not None else None, dg, db, 1, self.ws, self.ws_bytes, what="bnbwd(frozen)+maxpool_bwd:" + Lb.name)
+                self.frozen_bn_paths[Lb.name] = "stem" + ("" if dg is None and db is None else "+sums")
+                if dy is not None:
+                    dy.gfilled = True
                 return
             dy = self.grad_of(y)
             self.bwd.add(lib.zsg_bn_relu_maxpool_bwd, self.base(x.grad), idx, y.buf, B, H1, W1, Lb.c, mean, invstd, gam, bet, 3, 2, 1, H2, W2, dy.buf,
@@ -1818,7 +1983,7 @@ class _Plan:
                 self._hc_ev[k].synchronize()
             torch.stack([h0.float(), c0.float()], out=self._hc_pin[k])
             qv, ql = qvec.contiguous(), qlens.reshape(B).contiguous()
-            n_nbt = net._nbt.numel() if self.training else 0
+            n_nbt = net._nbt.numel() if (self.training and not self.frozen_bn) else 0
             check(lib.zsg_stage_inputs(qv.data_ptr(), B, T, net.emb_dim, self.T, self.in_qvec.data_ptr(), ql.data_ptr(),
                                        int(ql.dtype == torch.float32), self.in_qlens.data_ptr(),
                                        self._hc_pin[k].data_ptr(), self.in_hc.numel(), self.in_hc.data_ptr(),
@@ -1844,7 +2009,13 @@ class _Plan:
         self.fwd.calls[self.img_slot] = (fn, (C_.c_void_p(img.data_ptr()),) + args[1:], what)
         self._img_keepalive = img
         self.fwd_id += 1
-        if self.training and not staged:
+        if self.training and self.frozen_bn:
+            # frozen BatchNorm layers keep num_batches_tracked: the train-mode counters only (one add; the default program stages them all)
+            if getattr(self, "_nbt_inc", None) is None or self._nbt_inc.device != net._nbt.device:
+                fz = set(self.frozen_bn)
+                self._nbt_inc = torch.tensor([0 if n in fz else 1 for n in net.bns], dtype=net._nbt.dtype, device=net._nbt.device)
+            net._nbt.add_(self._nbt_inc)
+        elif self.training and not staged:
             net._nbt.add_(1)
         assert self.img_slot == 0
         if not self.training and self.fold_jobs:       # the weights may have changed since the last eval forward: refold (one launch)

@@ -43,6 +43,8 @@ class Learner:
         self.predictions_dir.mkdir(parents=True, exist_ok=True)
         self.logger = logging.getLogger("zsg." + uid)
         self.optimizer, self.lr_scheduler = None, None
+        if cfg.get("freeze_bn", False):        # (kept across the mdl.train() of every epoch: ZSGNet.train re-applies it)
+            getattr(mdl, "module", mdl).freeze_batchnorm()
         if cfg["resume"] and (cfg["resume_path"] or self.model_file.exists()):
             self.load_model_dict(cfg["resume_path"] or str(self.model_file), cfg["load_opt"])
 
