@@ -469,6 +469,20 @@ int zsg_adam_step_segments(float* p, const float* g, float* m, float* v, const z
                            const zsg_adam_group* groups, int32_t ngroups, float grad_scale, int32_t* counters, int32_t* ticket,
                            void* stream);
 
+/* Gradient-norm clipping over listed segments of the flat gradient buffer: torch.nn.utils.clip_grad_norm_ (torch/nn/utils/clip_grad.py)
+ * in two launches with no host round trip.  segs / nseg / nchunks: a DEVICE segment table as zsg_adam_step_segments takes it (group and
+ * counter are not read); nothing outside the listed ranges is read or written.  nseg == 0: no launch, nothing written.
+ * zsg_grad_norm replaces _get_total_norm (torch._foreach_norm + linalg.vector_norm) and the coefficient of _clip_grads_with_norm_: the
+ * total 2-norm (inf_norm = 0: sums of squares in fp64) or inf-norm (inf_norm = 1: max |g|, NaN propagates) of the listed ranges, and
+ * clip_coef = clamp(max_norm / (total_norm + 1e-6), max=1.0) computed as torch does (fp32, reciprocal times max_norm, NaN kept);
+ * out[0] = total_norm, out[1] = clip_coef (fp32, device).  partials: device fp64 scratch of nchunks; ticket: a device int32, 0 between
+ * launches.  The last block reduces the partials in a fixed order: the same bits from run to run, whatever ZSG_DETERMINISTIC says. */
+int zsg_grad_norm(const float* g, const zsg_adam_seg* segs, int32_t nseg, int32_t nchunks, int32_t inf_norm, float max_norm,
+                  double* partials, int32_t* ticket, float* out, void* stream);
+/* g *= *coef over the listed ranges (torch._foreach_mul_ of _clip_grads_with_norm_): coef is read on the device (zsg_grad_norm's out + 1);
+ * a coefficient of exactly 1.0f leaves the buffer untouched (g * 1.0f == g). */
+int zsg_grad_scale(float* g, const zsg_adam_seg* segs, int32_t nseg, int32_t nchunks, const float* coef, void* stream);
+
 int zsg_memset_f32(float* p, int64_t n, float value, void* stream);
 
 /* Wave priority of the kernels of the step's dependent chain (convolutions forward / data gradient, BatchNorm passes, the small

@@ -9,6 +9,12 @@ count and the number of stepped parameters.
 
 --frozen-bn measures every BatchNorm layer frozen (ZSGNet.freeze_batchnorm) against train-mode BatchNorm, with everything trainable
 and with the encoder's parameters frozen.
+
+    python tools/finetune_step.py --clip [--out profiles/finetune_step_clip.json]
+
+--clip measures gradient-norm clipping between backward and step, everything trainable: no clipping, the fused optim.clip_grad_norm_
+with a max_norm it never reaches (the scale pass reads its coefficient and exits), the fused clip engaged (every gradient scaled), and
+torch.nn.utils.clip_grad_norm_ engaged on the same p.grad views.
 """
 import argparse
 import json
@@ -36,6 +42,13 @@ BN_VARIANTS = {
     "encoder_frozen": ((ENC,), False),
     "encoder_frozen_bn_frozen": ((ENC,), True),
 }
+# (clip function, max_norm): 1e9 never engages, 1e-3 always does (the pre-clip 2-norm at configs[1] is far above it)
+CLIP_VARIANTS = {
+    "no_clip": None,
+    "fused_clip_not_engaged": ("fused", 1e9),
+    "fused_clip_engaged": ("fused", 1e-3),
+    "torch_clip_engaged": ("torch", 1e-3),
+}
 
 
 def main():
@@ -46,6 +59,7 @@ def main():
     ap.add_argument("--bs", type=int, default=16)
     ap.add_argument("--out", default="")
     ap.add_argument("--frozen-bn", action="store_true")
+    ap.add_argument("--clip", action="store_true")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     cfg = config.get_cfg()
@@ -55,8 +69,13 @@ def main():
     bt["h0"], bt["c0"] = torch.zeros(2, a.bs, 128), torch.zeros(2, a.bs, 128)
     sd = None
     runs = {}
-    variants = BN_VARIANTS if a.frozen_bn else {k: (v, False) for k, v in VARIANTS.items()}
-    for name, (prefixes, bn_frozen) in variants.items():
+    if a.clip:
+        variants = {k: ((), False, c) for k, c in CLIP_VARIANTS.items()}
+    elif a.frozen_bn:
+        variants = {k: (v[0], v[1], None) for k, v in BN_VARIANTS.items()}
+    else:
+        variants = {k: (v, False, None) for k, v in VARIANTS.items()}
+    for name, (prefixes, bn_frozen, clip) in variants.items():
         net = mdl.get_default_net(9, cfg)
         if sd is None:
             sd = {k: v.clone() for k, v in net.state_dict().items()}
@@ -66,11 +85,15 @@ def main():
             p.requires_grad_(not (prefixes and n.startswith(prefixes)))
         if bn_frozen:
             net.freeze_batchnorm()
-        runs[name] = dict(net=net, opt=optim.FusedAdam(net, lr=1e-4, betas=(0.9, 0.99)), ms=[])
+        runs[name] = dict(net=net, opt=optim.FusedAdam(net, lr=1e-4, betas=(0.9, 0.99)), ms=[], clip=clip, params=list(net.parameters()))
 
     def step(v):
         v["opt"].zero_grad()
         lf(v["net"](bt), bt)["loss"].backward()
+        if v["clip"] is not None:
+            kind, max_norm = v["clip"]
+            fn = optim.clip_grad_norm_ if kind == "fused" else torch.nn.utils.clip_grad_norm_
+            v["norm"] = fn(v["params"], max_norm)
         v["opt"].step()
     for v in runs.values():              # lowering (and any tuning) outside the timed rounds
         for _ in range(a.warmup):
@@ -98,6 +121,9 @@ def main():
                                      stepped_params=sum(p.numel() for p in net.parameters() if p.grad is not None),
                                      frozen_tensors=sum(1 for p in net.parameters() if not p.requires_grad),
                                      frozen_bn_layers=len(net._frozen_bn_key()))
+        if v["clip"] is not None:
+            res["variants"][name].update(clip=v["clip"][0], max_norm=v["clip"][1], last_grad_norm=round(float(v["norm"]), 6),
+                                         engaged=float(v["norm"]) > v["clip"][1])
     js = json.dumps(res, indent=1)
     print(js)
     if a.out:

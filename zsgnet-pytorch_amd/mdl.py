@@ -19,6 +19,7 @@ import ctypes as _ct
 import math
 import os
 import types
+import weakref
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Tuple
 
@@ -34,6 +35,8 @@ from .params import ParamStore, pad4, register_named
 
 VGG_BASE = [64, 64, "M", 128, 128, "M", 256, 256, 256, "C", 512, 512, 512, "M", 512, 512, 512]     # ssd_vgg.py:174-177
 SSD_EXTRAS = [256, "S", 512, 128, "S", 256, 128, 256, 128, 256]                                          # ssd_vgg.py:179-182
+
+LIVE_NETS = weakref.WeakSet()      # every ZSGNet alive: optim.clip_grad_norm_ finds a parameter's flat store here
 
 ARCHS = {
     "resnet18": ("basic", (2, 2, 2, 2)),
@@ -135,6 +138,7 @@ class ZSGNet(nn.Module):
         self._anchor = None
         self._bn_eval = set()          # BatchNorm layers freeze_batchnorm() keeps in eval mode across train()
         self.debug = False
+        LIVE_NETS.add(self)
 
     # ------------------------------------------------------------------------------------------------------
     # declaration (names == reference state_dict keys)
@@ -405,6 +409,12 @@ class ZSGNet(nn.Module):
             mods = dict(self.named_modules())
             self._plist = [mods[n.rsplit(".", 1)[0]]._parameters[n.rsplit(".", 1)[1]] for n in self._param_names]
         return self._plist
+
+    def _param_index(self) -> Dict[int, int]:
+        """id(parameter) -> its index in _ordered_params() (flat-storage order)"""
+        if getattr(self, "_pindex", None) is None:
+            self._pindex = {id(p): i for i, p in enumerate(self._ordered_params())}
+        return self._pindex
 
     def plan_geometry(self, inp: Dict[str, Any]) -> Tuple[int, int, int, int]:
         """(B, H, W, T_plan) of the launch plan forward(inp) will use (T is bucketed: see forward)"""

@@ -6,12 +6,34 @@ Fine-tuning (torch.optim semantics): `params=` takes the model's parameters or a
 eps / weight_decay (add_param_group too).  A parameter is stepped only when it is in some group AND its p.grad is not None — a
 frozen parameter (requires_grad=False: the backward leaves its p.grad at None) keeps its value and moments bit for bit.  With one
 group and every parameter stepped, the step is the single zsg_adam_step launch; otherwise zsg_adam_step_segments updates the
-listed parameters only, with per-group hyperparameters and per-parameter step counters (torch's state['step'])."""
+listed parameters only, with per-group hyperparameters and per-parameter step counters (torch's state['step']).
+
+clip_grad_norm_ is torch.nn.utils.clip_grad_norm_ over the same flat gradient buffer: two HIP launches (zsg_grad_norm, zsg_grad_scale)
+through the segment table the segmented Adam step uses, with no host round trip."""
 import ctypes as C
+import math
 
 import torch
 
+from . import mdl
 from ._lib import ADAM_CHUNK, ADAM_MAX_GROUPS, AdamGroup, AdamSeg, check, lib, stream_ptr
+
+
+def segment_table(net, key):
+    """(device table, work chunks) of the segments `key` = ((parameter index, group index), ...) in flat order: the table of
+    zsg_adam_step_segments, which zsg_grad_norm / zsg_grad_scale read too (group and counter unused).  Table None for an empty key."""
+    ents, names = net.store.entries, net._param_names
+    segs = (AdamSeg * max(1, len(key)))()
+    chunk = 0
+    for k, (i, gi) in enumerate(key):
+        e = ents[names[i]]
+        n = (e.size + 3) // 4 * 4                   # the store pads every parameter to 4 floats: step the padding as the full launch does
+        assert e.offset % 4 == 0 and e.offset + n <= net.store.flat.numel()
+        segs[k] = AdamSeg(e.offset, n, gi, i, chunk, 0)
+        chunk += (n + ADAM_CHUNK - 1) // ADAM_CHUNK
+    blob = bytes(segs)[:C.sizeof(AdamSeg) * len(key)]
+    tab = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(net.store.flat.device) if key else None
+    return tab, chunk
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -75,18 +97,8 @@ class FusedAdam(torch.optim.Optimizer):
         """device segment table of zsg_adam_step_segments for `key` (rebuilt only when the stepped set or the groups change)"""
         if key == self._seg_key:
             return
-        ents, names = self.net.store.entries, self.net._param_names
-        segs = (AdamSeg * max(1, len(key)))()
-        chunk = 0
-        for k, (i, gi) in enumerate(key):
-            e = ents[names[i]]
-            n = (e.size + 3) // 4 * 4                   # the store pads every parameter to 4 floats: step the padding as the full launch does
-            assert e.offset % 4 == 0 and e.offset + n <= self.net.store.flat.numel()
-            segs[k] = AdamSeg(e.offset, n, gi, i, chunk, 0)
-            chunk += (n + ADAM_CHUNK - 1) // ADAM_CHUNK
-        blob = bytes(segs)[:C.sizeof(AdamSeg) * len(key)]
-        self._seg_tab = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(self.net.store.flat.device) if key else None
-        self._seg_key, self._nchunks = key, chunk
+        self._seg_tab, self._nchunks = segment_table(self.net, key)
+        self._seg_key = key
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -160,3 +172,75 @@ class FusedAdam(torch.optim.Optimizer):
             for k in ("lr", "betas", "eps", "weight_decay"):
                 if k in gs:
                     g[k] = gs[k]
+
+
+# ---- gradient-norm clipping ---------------------------------------------------------------------------------------------------------
+def _flat_owner(tensors):
+    """(the ZSGNet whose flat store holds every tensor, its {id(parameter): flat index}); (None, None) for no tensors.  Any other tensor
+    is a ValueError, as FusedAdam.add_param_group rejects it (the kernels address gradients by their offset in the flat buffer)."""
+    net = index = None
+    for p in tensors:
+        if index is not None and id(p) in index:
+            continue
+        owner = next((n for n in list(mdl.LIVE_NETS) if id(p) in n._param_index()), None)
+        if owner is None or (net is not None and owner is not net):
+            shape = tuple(p.shape) if isinstance(p, torch.Tensor) else type(p).__name__
+            raise ValueError(f"clip_grad_norm_: a tensor of shape {shape} is not a parameter of " +
+                             ("a ZSGNet's flat parameter store" if owner is None else "the same ZSGNet as the others") +
+                             "; only one model's own parameters (model.parameters() or a subset) can be clipped")
+        net, index = owner, owner._param_index()
+    return net, index
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0, error_if_nonfinite: bool = False, foreach=None) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ for the parameters of a ZSGNet (any subset, e.g. net.lstm.parameters()): the total norm of the
+    gradients of the given parameters whose p.grad is not None (a parameter listed twice counts once), and those gradients scaled in place
+    by clamp(max_norm / (total_norm + 1e-6), max=1.0).  Frozen parameters (p.grad None) and the flat buffer's by-products that are never a
+    p.grad (a frozen BatchNorm's d(gamma) / d(beta)) are neither counted nor scaled.
+
+    Two launches on torch's current stream: zsg_grad_norm (fp64 sums of squares, a fixed reduction order: the same bits on every run and
+    every rank given the same gradients) writes the norm and the coefficient to the device; zsg_grad_scale reads the coefficient there and
+    writes nothing when it is 1.  No host synchronisation unless error_if_nonfinite=True.  No extra stream wait is needed: run_backward
+    returns with the main stream joined to the side stream's weight gradients (ops.Program.run, join at the end of the range) and, under
+    DDP, behind every bucket's all-reduce (the reducer's wait() runs inside run_backward).
+
+    norm_type: 2 or inf (ValueError otherwise).  foreach: accepted for torch's signature; the fused kernels serve every value.
+    Returns the total norm, a 0-dim fp32 tensor on the model's device allocated for this call (tensor(0.) when no gradient is listed:
+    nothing is launched)."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    else:
+        parameters = list(parameters)
+    norm_type = float(norm_type)
+    if norm_type not in (2.0, math.inf):
+        raise ValueError(f"clip_grad_norm_: norm_type {norm_type} is not supported (2.0 or inf)")
+    net, index = _flat_owner(parameters)
+    sel = tuple(sorted({index[id(p)] for p in parameters if p.grad is not None}))
+    if not sel:
+        return torch.tensor(0.0)
+    st = net.store
+    cache = net.__dict__.get("_clip_scratch")
+    if cache is None or cache[0] != (sel, st.grad.data_ptr()):
+        if not st.grad.is_cuda:
+            raise RuntimeError("clip_grad_norm_: the model's gradients are not on the MI355X (no CPU fallback)")
+        plist, base = net._ordered_params(), st.grad.untyped_storage().data_ptr()
+        for i in sel:
+            if plist[i].grad.untyped_storage().data_ptr() != base:
+                raise ValueError(f"clip_grad_norm_: the p.grad of {net._param_names[i]} is not a view of the model's flat gradient buffer")
+        tab, nch = segment_table(net, tuple((i, 0) for i in sel))
+        # the segment table, one fp64 partial per work chunk and the completion ticket (zero between launches): built once per set of
+        # parameters with gradients, reused while it does not change
+        cache = ((sel, st.grad.data_ptr()), tab, nch, torch.empty(nch, dtype=torch.float64, device=st.grad.device),
+                 torch.zeros(1, dtype=torch.int32, device=st.grad.device))
+        net._clip_scratch = cache
+    _, tab, nch, partials, ticket = cache
+    res = torch.empty(2, dtype=torch.float32, device=st.grad.device)          # [total_norm, clip_coef]
+    check(lib.zsg_grad_norm(st.grad.data_ptr(), tab.data_ptr(), len(sel), nch, 1 if norm_type == math.inf else 0, float(max_norm),
+                            partials.data_ptr(), ticket.data_ptr(), res.data_ptr(), stream_ptr()), "zsg_grad_norm")
+    total = res[0]
+    if error_if_nonfinite and not bool(torch.isfinite(total)):
+        raise RuntimeError(f"The total norm of order {norm_type} for gradients from `parameters` is non-finite, so it cannot be clipped. "
+                           "To disable this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
+    check(lib.zsg_grad_scale(st.grad.data_ptr(), tab.data_ptr(), len(sel), nch, res.data_ptr() + 4, stream_ptr()), "zsg_grad_scale")
+    return total

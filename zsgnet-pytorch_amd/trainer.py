@@ -101,6 +101,13 @@ class Learner:
         self.mdl.train()
         sm_loss = {k: SmoothenValue(0.9) for k in self.loss_keys}
         sm_met = {k: SmoothenValue(0.9) for k in self.met_keys}
+        # cfg clip_grad_norm > 0: the trainable gradients are clipped to that total 2-norm between backward and step (torch's
+        # clip_grad_norm_ recipe, fused: optim.clip_grad_norm_); the pre-clip norm is logged as grad_norm
+        clip = float(self.cfg.get("clip_grad_norm", 0.0))
+        if clip > 0:
+            from .optim import clip_grad_norm_
+            clip_params = [p for p in self.mdl.parameters() if p.requires_grad]
+            sm_gn = SmoothenValue(0.9)
         n_img, t0 = 0, time.perf_counter()
         for batch in self.data.train_dl:
             self.num_it += 1
@@ -109,6 +116,8 @@ class Learner:
             out = self.mdl(batch)
             out_loss = self.loss_fn(out, batch)
             out_loss["loss"].mean().backward()
+            if clip > 0:
+                grad_norm = clip_grad_norm_(clip_params, clip)
             self.optimizer.step()
             metric = self.eval_fn(out, batch)
             n_img += batch["img"].shape[0]
@@ -117,10 +126,14 @@ class Learner:
                     sm_loss[k].add_value(float(out_loss[k].detach()))
                 for k in self.met_keys:
                     sm_met[k].add_value(float(metric[k]))
+                if clip > 0:
+                    sm_gn.add_value(float(grad_norm))
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         res = {k: v.smooth for k, v in sm_loss.items()}
         res.update({k: v.smooth for k, v in sm_met.items()})
+        if clip > 0:
+            res["grad_norm"] = sm_gn.smooth
         res["images_per_s"] = n_img * zdist.get_world_size() / dt
         return res
 
