@@ -309,6 +309,38 @@ int zsg_bn_backward_from_partials(const float* dout, const uint8_t* relu_mask, c
                                   const float* mean, const float* invstd, const float* gamma, float* dx, float* g_out,
                                   float* dgamma, float* dbeta, int32_t accumulate, const float* partials, int32_t chunks,
                                   void* ws, size_t ws_bytes, void* stream);
+/* Synchronized BatchNorm (torch.nn.SyncBatchNorm) across data-parallel ranks, split at the collective: a sums launch writes the
+ * rank-local per-channel sums in fp64, the caller all-reduces them over the ranks (SUM), and the finalize / apply launch restarts from
+ * the global sums.  Fixed-order reductions, no float atomics: bit-reproducible.  With one rank and the same partial rows the results
+ * equal those of zsg_bn_stats, zsg_bn_stats_from_partials and zsg_bn_backward(_from_partials) bit for bit (not those of the in-kernel
+ * finalizes of the *_bnstat / *_bnb_tail convolutions or of zsg_bn_apply_from_partials, which sum in another order).
+ * Forward sums (2*C + 1 doubles): [sum x | sum x^2 | n], from the producing convolution's partial rows [chunks][2][C] (x and ws unused)
+ * or from one pass over x (partials NULL: ws >= zsg_bn_workspace_bytes(rows, C)).  The finalize writes mean / invstd / running
+ * statistics (unbiased variance, factor N / (N - 1), N = the all-reduced n) with zsg_bn_stats_from_partials's arithmetic. */
+int zsg_bn_sync_fwd_sums(const float* x, int64_t rows, int32_t C, const float* partials, int32_t chunks, double* sums, void* ws,
+                         size_t ws_bytes, void* stream);
+int zsg_bn_sync_fwd_finalize(const double* sums, int32_t C, float* mean, float* invstd, float* running_mean, float* running_var,
+                             float momentum, float eps, void* stream);
+/* Backward sums (2*C doubles): [sum g | sum g*xhat], g = dout * relu-bit, xhat from the global mean / invstd; from a *_bnb data
+ * gradient's partial rows (dout / x unread, ws unused) or one pass over dout and x (ws >= zsg_bn_workspace_bytes(rows, C)).  dgamma /
+ * dbeta (NULL to skip) receive the RANK-LOCAL sums, accumulated when accumulate != 0 (the gradient reducer averages them as any other).
+ * The apply writes dx = gamma*invstd*(g - sum g / N - xhat * sum g*xhat / N) from the all-reduced sums and the forward's all-reduced
+ * N (fwd_sums[2*C]); optional g_out = g. */
+int zsg_bn_sync_bwd_sums(const float* dout, const uint8_t* relu_mask, const float* x, int64_t rows, int32_t C, const float* mean,
+                         const float* invstd, const float* partials, int32_t chunks, double* sums, float* dgamma, float* dbeta,
+                         int32_t accumulate, void* ws, size_t ws_bytes, void* stream);
+int zsg_bn_sync_bwd_apply(const float* dout, const uint8_t* relu_mask, const float* x, int64_t rows, int32_t C, const float* mean,
+                          const float* invstd, const float* gamma, const double* sums, const double* fwd_sums, float* dx, float* g_out,
+                          void* stream);
+/* zsg_bn_relu_maxpool_bwd split at the collective: the sums over the pooled gradient (ws >= zsg_bn_workspace_bytes(B*Ho*Wo, C)), then
+ * the per-input-pixel apply with the all-reduced sums and N. */
+int zsg_bn_sync_relu_maxpool_bwd_sums(const float* dout, const uint8_t* idx, const float* x, int32_t B, int32_t H, int32_t W, int32_t C,
+                                      const float* mean, const float* invstd, const float* gamma, const float* beta, int32_t k, int32_t s,
+                                      int32_t p, int32_t Ho, int32_t Wo, double* sums, float* dgamma, float* dbeta, int32_t accumulate,
+                                      void* ws, size_t ws_bytes, void* stream);
+int zsg_bn_sync_relu_maxpool_bwd_apply(const float* dout, const uint8_t* idx, const float* x, int32_t B, int32_t H, int32_t W, int32_t C,
+                                       const float* mean, const float* invstd, const float* gamma, const float* beta, int32_t k, int32_t s,
+                                       int32_t p, int32_t Ho, int32_t Wo, const double* sums, const double* fwd_sums, float* dx, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Pooling / resampling / elementwise (NHWC, C % 4 == 0).

@@ -15,17 +15,25 @@ and with the encoder's parameters frozen.
 --clip measures gradient-norm clipping between backward and step, everything trainable: no clipping, the fused optim.clip_grad_norm_
 with a max_norm it never reaches (the scale pass reads its coefficient and exits), the fused clip engaged (every gradient scaled), and
 torch.nn.utils.clip_grad_norm_ engaged on the same p.grad views.
+
+    python tools/finetune_step.py --sync-bn [--out profiles/finetune_step_sync_bn.json]
+
+--sync-bn measures synchronized BatchNorm in a 1-rank nccl group with forced collectives: the DistributedDataParallel wrapper
+(force_collectives) against the same wrapper with dist.convert_sync_batchnorm(force=True) — one all-reduce per train-mode BatchNorm layer
+and direction on top of the gradient buckets.  host_enqueue_ms_per_step: host time to enqueue a step (starting from an idle GPU; equal
+to the GPU's ms_per_step when the host, not the GPU, sets the pace).  --only NAME[,NAME] runs the named variants alone (profiling).
 """
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from zsgnet_pytorch_amd import config, loss, mdl, ops, optim  # noqa: E402
+from zsgnet_pytorch_amd import config, dist as zdist, loss, mdl, ops, optim  # noqa: E402
 from zsgnet_pytorch_amd.synth import synthetic_batch  # noqa: E402
 
 ENC = "backbone.encoder."
@@ -49,6 +57,11 @@ CLIP_VARIANTS = {
     "fused_clip_engaged": ("fused", 1e-3),
     "torch_clip_engaged": ("torch", 1e-3),
 }
+# (DistributedDataParallel with forced collectives, synchronized BatchNorm)
+SYNC_VARIANTS = {
+    "ddp_forced": False,
+    "ddp_forced_sync_bn": True,
+}
 
 
 def main():
@@ -60,8 +73,18 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--frozen-bn", action="store_true")
     ap.add_argument("--clip", action="store_true")
+    ap.add_argument("--sync-bn", action="store_true")
+    ap.add_argument("--only", default="", help="comma-separated variant names to run (e.g. one variant under rocprofv3)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
+    if a.sync_bn:
+        import socket
+        import torch.distributed as dist
+        sk = socket.socket()
+        sk.bind(("127.0.0.1", 0))
+        os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(sk.getsockname()[1]))
+        sk.close()
+        dist.init_process_group("nccl", rank=0, world_size=1)
     cfg = config.get_cfg()
     r, s = config.ratios_scales(cfg)
     lf = loss.get_default_loss(r, s, cfg)
@@ -69,13 +92,17 @@ def main():
     bt["h0"], bt["c0"] = torch.zeros(2, a.bs, 128), torch.zeros(2, a.bs, 128)
     sd = None
     runs = {}
-    if a.clip:
-        variants = {k: ((), False, c) for k, c in CLIP_VARIANTS.items()}
+    if a.sync_bn:
+        variants = {k: ((), False, None, v) for k, v in SYNC_VARIANTS.items()}
+    elif a.clip:
+        variants = {k: ((), False, c, None) for k, c in CLIP_VARIANTS.items()}
     elif a.frozen_bn:
-        variants = {k: (v[0], v[1], None) for k, v in BN_VARIANTS.items()}
+        variants = {k: (v[0], v[1], None, None) for k, v in BN_VARIANTS.items()}
     else:
-        variants = {k: (v, False, None) for k, v in VARIANTS.items()}
-    for name, (prefixes, bn_frozen, clip) in variants.items():
+        variants = {k: (v, False, None, None) for k, v in VARIANTS.items()}
+    if a.only:
+        variants = {k: v for k, v in variants.items() if k in a.only.split(",")}
+    for name, (prefixes, bn_frozen, clip, sync_bn) in variants.items():
         net = mdl.get_default_net(9, cfg)
         if sd is None:
             sd = {k: v.clone() for k, v in net.state_dict().items()}
@@ -85,11 +112,17 @@ def main():
             p.requires_grad_(not (prefixes and n.startswith(prefixes)))
         if bn_frozen:
             net.freeze_batchnorm()
-        runs[name] = dict(net=net, opt=optim.FusedAdam(net, lr=1e-4, betas=(0.9, 0.99)), ms=[], clip=clip, params=list(net.parameters()))
+        model = net
+        if sync_bn is not None:              # (--sync-bn: the wrapper with forced collectives, converted or not)
+            model = zdist.DistributedDataParallel(net, device_ids=[0], force_collectives=True)
+            if sync_bn:
+                zdist.convert_sync_batchnorm(model, force=True)
+        runs[name] = dict(net=net, model=model, opt=optim.FusedAdam(net, lr=1e-4, betas=(0.9, 0.99)), ms=[], host_ms=[], clip=clip,
+                          params=list(net.parameters()))
 
     def step(v):
         v["opt"].zero_grad()
-        lf(v["net"](bt), bt)["loss"].backward()
+        lf(v["model"](bt), bt)["loss"].backward()
         if v["clip"] is not None:
             kind, max_norm = v["clip"]
             fn = optim.clip_grad_norm_ if kind == "fused" else torch.nn.utils.clip_grad_norm_
@@ -104,12 +137,16 @@ def main():
             for _ in range(a.warmup):
                 step(v)
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
             ev[0].record()
             for i in range(a.steps):
                 step(v)
                 ev[i + 1].record()
+            t1 = time.perf_counter()
             torch.cuda.synchronize()
             v["ms"].append(statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(a.steps)))
+            v["host_ms"].append((t1 - t0) * 1e3 / a.steps)
     res = dict(config="BASELINE configs[1] shape (ResNet-50 + FPN, 300x300, B=%d, 1 GPU)" % a.bs, rounds=a.rounds, steps=a.steps,
                tune_loaded=ops.TUNE_INFO.get("loaded", 0), stamp_match=ops.TUNE_INFO.get("table_stamp") == ops.TUNE_INFO.get("stamp"),
                variants={})
@@ -117,10 +154,13 @@ def main():
         net = v["net"]
         plan = [p for k, p in net._plans.items() if k[-1]][0]
         res["variants"][name] = dict(ms_per_step=round(statistics.median(v["ms"]), 4), round_medians=[round(x, 4) for x in v["ms"]],
+                                     host_enqueue_ms_per_step=round(statistics.median(v["host_ms"]), 4),
                                      bwd_launches=len(plan.bwd.calls), prep_launches=len(plan.prep.calls),
                                      stepped_params=sum(p.numel() for p in net.parameters() if p.grad is not None),
                                      frozen_tensors=sum(1 for p in net.parameters() if not p.requires_grad),
-                                     frozen_bn_layers=len(net._frozen_bn_key()))
+                                     frozen_bn_layers=len(net._frozen_bn_key()),
+                                     collectives_per_step=sum(c[0].__name__ == "host" for c in plan.fwd.calls + plan.bwd.calls),
+                                     sync_bn_layers=len(plan.sync_bn))
         if v["clip"] is not None:
             res["variants"][name].update(clip=v["clip"][0], max_norm=v["clip"][1], last_grad_norm=round(float(v["norm"]), 6),
                                          engaged=float(v["norm"]) > v["clip"][1])

@@ -84,6 +84,12 @@ SIGNATURES = {
     "zsg_bn_backward_from_partials": (I32, [P, P, P, I64, I32, P, P, P, P, P, P, P, I32, P, I32, P, SZ, P]),
     "zsg_bn_frozen_backward": (I32, [P, P, P, I64, I32, P, P, P, P, P, P, P, I32, P, I32, P, SZ, P]),
     "zsg_bn_frozen_relu_maxpool_bwd": (I32, [P, P, P, I32, I32, I32, I32, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, I32, P, SZ, P]),
+    "zsg_bn_sync_fwd_sums": (I32, [P, I64, I32, P, I32, P, P, SZ, P]),
+    "zsg_bn_sync_fwd_finalize": (I32, [P, I32, P, P, P, P, F32, F32, P]),
+    "zsg_bn_sync_bwd_sums": (I32, [P, P, P, I64, I32, P, P, P, I32, P, P, P, I32, P, SZ, P]),
+    "zsg_bn_sync_bwd_apply": (I32, [P, P, P, I64, I32, P, P, P, P, P, P, P, P]),
+    "zsg_bn_sync_relu_maxpool_bwd_sums": (I32, [P, P, P, I32, I32, I32, I32, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, I32, P, SZ, P]),
+    "zsg_bn_sync_relu_maxpool_bwd_apply": (I32, [P, P, P, I32, I32, I32, I32, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, P]),
     "zsg_wino_u_elems": (I64, [I32, I32]),
     "zsg_wino_weights": (I32, [P, I32, I32, P]),
     "zsg_conv_wgrad_workspace_bytes": (SZ, [DP]),

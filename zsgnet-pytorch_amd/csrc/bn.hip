@@ -986,3 +986,263 @@ extern "C" int zsg_bn_frozen_relu_maxpool_bwd(const float* dout, const uint8_t* 
     ZSG_CHECK_LAUNCH("bn_frozen_relu_maxpool_bwd");
     return 0;
 }
+
+// ---- synchronized BatchNorm (torch.nn.SyncBatchNorm) across data-parallel ranks -----------------------------------------------
+// The statistics are split at the collective: a sums launch writes the rank-local per-channel sums in fp64, the host all-reduces that
+// small buffer over the ranks (stream-ordered), and a finalize / apply launch restarts from the global sums.  Every reduction is the
+// fixed-order one of the separate-launch kernels (bn_partial_kernel / bn_pool_bwd_partial_kernel rows, bn_reduce_partials in fp64): with
+// one rank and the same partial rows the results are bit-identical to zsg_bn_stats, zsg_bn_stats_from_partials and
+// zsg_bn_backward(_from_partials) — NOT to the in-kernel finalizes (*_bnstat, *_bnb_tail) or bn_apply_inl_kernel's inline reduction,
+// which sum in another order, so a forced one-rank network matches the unsynchronized one to fp32 summation order only.
+// Forward sums: [sum x (C) | sum x^2 (C) | n]; backward sums: [sum g (C) | sum g * xhat (C)], g = dout * relu-bit.
+template <int FW>
+__global__ __launch_bounds__(64 * FW) void bn_sync_sums_kernel(const float* __restrict__ part, int chunks, int C, int64_t rows,
+                                                               double* __restrict__ sums, float* dgamma, float* dbeta, int accumulate) {
+    ZSG_SET_MAIN_PRIO();
+    const int c = blockIdx.x * 4;
+    double se, sse;
+    bn_reduce_partials<FW>(part, chunks, C, c, se, sse);
+    const int e = threadIdx.x;
+    if (e >= 4) return;
+    sums[c + e] = se;
+    sums[C + c + e] = sse;
+    if (rows >= 0 && c + e == 0) sums[2 * C] = (double)rows;       // (forward: the row count travels with the sums)
+    if (dbeta) dbeta[c + e] = (accumulate ? dbeta[c + e] : 0.f) + (float)se;
+    if (dgamma) dgamma[c + e] = (accumulate ? dgamma[c + e] : 0.f) + (float)sse;
+}
+
+__global__ __launch_bounds__(256) void bn_sync_finalize_kernel(const double* __restrict__ sums, int C, float* mean, float* invstd,
+                                                               float* rmean, float* rvar, float momentum, float eps) {
+    ZSG_SET_MAIN_PRIO();
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const double n = sums[2 * C];
+    const double m = sums[c] / n;                   // (bn_stats_finalize_kernel's arithmetic)
+    double var = sums[C + c] / n - m * m;
+    if (var < 0) var = 0;
+    mean[c] = (float)m;
+    invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+    if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)m;
+    if (rvar) rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)(n > 1 ? var * n / (n - 1) : var);
+}
+
+// (sum g / N, sum g * xhat / N) of channels c .. c + 3 from the global backward sums and the forward's global N: bn_bwd_finalize_kernel's
+// coefficients
+__device__ __forceinline__ void bn_sync_coef(const double* __restrict__ sums, const double* __restrict__ fwd_sums, int C, int c, f32x4& c1,
+                                             f32x4& c2) {
+    const double n = fwd_sums[2 * C];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        c1[e] = (float)(sums[c + e] / n);
+        c2[e] = (float)(sums[C + c + e] / n);
+    }
+}
+
+// bn_bwd_apply_kernel with the coefficients taken from the all-reduced fp64 sums
+__global__ __launch_bounds__(256) void bn_sync_bwd_apply_kernel(const float* __restrict__ dout, const uint8_t* __restrict__ relu_mask,
+                                                                const float* __restrict__ x, int64_t rows, int C, const float* __restrict__ mean,
+                                                                const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                                const double* __restrict__ sums, const double* __restrict__ fwd_sums,
+                                                                float* __restrict__ dx, float* __restrict__ g_out, int lanes, int rpb) {
+    ZSG_SET_MAIN_PRIO();
+    const int rowlanes = 256 / lanes;
+    const int l = threadIdx.x % lanes, rl = threadIdx.x / lanes;
+    const int c = (blockIdx.y * lanes + l) * 4;
+    if (c >= C) return;
+    const f32x4 mu = *(const f32x4*)(mean + c);
+    const f32x4 is = *(const f32x4*)(invstd + c);
+    const f32x4 sc = is * *(const f32x4*)(gamma + c);
+    f32x4 c1, c2;
+    bn_sync_coef(sums, fwd_sums, C, c, c1, c2);
+    const int64_t r_begin = (int64_t)blockIdx.x * rpb;
+    const int64_t r_end = min(rows, r_begin + (int64_t)rpb);
+    for (int64_t r = r_begin + rl; r < r_end; r += rowlanes) {
+        f32x4 g = *(const f32x4*)(dout + r * C + c);
+        if (relu_mask) {
+            const unsigned m = relu_mask[(r * C + c) >> 2];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) g[e] = ((m >> e) & 1u) ? g[e] : 0.f;
+        }
+        const f32x4 xh = (*(const f32x4*)(x + r * C + c) - mu) * is;
+        if (g_out) *(f32x4*)(g_out + r * C + c) = g;
+        *(f32x4*)(dx + r * C + c) = sc * (g - c1 - xh * c2);
+    }
+}
+
+// bn_pool_bwd_apply_kernel with the coefficients taken from the all-reduced fp64 sums (same gather order, same bits)
+__global__ __launch_bounds__(256) void bn_sync_pool_bwd_apply_kernel(const float* __restrict__ dout, const uint8_t* __restrict__ idx,
+                                                                     const float* __restrict__ x, int H, int W, int C, int k, int s, int p, int Ho,
+                                                                     int Wo, const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                     const double* __restrict__ sums, const double* __restrict__ fwd_sums,
+                                                                     int64_t rows, float* __restrict__ dx, int lanes, int rpb) {
+    ZSG_SET_MAIN_PRIO();
+    const int rowlanes = 256 / lanes;
+    const int l = threadIdx.x % lanes, rl = threadIdx.x / lanes;
+    const int c = (blockIdx.y * lanes + l) * 4;
+    if (c >= C) return;
+    const f32x4 mu = *(const f32x4*)(mean + c), is = *(const f32x4*)(invstd + c);
+    const f32x4 sc = is * *(const f32x4*)(gamma + c), be = *(const f32x4*)(beta + c);
+    f32x4 c1, c2;
+    bn_sync_coef(sums, fwd_sums, C, c, c1, c2);
+    const int64_t r_begin = (int64_t)blockIdx.x * rpb;
+    const int64_t r_end = min(rows, r_begin + (int64_t)rpb);
+    int64_t r = r_begin + rl;
+    int wi = (int)(r % W);
+    int64_t t0 = r / W;
+    int hi = (int)(t0 % H);
+    int64_t b = t0 / H;
+    const bool s2 = s == 2;
+    for (; r < r_end; r += rowlanes) {
+        const f32x4 xv = *(const f32x4*)(x + r * C + c);
+        const f32x4 v = bn_pool_val(xv, mu, sc, be);
+        f32x4 g = {0, 0, 0, 0};
+        const int hn0 = hi + p, wn0 = wi + p;
+        const int ho_hi = min(s2 ? (hn0 >> 1) : hn0 / s, Ho - 1), wo_hi = min(s2 ? (wn0 >> 1) : wn0 / s, Wo - 1);
+        const int hlo = hn0 - k + s, wlo = wn0 - k + s;
+        const int ho_lo = (hn0 - k + 1 <= 0) ? 0 : (s2 ? (hlo >> 1) : hlo / s), wo_lo = (wn0 - k + 1 <= 0) ? 0 : (s2 ? (wlo >> 1) : wlo / s);
+        for (int ho = ho_hi; ho >= ho_lo; --ho) {
+            const int rr = hn0 - ho * s;
+            for (int wo = wo_hi; wo >= wo_lo; --wo) {
+                const int64_t o = ((b * Ho + ho) * Wo + wo) * C + c;
+                const uchar4 u = *(const uchar4*)(idx + o);
+                const f32x4 d = *(const f32x4*)(dout + o);
+                const unsigned code = rr * k + (wn0 - wo * s);
+                g[0] += (u.x == code) ? d[0] : 0.f;
+                g[1] += (u.y == code) ? d[1] : 0.f;
+                g[2] += (u.z == code) ? d[2] : 0.f;
+                g[3] += (u.w == code) ? d[3] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) g[e] = v[e] > 0.f ? g[e] : 0.f;
+        const f32x4 xh = (xv - mu) * is;
+        *(f32x4*)(dx + r * C + c) = sc * (g - c1 - xh * c2);
+        wi += rowlanes;
+        while (wi >= W) {
+            wi -= W;
+            if (++hi == H) {
+                hi = 0;
+                ++b;
+            }
+        }
+    }
+}
+
+// partials: the [chunks][2][C] rows of the producing convolution's epilogue (x and ws unused), else one pass over x (ws >=
+// zsg_bn_workspace_bytes(rows, C)).  The reduction width follows zsg_bn_stats(_from_partials): the same bits for the same rows.
+extern "C" int zsg_bn_sync_fwd_sums(const float* x, int64_t rows, int32_t C, const float* partials, int32_t chunks, double* sums, void* ws,
+                                    size_t ws_bytes, void* stream) {
+    ZSG_REQUIRE(sums && rows > 0 && C > 0 && (C % 4) == 0 && (partials ? chunks > 0 : (x && ws)), "bn_sync_fwd_sums: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const float* part = partials;
+    if (!partials) {
+        if (ws_bytes < zsg_bn_workspace_bytes(rows, C)) ZSG_FAIL(-2, "bn_sync_fwd_sums: workspace too small");
+        const BnGeom g = bn_geom(rows, C);
+        ZSG_PROF("bn_stats", st, 0, (double)rows * C * 4);
+        ZSG_LAUNCH((bn_partial_kernel<0>), dim3(g.chunks, g.slabs), dim3(256), 0, st, x, nullptr, nullptr, nullptr, nullptr, nullptr, rows, C,
+                           g.lanes, g.rpb, (float*)ws);
+        part = (const float*)ws;
+        chunks = g.chunks;
+    } else {
+        ZSG_PROF("bn_stats", st, 0, (double)chunks * C * 8);
+    }
+    if (chunks > BN_MANY_ROWS)
+        ZSG_LAUNCH(bn_sync_sums_kernel<BN_FW_MANY>, dim3(C / 4), dim3(64 * BN_FW_MANY), 0, st, part, chunks, C, rows, sums, (float*)nullptr,
+                           (float*)nullptr, 0);
+    else
+        ZSG_LAUNCH(bn_sync_sums_kernel<BN_FW>, dim3(C / 4), dim3(64 * BN_FW), 0, st, part, chunks, C, rows, sums, (float*)nullptr,
+                           (float*)nullptr, 0);
+    ZSG_CHECK_LAUNCH("bn_sync_fwd_sums");
+    return 0;
+}
+
+extern "C" int zsg_bn_sync_fwd_finalize(const double* sums, int32_t C, float* mean, float* invstd, float* running_mean, float* running_var,
+                                        float momentum, float eps, void* stream) {
+    ZSG_REQUIRE(sums && mean && invstd && C > 0, "bn_sync_fwd_finalize: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("bn_stats", st, 0, (double)C * 16);
+    ZSG_LAUNCH(bn_sync_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sums, C, mean, invstd, running_mean, running_var, momentum, eps);
+    ZSG_CHECK_LAUNCH("bn_sync_fwd_finalize");
+    return 0;
+}
+
+// partials: the [chunks][2][C] rows of a *_bnb data gradient (x and dout unread, ws unused), else one pass over dout / x (ws >=
+// zsg_bn_workspace_bytes(rows, C)).  dgamma / dbeta: the rank-local sums, accumulated (+=) when accumulate != 0.
+extern "C" int zsg_bn_sync_bwd_sums(const float* dout, const uint8_t* relu_mask, const float* x, int64_t rows, int32_t C, const float* mean,
+                                    const float* invstd, const float* partials, int32_t chunks, double* sums, float* dgamma, float* dbeta,
+                                    int32_t accumulate, void* ws, size_t ws_bytes, void* stream) {
+    ZSG_REQUIRE(sums && rows > 0 && C > 0 && (C % 4) == 0 && (partials ? chunks > 0 : (dout && x && mean && invstd && ws)),
+                "bn_sync_bwd_sums: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const float* part = partials;
+    if (!partials) {
+        if (ws_bytes < zsg_bn_workspace_bytes(rows, C)) ZSG_FAIL(-2, "bn_sync_bwd_sums: workspace too small");
+        const BnGeom g = bn_geom(rows, C);
+        ZSG_PROF("bn_backward", st, 0, (double)rows * C * (8 + (relu_mask ? 0.25 : 0)));
+        ZSG_LAUNCH((bn_partial_kernel<1>), dim3(g.chunks, g.slabs), dim3(256), 0, st, x, dout, nullptr, relu_mask, mean, invstd, rows, C,
+                           g.lanes, g.rpb, (float*)ws);
+        part = (const float*)ws;
+        chunks = g.chunks;
+    } else {
+        ZSG_PROF("bn_backward", st, 0, (double)chunks * C * 8);
+    }
+    ZSG_LAUNCH(bn_sync_sums_kernel<BN_FW>, dim3(C / 4), dim3(64 * BN_FW), 0, st, part, chunks, C, (int64_t)-1, sums, dgamma, dbeta, accumulate);
+    ZSG_CHECK_LAUNCH("bn_sync_bwd_sums");
+    return 0;
+}
+
+extern "C" int zsg_bn_sync_bwd_apply(const float* dout, const uint8_t* relu_mask, const float* x, int64_t rows, int32_t C, const float* mean,
+                                     const float* invstd, const float* gamma, const double* sums, const double* fwd_sums, float* dx, float* g_out,
+                                     void* stream) {
+    ZSG_REQUIRE(dout && x && mean && invstd && gamma && sums && fwd_sums && dx && rows > 0 && C > 0 && (C % 4) == 0,
+                "bn_sync_bwd_apply: bad argument");
+    const BnGeom g = bn_geom(rows, C);
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("bn_backward", st, 0, (double)rows * C * (4 * (2 + 1 + (g_out ? 1 : 0)) + (relu_mask ? 0.25 : 0)));
+    ZSG_LAUNCH(bn_sync_bwd_apply_kernel, dim3(g.chunks, g.slabs), dim3(256), 0, st, dout, relu_mask, x, rows, C, mean, invstd, gamma, sums,
+                       fwd_sums, dx, g_out, g.lanes, g.rpb);
+    ZSG_CHECK_LAUNCH("bn_sync_bwd_apply");
+    return 0;
+}
+
+// Stem, split at the collective: the sums pass over the POOLED gradient (bn_pool_bwd_partial_kernel: the ReLU test at the arg-max
+// position) ...  ws: >= zsg_bn_workspace_bytes(B * Ho * Wo, C)
+extern "C" int zsg_bn_sync_relu_maxpool_bwd_sums(const float* dout, const uint8_t* idx, const float* x, int32_t B, int32_t H, int32_t W,
+                                                 int32_t C, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                                 int32_t k, int32_t s, int32_t p, int32_t Ho, int32_t Wo, double* sums, float* dgamma,
+                                                 float* dbeta, int32_t accumulate, void* ws, size_t ws_bytes, void* stream) {
+    ZSG_REQUIRE(dout && idx && x && mean && invstd && gamma && beta && sums && ws && B > 0 && Ho > 0 && Wo > 0 && C > 0 && (C % 4) == 0 &&
+                    k > 0 && k <= 15 && s > 0,
+                "bn_sync_relu_maxpool_bwd_sums: bad argument");
+    const int64_t prow = (int64_t)B * Ho * Wo;
+    if (ws_bytes < zsg_bn_workspace_bytes(prow, C)) ZSG_FAIL(-2, "bn_sync_relu_maxpool_bwd_sums: workspace too small");
+    const BnGeom gp = bn_geom(prow, C);
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("bn_backward", st, 0, (double)prow * 2.25 * C * 4);
+    float* part = (float*)ws;
+    ZSG_LAUNCH(bn_pool_bwd_partial_kernel, dim3(gp.chunks, gp.slabs), dim3(256), 0, st, dout, idx, x, H, W, C, k, s, p, Ho, Wo, mean, invstd,
+                       gamma, beta, prow, gp.lanes, gp.rpb, part);
+    ZSG_LAUNCH(bn_sync_sums_kernel<BN_FW>, dim3(C / 4), dim3(64 * BN_FW), 0, st, part, gp.chunks, C, (int64_t)-1, sums, dgamma, dbeta,
+                       accumulate);
+    ZSG_CHECK_LAUNCH("bn_sync_relu_maxpool_bwd_sums");
+    return 0;
+}
+
+// ... and the per-input-pixel apply with the global coefficients
+extern "C" int zsg_bn_sync_relu_maxpool_bwd_apply(const float* dout, const uint8_t* idx, const float* x, int32_t B, int32_t H, int32_t W,
+                                                  int32_t C, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                                  int32_t k, int32_t s, int32_t p, int32_t Ho, int32_t Wo, const double* sums,
+                                                  const double* fwd_sums, float* dx, void* stream) {
+    ZSG_REQUIRE(dout && idx && x && mean && invstd && gamma && beta && sums && fwd_sums && dx && B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 &&
+                    C > 0 && (C % 4) == 0 && k > 0 && k <= 15 && s > 0,
+                "bn_sync_relu_maxpool_bwd_apply: bad argument");
+    const int64_t prow = (int64_t)B * Ho * Wo, rows = (int64_t)B * H * W;
+    const BnGeom g = bn_geom(rows, C);
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("bn_backward", st, 0, ((double)prow * 1.25 + (double)rows * 2) * C * 4);
+    ZSG_LAUNCH(bn_sync_pool_bwd_apply_kernel, dim3(g.chunks, g.slabs), dim3(256), 0, st, dout, idx, x, H, W, C, k, s, p, Ho, Wo, mean, invstd,
+                       gamma, beta, sums, fwd_sums, rows, dx, g.lanes, g.rpb);
+    ZSG_CHECK_LAUNCH("bn_sync_relu_maxpool_bwd_apply");
+    return 0;
+}

@@ -263,6 +263,8 @@ class DistributedDataParallel(nn.Module):
         key = tuple(geo[:3]) + (self.module.training,)
         if self.module.training and hasattr(self.module, "_frozen_bn_key"):
             key += (self.module._frozen_bn_key(),)       # (frozen BatchNorm layers lower other launches: tuned anew, broadcast anew)
+        if self.module.training and hasattr(self.module, "_sync_bn_key"):
+            key += (self.module._sync_bn_key(),)         # (so do synchronized ones: no in-kernel statistics finalize)
         if key in self._tuned:
             return
         self._tuned.add(key)
@@ -295,6 +297,16 @@ class DistributedDataParallel(nn.Module):
 
     def make_reducer(self, spans) -> BucketReducer:
         return BucketReducer(self.module.store.grad, plan_buckets(spans, self.bucket_elems, self.tail_elems), self.group, self.comm)
+
+
+def convert_sync_batchnorm(module, process_group=None, force: bool = False):
+    """torch.nn.SyncBatchNorm.convert_sync_batchnorm for ZSGNet (whose BatchNorm layers torch's converter does not find): the train-mode
+    BatchNorm layers of `module` — a ZSGNet or its DistributedDataParallel wrapper — normalise with the statistics of the union of the
+    batches of `process_group`'s ranks (ZSGNet.sync_batchnorm).  A collective call: every rank of the default group makes it with the
+    same process_group (per-node subgroups are not supported), and it creates the BatchNorm collectives' own group.  force=True syncs in a 1-rank group too (tests, measurements).  Returns `module`."""
+    net = module.module if isinstance(module, DistributedDataParallel) else module
+    net.sync_batchnorm(process_group=process_group, enable=True, force=force)
+    return module
 
 
 def reduce_dict(input_dict, average=False, all_ranks: bool = True):

@@ -52,6 +52,8 @@ def learner_init(uid: str, cfg):
     mdl = get_default_net(num_anchors=num_anchors, cfg=cfg)
     mdl.to(device)
     if cfg["do_dist"]:
+        if cfg.get("sync_bn", False):
+            zdist.convert_sync_batchnorm(mdl)          # (a collective call: every rank reaches it)
         mdl = zdist.DistributedDataParallel(mdl, device_ids=[cfg["local_rank"]], output_device=cfg["local_rank"],
                                             broadcast_buffers=True, find_unused_parameters=True)
     loss_fn = get_default_loss(ratios, scales, cfg)

@@ -137,6 +137,8 @@ class ZSGNet(nn.Module):
         self._plans: Dict[Tuple, "_Plan"] = {}
         self._anchor = None
         self._bn_eval = set()          # BatchNorm layers freeze_batchnorm() keeps in eval mode across train()
+        self._sync_bn_group = None     # process group of the synchronized BatchNorm collectives (sync_batchnorm), None: per-rank statistics
+        self._sync_bn_conf = None      # (process group it was made for, force) of that group
         self.debug = False
         LIVE_NETS.add(self)
 
@@ -470,24 +472,58 @@ class ZSGNet(nn.Module):
         """running-statistics order indices of the BatchNorm layers in eval mode (frozen inside a training network)"""
         return tuple(i for i, (_, m) in enumerate(self.batchnorm_modules()) if not m.training)
 
+    def sync_batchnorm(self, process_group=None, enable: bool = True, force: bool = False) -> "ZSGNet":
+        """torch.nn.SyncBatchNorm for this network's BatchNorm layers (they are NamedTree nodes: torch's convert_sync_batchnorm finds none).
+        enable=True: every train-mode layer of a training forward normalises with the mean / variance of the union of the batches of
+        `process_group`'s ranks (default: the whole world) and back-propagates through them; its d(gamma) / d(beta) stay the rank's own
+        sums, which the gradient reducer averages.  Eval-mode layers (freeze_batchnorm) and eval forwards are not synced.  A collective call:
+        every rank of the default group makes it with the SAME process_group (dist.new_group over its ranks, which new_group requires of
+        every rank: the BatchNorm collectives get a group of their own, never the gradient reducer's).  Per-node subgroups — each rank
+        passing its own subgroup, as torch.nn.SyncBatchNorm allows — are not supported: a rank outside process_group raises.  A group of
+        one rank syncs only with force=True; without an initialised process group the network keeps per-rank statistics (torch's
+        SyncBatchNorm falls back to batch_norm there).  enable=False returns to per-rank statistics."""
+        import torch.distributed as dist
+        group = None
+        if enable and dist.is_available() and dist.is_initialized():
+            pg = process_group if process_group is not None else dist.group.WORLD
+            if pg is not dist.group.WORLD and dist.get_rank(pg) < 0:
+                raise ValueError("sync_batchnorm: this rank is not in process_group (every rank must pass the same group that contains it)")
+            ranks = dist.get_process_group_ranks(pg)
+            if len(ranks) > 1 or force:
+                if self._sync_bn_group is not None and self._sync_bn_conf == (pg, force):
+                    group = self._sync_bn_group
+                else:
+                    group = dist.new_group(ranks=ranks)
+        elif enable and force:
+            raise RuntimeError("sync_batchnorm(force=True) needs an initialised torch.distributed process group")
+        self._sync_bn_group = group
+        self._sync_bn_conf = (process_group if process_group is not None else dist.group.WORLD, force) if group is not None else None
+        return self
+
+    def _sync_bn_key(self) -> Tuple[int, ...]:
+        """running-statistics order indices of the BatchNorm layers a training forward synchronizes across ranks (sync_batchnorm)"""
+        if self._sync_bn_group is None:
+            return ()
+        return tuple(i for i, (_, m) in enumerate(self.batchnorm_modules()) if m.training)
+
     def _plan_for(self, B, H, W, T) -> "_Plan":
         if not self.training:
             key = (B, H, W, T, False)
             if key not in self._plans:
                 self._plans[key] = _Plan(self, B, H, W, T, False)
             return self._plans[key]
-        fz, fb = self._frozen_key(), self._frozen_bn_key()
-        key = (B, H, W, T, fz, fb, True)
+        fz, fb, sb = self._frozen_key(), self._frozen_bn_key(), self._sync_bn_key()
+        key = (B, H, W, T, fz, fb, sb, True)
         if key not in self._plans:
-            # a new trainable set or frozen-BatchNorm set: the training plans of the old one go (gradual unfreezing must not pile up
-            # activation buffers)
-            for k in [k for k in self._plans if k[-1] and (k[4], k[5]) != (fz, fb)]:
+            # a new trainable set, frozen-BatchNorm set or synchronized-BatchNorm set: the training plans of the old one go (gradual
+            # unfreezing must not pile up activation buffers)
+            for k in [k for k in self._plans if k[-1] and (k[4], k[5], k[6]) != (fz, fb, sb)]:
                 old = self._plans.pop(k)
                 if old._prep_pending:           # (its side-stream weight preparation may still be reading the weights)
                     torch.cuda.current_stream().wait_event(old._prep_ev)
             bn_names = list(self.bns)
             self._plans[key] = _Plan(self, B, H, W, T, True, frozen={self._param_names[i] for i in fz},
-                                     frozen_bn={bn_names[i] for i in fb})
+                                     frozen_bn={bn_names[i] for i in fb}, sync_bn={bn_names[i] for i in sb})
         return self._plans[key]
 
     def forward(self, inp: Dict[str, Any]) -> Dict[str, Any]:
@@ -540,12 +576,22 @@ class _NetFn(torch.autograd.Function):
 class _Plan:
     """Static lowering of ZSGNet for one (B, H, W, T, training) geometry."""
 
-    def __init__(self, net: ZSGNet, B: int, H: int, W: int, T: int, training: bool, frozen=frozenset(), frozen_bn=frozenset()):
+    def __init__(self, net: ZSGNet, B: int, H: int, W: int, T: int, training: bool, frozen=frozenset(), frozen_bn=frozenset(),
+                 sync_bn=frozenset()):
         self.net, self.B, self.H, self.W, self.T, self.training = net, B, H, W, T, training
         # BatchNorm layers in eval mode inside this training network: running statistics in the forward (one zsg_bn_eval_stats launch),
         # no statistics update, F.batch_norm(training=False)'s backward (zsg_bn_frozen_backward / zsg_bn_frozen_relu_maxpool_bwd)
         self.frozen_bn = frozenset(frozen_bn) if training else frozenset()
         self._ev_stats = None
+        # BatchNorm layers synchronized across the ranks of net._sync_bn_group (ZSGNet.sync_batchnorm): every statistics pass stops at
+        # rank-local fp64 sums (zsg_bn_sync_*), a host op of the program all-reduces them on the stream of its lane, and the finalize /
+        # apply restarts from the global sums.  sync_bn_paths records the forms each layer took: forward 'partials' (the producing
+        # convolution's epilogue rows) or 'x' (a pass over the input), '+bnpre' (applied by the next convolution's loader); backward
+        # 'bnb' (the data gradient's epilogue rows), 'plain' (a pass over dout / x) or 'stem'; '+alias' when the residual's gradient
+        # aliases dout
+        self.sync_bn = (frozenset(sync_bn) - self.frozen_bn) if training else frozenset()
+        self.sync_bn_paths: Dict[str, str] = {}
+        self._sync_sums: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
         # which backward form each frozen layer got (_bn_frozen_back): 'bnb+fin' / 'bnb' (sums from the data gradient's epilogue, with or
         # without its in-kernel finalize), 'onepass' (zsg_bn_frozen_backward reduces them), 'scale' (no sums: frozen affine); '+alias' when
         # the residual's gradient aliases dout
@@ -677,6 +723,43 @@ class _Plan:
         m, s = self._ev_stats
         return m[L.index:L.index + L.c], s[L.index:L.index + L.c]
 
+    def bn_synced(self, L: Optional[BnL]) -> bool:
+        """the BatchNorm layer L normalises with statistics all-reduced over the ranks (ZSGNet.sync_batchnorm)"""
+        return L is not None and L.name in self.sync_bn
+
+    def _sync_bufs(self, L: BnL) -> Tuple[torch.Tensor, torch.Tensor]:
+        """the layer's fp64 sums, allocated with the plan: forward [sum x | sum x^2 | n] (kept for the backward's N), backward
+        [sum g | sum g * xhat]"""
+        if L.name not in self._sync_sums:
+            f = torch.zeros(2 * L.c + 1, dtype=torch.float64, device=self.dev)
+            b = torch.zeros(2 * L.c, dtype=torch.float64, device=self.dev)
+            self.bytes += (f.numel() + b.numel()) * 8
+            self._sync_sums[L.name] = (f, b)
+        return self._sync_sums[L.name]
+
+    def _allreduce(self, prog: Program, buf: torch.Tensor, what: str, lane: int):
+        """a host op of `prog`: SUM-all-reduce of `buf` over the BatchNorm group, issued from the stream of `lane` (nccl: stream-ordered,
+        work.wait() makes that stream wait; gloo blocks the host)"""
+        import torch.distributed as dist
+        net = self.net
+
+        def allreduce():
+            # (the group is read when the op runs: a later conversion with another process group over the same layers keeps this plan)
+            dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=net._sync_bn_group, async_op=True).wait()
+        prog.add_host(allreduce, what=what, lane=lane)
+
+    def _sync_fwd_stats(self, L: BnL, x: Optional[torch.Tensor], rows: int, partials, chunks: int, mean, invstd, lane: int, ws=None):
+        """synchronized statistics: local sums (from the partial rows, else one pass over x) -> all-reduce -> finalize (mean, invstd,
+        running statistics from the global sums)"""
+        fs, _ = self._sync_bufs(L)
+        rm, rv = self.net._rm[L.index:L.index + L.c], self.net._rv[L.index:L.index + L.c]
+        if partials is not None:
+            self.fwd.add(lib.zsg_bn_sync_fwd_sums, None, rows, L.c, partials, chunks, fs, None, 0, what="bnsums:" + L.name, lane=lane)
+        else:
+            self.fwd.add(lib.zsg_bn_sync_fwd_sums, x, rows, L.c, None, 0, fs, ws, self.ws_bytes, what="bnsums:" + L.name, lane=lane)
+        self._allreduce(self.fwd, fs, "allreduce:" + L.name, lane)
+        self.fwd.add(lib.zsg_bn_sync_fwd_finalize, fs, L.c, mean, invstd, rm, rv, 0.1, 1e-5, what="stats:" + L.name, lane=lane)
+
     def P(self, name):      # raw parameter storage
         return self.net.store.raw(name)
 
@@ -788,7 +871,8 @@ class _Plan:
             self.prep_u.add(lib.zsg_memset_f32, out.buf[lv0.off:], out.B * lv0.bstride, 0.0, what="zero:" + L.name)
             pre_zero = out.buf
         tail_n = -1
-        if partials is not None:
+        sync = self.bn_synced(bn_fuse)
+        if partials is not None and not sync:
             # BatchNorm statistics FINALISED by the last-arriving tile of the convolution (csrc/bn_tail.h, round 5): no finalize launch, no
             # re-reduction in the apply pass, wherever the launch has <= 128 partial rows per column block (tail_n > 0)
             tail_n = int(lib.zsg_conv_bn_tail_tickets(_ct.byref(d), 1 if d.use_wino else 0))
@@ -808,6 +892,11 @@ class _Plan:
             self._zero_calls.append(self.fwd.calls[-1])
         if tail_n > 0:
             pass
+        elif partials is not None and sync:
+            # synchronized statistics from the partial rows, at once (the shared workspace is reused by the next launch)
+            rows = sum(src.B * d.seg[i].rows_y * d.seg[i].rows_x for i in range(d.nseg))
+            out.bn_mean, out.bn_invstd = self._buf(bn_fuse.c), self._buf(bn_fuse.c)
+            self._sync_fwd_stats(bn_fuse, None, rows, partials, out.bn_chunks, out.bn_mean, out.bn_invstd, self._lane)
         elif partials is not None and out.bn_chunks <= lib.zsg_bn_inline_max_chunks():
             # few partial rows: the BatchNorm apply launch (the very next launch on this stream: the workspace is still intact)
             # reduces them itself — no finalize launch
@@ -865,9 +954,16 @@ class _Plan:
         chunks = igemm_partial_rows(d)
         assert chunks * 2 * L.cout * 4 <= self.ws_bytes
         partials, out.bn_chunks = self._ws_now(), chunks
-        tail_n = int(lib.zsg_conv_bn_tail_tickets(_ct.byref(d), 0))
+        sync = self.bn_synced(Lb)
+        tail_n = int(lib.zsg_conv_bn_tail_tickets(_ct.byref(d), 0)) if not sync else 0
         rm, rv = self.net._rm[Lb.index:Lb.index + Lb.c], self.net._rv[Lb.index:Lb.index + Lb.c]
-        if tail_n > 0:
+        if sync:
+            # (no tickets: the partial rows stop at the rank-local sums, finalised from the all-reduced ones)
+            self.fwd.add(fn, d, x.buf, wt, out.buf, partials, None, None, None, None, None, 0.1, 1e-5, *pre, what=what, lane=lane)
+            out.bn_mean, out.bn_invstd = self._buf(Lb.c), self._buf(Lb.c)
+            self._sync_fwd_stats(Lb, None, src.B * d.seg[0].rows_y * d.seg[0].rows_x, partials, out.bn_chunks, out.bn_mean, out.bn_invstd,
+                                 self._lane)
+        elif tail_n > 0:
             tk = self._buf(tail_n, dtype=torch.int32)
             out.bn_mean, out.bn_invstd = self._buf(Lb.c), self._buf(Lb.c)
             self.fwd.add(fn, d, x.buf, wt, out.buf, partials, tk, out.bn_mean, out.bn_invstd, rm, rv, 0.1, 1e-5, *pre, what=what + "+bnstat", lane=lane)
@@ -1058,8 +1154,11 @@ class _Plan:
         rm, rv = net._rm[L.index:L.index + L.c], net._rv[L.index:L.index + L.c]
         self.ws_need = max(getattr(self, "ws_need", 0), lib.zsg_bn_workspace_bytes(rows, L.c))
         gam, bet = self.P(L.name + ".weight"), self.P(L.name + ".bias")
+        sync = self.bn_synced(L)
         if fused or frozen:
             pass                          # statistics were finalized right after the producing convolution / are the running ones
+        elif sync:
+            self._sync_fwd_stats(L, x.buf, rows, None, 0, mean, invstd, self._lane, ws=self._ws_now())
         elif self.training:
             self.fwd.add(lib.zsg_bn_stats, x.buf, rows, L.c, mean, invstd, rm, rv, 0.1, 1e-5, self._ws_now(), self.ws_bytes, what=L.name, lane=self._lane)
         else:
@@ -1080,12 +1179,17 @@ class _Plan:
                          int(relu), out.buf, rmask, what=L.name, lane=lane)
 
         out.bn_out = self.training
+        if sync:
+            self.sync_bn_paths[L.name] = ("partials" if fused else "x") + ("+bnpre" if defer else "")
 
         def back():
             if out.grad is None:
                 return
             if frozen:
                 self._bn_frozen_back(L, x, out, residual, relu, rmask, rows, mean, invstd, gam)
+                return
+            if sync:
+                self._bn_sync_back(L, x, out, residual, relu, rmask, rows, mean, invstd, gam)
                 return
             dx = self.grad_of(x)
             lw = getattr(out.grad, "last_writer", None)
@@ -1145,6 +1249,50 @@ class _Plan:
             dx.gfilled = True
         self.tape.append(back)
         return out
+
+    def _bn_sync_back(self, L: BnL, x: Act, out: Act, residual: Optional[Act], relu: bool, rmask, rows: int, mean, invstd, gam):
+        """Backward of a synchronized BatchNorm [+ residual] [+ ReLU] (torch's SyncBatchNorm): the rank-local (sum g, sum g * xhat) — from
+        the epilogue of the data gradient that completed dout (zsg_conv_*_bnb, never the in-kernel finalize: the sums are not final
+        here) or from one pass over dout / x — with the rank's own d(gamma) / d(beta); an all-reduce; the apply from the global sums and
+        the forward's global N.  The residual gradient may alias dout exactly as in bn()'s back."""
+        dx = self.grad_of(x)
+        fs, bs = self._sync_bufs(L)
+        lw = getattr(out.grad, "last_writer", None)
+        fuse = (BNB_FUSE and lw is not None and lw[0] == len(self.bwd.calls) - 1 and self.bwd.lanes[lw[0]] == 0
+                and len(out.grad.levels) == 1 and out.grad.levels[0].off == 0 and x.levels[0].off == 0 and out.grad.ld == L.c and x.ld == L.c)
+        if fuse:
+            idx, d, a, what = lw
+            chunks = self._wino_chunks(d, x.B) if d.use_wino else igemm_partial_rows(d)
+            fuse = chunks * 2 * L.c * 4 + 2 * L.c * 4 <= self.ws_bytes
+        g_out, bits = None, rmask
+        if residual is not None and residual.requires_grad:
+            alias = (fuse and relu and rmask is not None and residual.grad is None and len(residual.levels) == 1
+                     and residual.levels[0].off == 0 and residual.ld == L.c and residual.C == L.c and residual.buf.numel() == out.grad.buf.numel())
+            if alias:
+                residual.grad = out.grad
+                lw[1].epi_flags |= 1
+                bits = None
+            else:
+                rg = self.grad_of(residual)
+                assert not rg.gfilled, "residual gradient must be produced first (tape order)"
+                g_out = rg.buf
+                rg.gfilled = True
+        dg, db = self.G(L.name + ".weight"), self.G(L.name + ".bias")
+        if fuse:
+            part = self.ws[2 * L.c:]
+            assert a[3] is None and a[5] is None and a[6] is None
+            fn = lib.zsg_conv_wino_bnb if d.use_wino else lib.zsg_conv_igemm_bnb
+            self.bwd.calls[idx] = (fn, marshal(fn, (d, a[0], a[1], a[2], a[4], x.buf, mean, invstd, rmask, part), self.bwd.keep), what + "+bnb")
+            self.bwd.add(lib.zsg_bn_sync_bwd_sums, None, None, None, rows, L.c, None, None, part, chunks, bs, dg, db, 1, None, 0,
+                         what="bnsums:" + L.name)
+        else:
+            self.bwd.add(lib.zsg_bn_sync_bwd_sums, self.base(out.grad), rmask, x.buf, rows, L.c, mean, invstd, None, 0, bs, dg, db, 1,
+                         self.ws, self.ws_bytes, what="bnsums:" + L.name)
+        self._allreduce(self.bwd, bs, "allreduce:bnbwd:" + L.name, 0)
+        self.bwd.add(lib.zsg_bn_sync_bwd_apply, self.base(out.grad), bits, x.buf, rows, L.c, mean, invstd, gam, bs, fs, dx.buf, g_out,
+                     what="bnbwd:" + L.name)
+        self.sync_bn_paths[L.name] += "/" + ("bnb" if fuse else "plain") + ("+alias" if bits is None and rmask is not None else "")
+        dx.gfilled = True
 
     def _bn_frozen_back(self, L: BnL, x: Act, out: Act, residual: Optional[Act], relu: bool, rmask, rows: int, mean, invstd, gam):
         """Backward of a frozen BatchNorm [+ residual] [+ ReLU]: dx = gamma * invstd * g with g = dout * relu-bit, d(gamma) / d(beta) for
@@ -1403,8 +1551,16 @@ class _Plan:
         gam, bet = self.P(Lb.name + ".weight"), self.P(Lb.name + ".bias")
         self.ws_need = max(getattr(self, "ws_need", 0), lib.zsg_bn_workspace_bytes(rows, Lb.c))
         frozen = self.bn_frozen(Lb)
+        sync = self.bn_synced(Lb)
         if frozen:
             mean, invstd = self._eval_stats(Lb)         # (conv() computed no statistics: the forward pass runs on the running ones)
+        elif sync:
+            if getattr(y, "bn_chunks", 0) > 0:          # (conv() synchronized them from its partial rows)
+                mean, invstd = y.bn_mean, y.bn_invstd
+            else:
+                mean, invstd = self._buf(Lb.c), self._buf(Lb.c)
+                self._sync_fwd_stats(Lb, y.buf, rows, None, 0, mean, invstd, 0, ws=self.ws)
+            self.sync_bn_paths[Lb.name] = "partials" if getattr(y, "bn_chunks", 0) > 0 else "x"
         elif getattr(y, "bn_chunks", 0) > 0:
             mean, invstd = y.bn_mean, y.bn_invstd
             if y.bn_inline is not None:          # few partial rows (small inputs): nobody else will finalize them
@@ -1433,6 +1589,18 @@ class _Plan:
                     dy.gfilled = True
                 return
             dy = self.grad_of(y)
+            if sync:
+                # zsg_bn_relu_maxpool_bwd split at the collective: rank-local sums over the pooled gradient, all-reduce, apply per input pixel
+                fs, bs = self._sync_bufs(Lb)
+                self.bwd.add(lib.zsg_bn_sync_relu_maxpool_bwd_sums, self.base(x.grad), idx, y.buf, B, H1, W1, Lb.c, mean, invstd, gam, bet, 3, 2,
+                             1, H2, W2, bs, self.G(Lb.name + ".weight"), self.G(Lb.name + ".bias"), 1, self.ws, self.ws_bytes,
+                             what="bnsums+maxpool_bwd:" + Lb.name)
+                self._allreduce(self.bwd, bs, "allreduce:bnbwd:" + Lb.name, 0)
+                self.bwd.add(lib.zsg_bn_sync_relu_maxpool_bwd_apply, self.base(x.grad), idx, y.buf, B, H1, W1, Lb.c, mean, invstd, gam, bet, 3, 2,
+                             1, H2, W2, bs, fs, dy.buf, what="bnbwd+maxpool_bwd:" + Lb.name)
+                self.sync_bn_paths[Lb.name] += "/stem"
+                dy.gfilled = True
+                return
             self.bwd.add(lib.zsg_bn_relu_maxpool_bwd, self.base(x.grad), idx, y.buf, B, H1, W1, Lb.c, mean, invstd, gam, bet, 3, 2, 1, H2, W2, dy.buf,
                          self.G(Lb.name + ".weight"), self.G(Lb.name + ".bias"), 1, self.ws, self.ws_bytes, what="bnbwd+maxpool_bwd:" + Lb.name)
             dy.gfilled = True

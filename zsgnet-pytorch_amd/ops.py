@@ -272,8 +272,46 @@ def ensure_stream_scratch(stream: int):
     return _SCRATCH[key]
 
 
+_EXT_STREAMS = {}
+
+
+def torch_stream(ptr: int) -> torch.cuda.Stream:
+    """torch's Stream object for a hipStream_t (the caller's current stream, the shared side stream, or a wrapped external one)"""
+    cur = torch.cuda.current_stream()
+    if cur.cuda_stream == ptr:
+        return cur
+    for s in _SIDE.values():
+        if s.cuda_stream == ptr:
+            return s
+    if ptr not in _EXT_STREAMS:
+        _EXT_STREAMS[ptr] = torch.cuda.ExternalStream(ptr)
+    return _EXT_STREAMS[ptr]
+
+
+class HostOp:
+    """A Python callable in a Program's launch order (Program.add_host): fn() runs on the host when the replay reaches it, with torch's
+    current stream set to the stream of its lane — a collective it issues is ordered after everything enqueued there before it, and
+    whatever the program enqueues on that stream afterwards is ordered after the collective (nccl: work.wait() makes the stream wait; the
+    host does not block).  It launches nothing through the library, so a completion event the schedule wants on it becomes a marker
+    (Program._run_lanes)."""
+    __name__ = "host"
+
+    def __init__(self, fn):
+        self.fn = fn
+
+    def __call__(self, st) -> int:
+        s = torch_stream((st.value if isinstance(st, C.c_void_p) else st) or 0)
+        if s == torch.cuda.current_stream():
+            self.fn()
+        else:
+            with torch.cuda.stream(s):
+                self.fn()
+        return 0
+
+
 class Program:
-    """A static list of foreign calls.  `add(fn, *args)` marshals once; `run(stream)` replays."""
+    """A static list of foreign calls.  `add(fn, *args)` marshals once; `run(stream)` replays.  `add_host(fn)` puts a Python callable
+    (a collective) in the same order."""
 
     def __init__(self, name: str = ""):
         self.name = name
@@ -290,6 +328,11 @@ class Program:
 
     def add(self, fn, *args, what: str = "", lane: int = 0):
         self.calls.append((fn, marshal(fn, args, self.keep), what or fn.__name__))
+        self.lanes.append(lane)
+
+    def add_host(self, fn, what: str = "", lane: int = 0):
+        """fn() called on the host in program order, with torch's current stream = the stream of `lane` (HostOp)"""
+        self.calls.append((HostOp(fn), (), what or getattr(fn, "__name__", "host")))
         self.lanes.append(lane)
 
     def _error(self, what: str, rc: int) -> ZsgError:
