@@ -406,6 +406,14 @@ int zsg_stage_inputs(const float* qvec, int32_t B, int32_t T, int32_t E, int32_t
  * starts at B * N * sum_{j<i} h_j w_j); G (or NULL) packed the same way with B = 1; hw = {h_0, w_0, h_1, w_1, ...} (host memory,
  * nlev <= ZSG_MAX_SEG pairs).  A block sums V's taps once per border class instead of once per output element. */
 int zsg_head_lang_map_packed(const float* V, const float* G, int32_t B, int32_t nlev, const int32_t* hw, int32_t N, float* out, void* stream);
+/* conv0's epilogue of the eval-only shared-image plan (Q queries over Bi <= Q images, one launch per head stack):
+ *   h1[q][p][n] = relu( Y[img_idx[q]][p][n] + bias[n] + G[p][n] + sum_{tap valid at p} V[q][n*9 + tap] )
+ * Y [Bi][h_i*w_i][N]: the raw accumulator of conv0's feature GEMM (no bias, no ReLU); G (or NULL) and `out` as in
+ * zsg_head_lang_map_packed with batch counts 1 and Q; V [Q][N*9] or NULL; img_idx: Q device integers (int64 when idx_i64, else int32),
+ * read by the kernel — a value outside [0, Bi) yields NaN rows for that query and no access outside Y.  Image slots no query points to
+ * are never read.  Summation order: ((Y + G) + (taps row-major + bias)); N % 4 == 0, N <= 1024. */
+int zsg_head_shared_conv0(const float* Y, const void* img_idx, int32_t idx_i64, const float* bias, const float* G, const float* V, int32_t Bi, int32_t Q,
+                          int32_t nlev, const int32_t* hw, int32_t N, float* out, void* stream);
 int zsg_head_border_sums(const float* dy, int32_t B, int32_t h, int32_t w, int32_t N, float* Q /* [9][B][N], += */, void* stream);
 int zsg_head_border_finalize(const float* Q, int32_t B, int32_t N, float* S1, float* S2, float* bias_grad /* [N], += ; or NULL */,
                              void* stream);

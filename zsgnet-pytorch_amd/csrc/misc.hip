@@ -867,6 +867,100 @@ extern "C" int zsg_head_lang_map_packed(const float* V, const float* G, int32_t 
     return 0;
 }
 
+// Head conv0's epilogue when several queries share one image (the eval-only shared plan, mdl._Plan with Q queries over Bi images): the
+// feature GEMM ran once per IMAGE and left its raw accumulator Y[Bi][P][N]; this launch expands it to one h1 row block per QUERY,
+//   h1[q][p][n] = relu( Y[img_idx[q]][p][n] + bias[n] + G[p][n] + sum_{tap valid at p} V[q][n*9 + tap] ),
+// for every pyramid level at once (Y, G, h1 packed level-major with batch counts Bi, 1, Q) — it replaces zsg_head_lang_map_packed AND the
+// bias / add_src / ReLU epilogue of conv0.  FIXED SUMMATION ORDER (the result is pinned to a tolerance, not to the bits of the unshared
+// path, whose epilogue adds in another order):  c = (taps in row-major order, summed from 0) + bias;  h1 = relu((Y + G) + c);  without G:
+// relu(Y + c);  without V: c = bias.  As in the packed map, a block builds the 16 border-class values c[cls][n] of ITS query once in LDS,
+// then streams 16 bytes per lane.  Block order: the query index runs fastest, so the Q blocks that cover one pixel range are adjacent and
+// the queries of one image read the same Y lines back to back; the blocks are dealt so that such a run lands on one XCD (b and b + 8
+// share an L2 under round-robin placement: a speed matter only), i.e. Y is read from HBM once per image and from L2 for the other queries.
+// A query whose index lies outside [0, Bi) gets NaN rows: nothing is ever read outside Y.
+__global__ __launch_bounds__(256) void head_shared_conv0_kernel(const float* __restrict__ Y, const void* __restrict__ img_idx, int idx_i64,
+                                                                const float* __restrict__ bias, const float* __restrict__ G, const float* __restrict__ V,
+                                                                int Bi, int Q, int N, LangMapLevels L, float* __restrict__ out, int parts, int nblocks, int n8) {
+    extern __shared__ __attribute__((aligned(16))) float S[];      // [16][N]
+    const int lb = (int)(blockIdx.x % 8) * n8 + (int)(blockIdx.x / 8);
+    if (lb >= nblocks) return;                                     // (block-uniform, in front of the barrier)
+    const int part = lb / Q, q = lb - part * Q;
+    const long long im = idx_i64 ? ((const long long*)img_idx)[q] : (long long)((const int*)img_idx)[q];
+    const bool live = im >= 0 && im < Bi;
+    for (int n = threadIdx.x; n < N; n += 256) {
+        float v[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) v[t] = V ? V[(int64_t)q * N * 9 + (int64_t)n * 9 + t] : 0.f;
+        const float bn = bias[n];
+#pragma unroll
+        for (int cls = 0; cls < 16; ++cls) {       // bit 0: top row, 1: bottom row, 2: left column, 3: right column
+            float a = 0.f;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                if ((r == 0 && (cls & 1)) || (r == 2 && (cls & 2))) continue;
+#pragma unroll
+                for (int t = 0; t < 3; ++t) {
+                    if ((t == 0 && (cls & 4)) || (t == 2 && (cls & 8))) continue;
+                    a += v[r * 3 + t];
+                }
+            }
+            S[cls * N + n] = a + bn;
+        }
+    }
+    __syncthreads();
+    const int n4 = N / 4, P = L.p0[L.nlev];
+    const int64_t total = (int64_t)P * n4;
+    const float qnan = __builtin_nanf("");
+    for (int64_t i = (int64_t)part * 256 + threadIdx.x; i < total; i += (int64_t)parts * 256) {
+        const int c = (int)(i % n4) * 4;
+        const int p = (int)(i / n4);
+        int lv = 0;
+#pragma unroll
+        for (int j = 1; j < ZSG_MAX_SEG; ++j)
+            if (j < L.nlev && p >= L.p0[j]) lv = j;
+        const int px = p - L.p0[lv], w = L.w[lv], h = L.h[lv];
+        const int y = px / w, x = px - y * w;
+        const int cls = (y == 0 ? 1 : 0) | (y == h - 1 ? 2 : 0) | (x == 0 ? 4 : 0) | (x == w - 1 ? 8 : 0);
+        f32x4 acc;
+        if (live) {
+            acc = *(const f32x4*)(Y + ((int64_t)Bi * L.p0[lv] + im * h * w + px) * N + c);
+            if (G) acc += *(const f32x4*)(G + ((int64_t)L.p0[lv] + px) * N + c);
+            acc += *(const f32x4*)(S + cls * N + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] = fmaxf(acc[e], 0.f);
+        } else {
+            acc = f32x4{qnan, qnan, qnan, qnan};
+        }
+        *(f32x4*)(out + ((int64_t)Q * L.p0[lv] + (int64_t)q * h * w + px) * N + c) = acc;
+    }
+}
+extern "C" int zsg_head_shared_conv0(const float* Y, const void* img_idx, int32_t idx_i64, const float* bias, const float* G, const float* V, int32_t Bi, int32_t Q,
+                                     int32_t nlev, const int32_t* hw, int32_t N, float* out, void* stream) {
+    ZSG_REQUIRE(Y && img_idx && bias && out && hw && Bi > 0 && Q > 0 && nlev > 0 && nlev <= ZSG_MAX_SEG && N > 0 && (N % 4) == 0 && N <= 1024,
+                "head_shared_conv0: bad argument");
+    LangMapLevels L;
+    memset(&L, 0, sizeof(L));
+    L.nlev = nlev;
+    for (int i = 0; i < nlev; ++i) {
+        ZSG_REQUIRE(hw[2 * i] > 0 && hw[2 * i + 1] > 0, "head_shared_conv0: level %d is empty", i);
+        L.h[i] = hw[2 * i];
+        L.w[i] = hw[2 * i + 1];
+        L.p0[i + 1] = L.p0[i] + L.h[i] * L.w[i];
+    }
+    const int64_t per = (int64_t)L.p0[nlev] * (N / 4);
+    int parts = (int)((per + 256 * 8 - 1) / (256 * 8));        // ~8 16-byte elements per thread
+    const int cap = (4 * ZSG_NUM_CU + Q - 1) / Q;
+    if (parts > cap) parts = cap;
+    if (parts < 1) parts = 1;
+    const int nblocks = parts * Q, n8 = (nblocks + 7) / 8;
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("head_shared_conv0", st, 0, ((double)Q + Bi) * L.p0[nlev] * N * 4);
+    ZSG_LAUNCH(head_shared_conv0_kernel, dim3(8 * n8), dim3(256), (size_t)16 * N * sizeof(float), st, Y, img_idx, idx_i64, bias, G, V, Bi, Q, N, L, out, parts,
+               nblocks, n8);
+    ZSG_CHECK_LAUNCH("head_shared_conv0");
+    return 0;
+}
+
 // The nine validity-masked sums follow by inclusion-exclusion from nine plain sums per (image, channel):
 //   Q[0] = all pixels, Q[1]/Q[2] = first / last row, Q[3]/Q[4] = first / last column, Q[5..8] = the four corners;
 //   S(r,q) = Q0 - R(r) - C(q) + X(r,q)   with R(0) = first row (tap row 0 reads y-1: invalid at y = 0), R(2) = last row, ...

@@ -269,28 +269,56 @@ class ImgQuDataset(Dataset):
     def __len__(self):
         return len(self.files)
 
-    def __getitem__(self, idx: int) -> Dict[str, torch.Tensor]:
+    def load_image(self, idx: int) -> Tuple[torch.Tensor, int, int]:
+        """the image of row idx as the batch carries it (decoded, resized unless gpu_resize) + its decoded height / width"""
         import PIL.Image
-        q = self.queries[idx]
-        if isinstance(q, list):
-            q = str(np.random.choice(q))                          # dat_loader.py:153-154
-        q = q.replace("_", " ")
         img = PIL.Image.open(self.img_dir / self.files[idx]).convert("RGB")
         h, w = img.height, img.width
-        qvec, qlen = embed_query(self.embedder, q, self.phrase_len)
-        x1, y1, x2, y2 = self.boxes[idx]
         rs = self.cfg["resize_img"]
         if not self.gpu_resize:
             img = img.resize((rs[0], rs[1]))                      # PIL's default filter, as the reference (dat_loader.py:121)
-        target = 2 * np.array([y1 / h, x1 / w, y2 / h, x2 / w]) - 1          # y1x1y2x2 in [-1, 1] (anchors are row, column)
         a = np.asarray(img)                                       # [H, W, 3] uint8
         if self.gpu_normalise:
             img_t = torch.from_numpy(a.copy())                    # normalised on the GPU (zsg_u8hwc_to_nhwc4)
         else:
             img_t = torch.from_numpy(a.transpose(2, 0, 1).astype(np.float64)).float().div_(255)     # pil2tensor(...).float().div_(255)
-        return {"img": img_t, "idxs": torch.tensor(idx).long(), "qvec": torch.from_numpy(qvec),
+        return img_t, h, w
+
+    def query_item(self, idx: int, h: int, w: int) -> Dict[str, torch.Tensor]:
+        """the per-query fields of row idx (everything but the image, whose decoded size h, w scales the box)"""
+        q = self.queries[idx]
+        if isinstance(q, list):
+            q = str(np.random.choice(q))                          # dat_loader.py:153-154
+        q = q.replace("_", " ")
+        qvec, qlen = embed_query(self.embedder, q, self.phrase_len)
+        x1, y1, x2, y2 = self.boxes[idx]
+        target = 2 * np.array([y1 / h, x1 / w, y2 / h, x2 / w]) - 1          # y1x1y2x2 in [-1, 1] (anchors are row, column)
+        return {"idxs": torch.tensor(idx).long(), "qvec": torch.from_numpy(qvec),
                 "qlens": torch.tensor(min(qlen, self.phrase_len)), "annot": torch.from_numpy(target).float(),
                 "orig_annot": torch.tensor([x1, y1, x2, y2]).float(), "img_size": torch.tensor([h, w])}
+
+    def __getitem__(self, idx: int) -> Dict[str, torch.Tensor]:
+        img_t, h, w = self.load_image(idx)
+        item = {"img": img_t}
+        item.update(self.query_item(idx, h, w))
+        return item
+
+    def grouped_batch(self, rows: List[int]) -> Dict[str, torch.Tensor]:
+        """One batch of the grouped validation loader (cfg group_val_by_image): every distinct image file among `rows` is decoded (and
+        resized) ONCE; `img` holds the distinct images in order of first appearance and `img_idx` [Q] int64 names each query's image
+        (ZSGNet.forward's shared-image contract).  The per-query fields are collater's, in the order of `rows`."""
+        slot, imgs, sizes, items, idx = {}, [], [], [], []
+        for r in rows:
+            f = self.files[r]
+            if f not in slot:
+                img_t, h, w = self.load_image(r)
+                slot[f] = len(imgs)
+                imgs.append(img_t)
+                sizes.append((h, w))
+            k = slot[f]
+            items.append(self.query_item(r, *sizes[k]))
+            idx.append(k)
+        return grouped_collater(items, imgs, idx)
 
 
 def collater(batch: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
@@ -312,9 +340,78 @@ def collater(batch: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
     return out
 
 
+def grouped_collater(items: List[Dict[str, torch.Tensor]], imgs: List[torch.Tensor], img_idx: List[int]) -> Dict[str, torch.Tensor]:
+    """collater for queries that share images: `items` carry no image; `imgs` are the distinct images, img_idx[q] the image of query q.
+    This is where the index range is checked (on the host, once per batch): the forward reads img_idx on the device only."""
+    if not imgs or len(img_idx) != len(items) or min(img_idx) < 0 or max(img_idx) >= len(imgs):
+        raise ValueError(f"grouped_collater: img_idx out of range for {len(imgs)} images / {len(items)} queries")
+    out = collater(items)
+    if imgs[0].dtype == torch.uint8 and len({tuple(im.shape) for im in imgs}) > 1:
+        out["img"], out["img_hw"] = flatten_raw(imgs)            # raw images of different sizes (gpu_resize), as collater
+        out["img_hw"] = out["img_hw"].int()
+    else:
+        t = torch.stack(imgs)
+        out["img"] = t if t.dtype == torch.uint8 else t.float()
+    out["img_idx"] = torch.tensor(img_idx, dtype=torch.long)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # samplers / loaders
 # ---------------------------------------------------------------------------------------------------------------------
+def group_rows_by_image(files: List[str], rank: int = 0, world: int = 1) -> List[int]:
+    """Dataset rows ordered so that the rows of one image file are adjacent: files in order of first appearance, the rows of a file in
+    dataset order (the documented reordering of the grouped validation loader).  world > 1: this rank's share of that order — whole
+    image groups, contiguous, the same on every call (no shuffle, no padding), balanced by rows: the group that starts at position c of
+    the n rows goes to rank floor(c * world / n).  Every row appears exactly once across the ranks."""
+    first: Dict[str, int] = {}
+    for i, f in enumerate(files):
+        first.setdefault(f, i)
+    order = sorted(range(len(files)), key=lambda i: (first[files[i]], i))
+    if world <= 1:
+        return order
+    n, mine, owner = len(order), [], 0
+    for c, i in enumerate(order):
+        if c == 0 or files[i] != files[order[c - 1]]:
+            owner = min(world - 1, c * world // n)
+        if owner == rank:
+            mine.append(i)
+    return mine
+
+
+class _GroupedBatches(Dataset):
+    """item i = the i-th whole batch of the grouped order, built by ImgQuDataset.grouped_batch in a worker (DataLoader(batch_size=None))"""
+
+    def __init__(self, dataset, batches: List[List[int]]):
+        self.dataset, self.batches = dataset, batches
+
+    def __len__(self):
+        return len(self.batches)
+
+    def __getitem__(self, i: int):
+        return self.dataset.grouped_batch(self.batches[i])
+
+
+def _identity(x):
+    return x
+
+
+def get_grouped_dataloader(cfg, dataset, rank: Optional[int] = None, world: Optional[int] = None) -> DataLoader:
+    """Validation / test loader of cfg group_val_by_image: batches of bsv queries (the last one shorter) in group_rows_by_image's
+    order, each distinct image of a batch decoded once and emitted once, with `img_idx`.  Under do_dist every rank reads its own share
+    of whole image groups, in a fixed order (NewDistributedSampler would shuffle rows and tear the groups apart)."""
+    if rank is None or world is None:
+        rank, world = 0, 1
+        if bool(cfg["do_dist"]) and torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
+    rows = group_rows_by_image(dataset.files, rank, world)
+    bs = cfg["bsv"] if "bsv" in cfg else cfg["bs"]
+    nw = cfg["nwv"] if "nwv" in cfg else cfg["nw"]
+    batches = [rows[i:i + bs] for i in range(0, len(rows), bs)]
+    return DataLoader(_GroupedBatches(dataset, batches), batch_size=None, shuffle=False, num_workers=nw, collate_fn=_identity,
+                      pin_memory=torch.cuda.is_available(), persistent_workers=nw > 0)
+
+
 class NewDistributedSampler(DistributedSampler):
     """DistributedSampler with a shuffle switch, so validation can be sharded too (dat_loader.py:36-65): deterministic
     per-epoch permutation, padded with the head of the list to a multiple of the world size, contiguous rank slices."""
@@ -338,6 +435,8 @@ class NewDistributedSampler(DistributedSampler):
 
 def get_dataloader(cfg, dataset: Dataset, is_train: bool) -> DataLoader:
     """dat_loader.py:208-230 (one process per GPU: per-rank batch = cfg.bs; validation is sharded and shuffled under DDP)."""
+    if not is_train and bool(cfg["group_val_by_image"] if "group_val_by_image" in cfg else False):
+        return get_grouped_dataloader(cfg, dataset)
     dist_on = bool(cfg["do_dist"])
     if dist_on:
         sampler = NewDistributedSampler(dataset, shuffle=True)

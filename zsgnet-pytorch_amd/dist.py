@@ -260,6 +260,10 @@ class DistributedDataParallel(nn.Module):
             return
         from . import ops
         geo = self.module.plan_geometry(inp)
+        if inp.get("img_idx") is not None:
+            # queries sharing images (eval-only): the number of distinct images, hence the plan, differs from rank to rank and batch to
+            # batch, so no decision about a collective can be keyed on it; every rank tunes its own plans
+            return
         key = tuple(geo[:3]) + (self.module.training,)
         if self.module.training and hasattr(self.module, "_frozen_bn_key"):
             key += (self.module._frozen_bn_key(),)       # (frozen BatchNorm layers lower other launches: tuned anew, broadcast anew)

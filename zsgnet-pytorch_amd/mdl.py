@@ -78,6 +78,18 @@ STAGE_INPUTS = True      # run_forward stages its inputs in one launch (tests/te
 WG_BATCH = os.environ.get("ZSG_WG_BATCH", "1") != "0"      # identical-shape Winograd weight gradients of a stage in ONE launch (_Plan._batch_wgrads)
 
 
+SHARED_PLANS_MAX = 12     # shared-image eval plans kept per network (least recently used goes first): two token buckets of a 32-query loader
+
+
+def bucket_images(Bi: int, Q: int) -> int:
+    """Image-batch bucket of the shared-image eval plan: the smallest power of two >= Bi, capped at Q.  A grouped loader yields another
+    number of distinct images in almost every batch and each plan geometry costs a set of activation buffers and a tuner run, so for a
+    given Q only {1, 2, 4, ..., Q} occur: at most ceil(log2 Q) + 1 values, each >= Bi."""
+    if not 1 <= Bi <= Q:
+        raise ValueError(f"shared images: {Bi} images for {Q} queries (need 1 <= images <= queries)")
+    return min(Q, 1 << (Bi - 1).bit_length())
+
+
 class Act(TView):
     """TView + autograd bookkeeping used while lowering (grad buffer, whether it already holds a partial sum, and
     whether the gradient stored there is w.r.t. the pre-ReLU value so producers must apply the ReLU mask)."""
@@ -426,7 +438,13 @@ class ZSGNet(nn.Module):
         else:
             B, _, H, W = img.shape
         T = inp["qvec"].shape[1]
-        return B, H, W, (20 if T <= 20 else (50 if T <= 50 else T))
+        Tp = 20 if T <= 20 else (50 if T <= 50 else T)
+        if inp.get("img_idx") is not None:
+            # queries sharing images: (Bi_plan, Q, H, W, T_plan), the image count bucketed as T is (bucket_images); the blind variants
+            # gather the images into the plain plan of Q pairs
+            Q = inp["qvec"].shape[0]
+            return (bucket_images(B, Q), Q, H, W, Tp) if (self.use_img and self.use_lang) else (Q, H, W, Tp)
+        return B, H, W, Tp
 
     def _frozen_key(self) -> Tuple[int, ...]:
         """flat-order indices of the parameters with requires_grad=False (the training plans are lowered for one trainable set)"""
@@ -506,7 +524,19 @@ class ZSGNet(nn.Module):
             return ()
         return tuple(i for i, (_, m) in enumerate(self.batchnorm_modules()) if m.training)
 
-    def _plan_for(self, B, H, W, T) -> "_Plan":
+    def _plan_for(self, B, H, W, T, Q: Optional[int] = None) -> "_Plan":
+        if Q is not None:
+            # eval-only plan of Q queries over B (bucketed) images; the cache of these is bounded: least recently used first out
+            assert not self.training
+            key = (B, Q, H, W, T, "shared", False)
+            if key in self._plans:
+                self._plans[key] = self._plans.pop(key)         # (most recently used last)
+            else:
+                old = [k for k in self._plans if len(k) == 7 and k[5] == "shared"]
+                for k in old[:max(0, len(old) + 1 - SHARED_PLANS_MAX)]:
+                    del self._plans[k]
+                self._plans[key] = _Plan(self, B, H, W, T, False, Q=Q)
+            return self._plans[key]
         if not self.training:
             key = (B, H, W, T, False)
             if key not in self._plans:
@@ -526,11 +556,45 @@ class ZSGNet(nn.Module):
                                      frozen_bn={bn_names[i] for i in fb}, sync_bn={bn_names[i] for i in sb})
         return self._plans[key]
 
+    def _forward_shared(self, inp: Dict[str, Any]) -> Dict[str, Any]:
+        """forward for `img` [Bi, ...] shared by Q >= Bi queries, img_idx [Q] (device integers in [0, Bi)) naming each query's image: row
+        q of the result is what forward returns for the pair (img[img_idx[q]], query q).  Eval-only, forward-only.  The image trunk and
+        head conv0's feature GEMM run once per image, everything that depends on the phrase once per query; img_idx is read by the
+        kernel (zsg_head_shared_conv0), never by the host: its range is the batch builder's business (dat_loader's grouped collater)."""
+        img, qvec, idx = inp["img"], inp["qvec"], inp["img_idx"]
+        if self.training:
+            raise RuntimeError("ZSGNet.forward: a batch with img_idx (queries sharing images) is eval-only; call net.eval() (gradients "
+                               "through shared images are not supported)")
+        if not isinstance(idx, torch.Tensor) or idx.device != img.device or idx.dim() != 1 or idx.dtype not in (torch.int64, torch.int32):
+            raise ValueError("img_idx must be a 1-d int64 / int32 tensor on the device of img")
+        Q = qvec.shape[0]
+        if idx.numel() != Q or inp["qlens"].numel() != Q:
+            raise ValueError(f"img_idx / qlens must have one entry per query ({Q})")
+        if not (self.use_img and self.use_lang):
+            # blind variants: no image path or no phrase path to share; the plain plan on the gathered images (a device gather)
+            sub = {k: v for k, v in inp.items() if k != "img_idx"}
+            sub["img"] = img.index_select(0, idx.long())
+            return self.forward(sub)
+        Bp, Q, H, W, Tp = self.plan_geometry(inp)
+        plan = self._plan_for(Bp, H, W, Tp, Q=Q)
+        if "h0" in inp:
+            h0, c0 = inp["h0"], inp["c0"]
+        else:
+            h0, c0 = self.lstm_init_hidden(Q)
+        if self._anchor is None or self._anchor.device != img.device:
+            self._anchor = torch.zeros(1, device=img.device, requires_grad=True)
+        plan.expect_backward = False
+        out5 = _SharedFn.apply(plan, img, qvec, inp["qlens"], h0, c0, idx, self._anchor)
+        return dict(att_out=out5[..., 4:5], bbx_out=out5[..., :4], feat_sizes=plan.feat_sizes_t,
+                    num_f_out=plan.num_f_out_t, att_bbx_out=out5)
+
     def forward(self, inp: Dict[str, Any]) -> Dict[str, Any]:
         require_gpu()
         img, qvec, qlens = inp["img"], inp["qvec"], inp["qlens"]
         if img.device.type != "cuda" or self.device.type != "cuda":
             raise RuntimeError("ZSGNet.forward needs the model and the batch on the MI355X (no CPU fallback)")
+        if inp.get("img_idx") is not None:
+            return self._forward_shared(inp)
         # (img may be uint8 [B, H, W, 3] as PIL decodes (dat_loader gpu_normalise): /255 then happens on the GPU.)
         # The collater cuts qvec to the longest query of the batch (dat_loader.py:187-196), so T changes from batch to batch;
         # a launch plan (and its buffers) is built per geometry, so T is bucketed: the plan processes T_plan >= T tokens of
@@ -555,6 +619,18 @@ class ZSGNet(nn.Module):
                     num_f_out=plan.num_f_out_t, att_bbx_out=out5)
 
 
+class _SharedFn(torch.autograd.Function):
+    """forward of the shared-image eval plan; it has no backward"""
+    @staticmethod
+    def forward(ctx, plan, img, qvec, qlens, h0, c0, img_idx, anchor):
+        return plan.run_forward(img, qvec, qlens, h0, c0, img_idx=img_idx)
+
+    @staticmethod
+    def backward(ctx, g5):
+        raise RuntimeError("ZSGNet: a batch with img_idx (queries sharing images) is eval-only and forward-only: there are no gradients "
+                           "through the shared-image path")
+
+
 class _NetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, plan, img, qvec, qlens, h0, c0, anchor):
@@ -577,8 +653,13 @@ class _Plan:
     """Static lowering of ZSGNet for one (B, H, W, T, training) geometry."""
 
     def __init__(self, net: ZSGNet, B: int, H: int, W: int, T: int, training: bool, frozen=frozenset(), frozen_bn=frozenset(),
-                 sync_bn=frozenset()):
+                 sync_bn=frozenset(), Q: Optional[int] = None):
         self.net, self.B, self.H, self.W, self.T, self.training = net, B, H, W, T, training
+        # Q: the shared-image eval plan (ZSGNet._forward_shared) — the image trunk up to conv0's feature GEMM is lowered at batch B (image
+        # slots), the query encoder and everything behind zsg_head_shared_conv0 at batch Q; every other plan has one batch, Q == B
+        self.shared = Q is not None
+        self.Q = Q if Q is not None else B
+        assert not (self.shared and training), "the shared-image plan is eval-only"
         # BatchNorm layers in eval mode inside this training network: running statistics in the forward (one zsg_bn_eval_stats launch),
         # no statistics update, F.batch_norm(training=False)'s backward (zsg_bn_frozen_backward / zsg_bn_frozen_relu_maxpool_bwd)
         self.frozen_bn = frozenset(frozen_bn) if training else frozenset()
@@ -1369,11 +1450,13 @@ class _Plan:
         self.tune_dw = self._buf(max(e.size for e in net.store.entries.values()) + 64)
 
         # ---- static inputs ------------------------------------------------------------------------------------------
-        self.in_qvec = self._buf(B * T * net.emb_dim)
-        self.in_qlens = self._buf(B)
+        Qn = self.Q                      # queries (== B unless images are shared)
+        self.in_qvec = self._buf(Qn * T * net.emb_dim)
+        self.in_qlens = self._buf(Qn)
+        self.in_idx = self._buf(Qn, dtype=torch.int64) if self.shared else None      # img_idx of the forward being replayed
         nd = 2 if net.bid else 1
-        self.in_hc = self._buf(2 * nd * B * net.lstm_dim)            # (h0 | c0: ONE host-to-device copy per step when both come from the host)
-        self.in_h0, self.in_c0 = self.in_hc[:nd * B * net.lstm_dim], self.in_hc[nd * B * net.lstm_dim:]
+        self.in_hc = self._buf(2 * nd * Qn * net.lstm_dim)            # (h0 | c0: ONE host-to-device copy per step when both come from the host)
+        self.in_h0, self.in_c0 = self.in_hc[:nd * Qn * net.lstm_dim], self.in_hc[nd * Qn * net.lstm_dim:]
         self.img_slot = len(self.fwd.calls)
         x0 = self.act("img_nhwc4", B, H, W, 4, requires_grad=False)
         self.fwd.add(lib.zsg_nchw_to_nhwc4, self.in_qvec, B, 3, H, W, x0.buf, what="img")     # src pointer patched per call
@@ -1855,7 +1938,7 @@ class _Plan:
 
     def _lower_lstm(self) -> Act:
         """mdl.py:296-336.  we [B, 2H] = [h_fwd(len-1) | reverse-cell(x[len-1])]"""
-        net, B, T = self.net, self.B, self.T
+        net, B, T = self.net, self.Q, self.T
         E, Hd = net.emb_dim, net.lstm_dim
         H4 = 4 * Hd
         we = self.act("we", B, 1, 1, net.lstm_out_dim)
@@ -1905,7 +1988,7 @@ class _Plan:
     def _lower_head(self, feats: List[Act], we: Optional[Act]):
         """concat_we (mdl.py:69-104, blind variants :363-375, do_norm :118-130) + the head(s) (mdl.py:211-244, 377-389)
         over all pyramid levels in grouped launches."""
-        net, B = self.net, self.B
+        net, B = self.net, self.Q          # (the head's batch is the queries'; the features keep the images': self.B)
         sizes = self.feat_sizes
         Cf, Cw, Cg = net.cf, net.cw, (4 if net.use_grid else 0)
         assert [(f.levels[0].H, f.levels[0].W) for f in feats] == sizes
@@ -1917,7 +2000,7 @@ class _Plan:
             self.Fpack.requires_grad = feat_rg
         heads_in = feats                         # the Acts whose .grad conv0's data gradient fills
         if net.do_norm and Cf:
-            hc.Fp = self.packed("head.feat", B, sizes, 256)
+            hc.Fp = self.packed("head.feat", self.B, sizes, 256)
             hc.Fp.requires_grad = feat_rg
             heads_in = [self.l2norm(f, f"featnorm{i}", out=hc.Fp.lvl(i)) for i, f in enumerate(feats)]
         if net.do_norm and Cw:
@@ -1984,7 +2067,7 @@ class _Plan:
     def _head_stack(self, prefix: str, nout: int, hc, out: Act, g_in: Optional[torch.Tensor]):
         """One 6-convolution head `prefix`.{0..4}.0 / .5 (mdl.py:235-244) on the shared input described by hc; writes
         `out` [B][P][nout]; its backward starts from g_in (same layout)."""
-        net, B = self.net, self.B
+        net, B = self.net, self.Q
         C = net.convs
         sizes = self.feat_sizes
         Cf, Cw, Cg, we, Fp, gridmap = hc.Cf, hc.Cw, hc.Cg, hc.we, hc.Fp, hc.gridmap
@@ -1997,7 +2080,38 @@ class _Plan:
         # mdl.py:363-375): only the features go through the big implicit GEMM; the rest enters as an additive map
         #   lmap[b][p][n] = G[p][n] + sum_{tap valid at p} V[b][n*9+tap],  V = W0[:, :, :, lang] . we[b],  G = conv(grid, W0[..., grid])
         lmap = None
-        if Cw or Cg:
+        if self.shared:
+            # Queries sharing images: the feature GEMM runs once per IMAGE SLOT and leaves its raw accumulator Y (no bias, no ReLU, no
+            # additive map); ONE zsg_head_shared_conv0 launch then writes every query's h1 = relu(Y[img_idx[q]] + bias + G + taps of V[q]),
+            # which takes the place of the language map launch and of conv0's epilogue.  Nothing here reduces across image slots, so a
+            # slot no query points to (the padding of the image bucket) never reaches an output row.
+            assert Cf and not self.training
+            V = G = None
+            if Cw:
+                V = self.act(prefix + ".V", B, 1, 1, 9 * 256, requires_grad=False)
+                dv = fwd_desc(we, V, Cw, 9 * 256, 1, 1, 0, 1, wC=cp, wt_ld=cp, wc0=Cf)
+                self.fwd.add(lib.zsg_conv_igemm, dv, we.buf, self.P(W0n), V.buf, None, None, None, None, what=prefix + "0.V", lane=2)
+            if Cg:
+                G = self.packed(prefix + ".G", 1, sizes, 256)
+                dg = fwd_desc(gridmap, G, 4, 256, 3, 1, 1, 1, wC=cp, wc0=Cf + Cw)
+                self.fwd.add(lib.zsg_conv_igemm, dg, gridmap.buf, self.P(W0n), G.buf, None, None, None, None, what=prefix + "0.G")
+            Y = self.packed(prefix + ".Y", self.B, sizes, 256)
+            d0 = fwd_desc(Fp, Y, Cf, 256, 3, 1, 1, 1, wC=cp, wc0=0, relu=False)
+            a0 = (Fp.buf, self.P(W0n), Y.buf, None, None, None, None)
+            wargs = None
+            if wino_mode() != "0":
+                U0, job0 = self._wino_u(self.P(W0n).data_ptr(), 256, Cf, 9 * cp, cp, 0)
+                wargs = (Fp.buf, U0) + a0[2:]
+            self._tune("igemm", lib.zsg_conv_igemm, d0, a0, stream_ptr(), wino_args=wargs)
+            if d0.use_wino:
+                self.wino_jobs["fwd"].add(*job0)
+                self.fwd.add(lib.zsg_conv_wino, d0, *wargs, what=L0.name + ".feat")
+            else:
+                self.fwd.add(lib.zsg_conv_igemm, d0, *a0, what=L0.name + ".feat")
+            hw = torch.tensor([v for hw_ in sizes for v in hw_], dtype=torch.int32)
+            self.fwd.add(lib.zsg_head_shared_conv0, Y.buf, self.in_idx, 1, self.P(L0.name + ".bias"), G.buf if G is not None else None,
+                         V.buf if V is not None else None, self.B, B, len(sizes), hw, 256, h1.buf, what=L0.name + ".shared")
+        elif Cw or Cg:
             # None of this depends on the image: in training it runs on the side stream right behind the query encoder (the
             # launches are moved there after lowering, see _hoist_language_maps) and conv0 joins.
             side = 1 if (self.training and Cf) else 0
@@ -2019,7 +2133,9 @@ class _Plan:
             if side:
                 self._hoist.append((i0, len(self.fwd.calls)))
                 self._join_side()
-        if Cf:
+        if self.shared:
+            pass                          # (h1 is written by zsg_head_shared_conv0 above)
+        elif Cf:
             d0 = fwd_desc(Fp, h1, Cf, 256, 3, 1, 1, 1, wC=cp, wc0=0, relu=True)
             a0 = (Fp.buf, self.P(W0n), h1.buf, self.P(L0.name + ".bias"), lmap.buf if lmap is not None else None, None, None)
             wargs = None
@@ -2130,9 +2246,16 @@ class _Plan:
         self.tape.append(head5_back)
 
     # ---- execution -------------------------------------------------------------------------------------------------------
-    def run_forward(self, img, qvec, qlens, h0, c0) -> torch.Tensor:
+    def run_forward(self, img, qvec, qlens, h0, c0, img_idx=None) -> torch.Tensor:
         net = self.net
-        B = self.B
+        B = self.Q                               # the staged inputs and the output are per query
+        n_img = self.B
+        if self.shared:
+            # the batch's own image count (<= the plan's slots; the slots behind it keep what they hold and no query points to them)
+            n_img = img.shape[0]
+            if img_idx is None or not 1 <= n_img <= self.B or qvec.shape[0] != B:
+                raise ValueError("shared-image plan: img / qvec / img_idx do not fit the plan's geometry")
+            self.in_idx.copy_(img_idx, non_blocking=True)          # (device to device: no host synchronisation)
         ensure_stream_scratch(stream_ptr())      # (stream-K launches take their scratch from the stream they run on)
         do_prep = self.training and self.expect_backward and len(self.prep)
         if do_prep or len(self.prep_u):
@@ -2184,7 +2307,7 @@ class _Plan:
         # patch the one dynamic pointer (the caller's image tensor)
         fn, args, what = self.fwd.calls[self.img_slot]
         import ctypes as C_
-        self.fwd.calls[self.img_slot] = (fn, (C_.c_void_p(img.data_ptr()),) + args[1:], what)
+        self.fwd.calls[self.img_slot] = (fn, (C_.c_void_p(img.data_ptr()), C_.c_int32(n_img)) + args[2:], what)
         self._img_keepalive = img
         self.fwd_id += 1
         if self.training and self.frozen_bn:
@@ -2200,7 +2323,7 @@ class _Plan:
             check(lib.zsg_bn_fold(net.store.flat.data_ptr(), net._rm.data_ptr(), net._rv.data_ptr(), 1e-5, self.fold_jobs_dev.data_ptr(),
                                   len(self.fold_jobs), self.fold_rows, self.fold_arena.data_ptr(), stream_ptr()), "bn_fold")
         if u8:
-            check(lib.zsg_u8hwc_to_nhwc4(img.data_ptr(), B * self.H * self.W, self.fwd.calls[self.img_slot][1][5], stream_ptr()), "u8hwc_to_nhwc4")
+            check(lib.zsg_u8hwc_to_nhwc4(img.data_ptr(), n_img * self.H * self.W, self.fwd.calls[self.img_slot][1][5], stream_ptr()), "u8hwc_to_nhwc4")
         else:
             self.fwd.run(stream_ptr(), 0, 1)          # the one launch with a per-call pointer (the caller's image)
         if do_prep or len(self.prep_u):

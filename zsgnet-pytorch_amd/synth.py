@@ -19,6 +19,27 @@ def synthetic_batch(B: int, H: int = 300, W: int = 300, T: int = 20, seed: int =
                 img_size=torch.tensor([[360.0, 480.0]]).repeat(B, 1))
 
 
+def synthetic_shared_batch(Bi: int, Q: int, H: int = 300, W: int = 300, T: int = 20, seed: int = 1234, tmax: int = 20, emb: int = 300) -> Dict[str, torch.Tensor]:
+    """A batch of Q queries over Bi <= Q distinct images (ZSGNet.forward's `img_idx` contract): `img` [Bi,3,H,W], the per-query fields
+    of synthetic_batch with leading dimension Q, and `img_idx` [Q] int64 — shuffled, every image used at least once.  The per-query
+    fields are exactly synthetic_batch(Q, ...)'s for the same seed; its Q images are not used."""
+    if not 1 <= Bi <= Q:
+        raise ValueError(f"synthetic_shared_batch: {Bi} images for {Q} queries")
+    bt = synthetic_batch(Q, 8, 8, T, seed, tmax, emb)
+    g = torch.Generator().manual_seed(seed + 7919)
+    bt["img"] = torch.rand(Bi, 3, H, W, generator=g)
+    idx = torch.cat([torch.arange(Bi), torch.randint(0, Bi, (Q - Bi,), generator=g)])
+    bt["img_idx"] = idx[torch.randperm(Q, generator=g)].long()
+    return bt
+
+
+def expand_shared(bt: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """the one-image-per-query batch a shared batch stands for: img[img_idx], no `img_idx`"""
+    out = {k: v for k, v in bt.items() if k != "img_idx"}
+    out["img"] = bt["img"].index_select(0, bt["img_idx"].long())
+    return out
+
+
 class SyntheticLoader:
     """Iterable with len(): `steps` batches per epoch, deterministic per (seed, rank, step); a pool of `pool` distinct
     batches is generated once on the host and kept on the device (generating 16 x 3 x 300 x 300 uniform numbers on the CPU

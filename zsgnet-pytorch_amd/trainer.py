@@ -154,7 +154,7 @@ class Learner:
             out = self.mdl(batch)
             ls = self.loss_fn(out, batch)
             met = self.eval_fn(out, batch)
-            b = batch["img"].shape[0]
+            b = batch["qlens"].shape[0]          # queries (a grouped batch carries fewer images than queries: dat_loader.grouped_batch)
             for k in self.loss_keys:
                 sums[k] += ls[k].detach() * b
             for k in self.met_keys:
