@@ -414,6 +414,15 @@ int zsg_head_lang_map_packed(const float* V, const float* G, int32_t B, int32_t 
  * are never read.  Summation order: ((Y + G) + (taps row-major + bias)); N % 4 == 0, N <= 1024. */
 int zsg_head_shared_conv0(const float* Y, const void* img_idx, int32_t idx_i64, const float* bias, const float* G, const float* V, int32_t Bi, int32_t Q,
                           int32_t nlev, const int32_t* hw, int32_t N, float* out, void* stream);
+/* Backward of that sharing point (the shared-image training plan; the reference has no counterpart: it is the adjoint of the
+ * `Y[img_idx[q]]` read above, i.e. of concat_we's per-pair feature copy, mdl.py:69-104, folded over the queries of one image):
+ *   dY[i][p][n] = sum over q ascending with img_idx[q] == i of dy[q][p][n]
+ * dy [Q][h_i*w_i][N] per level (the gradient of h1, already ReLU-masked), dY [Bi][h_i*w_i][N] per level, both packed level-major.
+ * dY is WRITTEN (no zero fill needed): an image slot no query points to gets zeros.  A query whose index lies outside [0, Bi)
+ * contributes to no slot; nothing is read or written outside the buffers.  Fixed order, plain fp32 adds, no atomics: bit-identical
+ * run to run.  img_idx is read by the kernel.  N % 4 == 0, N <= 1024, Q <= 8192. */
+int zsg_head_shared_conv0_bwd(const float* dy, const void* img_idx, int32_t idx_i64, int32_t Bi, int32_t Q, int32_t nlev, const int32_t* hw, int32_t N,
+                              float* dY, void* stream);
 int zsg_head_border_sums(const float* dy, int32_t B, int32_t h, int32_t w, int32_t N, float* Q /* [9][B][N], += */, void* stream);
 int zsg_head_border_finalize(const float* Q, int32_t B, int32_t N, float* S1, float* S2, float* bias_grad /* [N], += ; or NULL */,
                              void* stream);

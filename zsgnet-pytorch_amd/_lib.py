@@ -128,6 +128,7 @@ SIGNATURES = {
     "zsg_head_lang_map": (I32, [P, P, I32, I32, I32, I32, P, P]),
     "zsg_head_lang_map_packed": (I32, [P, P, I32, I32, P, I32, P, P]),
     "zsg_head_shared_conv0": (I32, [P, P, I32, P, P, P, I32, I32, I32, P, I32, P, P]),
+    "zsg_head_shared_conv0_bwd": (I32, [P, P, I32, I32, I32, I32, P, I32, P, P]),
     "zsg_stage_inputs": (I32, [P, I32, I32, I32, I32, P, P, I32, P, P, I32, P, P, I32, P]),
     "zsg_head_border_sums": (I32, [P, I32, I32, I32, I32, P, P]),
     "zsg_head_border_finalize": (I32, [P, I32, I32, P, P, P, P]),

@@ -27,7 +27,9 @@ DEFAULTS: Dict[str, Any] = {
     "freeze_bn": False,             # every BatchNorm layer in eval mode while training (running statistics, no update): ZSGNet.freeze_batchnorm
     "clip_grad_norm": 0.0,          # > 0: Learner clips the trainable gradients to this total 2-norm before every step (optim.clip_grad_norm_); 0 = off
     "group_val_by_image": False,    # validation / test batches grouped by image file: each distinct image once + img_idx (ZSGNet's shared-image eval plan)
-    "sync_bn": False,               # with do_dist: BatchNorm statistics over the union of all ranks' batches (dist.convert_sync_batchnorm)
+    "group_trn_by_image": False,    # training batches of bs queries over bs / trn_queries_per_image image slots + img_idx (ZSGNet.shared_training)
+    "trn_queries_per_image": 4,     # ... queries per image slot (bs must be a multiple); rows of one file are cut into chunks of this size
+    "sync_bn": False,              # with do_dist: BatchNorm statistics over the union of all ranks' batches (dist.convert_sync_batchnorm)
     # configs/ds_info.json: where each dataset's images and csv files live (override with --ds_info.<name>.<key>=...)
     "ds_info": {name: {"data_dir": f"./data/{root}", "img_dir": f"./data/{imgs}",
                        **{f"{s}_csv_file": f"./data/{csv}/csv_dir/{f}.csv" for s, f in (("trn", trn), ("val", "val"), ("test", "test"))}}

@@ -961,6 +961,86 @@ extern "C" int zsg_head_shared_conv0(const float* Y, const void* img_idx, int32_
     return 0;
 }
 
+// Backward of the sharing point (the shared-image TRAINING plan): h1[q] reads Y[img_idx[q]], so the gradient of the per-image
+// accumulator is the segmented sum
+//   dY[i][p][n] = sum over q ascending with img_idx[q] == i of dy[q][p][n]
+// over every pyramid level at once (dy, dY packed level-major with batch counts Q, Bi; dy arrives ReLU-masked from conv1's data
+// gradient).  A block owns ONE image slot and a strided set of 16-byte elements of it: it fetches the Q indices once into LDS (a value
+// outside [0, Bi) becomes -1 and matches no slot), then walks q = 0 .. Q-1 — a block-uniform loop and a block-uniform branch — and adds
+// the rows of its slot's queries in that fixed order with plain fp32 adds: no atomics, bit-identical run to run.  Every element of dY is
+// WRITTEN (zeros for a slot no query points to), every dy row of a valid query is read exactly once by the whole grid and nothing is
+// read twice, so the pass moves (Q + Bi) * P * N * 4 bytes and is HBM-bound (no reuse for a cache to serve; at 16 queries over 4 images
+// of the 300^2 ResNet-50 pyramid 40 MB).  Four independent 16-byte loads per lane per query keep the memory pipe busy: the adds of one
+// element are dependent, the four elements are not.
+__global__ __launch_bounds__(256) void head_shared_conv0_bwd_kernel(const float* __restrict__ dy, const void* __restrict__ img_idx, int idx_i64, int Bi, int Q,
+                                                                    int N, LangMapLevels L, float* __restrict__ dY, int parts) {
+    extern __shared__ __attribute__((aligned(16))) int sidx[];     // [Q]
+    const int part = (int)blockIdx.x / Bi, im = (int)blockIdx.x - part * Bi;
+    for (int q = threadIdx.x; q < Q; q += 256) {
+        const long long v = idx_i64 ? ((const long long*)img_idx)[q] : (long long)((const int*)img_idx)[q];
+        sidx[q] = (v >= 0 && v < Bi) ? (int)v : -1;
+    }
+    __syncthreads();
+    const int n4 = N / 4, P = L.p0[L.nlev];
+    const int64_t total = (int64_t)P * n4, step = (int64_t)parts * 256;
+    for (int64_t i0 = (int64_t)part * 256 + threadIdx.x; i0 < total; i0 += 4 * step) {
+        int64_t src[4], qs[4], dst[4];
+        f32x4 acc[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t i = i0 + k * step;
+            acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+            src[k] = -1;
+            qs[k] = dst[k] = 0;
+            if (i < total) {
+                const int c = (int)(i % n4) * 4;
+                const int p = (int)(i / n4);
+                int lv = 0;
+#pragma unroll
+                for (int j = 1; j < ZSG_MAX_SEG; ++j)
+                    if (j < L.nlev && p >= L.p0[j]) lv = j;
+                const int64_t hw = (int64_t)L.h[lv] * L.w[lv], px = p - L.p0[lv];
+                src[k] = ((int64_t)Q * L.p0[lv] + px) * N + c;               // query 0's element; query q lies q * hw * N behind it
+                qs[k] = hw * N;
+                dst[k] = ((int64_t)Bi * L.p0[lv] + (int64_t)im * hw + px) * N + c;
+            }
+        }
+        for (int q = 0; q < Q; ++q) {
+            if (sidx[q] != im) continue;                                   // (block-uniform)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (src[k] >= 0) acc[k] += *(const f32x4*)(dy + src[k] + (int64_t)q * qs[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (src[k] >= 0) *(f32x4*)(dY + dst[k]) = acc[k];
+    }
+}
+extern "C" int zsg_head_shared_conv0_bwd(const float* dy, const void* img_idx, int32_t idx_i64, int32_t Bi, int32_t Q, int32_t nlev, const int32_t* hw, int32_t N,
+                                         float* dY, void* stream) {
+    ZSG_REQUIRE(dy && img_idx && dY && hw && Bi > 0 && Q > 0 && Q <= 8192 && nlev > 0 && nlev <= ZSG_MAX_SEG && N > 0 && (N % 4) == 0 && N <= 1024,
+                "head_shared_conv0_bwd: bad argument");
+    LangMapLevels L;
+    memset(&L, 0, sizeof(L));
+    L.nlev = nlev;
+    for (int i = 0; i < nlev; ++i) {
+        ZSG_REQUIRE(hw[2 * i] > 0 && hw[2 * i + 1] > 0, "head_shared_conv0_bwd: level %d is empty", i);
+        L.h[i] = hw[2 * i];
+        L.w[i] = hw[2 * i + 1];
+        L.p0[i + 1] = L.p0[i] + L.h[i] * L.w[i];
+    }
+    const int64_t per = (int64_t)L.p0[nlev] * (N / 4);
+    int parts = (int)((per + 256 * 4 - 1) / (256 * 4));        // 4 16-byte elements per thread per query of the slot
+    const int cap = (8 * ZSG_NUM_CU + Bi - 1) / Bi;
+    if (parts > cap) parts = cap;
+    if (parts < 1) parts = 1;
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("head_shared_conv0_bwd", st, 0, ((double)Q + Bi) * L.p0[nlev] * N * 4);
+    ZSG_LAUNCH(head_shared_conv0_bwd_kernel, dim3(parts * Bi), dim3(256), (size_t)Q * sizeof(int), st, dy, img_idx, idx_i64, Bi, Q, N, L, dY, parts);
+    ZSG_CHECK_LAUNCH("head_shared_conv0_bwd");
+    return 0;
+}
+
 // The nine validity-masked sums follow by inclusion-exclusion from nine plain sums per (image, channel):
 //   Q[0] = all pixels, Q[1]/Q[2] = first / last row, Q[3]/Q[4] = first / last column, Q[5..8] = the four corners;
 //   S(r,q) = Q0 - R(r) - C(q) + X(r,q)   with R(0) = first row (tap row 0 reads y-1: invalid at y = 0), R(2) = last row, ...

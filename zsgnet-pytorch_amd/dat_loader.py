@@ -320,6 +320,21 @@ class ImgQuDataset(Dataset):
             idx.append(k)
         return grouped_collater(items, imgs, idx)
 
+    def grouped_train_batch(self, chunks: List[List[int]]) -> Dict[str, torch.Tensor]:
+        """One batch of the grouped TRAINING loader (cfg group_trn_by_image): one image slot per chunk — the rows of a chunk share an image
+        file, which is decoded (and resized) once, from the chunk's first row — even if two chunks of one file meet in a batch; the
+        queries in chunk order.  Exactly len(chunks) slots, every one used (checked by the collater)."""
+        imgs, items, idx = [], [], []
+        for s, rows in enumerate(chunks):
+            if len({self.files[r] for r in rows}) != 1:
+                raise ValueError(f"grouped_train_batch: chunk {s} mixes image files")
+            img_t, h, w = self.load_image(rows[0])
+            imgs.append(img_t)
+            for r in rows:
+                items.append(self.query_item(r, h, w))
+                idx.append(s)
+        return grouped_collater(items, imgs, idx, all_slots_used=True)
+
 
 def collater(batch: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
     """dat_loader.py:187-196: every field stacked as float (uint8 images stay uint8: they become float on the GPU);
@@ -340,11 +355,15 @@ def collater(batch: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
     return out
 
 
-def grouped_collater(items: List[Dict[str, torch.Tensor]], imgs: List[torch.Tensor], img_idx: List[int]) -> Dict[str, torch.Tensor]:
+def grouped_collater(items: List[Dict[str, torch.Tensor]], imgs: List[torch.Tensor], img_idx: List[int],
+                     all_slots_used: bool = False) -> Dict[str, torch.Tensor]:
     """collater for queries that share images: `items` carry no image; `imgs` are the distinct images, img_idx[q] the image of query q.
-    This is where the index range is checked (on the host, once per batch): the forward reads img_idx on the device only."""
+    This is where the index range is checked (on the host, once per batch): the forward reads img_idx on the device only.
+    all_slots_used (training batches): every image slot must be named by some query — train-mode BatchNorm reduces over all slots."""
     if not imgs or len(img_idx) != len(items) or min(img_idx) < 0 or max(img_idx) >= len(imgs):
         raise ValueError(f"grouped_collater: img_idx out of range for {len(imgs)} images / {len(items)} queries")
+    if all_slots_used and len(set(img_idx)) != len(imgs):
+        raise ValueError(f"grouped_collater: {len(imgs) - len(set(img_idx))} of {len(imgs)} image slots are used by no query")
     out = collater(items)
     if imgs[0].dtype == torch.uint8 and len({tuple(im.shape) for im in imgs}) > 1:
         out["img"], out["img_hw"] = flatten_raw(imgs)            # raw images of different sizes (gpu_resize), as collater
@@ -412,6 +431,81 @@ def get_grouped_dataloader(cfg, dataset, rank: Optional[int] = None, world: Opti
                       pin_memory=torch.cuda.is_available(), persistent_workers=nw > 0)
 
 
+class GroupedTrainSampler(torch.utils.data.Sampler):
+    """Batches of the grouped TRAINING loader (cfg group_trn_by_image), one per iteration step: a list of bs // k chunks, each k rows of
+    ONE image file.  Per epoch: the rows of each file are shuffled and cut into chunks of k; a short last chunk is filled by re-drawing
+    rows of the same file; the chunks are shuffled — seeded by the epoch, as NewDistributedSampler, so every rank sees the same
+    list — and dealt to the ranks in equal numbers (rank r takes every world-th chunk from r); every batch is bs // k chunks, hence
+    exactly bs // k image slots and bs queries on every rank; the last short batch is dropped, as drop_last does for the ungrouped
+    training loader.  The number of batches does not depend on the epoch."""
+
+    def __init__(self, files: List[str], bs: int, k: int, rank: int = 0, world: int = 1, seed: int = 0):
+        if k < 1 or bs < k or bs % k != 0:
+            raise ValueError(f"grouped training loader: bs={bs} must be a positive multiple of trn_queries_per_image={k}")
+        self.bs, self.k, self.rank, self.world, self.seed, self.epoch = bs, k, rank, max(1, world), seed, 0
+        self.by_file: Dict[str, List[int]] = {}
+        for i, f in enumerate(files):
+            self.by_file.setdefault(f, []).append(i)
+        n_chunks = sum((len(r) + k - 1) // k for r in self.by_file.values())
+        self.n_batches = n_chunks // (self.world * (bs // k))
+
+    def set_epoch(self, epoch: int):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return self.n_batches
+
+    def chunks(self, epoch: int) -> List[List[int]]:
+        """every chunk of the epoch, in the shuffled order all ranks share"""
+        g = torch.Generator()
+        g.manual_seed(self.seed + epoch)
+        out, k = [], self.k
+        for rows in self.by_file.values():
+            perm = [rows[i] for i in torch.randperm(len(rows), generator=g).tolist()]
+            for c in range(0, len(perm), k):
+                ch = perm[c:c + k]
+                if len(ch) < k:
+                    ch = ch + [rows[i] for i in torch.randint(0, len(rows), (k - len(ch),), generator=g).tolist()]
+                out.append(ch)
+        return [out[i] for i in torch.randperm(len(out), generator=g).tolist()]
+
+    def batches(self, epoch: Optional[int] = None) -> List[List[List[int]]]:
+        mine = self.chunks(self.epoch if epoch is None else epoch)[self.rank::self.world]
+        cpb = self.bs // self.k
+        return [mine[b * cpb:(b + 1) * cpb] for b in range(self.n_batches)]
+
+    def __iter__(self):
+        yield from self.batches()
+        self.epoch += 1          # (a caller that never calls set_epoch still gets a new order every epoch)
+
+
+class _GroupedTrainBatches(Dataset):
+    """indexed by a batch of GroupedTrainSampler (DataLoader(batch_size=None) hands the sampler's item over as the index): the whole
+    batch is built by ImgQuDataset.grouped_train_batch in ONE worker call"""
+
+    def __init__(self, dataset):
+        self.dataset = dataset
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getitem__(self, chunks):
+        return self.dataset.grouped_train_batch(chunks)
+
+
+def get_grouped_train_dataloader(cfg, dataset, rank: Optional[int] = None, world: Optional[int] = None) -> DataLoader:
+    """Training loader of cfg group_trn_by_image: every batch is cfg.bs queries over cfg.bs // cfg.trn_queries_per_image image slots with
+    `img_idx`, equal groups (GroupedTrainSampler), for ZSGNet.shared_training."""
+    if rank is None or world is None:
+        rank, world = 0, 1
+        if bool(cfg["do_dist"]) and torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
+    sampler = GroupedTrainSampler(dataset.files, int(cfg["bs"]), int(cfg["trn_queries_per_image"]), rank, world)
+    nw = cfg["nw"]
+    return DataLoader(_GroupedTrainBatches(dataset), batch_size=None, sampler=sampler, num_workers=nw, collate_fn=_identity,
+                      pin_memory=torch.cuda.is_available(), persistent_workers=nw > 0)
+
+
 class NewDistributedSampler(DistributedSampler):
     """DistributedSampler with a shuffle switch, so validation can be sharded too (dat_loader.py:36-65): deterministic
     per-epoch permutation, padded with the head of the list to a multiple of the world size, contiguous rank slices."""
@@ -437,6 +531,8 @@ def get_dataloader(cfg, dataset: Dataset, is_train: bool) -> DataLoader:
     """dat_loader.py:208-230 (one process per GPU: per-rank batch = cfg.bs; validation is sharded and shuffled under DDP)."""
     if not is_train and bool(cfg["group_val_by_image"] if "group_val_by_image" in cfg else False):
         return get_grouped_dataloader(cfg, dataset)
+    if is_train and bool(cfg["group_trn_by_image"] if "group_trn_by_image" in cfg else False):
+        return get_grouped_train_dataloader(cfg, dataset)
     dist_on = bool(cfg["do_dist"])
     if dist_on:
         sampler = NewDistributedSampler(dataset, shuffle=True)

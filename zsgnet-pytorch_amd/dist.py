@@ -260,11 +260,19 @@ class DistributedDataParallel(nn.Module):
             return
         from . import ops
         geo = self.module.plan_geometry(inp)
-        if inp.get("img_idx") is not None:
-            # queries sharing images (eval-only): the number of distinct images, hence the plan, differs from rank to rank and batch to
-            # batch, so no decision about a collective can be keyed on it; every rank tunes its own plans
+        shared = inp.get("img_idx") is not None
+        if shared and not (self.module.training and getattr(self.module, "_shared_train", False) and len(geo) == 5
+                           and not (hasattr(self.module, "_sync_bn_key") and self.module._sync_bn_key())):
+            # queries sharing images in eval mode: the number of distinct images, hence the plan, differs from rank to rank and batch to
+            # batch, so no decision about a collective can be keyed on it; every rank tunes its own plans.  (Nor for the blind variants,
+            # which gather into the plain plan, or a training batch the forward is about to refuse.)
             return
-        key = tuple(geo[:3]) + (self.module.training,)
+        if shared:
+            # a shared TRAINING batch: the grouped training loader gives every rank the same (Bi, Q), so the broadcast is keyed on
+            # (Bi, Q, H, W, training, ...) — again not on the query-length bucket; rank 0 lowers the shared plan of ITS bucket
+            key = ("shared",) + tuple(geo[:4]) + (True,)
+        else:
+            key = tuple(geo[:3]) + (self.module.training,)
         if self.module.training and hasattr(self.module, "_frozen_bn_key"):
             key += (self.module._frozen_bn_key(),)       # (frozen BatchNorm layers lower other launches: tuned anew, broadcast anew)
         if self.module.training and hasattr(self.module, "_sync_bn_key"):
@@ -272,7 +280,11 @@ class DistributedDataParallel(nn.Module):
         if key in self._tuned:
             return
         self._tuned.add(key)
-        if get_rank() == 0 and (tuple(geo) + (self.module.training,)) not in self.module._plans:
+        if shared:
+            if get_rank() == 0:
+                Bi, Q, H, W, Tp = geo
+                self.module._plan_for(Bi, H, W, Tp, Q=Q)          # (cached: lowers only when this (Bi, Q) / bucket is new)
+        elif get_rank() == 0 and (tuple(geo) + (self.module.training,)) not in self.module._plans:
             self.module._plan_for(*geo[:4])
         payload = [dict(ops._TUNE_CACHE) if get_rank() == 0 else None]
         dist.broadcast_object_list(payload, src=0, group=self.group)
@@ -280,6 +292,8 @@ class DistributedDataParallel(nn.Module):
             ops._TUNE_CACHE.update(payload[0])
 
     def forward(self, inp):
+        if hasattr(self.module, "_refuse_sync_shared"):
+            self.module._refuse_sync_shared(inp)       # (raises before any collective of this forward)
         if self.world > 1:
             self._sync_tuning(inp)
         if self.active and self.broadcast_buffers and self.module.training:

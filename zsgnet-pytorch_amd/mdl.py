@@ -441,9 +441,12 @@ class ZSGNet(nn.Module):
         Tp = 20 if T <= 20 else (50 if T <= 50 else T)
         if inp.get("img_idx") is not None:
             # queries sharing images: (Bi_plan, Q, H, W, T_plan), the image count bucketed as T is (bucket_images); the blind variants
-            # gather the images into the plain plan of Q pairs
+            # gather the images into the plain plan of Q pairs.  A shared TRAINING plan has exactly the batch's image slots (train-mode
+            # BatchNorm reduces across slots: no padding)
             Q = inp["qvec"].shape[0]
-            return (bucket_images(B, Q), Q, H, W, Tp) if (self.use_img and self.use_lang) else (Q, H, W, Tp)
+            if not (self.use_img and self.use_lang):
+                return Q, H, W, Tp
+            return (B if self.training else bucket_images(B, Q), Q, H, W, Tp)
         return B, H, W, Tp
 
     def _frozen_key(self) -> Tuple[int, ...]:
@@ -524,7 +527,39 @@ class ZSGNet(nn.Module):
             return ()
         return tuple(i for i, (_, m) in enumerate(self.batchnorm_modules()) if m.training)
 
+    def shared_training(self, enable: bool = True) -> "ZSGNet":
+        """Opt-in: a TRAIN-mode batch with `img_idx` (Q queries over Bi distinct images) runs the image trunk and head conv0's feature GEMM
+        once per image, forward and backward, instead of raising "eval-only".  The result is the gradient of
+        sum_q loss(net(img[img_idx[q]], query q)) with the trunk evaluated once per distinct image; train-mode BatchNorm statistics are
+        taken over the Bi distinct images, each counted once — equal to plain training on the expanded batch img[img_idx] when every image
+        has the same number of queries (or BatchNorm is frozen / absent), a different function otherwise (INTEGRATION, "Many phrases per
+        image").  Every image slot must be used by some query (the batch builder's business).  Not together with sync_batchnorm."""
+        self._shared_train = bool(enable)
+        return self
+
+    def _refuse_sync_shared(self, inp) -> None:
+        """sync_batchnorm + a shared training batch is out of scope: refused before any collective of the forward is issued (the
+        data-parallel wrapper calls this ahead of its buffer broadcast)"""
+        if (inp.get("img_idx") is not None and self.training and getattr(self, "_shared_train", False) and self.use_img and self.use_lang
+                and self._sync_bn_key()):
+            raise RuntimeError("ZSGNet.forward: sync_batchnorm together with shared_training (a training batch with img_idx) is not "
+                               "supported; use per-rank BatchNorm statistics (sync_batchnorm(enable=False)) or freeze_batchnorm()")
+
     def _plan_for(self, B, H, W, T, Q: Optional[int] = None) -> "_Plan":
+        if Q is not None and self.training:
+            # shared-image training plan: exactly B image slots and Q queries.  One (B, Q) at a time: a new one, like a new trainable set,
+            # drops the shared training plans of the old (activation buffers must not pile up)
+            fz, fb, sb = self._frozen_key(), self._frozen_bn_key(), self._sync_bn_key()
+            key = (B, H, W, T, fz, fb, sb, ("shared", Q), True)
+            if key not in self._plans:
+                for k in [k for k in self._plans if k[-1] and ((k[4], k[5], k[6]) != (fz, fb, sb) or (len(k) == 9 and (k[0], k[7][1]) != (B, Q)))]:
+                    old = self._plans.pop(k)
+                    if old._prep_pending:
+                        torch.cuda.current_stream().wait_event(old._prep_ev)
+                bn_names = list(self.bns)
+                self._plans[key] = _Plan(self, B, H, W, T, True, frozen={self._param_names[i] for i in fz},
+                                         frozen_bn={bn_names[i] for i in fb}, Q=Q)
+            return self._plans[key]
         if Q is not None:
             # eval-only plan of Q queries over B (bucketed) images; the cache of these is bounded: least recently used first out
             assert not self.training
@@ -562,7 +597,9 @@ class ZSGNet(nn.Module):
         head conv0's feature GEMM run once per image, everything that depends on the phrase once per query; img_idx is read by the
         kernel (zsg_head_shared_conv0), never by the host: its range is the batch builder's business (dat_loader's grouped collater)."""
         img, qvec, idx = inp["img"], inp["qvec"], inp["img_idx"]
-        if self.training:
+        train = self.training and getattr(self, "_shared_train", False)
+        self._refuse_sync_shared(inp)
+        if self.training and not train:
             raise RuntimeError("ZSGNet.forward: a batch with img_idx (queries sharing images) is eval-only; call net.eval() (gradients "
                                "through shared images are not supported)")
         if not isinstance(idx, torch.Tensor) or idx.device != img.device or idx.dim() != 1 or idx.dtype not in (torch.int64, torch.int32):
@@ -583,6 +620,15 @@ class ZSGNet(nn.Module):
             h0, c0 = self.lstm_init_hidden(Q)
         if self._anchor is None or self._anchor.device != img.device:
             self._anchor = torch.zeros(1, device=img.device, requires_grad=True)
+        if train:
+            # the shared-image TRAINING plan (shared_training): exactly img.shape[0] image slots; the loss / evaluator / optimizer see
+            # Q rows and the flat gradient buffer, as with the plain plan
+            plan.expect_backward = torch.is_grad_enabled()
+            out5 = _SharedTrainFn.apply(self, plan, img, qvec, inp["qlens"], h0, c0, idx, self._anchor)
+            out5._zsg_g5 = plan.g5_in
+            out5._zsg_plan = plan
+            return dict(att_out=out5[..., 4:5], bbx_out=out5[..., :4], feat_sizes=plan.feat_sizes_t,
+                        num_f_out=plan.num_f_out_t, att_bbx_out=out5)
         plan.expect_backward = False
         out5 = _SharedFn.apply(plan, img, qvec, inp["qlens"], h0, c0, idx, self._anchor)
         return dict(att_out=out5[..., 4:5], bbx_out=out5[..., :4], feat_sizes=plan.feat_sizes_t,
@@ -631,6 +677,24 @@ class _SharedFn(torch.autograd.Function):
                            "through the shared-image path")
 
 
+class _SharedTrainFn(torch.autograd.Function):
+    """forward / backward of the shared-image training plan (ZSGNet.shared_training)"""
+    @staticmethod
+    def forward(ctx, net, plan, img, qvec, qlens, h0, c0, img_idx, anchor):
+        ctx.plan = plan
+        out = plan.run_forward(img, qvec, qlens, h0, c0, img_idx=img_idx)
+        ctx.fwd_id = plan.fwd_id
+        return out
+
+    @staticmethod
+    def backward(ctx, g5):
+        if ctx.fwd_id != ctx.plan.fwd_id:
+            raise RuntimeError("backward of a forward whose activations were overwritten: this geometry's plan ran another "
+                               "forward since (one backward per forward per input geometry)")
+        ctx.plan.run_backward(g5)
+        return (None,) * 9
+
+
 class _NetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, plan, img, qvec, qlens, h0, c0, anchor):
@@ -655,11 +719,14 @@ class _Plan:
     def __init__(self, net: ZSGNet, B: int, H: int, W: int, T: int, training: bool, frozen=frozenset(), frozen_bn=frozenset(),
                  sync_bn=frozenset(), Q: Optional[int] = None):
         self.net, self.B, self.H, self.W, self.T, self.training = net, B, H, W, T, training
-        # Q: the shared-image eval plan (ZSGNet._forward_shared) — the image trunk up to conv0's feature GEMM is lowered at batch B (image
-        # slots), the query encoder and everything behind zsg_head_shared_conv0 at batch Q; every other plan has one batch, Q == B
+        # Q: a shared-image plan (ZSGNet._forward_shared) — the image trunk up to conv0's feature GEMM is lowered at batch B (image
+        # slots), the query encoder and everything behind zsg_head_shared_conv0 at batch Q; every other plan has one batch, Q == B.  A
+        # shared TRAINING plan (ZSGNet.shared_training) has exactly B slots, all used; its backward turns the gradient of h1 [Q] into
+        # the gradient of conv0's per-image accumulator with zsg_head_shared_conv0_bwd and runs conv0's feature weight / data gradients
+        # and the whole trunk backward at batch B
         self.shared = Q is not None
         self.Q = Q if Q is not None else B
-        assert not (self.shared and training), "the shared-image plan is eval-only"
+        assert not (self.shared and training and sync_bn), "shared training does not synchronize BatchNorm across ranks"
         # BatchNorm layers in eval mode inside this training network: running statistics in the forward (one zsg_bn_eval_stats launch),
         # no statistics update, F.batch_norm(training=False)'s backward (zsg_bn_frozen_backward / zsg_bn_frozen_relu_maxpool_bwd)
         self.frozen_bn = frozenset(frozen_bn) if training else frozenset()
@@ -2085,7 +2152,9 @@ class _Plan:
             # additive map); ONE zsg_head_shared_conv0 launch then writes every query's h1 = relu(Y[img_idx[q]] + bias + G + taps of V[q]),
             # which takes the place of the language map launch and of conv0's epilogue.  Nothing here reduces across image slots, so a
             # slot no query points to (the padding of the image bucket) never reaches an output row.
-            assert Cf and not self.training
+            # In a training plan the same launches run (Y is not kept for the backward: the ReLU mask is h1's own); train-mode BatchNorm
+            # upstream DOES reduce across slots, which is why such a plan has no padding slots.
+            assert Cf
             V = G = None
             if Cw:
                 V = self.act(prefix + ".V", B, 1, 1, 9 * 256, requires_grad=False)
@@ -2165,11 +2234,20 @@ class _Plan:
             if not Cw and b0t:       # (with language the bias gradient falls out of the border sums below)
                 self.bwd.add(lib.zsg_colsum, dy.buf, 1, 0, dy.rows(), 256, 0, 256, self.G(L0.name + ".bias"), 1, what="bgrad:" + L0.name, lane=1)
             if Cf:
+                dyf = dy                 # the gradient of conv0's feature GEMM output, at the batch of the features
+                if self.shared and (w0t or Fp.requires_grad):
+                    # queries sharing images: sum_q X[idx q]^T dy[q] = sum_i X[i]^T dY[i], so the feature columns of dW0 and d(Fp) take
+                    # the segmented sum dY[i] = sum_{q: idx q == i} dy[q] (dy is already ReLU-masked) at batch self.B; img_idx is the
+                    # forward's copy in in_idx, read by the kernel
+                    dyf = self.packed(prefix + ".dY", self.B, sizes, 256)
+                    hwb = torch.tensor([v for hw_ in sizes for v in hw_], dtype=torch.int32)
+                    self.bwd.add(lib.zsg_head_shared_conv0_bwd, dy.buf, self.in_idx, 1, self.B, B, len(sizes), hwb, 256, dyf.buf,
+                                 what=L0.name + ".shared_bwd")
                 if w0t:
-                    dwf = fwd_desc(Fp, dy, Cf, 256, 3, 1, 1, 1, wC=cp, wc0=0)
-                    self.wgrad(dwf, Fp, dy, W0n, "wgrad:" + L0.name)
+                    dwf = fwd_desc(Fp, dyf, Cf, 256, 3, 1, 1, 1, wC=cp, wc0=0)
+                    self.wgrad(dwf, Fp, dyf, W0n, "wgrad:" + L0.name)
                 if Fp.requires_grad:
-                    self.dgrad(L0, dy, Fp, n=Cf, row0=0, dx=self.grad_of(Fp))
+                    self.dgrad(L0, dyf, Fp, n=Cf, row0=0, dx=self.grad_of(Fp))
             # The language / grid columns of dW0, the bias gradient and d(we) hang off dy only and feed nothing but the query encoder's
             # backward (itself on the side stream): with features present they are leaves of the main chain and go to the side stream,
             # so that the pyramid's backward starts right behind conv0's data gradient.
@@ -2253,7 +2331,7 @@ class _Plan:
         if self.shared:
             # the batch's own image count (<= the plan's slots; the slots behind it keep what they hold and no query points to them)
             n_img = img.shape[0]
-            if img_idx is None or not 1 <= n_img <= self.B or qvec.shape[0] != B:
+            if img_idx is None or not 1 <= n_img <= self.B or qvec.shape[0] != B or (self.training and n_img != self.B):
                 raise ValueError("shared-image plan: img / qvec / img_idx do not fit the plan's geometry")
             self.in_idx.copy_(img_idx, non_blocking=True)          # (device to device: no host synchronisation)
         ensure_stream_scratch(stream_ptr())      # (stream-K launches take their scratch from the stream they run on)

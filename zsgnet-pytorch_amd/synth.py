@@ -45,8 +45,13 @@ class SyntheticLoader:
     batches is generated once on the host and kept on the device (generating 16 x 3 x 300 x 300 uniform numbers on the CPU
     every step costs as much as the GPU training step itself), then cycled with fresh row ids."""
 
-    def __init__(self, cfg, bs: int, steps: int, seed: int = 1234, rank: int = 0, device="cuda", pool: int = 8):
+    def __init__(self, cfg, bs: int, steps: int, seed: int = 1234, rank: int = 0, device="cuda", pool: int = 8, group_k: int = 0):
+        """group_k > 0 (the training loader under cfg group_trn_by_image): batches of bs queries over bs // group_k image slots with
+        `img_idx`, group_k queries per slot in shuffled order — what dat_loader's grouped training loader makes."""
         self.cfg, self.bs, self.steps, self.seed, self.rank, self.device = cfg, bs, steps, seed, rank, device
+        if group_k and (bs < group_k or bs % group_k):
+            raise ValueError(f"grouped training loader: bs={bs} must be a positive multiple of trn_queries_per_image={group_k}")
+        self.group_k = int(group_k)
         self.epoch = 0
         self.pool, self._cache = pool, {}
 
@@ -59,8 +64,15 @@ class SyntheticLoader:
         for i in range(self.steps):
             k = i % self.pool
             if k not in self._cache:
-                bt = synthetic_batch(self.bs, H, W, seed=self.seed + 1000003 * self.rank + k, emb=self.cfg["emb_dim"])
-                self._cache[k] = {n: v.to(dev) for n, v in bt.items()}
+                sd = self.seed + 1000003 * self.rank + k
+                if self.group_k:
+                    Bi = self.bs // self.group_k
+                    bt = synthetic_shared_batch(Bi, self.bs, H, W, seed=sd, emb=self.cfg["emb_dim"])
+                    g = torch.Generator().manual_seed(sd + 104729)
+                    bt["img_idx"] = torch.arange(Bi).repeat_interleave(self.group_k)[torch.randperm(self.bs, generator=g)]       # equal groups
+                else:
+                    bt = synthetic_batch(self.bs, H, W, seed=sd, emb=self.cfg["emb_dim"])
+                self._cache[k] ={n: v.to(dev) for n, v in bt.items()}
             bt = dict(self._cache[k])
             bt["idxs"] = bt["idxs"] + float((self.rank * self.steps + i) * self.bs)      # dataset row ids (dat_loader.py:140), unique per sample
             yield bt
@@ -77,5 +89,6 @@ class DataWrap:
 def get_data(cfg, rank: int = 0) -> DataWrap:
     """dat_loader.get_data counterpart for synthetic runs (per-rank batch = cfg.bs, dat_loader.py:212-215)."""
     steps = int(cfg["steps_per_epoch"])
-    return DataWrap(SyntheticLoader(cfg, cfg["bs"], steps, 1234, rank), SyntheticLoader(cfg, cfg["bsv"], max(1, steps // 5), 4321, rank),
+    gk = int(cfg["trn_queries_per_image"]) if ("group_trn_by_image" in cfg and cfg["group_trn_by_image"]) else 0
+    return DataWrap(SyntheticLoader(cfg, cfg["bs"], steps, 1234, rank, group_k=gk),SyntheticLoader(cfg, cfg["bsv"], max(1, steps // 5), 4321, rank),
                     {"synthetic_test": SyntheticLoader(cfg, cfg["bsv"], max(1, steps // 5), 9999, rank)}, cfg["tmp_path"])

@@ -45,6 +45,10 @@ class Learner:
         self.optimizer, self.lr_scheduler = None, None
         if cfg.get("freeze_bn", False):        # (kept across the mdl.train() of every epoch: ZSGNet.train re-applies it)
             getattr(mdl, "module", mdl).freeze_batchnorm()
+        # training batches grouped by image (img_idx): the trunk once per image slot, forward and backward (ZSGNet.shared_training)
+        self.grouped_trn = bool(cfg.get("group_trn_by_image", False))
+        if self.grouped_trn:
+            getattr(mdl, "module", mdl).shared_training(True)
         if cfg["resume"] and (cfg["resume_path"] or self.model_file.exists()):
             self.load_model_dict(cfg["resume_path"] or str(self.model_file), cfg["load_opt"])
 
@@ -108,6 +112,7 @@ class Learner:
             from .optim import clip_grad_norm_
             clip_params = [p for p in self.mdl.parameters() if p.requires_grad]
             sm_gn = SmoothenValue(0.9)
+        n_qu = 0
         n_img, t0 = 0, time.perf_counter()
         for batch in self.data.train_dl:
             self.num_it += 1
@@ -121,6 +126,8 @@ class Learner:
             self.optimizer.step()
             metric = self.eval_fn(out, batch)
             n_img += batch["img"].shape[0]
+            if self.grouped_trn:
+                n_qu += batch["qlens"].shape[0]
             if self.num_it % 2 == 0:             # the reference logs every 2 iterations (utils.py:428); this is its D2H sync
                 for k in self.loss_keys:
                     sm_loss[k].add_value(float(out_loss[k].detach()))
@@ -135,6 +142,8 @@ class Learner:
         if clip > 0:
             res["grad_norm"] = sm_gn.smooth
         res["images_per_s"] = n_img * zdist.get_world_size() / dt
+        if self.grouped_trn:       # (a grouped batch carries fewer images than queries)
+            res["queries_per_s"] = n_qu * zdist.get_world_size() / dt
         return res
 
     @torch.no_grad()
