@@ -475,6 +475,19 @@ size_t zsg_eval_workspace_bytes(int32_t B);
 int zsg_eval(const float* out5, const float* annot, const float* anchors, const float* img_size, int32_t B, int32_t A,
              float acc_thr, float* metrics, float* pred_boxes, float* pred_scores, int32_t* pred_idx, int32_t* best_idx,
              float* ws /* zsg_eval_workspace_bytes(B): per-sample, per-anchor-range arg-max records */, void* stream);
+/* Top-k grounding per query (no counterpart in the reference, whose evaluator keeps one box: evaluator.py:74-75 ranks by the sigmoid
+ * score, anchors.py:182-197 decodes, anchors.py:106-116 is the IoU; the pieces are the reference's, the NMS is this build's).
+ * Candidates are ordered by (score descending, anchor index ascending), a NaN score below every number; the first min(pre_n, A) are
+ * decoded; greedy NMS in that order keeps a candidate unless IoU(kept, candidate) > nms_thr for a box already kept, up to K boxes.
+ * topk_boxes [B][K][4] pixels x1y1x2y2, topk_scores [B][K], topk_idx [B][K] int32 anchor index, topk_n [B] int32 boxes kept; rows past
+ * topk_n are boxes 0, score 0, index -1.  Row 0 is bit-identical to zsg_eval's pred_boxes / pred_scores / pred_idx.
+ * With annot: hit_rank [B] int32 = first rank r with IoU(box_r, annot) >= acc_thr (evaluator.py:115-117), K when none;
+ * acc_at [K] = mean over the batch of (hit_rank <= j).  annot, hit_rank and acc_at may be NULL (acc_at needs hit_rank, hit_rank
+ * needs annot).  Limits: 1 <= K <= 64, K <= pre_n <= 512.  ws: zsg_eval_topk_workspace_bytes(B, A, pre_n, K) bytes, 8-byte aligned. */
+size_t zsg_eval_topk_workspace_bytes(int32_t B, int32_t A, int32_t pre_n, int32_t K);
+int zsg_eval_topk(const float* out5, const float* annot, const float* anchors, const float* img_size, int32_t B, int32_t A,
+                  int32_t pre_n, int32_t K, float nms_thr, float acc_thr, float* topk_boxes, float* topk_scores,
+                  int32_t* topk_idx, int32_t* topk_n, int32_t* hit_rank, float* acc_at, void* ws, void* stream);
 /* IoU table [B][A] (tests / diagnostics) */
 int zsg_iou(const float* boxes, const float* anchors, int32_t B, int32_t A, float* iou, void* stream);
 

@@ -1,7 +1,11 @@
 """Developer tool: eval-mode (validation) forward + loss + evaluator throughput, ResNet-50 FPN 300x300, B=16.
 --images N [--queries Q]: the shared-image eval plan instead (ZSGNet.forward with img_idx): Q queries (default 16) over N distinct
-images per batch; without --images the one-image-per-query path, as before."""
+images per batch; without --images the one-image-per-query path, as before.
+--topk K [--pre-nms N] [--queries Q]: the evaluator call alone, on a fixed [Q, 17460, 5] head output: eval_topk = 1 (zsg_eval only) against
+eval_topk = K in eval mode (zsg_eval + zsg_eval_topk), alternating; device events around groups of calls, the median per call of each, one
+JSON line (--json PATH also writes it to a file)."""
 import argparse
+import json
 import os
 import sys
 import time
@@ -15,9 +19,52 @@ from zsgnet_pytorch_amd.synth import synthetic_batch, synthetic_shared_batch
 ap = argparse.ArgumentParser()
 ap.add_argument("--images", type=int, default=None, help="distinct images per batch (shared-image plan); default: one image per query")
 ap.add_argument("--queries", type=int, default=16, help="queries per batch")
+ap.add_argument("--topk", type=int, default=None, help="time the evaluator call with and without the top-k launch (K boxes per query)")
+ap.add_argument("--pre-nms", type=int, default=128, help="with --topk: candidates per query that enter the NMS")
+ap.add_argument("--json", default=None, help="with --topk: also write the result line to this file")
 args = ap.parse_args()
 Q = args.queries
 cfg = config.get_cfg()
+
+
+def time_topk():
+    from oracle import zsg_oracle as O
+    A, groups, per_group = 17460, 41, 25
+    gen = torch.Generator().manual_seed(7)
+    out5 = torch.cat([torch.randn(Q, A, 4, generator=gen) * 0.6, torch.randn(Q, A, 1, generator=gen) * 1.5 - 3.0], dim=2).cuda()
+    bt = synthetic_batch(Q, 8, 8, seed=1)
+    out = dict(att_bbx_out=out5, feat_sizes=torch.tensor(O.feat_sizes_for(300, 300)), num_f_out=torch.tensor([6]))
+    inp = {k: bt[k].cuda() for k in ("annot", "img_size", "idxs")}
+    evs = {}
+    for name, k in (("plain", 1), ("topk", args.topk)):
+        c = config.get_cfg(eval_topk=k, eval_pre_nms=args.pre_nms)
+        evs[name] = evaluator.get_default_eval(*config.ratios_scales(c), c).eval()
+    ms = {name: [] for name in evs}
+    for g in range(groups + 3):                      # the first 3 groups are warm-up
+        for name, e in evs.items():                  # alternating: both see the same clock state
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(per_group):
+                e(out, inp)
+            t1.record()
+            t1.synchronize()
+            if g >= 3:
+                ms[name].append(t0.elapsed_time(t1) / per_group)
+    med = {name: sorted(v)[len(v) // 2] for name, v in ms.items()}
+    res = {"what": "evaluator call, eval mode, device events, median of %d groups of %d calls" % (groups, per_group), "B": Q, "A": A,
+           "K": args.topk, "pre_nms": args.pre_nms, "plain_us": round(1e3 * med["plain"], 2), "topk_us": round(1e3 * med["topk"], 2),
+           "ratio": round(med["topk"] / med["plain"], 3), "plain_min_max_us": [round(1e3 * min(ms["plain"]), 2), round(1e3 * max(ms["plain"]), 2)],
+           "topk_min_max_us": [round(1e3 * min(ms["topk"]), 2), round(1e3 * max(ms["topk"]), 2)]}
+    line = json.dumps(res)
+    print(line)
+    if args.json:
+        with open(args.json, "w") as f:
+            f.write(line + "\n")
+
+
+if args.topk is not None:
+    time_topk()
+    sys.exit(0)
 net = mdl.get_default_net(9, cfg).to("cuda").eval()
 if args.images is None:
     bt = synthetic_batch(Q, 300, 300, seed=1)

@@ -30,6 +30,9 @@ DEFAULTS: Dict[str, Any] = {
     "group_trn_by_image": False,    # training batches of bs queries over bs / trn_queries_per_image image slots + img_idx (ZSGNet.shared_training)
     "trn_queries_per_image": 4,     # ... queries per image slot (bs must be a multiple); rows of one file are cut into chunks of this size
     "sync_bn": False,              # with do_dist: BatchNorm statistics over the union of all ranks' batches (dist.convert_sync_batchnorm)
+    "eval_topk": 1,                 # K > 1: in eval mode the evaluator also returns the K best NMS-filtered boxes per query and Acc@K (zsg_eval_topk)
+    "eval_nms_thr": 0.5,            # ... a candidate is dropped when its IoU with a box already kept is > this
+    "eval_pre_nms": 128,            # ... candidates per query (best scores first) that enter the NMS; K <= eval_pre_nms <= 512
     # configs/ds_info.json: where each dataset's images and csv files live (override with --ds_info.<name>.<key>=...)
     "ds_info": {name: {"data_dir": f"./data/{root}", "img_dir": f"./data/{imgs}",
                        **{f"{s}_csv_file": f"./data/{csv}/csv_dir/{f}.csv" for s, f in (("trn", trn), ("val", "val"), ("test", "test"))}}

@@ -422,6 +422,197 @@ extern "C" int zsg_eval(const float* out5, const float* annot, const float* anch
     return 0;
 }
 
+// ---- top-k grounding: score ranking + greedy NMS per query -----------------------------------------------------------
+// Ordering contract: candidates are ranked by (sigmoid score descending, anchor index ascending); a NaN score ranks below every
+// number.  One 64-bit composite carries it: the high word is the score's bit pattern + 1 (scores are in [0, 1], so the pattern is
+// monotone; 0 is left for NaN), the low word is ~index, and a larger composite is a better rank.  Composite 0 (index 0xffffffff) is
+// padding.  Rank 0 is therefore the anchor eval_chunk_kernel / argmax_merge pick, saturated scores and all-NaN rows included.
+// Three launches, the evaluator's two-stage pattern: (EV_CHUNKS x B) blocks each sort their anchor range in LDS and leave its best
+// pre_n composites, sorted, in the workspace; one block per query merges the EV_CHUNKS lists by rank counting (composites are unique,
+// so the rank of one is the number of larger ones: a binary search per list, no barriers), decodes the pre_n boxes into LDS and
+// runs K rounds of "the first candidate still alive is kept; every later one is tested against it"; one tiny block averages.
+typedef unsigned long long u64;
+#define TK_SORT 2048            // LDS sort buffer of a range block (composites)
+#define TK_MAX_PRE 512
+#define TK_MAX_K 64
+#define TK_LDS_PRE 256          // the finishing block keeps the lists in LDS up to this pre_n (32 KB), beyond it it reads them from L2
+
+__device__ __forceinline__ u64 tk_pack(float p, int a) {
+    const unsigned key = (p != p) ? 0u : __float_as_uint(p) + 1u;
+    return ((u64)key << 32) | (unsigned)~a;
+}
+__device__ __forceinline__ float tk_score(u64 c) {
+    const unsigned key = (unsigned)(c >> 32);
+    return key ? __uint_as_float(key - 1u) : __uint_as_float(0x7fc00000u);
+}
+__device__ __forceinline__ int tk_index(u64 c) { return (int)~(unsigned)c; }
+
+__global__ __launch_bounds__(256) void topk_chunk_kernel(const float* __restrict__ out5, int A, int pre_n, u64* __restrict__ lists) {
+    __shared__ u64 sm[TK_SORT];
+    const int b = blockIdx.y, c = blockIdx.x;
+    const int per = (A + EV_CHUNKS - 1) / EV_CHUNKS;
+    const int a0 = min(A, c * per), a1 = min(A, a0 + per);
+    const float* o = out5 + (size_t)b * A * 5;
+    u64* dst = lists + ((size_t)b * EV_CHUNKS + c) * pre_n;
+    if (a0 >= a1) {                                                // an empty range (A < EV_CHUNKS ranges): padding only
+        for (int i = threadIdx.x; i < pre_n; i += 256) dst[i] = 0;
+        return;
+    }
+    int N = 64;                                                   // sort width: the carried list + one tile of the range
+    while (N < pre_n + (a1 - a0) && N < TK_SORT) N <<= 1;       // (N > pre_n: the range is not empty and pre_n <= 512 < TK_SORT)
+    const int tile = N - pre_n;
+    for (int i = threadIdx.x; i < pre_n; i += 256) sm[i] = 0;
+    int base = a0;
+    do {
+        for (int i = threadIdx.x; i < tile; i += 256) {
+            const int a = base + i;
+            u64 v = 0;
+            if (a < a1) v = tk_pack(1.0f / (1.0f + expf(-o[a * 5 + 4])), a);     // the score expression of eval_chunk_kernel
+            sm[pre_n + i] = v;
+        }
+        __syncthreads();
+        for (int k = 2; k <= N; k <<= 1) {                         // bitonic sort, descending
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int i = threadIdx.x; i < (N >> 1); i += 256) {
+                    const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;
+                    const u64 x = sm[lo], y = sm[hi];
+                    const bool desc = (lo & k) == 0;
+                    if (desc ? (x < y) : (x > y)) { sm[lo] = y; sm[hi] = x; }
+                }
+                __syncthreads();
+            }
+        }
+        base += tile;
+    } while (base < a1);
+    for (int i = threadIdx.x; i < pre_n; i += 256) dst[i] = sm[i];
+}
+
+__device__ __forceinline__ int tk_count_greater(const u64* l, int n, u64 x) {     // l sorted descending
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (l[mid] > x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void topk_finish_kernel(const float* __restrict__ out5, const float* __restrict__ annot,
+                                                          const float* __restrict__ anchors, const float* __restrict__ img_size, int A,
+                                                          int pre_n, int K, float nms_thr, float acc_thr, const u64* __restrict__ lists,
+                                                          float* __restrict__ topk_boxes, float* __restrict__ topk_scores,
+                                                          int* __restrict__ topk_idx, int* __restrict__ topk_n, int* __restrict__ hit_rank) {
+    __shared__ u64 sm_lists[EV_CHUNKS * TK_LDS_PRE];
+    __shared__ u64 sm_cand[TK_MAX_PRE];
+    __shared__ f32x4 sm_box[TK_MAX_PRE];
+    __shared__ u64 sm_alive[2][2 * 4];
+    const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
+    const float* o = out5 + (size_t)b * A * 5;
+    const u64* L = lists + (size_t)b * EV_CHUNKS * pre_n;
+    const int nl = EV_CHUNKS * pre_n;
+    for (int r = tid; r < TK_MAX_PRE; r += 256) sm_cand[r] = 0;
+    if (pre_n <= TK_LDS_PRE) {
+        for (int e = tid; e < nl; e += 256) sm_lists[e] = L[e];
+        L = sm_lists;
+    }
+    __syncthreads();
+    for (int e = tid; e < nl; e += 256) {                          // merge: a composite's rank is the number of larger ones
+        const u64 x = L[e];
+        if (x == 0) continue;
+        int r = 0;
+        for (int c = 0; c < EV_CHUNKS; ++c) r += tk_count_greater(L + c * pre_n, pre_n, x);
+        if (r < pre_n) sm_cand[r] = x;
+    }
+    __syncthreads();
+    const int nc = min(pre_n, A);
+    bool alive[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {                                  // candidate r = tid + 256 s
+        const int r = tid + 256 * s;
+        const int a = r < nc ? tk_index(sm_cand[r]) : -1;
+        alive[s] = (unsigned)a < (unsigned)A;                      // (every rank below nc is filled; the test keeps a stray index off memory)
+        if (alive[s]) sm_box[r] = decode_box(*(const f32x4*)(anchors + 4 * a), o + a * 5);
+    }
+    f32x4 gt = {0.f, 0.f, 0.f, 0.f};
+    if (annot) gt = *(const f32x4*)(annot + 4 * b);
+    const float hh = img_size[2 * b], ww = img_size[2 * b + 1];
+    int kept = 0, hit = K;
+    for (; kept < K; ++kept) {
+        u64* al = sm_alive[kept & 1];
+        const u64 m0 = __ballot(alive[0]), m1 = __ballot(alive[1]);
+        if ((tid & 63) == 0) { al[wave] = m0; al[4 + wave] = m1; }
+        __syncthreads();                                           // (also orders sm_box before the first round's reads)
+        int first = -1;
+        for (int q = 7; q >= 0; --q) {
+            const u64 m = al[q];
+            if (m) first = 64 * q + __builtin_ctzll(m);
+        }
+        if (first < 0) break;                                      // block-uniform
+        const f32x4 kb = sm_box[first];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int r = tid + 256 * s;
+            if (alive[s] && (r == first || iou_exact(kb, sm_box[r]) > nms_thr)) alive[s] = false;
+        }
+        if (tid == 0) {
+            const u64 cd = sm_cand[first];
+            float* pb = topk_boxes + ((size_t)b * K + kept) * 4;
+            // (box+1)/2 * (h,w) then y1x1y2x2 -> x1y1x2y2, the expressions of eval_finish_kernel
+            pb[0] = ww * ((kb[1] + 1.f) / 2.f);
+            pb[1] = hh * ((kb[0] + 1.f) / 2.f);
+            pb[2] = ww * ((kb[3] + 1.f) / 2.f);
+            pb[3] = hh * ((kb[2] + 1.f) / 2.f);
+            topk_scores[(size_t)b * K + kept] = tk_score(cd);
+            topk_idx[(size_t)b * K + kept] = tk_index(cd);
+            if (annot && hit == K && iou_exact(kb, gt) >= acc_thr) hit = kept;
+        }
+    }
+    for (int k = kept + tid; k < K; k += 256) {                    // rows past topk_n
+        float* pb = topk_boxes + ((size_t)b * K + k) * 4;
+        pb[0] = pb[1] = pb[2] = pb[3] = 0.f;
+        topk_scores[(size_t)b * K + k] = 0.f;
+        topk_idx[(size_t)b * K + k] = -1;
+    }
+    if (tid == 0) {
+        topk_n[b] = kept;
+        if (hit_rank) hit_rank[b] = hit;
+    }
+}
+
+__global__ __launch_bounds__(64) void topk_acc_kernel(const int* __restrict__ hit_rank, int B, int K, float* __restrict__ acc_at) {
+    const int j = threadIdx.x;
+    if (j >= K) return;
+    double ok = 0;                                                 // (counts of 0 / 1: exact in any order)
+    for (int b = 0; b < B; ++b) ok += hit_rank[b] <= j ? 1.0 : 0.0;
+    acc_at[j] = (float)ok / (float)B;
+}
+
+extern "C" size_t zsg_eval_topk_workspace_bytes(int32_t B, int32_t A, int32_t pre_n, int32_t K) {
+    (void)A; (void)K;
+    if (B <= 0 || pre_n <= 0) return 0;
+    return (size_t)B * EV_CHUNKS * (size_t)pre_n * sizeof(u64);
+}
+
+extern "C" int zsg_eval_topk(const float* out5, const float* annot, const float* anchors, const float* img_size, int32_t B, int32_t A,
+                             int32_t pre_n, int32_t K, float nms_thr, float acc_thr, float* topk_boxes, float* topk_scores,
+                             int32_t* topk_idx, int32_t* topk_n, int32_t* hit_rank, float* acc_at, void* ws, void* stream) {
+    ZSG_REQUIRE(out5 && anchors && img_size && topk_boxes && topk_scores && topk_idx && topk_n && ws, "eval_topk: null pointer argument");
+    ZSG_REQUIRE(B > 0 && B <= 65535 && A > 0, "eval_topk: bad shape B=%d A=%d", B, A);
+    ZSG_REQUIRE(pre_n >= 1 && pre_n <= TK_MAX_PRE, "eval_topk: pre_n=%d outside 1..%d", pre_n, TK_MAX_PRE);
+    ZSG_REQUIRE(K >= 1 && K <= TK_MAX_K, "eval_topk: K=%d outside 1..%d", K, TK_MAX_K);
+    ZSG_REQUIRE(K <= pre_n, "eval_topk: K=%d exceeds pre_n=%d", K, pre_n);
+    ZSG_REQUIRE(!hit_rank || annot, "eval_topk: hit_rank needs annot");
+    ZSG_REQUIRE(!acc_at || hit_rank, "eval_topk: acc_at needs hit_rank");
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("eval_topk", st, 0, (double)B * A * 4);
+    u64* lists = (u64*)ws;                           // [B][EV_CHUNKS][pre_n]
+    ZSG_LAUNCH(topk_chunk_kernel, dim3(EV_CHUNKS, B), dim3(256), 0, st, out5, A, pre_n, lists);
+    ZSG_LAUNCH(topk_finish_kernel, dim3(B), dim3(256), 0, st, out5, annot, anchors, img_size, A, pre_n, K, nms_thr, acc_thr,
+                       (const u64*)lists, topk_boxes, topk_scores, topk_idx, topk_n, hit_rank);
+    if (acc_at) ZSG_LAUNCH(topk_acc_kernel, dim3(1), dim3(64), 0, st, (const int*)hit_rank, B, K, acc_at);
+    ZSG_CHECK_LAUNCH("eval_topk");
+    return 0;
+}
+
 __global__ void iou_kernel(const float* __restrict__ boxes, const float* __restrict__ anchors, int B, int A, float* __restrict__ iou) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)B * A) return;

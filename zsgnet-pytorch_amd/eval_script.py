@@ -7,8 +7,11 @@ A prediction is correct when IoU > acc_iou_thresh — STRICT, unlike the in-loop
 id counts once (DDP's padded sampler repeats samples).  When `pred_file` is missing, the per-rank files
 '<rank>_<name>' of a `num_gpus`-rank run are merged into it first (eval_script.py:22-33).
 
+topk=k > 1: a prediction is correct when ANY of its first k 'topk_boxes' (the NMS-filtered boxes a run with cfg eval_topk >= k
+writes, best first) has IoU > acc_iou_thresh; a record without 'topk_boxes' is an error.  topk absent or 1: 'pred_boxes', as above.
+
 Host-side bookkeeping (pandas + a scalar IoU per row), not part of the GPU hot path.
-    python -m zsgnet_pytorch_amd.eval_script <pred_file> <gt_file> [--acc_iou_thresh=0.5] [--num_gpus=N]
+    python -m zsgnet_pytorch_amd.eval_script <pred_file> <gt_file> [--acc_iou_thresh=0.5] [--num_gpus=N] [--topk=K]
 """
 import ast
 import pickle
@@ -48,6 +51,8 @@ def evaluate(pred_file, gt_file, **kwargs):
     """-> (accuracy, n_correct, n_total)"""
     import pandas as pd
     thr = float(kwargs.get("acc_iou_thresh", 0.5))
+    topk = int(kwargs.get("topk", 1))
+    assert topk >= 1, f"topk={topk}: must be >= 1"
     pred_file = Path(pred_file)
     if not pred_file.exists():
         assert "num_gpus" in kwargs, f"{pred_file} does not exist: pass num_gpus=N to merge the per-rank files"
@@ -62,7 +67,12 @@ def evaluate(pred_file, gt_file, **kwargs):
         if ind in seen:
             continue
         seen.add(ind)
-        corr += int(box_iou(p["pred_boxes"], boxes[ind]) > thr)
+        if topk > 1:
+            if "topk_boxes" not in p:
+                raise KeyError(f"prediction id {ind} has no 'topk_boxes': topk={topk} needs predictions written with cfg eval_topk >= {topk}")
+            corr += int(any(box_iou(bx, boxes[ind]) > thr for bx in p["topk_boxes"][:topk]))
+        else:
+            corr += int(box_iou(p["pred_boxes"], boxes[ind]) > thr)
         tot += 1
     return corr / tot, corr, tot
 

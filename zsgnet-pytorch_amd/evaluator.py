@@ -1,5 +1,8 @@
 """Evaluator on MI355X (reference `code/evaluator.py`): arg-max score anchor -> box decode -> IoU>=thr accuracy, one
-HIP launch per batch (csrc/loss.hip: eval_kernel); only the two boxes per sample that are needed are decoded."""
+HIP launch per batch (csrc/loss.hip: eval_kernel); only the two boxes per sample that are needed are decoded.
+
+cfg eval_topk = K > 1 (an extension of this build): in eval mode the K best distinct boxes per query as well — score ranking,
+greedy NMS at eval_nms_thr over the eval_pre_nms best candidates (csrc/loss.hip: zsg_eval_topk) — and Acc@K."""
 from functools import partial
 from typing import Dict
 
@@ -21,22 +24,54 @@ class Evaluator(nn.Module):
         self.anchs = None
         self.get_anchors = partial(create_anchors, ratios=self.ratios, scales=self.scales, flatten=True)
         self.acc_iou_threshold = cfg["acc_iou_threshold"]
+        self.topk = int(cfg.get("eval_topk", 1))
+        self.nms_thr = float(cfg.get("eval_nms_thr", 0.5))
+        self.pre_nms = int(cfg.get("eval_pre_nms", 128))
+        if self.topk > 1:                                  # met_keys[0] stays Acc: checkpoint gating / the LR scheduler read it
+            self.met_keys = self.met_keys + [f"Acc@{self.topk}"]
 
-    @torch.no_grad()
-    def forward(self, out: Dict[str, torch.Tensor], inp: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        annot = inp["annot"].contiguous().float()
+    def _out5_anchors(self, out):
         if "att_bbx_out" in out:
             out5 = out["att_bbx_out"].detach()
         else:
             out5 = torch.cat([out["bbx_out"], out["att_out"]], dim=2).detach()
         out5 = out5.contiguous()
-        B, A, _ = out5.shape
-        dev = out5.device
         if self.anchs is None:
             fs = out["feat_sizes"]
             if "num_f_out" in out and out["num_f_out"].numel() > 1:
                 fs = fs[:int(out["num_f_out"][0])]
-            self.anchs = self.get_anchors(fs, device=dev)
+            self.anchs = self.get_anchors(fs, device=out5.device)
+        return out5
+
+    def _topk(self, out5, annot, img_size) -> Dict[str, torch.Tensor]:
+        """one zsg_eval_topk call; annot None: boxes only (no hit_rank / Acc@K)"""
+        B, A, _ = out5.shape
+        dev, K = out5.device, self.topk
+        boxes = torch.empty(B, K, 4, device=dev)
+        scores = torch.empty(B, K, device=dev)
+        self.topk_idx = torch.empty(B, K, dtype=torch.int32, device=dev)
+        n = torch.empty(B, dtype=torch.int32, device=dev)
+        hit = torch.empty(B, dtype=torch.int32, device=dev) if annot is not None else None
+        acc = torch.empty(K, device=dev) if annot is not None else None
+        ws = torch.empty((int(lib.zsg_eval_topk_workspace_bytes(B, A, self.pre_nms, K)) + 7) // 8, dtype=torch.int64, device=dev)
+        check(lib.zsg_eval_topk(out5.data_ptr(), annot.data_ptr() if annot is not None else None, self.anchs.data_ptr(),
+                                img_size.data_ptr(), B, A, self.pre_nms, K, self.nms_thr, float(self.acc_iou_threshold),
+                                boxes.data_ptr(), scores.data_ptr(), self.topk_idx.data_ptr(), n.data_ptr(),
+                                hit.data_ptr() if hit is not None else None, acc.data_ptr() if acc is not None else None,
+                                ws.data_ptr(), stream_ptr()), "zsg_eval_topk")
+        res = {"topk_boxes": boxes, "topk_scores": scores, "topk_n": n}
+        if annot is not None:
+            self.acc_at = acc
+            res["hit_rank"] = hit
+            res[f"Acc@{K}"] = acc[K - 1]
+        return res
+
+    @torch.no_grad()
+    def forward(self, out: Dict[str, torch.Tensor], inp: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        annot = inp["annot"].contiguous().float()
+        out5 = self._out5_anchors(out)
+        B, A, _ = out5.shape
+        dev = out5.device
         img_size = inp["img_size"].contiguous().float()
         metrics = torch.empty(2, device=dev)
         pred_boxes = torch.empty(B, 4, device=dev)
@@ -47,7 +82,17 @@ class Evaluator(nn.Module):
         check(lib.zsg_eval(out5.data_ptr(), annot.data_ptr(), self.anchs.data_ptr(), img_size.data_ptr(), B, A,
                            float(self.acc_iou_threshold), metrics.data_ptr(), pred_boxes.data_ptr(), pred_scores.data_ptr(),
                            self.pred_idx.data_ptr(), self.best_idx.data_ptr(), ws.data_ptr(), stream_ptr()), "zsg_eval")
-        return {"Acc": metrics[0], "MaxPos": metrics[1], "idxs": inp["idxs"], "pred_boxes": pred_boxes, "pred_scores": pred_scores}
+        res = {"Acc": metrics[0], "MaxPos": metrics[1], "idxs": inp["idxs"], "pred_boxes": pred_boxes, "pred_scores": pred_scores}
+        if self.topk > 1 and not self.training:            # nothing is added to the per-step path of training
+            res.update(self._topk(out5, annot, img_size))
+        return res
+
+    @torch.no_grad()
+    def predict(self, out: Dict[str, torch.Tensor], inp: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """Pure inference: the eval_topk best boxes per query without ground truth (inp needs img_size only).
+        -> topk_boxes [B, K, 4] pixels x1y1x2y2, topk_scores [B, K], topk_n [B]; rows past topk_n are zeros."""
+        out5 = self._out5_anchors(out)
+        return self._topk(out5, None, inp["img_size"].contiguous().float())
 
 
 def get_default_eval(ratios, scales, cfg):

@@ -103,6 +103,7 @@ class Learner:
     def train_epoch(self) -> Dict[str, float]:
         """the hot loop, utils.py:393-437"""
         self.mdl.train()
+        self.eval_fn.train()          # (validate puts the evaluator in eval mode: its top-k launch is not part of the training step)
         sm_loss = {k: SmoothenValue(0.9) for k in self.loss_keys}
         sm_met = {k: SmoothenValue(0.9) for k in self.met_keys}
         # cfg clip_grad_norm > 0: the trainable gradients are clipped to that total 2-norm between backward and step (torch's
@@ -112,6 +113,7 @@ class Learner:
             from .optim import clip_grad_norm_
             clip_params = [p for p in self.mdl.parameters() if p.requires_grad]
             sm_gn = SmoothenValue(0.9)
+        eval_only = set()            # metric keys the evaluator returns in eval mode only: not logged here
         n_qu = 0
         n_img, t0 = 0, time.perf_counter()
         for batch in self.data.train_dl:
@@ -132,13 +134,16 @@ class Learner:
                 for k in self.loss_keys:
                     sm_loss[k].add_value(float(out_loss[k].detach()))
                 for k in self.met_keys:
-                    sm_met[k].add_value(float(metric[k]))
+                    if k in metric:              # (Acc@K is an eval-mode key: evaluator.py)
+                        sm_met[k].add_value(float(metric[k]))
+                    else:
+                        eval_only.add(k)
                 if clip > 0:
                     sm_gn.add_value(float(grad_norm))
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         res = {k: v.smooth for k, v in sm_loss.items()}
-        res.update({k: v.smooth for k, v in sm_met.items()})
+        res.update({k: v.smooth for k, v in sm_met.items() if k not in eval_only})
         if clip > 0:
             res["grad_norm"] = sm_gn.smooth
         res["images_per_s"] = n_img * zdist.get_world_size() / dt
@@ -152,8 +157,11 @@ class Learner:
         ALL-reduced: every rank steps ReduceLROnPlateau and gates best_met / checkpoints on the same global numbers (the
         reference reduces to rank 0 only, so its replicas' learning rates can drift apart).
         with_predictions: also return the per-sample records the reference pickles — a list of
-        {'id': idxs, 'pred_boxes': [x1,y1,x2,y2] pixels, 'pred_scores': float} (utils.py:377-383, README 'Evaluation')."""
+        {'id': idxs, 'pred_boxes': [x1,y1,x2,y2] pixels, 'pred_scores': float} (utils.py:377-383, README 'Evaluation').
+        cfg eval_topk = K > 1: each record also carries 'topk_boxes' (the topk_n <= K NMS-filtered boxes, best first) and
+        'topk_scores' (their scores); Acc@K is averaged and reduced with the other metrics."""
         self.mdl.eval()
+        self.eval_fn.eval()
         dl = dl or self.data.valid_dl
         sums = {k: torch.zeros((), device=self.device) for k in self.loss_keys + self.met_keys}
         n = 0
@@ -170,7 +178,8 @@ class Learner:
                 sums[k] += met[k] * b
             n += b
             if with_predictions:
-                recs.append((met["idxs"], met["pred_boxes"], met["pred_scores"]))
+                recs.append((met["idxs"], met["pred_boxes"], met["pred_scores"]) +
+                            ((met["topk_boxes"], met["topk_scores"], met["topk_n"]) if "topk_boxes" in met else ()))
         sums["__n"] = torch.tensor(float(n), device=self.device)
         red = zdist.reduce_dict(sums)
         tot = float(red["__n"])
@@ -183,6 +192,12 @@ class Learner:
             boxes = torch.cat([r[1] for r in recs]).cpu().tolist()
             scores = torch.cat([r[2].reshape(-1) for r in recs]).cpu().tolist()
             preds = [{"id": i, "pred_boxes": bx, "pred_scores": sc} for i, bx, sc in zip(ids, boxes, scores)]
+            if len(recs[0]) > 3:
+                tb = torch.cat([r[3] for r in recs]).cpu().tolist()
+                ts = torch.cat([r[4] for r in recs]).cpu().tolist()
+                tn = torch.cat([r[5] for r in recs]).cpu().tolist()
+                for p, bx, sc, n in zip(preds, tb, ts, tn):
+                    p["topk_boxes"], p["topk_scores"] = bx[:n], sc[:n]
         return res, preds
 
     def update_prediction_file(self, predictions, pred_file: Path):
