@@ -545,6 +545,26 @@ int zsg_grad_norm(const float* g, const zsg_adam_seg* segs, int32_t nseg, int32_
  * a coefficient of exactly 1.0f leaves the buffer untouched (g * 1.0f == g). */
 int zsg_grad_scale(float* g, const zsg_adam_seg* segs, int32_t nseg, int32_t nchunks, const float* coef, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Weight EMA: an exponential moving average of flat fp32 buffers — torch.optim.swa_utils.AveragedModel with
+ * multi_avg_fn=get_ema_multi_avg_fn(decay), use_buffers=True (torch._foreach_lerp_(ema, p, 1 - decay)).  The rule, for every element
+ * and the same in every kernel below:
+ *     ema <- fmaf(w, p - ema, ema),   w = 1 - decay in fp32          (one subtraction, one fused multiply-add)
+ * w == 1.0f stores p exactly (a copy, as torch.lerp returns `end` at weight 1); w == 0.0f leaves a finite ema unchanged; NaN and inf in p
+ * propagate.  w is passed by value: the caller keeps the update count on the host, nothing is read back.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* One launch over one or two ranges (the flat parameter buffer and the BatchNorm statistics buffer); ema_b = b = NULL and nb = 0 for
+ * one.  Any lengths > 0 (16-byte accesses plus a tail), every pointer 16-byte aligned, ema_x and x disjoint.  w outside [0, 1] (NaN
+ * included), a NULL required pointer or a misaligned buffer returns -1 before anything is launched.  12 B per element of HBM traffic. */
+int zsg_ema_update(float* ema_a, const float* a, int64_t na, float* ema_b, const float* b, int64_t nb, float w, void* stream);
+/* zsg_adam_step with the average updated in the same launch (the same kernel body): the rule is applied to the freshly updated p before
+ * it is stored.  p, m, v and step_count come out bit-identical to zsg_adam_step, ema bit-identical to zsg_ema_update on the post-step p.
+ * 36 B per parameter, against 28 + 12 for the step followed by a separate update.  All buffers 16-byte aligned; ema_w as w above. */
+int zsg_adam_step_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                      float weight_decay, float grad_scale, int32_t* step_count, float* ema, float ema_w, void* stream);
+/* Exchanges the contents of two disjoint buffers of n > 0 floats in one pass (16 B per element); overlapping ranges return -1. */
+int zsg_swap_f32(float* a, float* b, int64_t n, void* stream);
+
 int zsg_memset_f32(float* p, int64_t n, float value, void* stream);
 
 /* Wave priority of the kernels of the step's dependent chain (convolutions forward / data gradient, BatchNorm passes, the small

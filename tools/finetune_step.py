@@ -20,7 +20,15 @@ torch.nn.utils.clip_grad_norm_ engaged on the same p.grad views.
 
 --sync-bn measures synchronized BatchNorm in a 1-rank nccl group with forced collectives: the DistributedDataParallel wrapper
 (force_collectives) against the same wrapper with dist.convert_sync_batchnorm(force=True) — one all-reduce per train-mode BatchNorm layer
-and direction on top of the gradient buckets.  host_enqueue_ms_per_step: host time to enqueue a step (starting from an idle GPU; equal
+and direction on top of the gradient buckets.
+
+    python tools/finetune_step.py --ema [--out profiles/ema_step.json]
+
+--ema measures the weight average (ema.ModelEma, decay 0.999), everything trainable: none, attached to FusedAdam (the update rides in the
+Adam launch: zsg_adam_step_ema + the statistics' zsg_ema_update), update() after an unattached step (one zsg_ema_update over both
+buffers), and the out-of-tree way, torch._foreach_lerp_ over clones of the ~170 strided parameter views.
+
+host_enqueue_ms_per_step: host time to enqueue a step (starting from an idle GPU; equal
 to the GPU's ms_per_step when the host, not the GPU, sets the pace).  --only NAME[,NAME] runs the named variants alone (profiling).
 """
 import argparse
@@ -33,7 +41,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from zsgnet_pytorch_amd import config, dist as zdist, loss, mdl, ops, optim  # noqa: E402
+from zsgnet_pytorch_amd import config, dist as zdist, ema as zema, loss, mdl, ops, optim  # noqa: E402
 from zsgnet_pytorch_amd.synth import synthetic_batch  # noqa: E402
 
 ENC = "backbone.encoder."
@@ -57,6 +65,14 @@ CLIP_VARIANTS = {
     "fused_clip_engaged": ("fused", 1e-3),
     "torch_clip_engaged": ("torch", 1e-3),
 }
+# how the weight average is updated after every step
+EMA_VARIANTS = {
+    "no_ema": None,
+    "ema_fused": "fused",
+    "ema_separate": "separate",
+    "torch_foreach_lerp": "foreach",
+}
+EMA_DECAY = 0.999
 # (DistributedDataParallel with forced collectives, synchronized BatchNorm)
 SYNC_VARIANTS = {
     "ddp_forced": False,
@@ -74,6 +90,7 @@ def main():
     ap.add_argument("--frozen-bn", action="store_true")
     ap.add_argument("--clip", action="store_true")
     ap.add_argument("--sync-bn", action="store_true")
+    ap.add_argument("--ema", action="store_true")
     ap.add_argument("--only", default="", help="comma-separated variant names to run (e.g. one variant under rocprofv3)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
@@ -93,16 +110,18 @@ def main():
     sd = None
     runs = {}
     if a.sync_bn:
-        variants = {k: ((), False, None, v) for k, v in SYNC_VARIANTS.items()}
+        variants = {k: ((), False, None, v, None) for k, v in SYNC_VARIANTS.items()}
+    elif a.ema:
+        variants = {k: ((), False, None, None, v) for k, v in EMA_VARIANTS.items()}
     elif a.clip:
-        variants = {k: ((), False, c, None) for k, c in CLIP_VARIANTS.items()}
+        variants = {k: ((), False, c, None, None) for k, c in CLIP_VARIANTS.items()}
     elif a.frozen_bn:
-        variants = {k: (v[0], v[1], None, None) for k, v in BN_VARIANTS.items()}
+        variants = {k: (v[0], v[1], None, None, None) for k, v in BN_VARIANTS.items()}
     else:
-        variants = {k: (v, False, None, None) for k, v in VARIANTS.items()}
+        variants = {k: (v, False, None, None, None) for k, v in VARIANTS.items()}
     if a.only:
         variants = {k: v for k, v in variants.items() if k in a.only.split(",")}
-    for name, (prefixes, bn_frozen, clip, sync_bn) in variants.items():
+    for name, (prefixes, bn_frozen, clip, sync_bn, ema) in variants.items():
         net = mdl.get_default_net(9, cfg)
         if sd is None:
             sd = {k: v.clone() for k, v in net.state_dict().items()}
@@ -118,7 +137,14 @@ def main():
             if sync_bn:
                 zdist.convert_sync_batchnorm(model, force=True)
         runs[name] = dict(net=net, model=model, opt=optim.FusedAdam(net, lr=1e-4, betas=(0.9, 0.99)), ms=[], host_ms=[], clip=clip,
-                          params=list(net.parameters()))
+                          params=list(net.parameters()), ema=ema)
+        if ema == "fused":
+            runs[name]["avg"] = zema.ModelEma(net, decay=EMA_DECAY).attach(runs[name]["opt"])
+        elif ema == "separate":
+            runs[name]["avg"] = zema.ModelEma(net, decay=EMA_DECAY)
+        elif ema == "foreach":
+            runs[name]["src"] = [p.detach() for p in net.parameters()]
+            runs[name]["shadow"] = [p.clone() for p in runs[name]["src"]]
 
     def step(v):
         v["opt"].zero_grad()
@@ -128,6 +154,10 @@ def main():
             fn = optim.clip_grad_norm_ if kind == "fused" else torch.nn.utils.clip_grad_norm_
             v["norm"] = fn(v["params"], max_norm)
         v["opt"].step()
+        if v["ema"] == "separate":
+            v["avg"].update()
+        elif v["ema"] == "foreach":
+            torch._foreach_lerp_(v["shadow"], v["src"], 1.0 - EMA_DECAY)
     for v in runs.values():              # lowering (and any tuning) outside the timed rounds
         for _ in range(a.warmup):
             step(v)
@@ -164,6 +194,10 @@ def main():
         if v["clip"] is not None:
             res["variants"][name].update(clip=v["clip"][0], max_norm=v["clip"][1], last_grad_norm=round(float(v["norm"]), 6),
                                          engaged=float(v["norm"]) > v["clip"][1])
+        if v["ema"] is not None:
+            res["variants"][name].update(ema=v["ema"], ema_decay=EMA_DECAY)
+            if "avg" in v:
+                res["variants"][name].update(ema_updates=v["avg"].n_averaged)
     js = json.dumps(res, indent=1)
     print(js)
     if a.out:

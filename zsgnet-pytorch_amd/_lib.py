@@ -148,6 +148,9 @@ SIGNATURES = {
     "zsg_adam_step_segments": (I32, [P, P, P, P, P, I32, I32, P, I32, F32, P, P, P]),
     "zsg_grad_norm": (I32, [P, P, I32, I32, I32, F32, P, P, P, P]),
     "zsg_grad_scale": (I32, [P, P, I32, I32, P, P]),
+    "zsg_ema_update": (I32, [P, P, I64, P, P, I64, F32, P]),
+    "zsg_adam_step_ema": (I32, [P, P, P, P, I64, F32, F32, F32, F32, F32, F32, P, P, F32, P]),
+    "zsg_swap_f32": (I32, [P, P, I64, P]),
     "zsg_memset_f32": (I32, [P, I64, F32, P]),
     "zsg_set_stream_workspace": (I32, [P, P, SZ]),
     "zsg_set_main_priority": (I32, [I32]),

@@ -33,6 +33,9 @@ DEFAULTS: Dict[str, Any] = {
     "eval_topk": 1,                 # K > 1: in eval mode the evaluator also returns the K best NMS-filtered boxes per query and Acc@K (zsg_eval_topk)
     "eval_nms_thr": 0.5,            # ... a candidate is dropped when its IoU with a box already kept is > this
     "eval_pre_nms": 128,            # ... candidates per query (best scores first) that enter the NMS; K <= eval_pre_nms <= 512
+    "ema_decay": 0.0,               # > 0: an exponential moving average of the weights, updated in every optimizer step (ema.ModelEma); 0 = off
+    "ema_warmup": False,            # ... its decay ramps up as min(ema_decay, (1 + n) / (10 + n)) over the first updates
+    "ema_eval": True,               # ... validation / testing (and with them the LR scheduler, best_met, the prediction files) use the average
     # configs/ds_info.json: where each dataset's images and csv files live (override with --ds_info.<name>.<key>=...)
     "ds_info": {name: {"data_dir": f"./data/{root}", "img_dir": f"./data/{imgs}",
                        **{f"{s}_csv_file": f"./data/{csv}/csv_dir/{f}.csv" for s, f in (("trn", trn), ("val", "val"), ("test", "test"))}}

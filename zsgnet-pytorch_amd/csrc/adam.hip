@@ -1,6 +1,8 @@
 // adam.hip — fused Adam over one flat fp32 parameter buffer (torch.optim.Adam semantics, amsgrad off).  HBM-bound:
-// reads p,g,m,v and writes p,m,v once: 28 B per parameter.
+// reads p,g,m,v and writes p,m,v once: 28 B per parameter.  With the weight average riding in the launch (adam_kernel<true>,
+// zsg_adam_step_ema) it reads and writes ema too: 36 B per parameter, against 28 + 12 for the step followed by zsg_ema_update.
 #include "common.h"
+#include "ema.h"
 
 // The step counter lives on the device (the launch is hipGraph-capturable): step[0] = steps taken, step[1] = the ticket of the launch
 // in flight — both belong to ONE optimizer (two optimizers stepping on different streams never share a ticket).  Every block reads
@@ -8,9 +10,11 @@
 // every block has read the old value.  (A separate one-thread "tick" launch ahead of the update was 8 us of dependent launch at the
 // end of every step.)
 
+// EMA: the weight average takes the freshly updated p before it is stored (ema.h's rule: the bits zsg_ema_update gives on the stored p).
+template <bool EMA>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, int64_t n4, int64_t n, float lr, float b1, float b2, float eps,
-                                                   float wd, float gs, int* step, int tick) {
+                                                   float wd, float gs, int* step, int tick, float* __restrict__ ema, float ema_w) {
     const int t = __hip_atomic_load(step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
     const float bc1 = 1.f - powf(b1, (float)t);
     const float bc2s = sqrtf(1.f - powf(b2, (float)t));
@@ -28,6 +32,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         *(f32x4*)(p + 4 * i) = pp;
         *(f32x4*)(m + 4 * i) = mm;
         *(f32x4*)(v + 4 * i) = vv;
+        if (EMA) {
+            f32x4 ee = *(const f32x4*)(ema + 4 * i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ee[e] = zsg_ema_rule(ee[e], pp[e], ema_w);
+            *(f32x4*)(ema + 4 * i) = ee;
+        }
     }
     // tail (n not a multiple of 4)
     if (blockIdx.x == 0 && threadIdx.x < (int)(n - 4 * n4)) {
@@ -39,6 +49,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         p[i] -= step_size * (mm / (sqrtf(vv) / bc2s + eps));
         m[i] = mm;
         v[i] = vv;
+        if (EMA) ema[i] = zsg_ema_rule(ema[i], p[i], ema_w);
     }
     if (!tick) return;          // (a partial update of the step: the launch that covers the rest publishes the counter)
     __syncthreads();
@@ -49,23 +60,36 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 }
 
 static int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                       float weight_decay, float grad_scale, int32_t* step_count, int tick, void* stream) {
+                       float weight_decay, float grad_scale, int32_t* step_count, int tick, float* ema, float ema_w, void* stream) {
     ZSG_REQUIRE(p && g && m && v && step_count && n > 0, "adam_step: bad argument");
     hipStream_t st = (hipStream_t)stream;
-    ZSG_PROF("adam_step", st, 0, (double)n * 28);
+    ZSG_PROF(ema ? "adam_step_ema" : "adam_step", st, 0, (double)n * (ema ? 36 : 28));
     const int64_t n4 = n / 4;
     int64_t blocks = (n4 + 255) / 256;
     if (blocks > ZSG_NUM_CU * 8) blocks = ZSG_NUM_CU * 8;
     if (blocks < 1) blocks = 1;
-    ZSG_LAUNCH(adam_kernel, dim3((int)blocks), dim3(256), 0, st, p, g, m, v, n4, n, lr, beta1, beta2, eps, weight_decay, grad_scale,
-                       step_count, tick);
+    if (ema)
+        ZSG_LAUNCH(adam_kernel<true>, dim3((int)blocks), dim3(256), 0, st, p, g, m, v, n4, n, lr, beta1, beta2, eps, weight_decay, grad_scale,
+                   step_count, tick, ema, ema_w);
+    else
+        ZSG_LAUNCH(adam_kernel<false>, dim3((int)blocks), dim3(256), 0, st, p, g, m, v, n4, n, lr, beta1, beta2, eps, weight_decay, grad_scale,
+                   step_count, tick, ema, ema_w);
     ZSG_CHECK_LAUNCH("adam_step");
     return 0;
 }
 
 extern "C" int zsg_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                              float weight_decay, float grad_scale, int32_t* step_count, void* stream) {
-    return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, grad_scale, step_count, 1, stream);
+    return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, grad_scale, step_count, 1, nullptr, 0.f, stream);
+}
+
+// The same step with the weight average updated in the launch: ema <- ema.h's rule on the p this step stores.
+extern "C" int zsg_adam_step_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, float grad_scale, int32_t* step_count, float* ema, float ema_w, void* stream) {
+    ZSG_REQUIRE(ema, "adam_step_ema: null average buffer");
+    ZSG_REQUIRE(ema_w >= 0.f && ema_w <= 1.f, "adam_step_ema: weight %g outside [0, 1]", (double)ema_w);
+    ZSG_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0, "adam_step_ema: buffers must be 16-byte aligned");
+    return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, grad_scale, step_count, 1, ema, ema_w, stream);
 }
 
 // One optimizer step as several launches over disjoint ranges of the flat buffer (so that the part whose gradients are complete can
@@ -73,7 +97,7 @@ extern "C" int zsg_adam_step(float* p, const float* g, float* m, float* v, int64
 // exactly the LAST one passes publish = 1 and advances the counter.
 extern "C" int zsg_adam_step_range(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                                    float weight_decay, float grad_scale, int32_t* step_count, int32_t publish, void* stream) {
-    return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, grad_scale, step_count, publish ? 1 : 0, stream);
+    return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, grad_scale, step_count, publish ? 1 : 0, nullptr, 0.f, stream);
 }
 
 // ---- Adam over listed segments (fine-tuning: frozen parameters, parameter groups) -----------------------------------------------------

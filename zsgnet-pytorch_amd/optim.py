@@ -9,7 +9,10 @@ group and every parameter stepped, the step is the single zsg_adam_step launch; 
 listed parameters only, with per-group hyperparameters and per-parameter step counters (torch's state['step']).
 
 clip_grad_norm_ is torch.nn.utils.clip_grad_norm_ over the same flat gradient buffer: two HIP launches (zsg_grad_norm, zsg_grad_scale)
-through the segment table the segmented Adam step uses, with no host round trip."""
+through the segment table the segmented Adam step uses, with no host round trip.
+
+A weight average (ema.ModelEma.attach) rides in the step: inside the single launch (zsg_adam_step_ema), or as one zsg_ema_update over the
+whole flat buffer behind the segmented step.  Which one follows from the path the step takes; nothing else selects it."""
 import ctypes as C
 import math
 
@@ -54,6 +57,7 @@ class FusedAdam(torch.optim.Optimizer):
         self._pcount = torch.zeros(len(plist) + 1, dtype=torch.int32, device=flat.device)
         self._seg, self._uniform = False, True
         self._seg_key, self._seg_tab, self._nchunks = None, None, 0
+        self._ema = None          # ema.ModelEma.attach: step() updates this weight average
 
     def add_param_group(self, param_group):
         """torch's add_param_group, restricted to parameters of the model's flat store (the kernels address them by offset)."""
@@ -102,6 +106,21 @@ class FusedAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self.net.__dict__.get("_ema_applied") is not None:
+            raise RuntimeError("FusedAdam.step inside ModelEma.applied(): the network holds the averaged weights, not the trained ones")
+        ema = self._ema
+        if ema is None:
+            self._step(None, 0.0)
+            return
+        ema._check_launch("attach: step")
+        w = ema._next_weight()
+        if self._step(ema, w):
+            ema._update(w, stats_only=True)       # the parameters' average rode in the Adam launch: the BatchNorm statistics remain
+        else:
+            ema._update(w)                        # segmented step: the whole flat buffer, frozen parameters included
+
+    def _step(self, ema, ema_w):
+        """the Adam update; True when the single launch took the weight average `ema` along (zsg_adam_step_ema)"""
         st = self.net.store
         self.net.join_weight_readers()          # (a forward without backward may still be reading the weights on the side stream)
         sel = self._stepped()
@@ -113,9 +132,13 @@ class FusedAdam(torch.optim.Optimizer):
         if sel is None and not self._seg:
             g = self.param_groups[0]
             hp = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(self.grad_scale))
+            if ema is not None:
+                check(lib.zsg_adam_step_ema(st.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), st.flat.numel(), *hp,
+                                            self.step_count.data_ptr(), ema.flat.data_ptr(), ema_w, stream_ptr()), "zsg_adam_step_ema")
+                return True
             check(lib.zsg_adam_step(st.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), st.flat.numel(), *hp,
                                     self.step_count.data_ptr(), stream_ptr()), "zsg_adam_step")
-            return
+            return False
         if sel is None:
             sel = tuple((i, 0) for i in range(len(self._index)))
         if not self._seg:                        # the counts move to the per-parameter counters
@@ -127,13 +150,14 @@ class FusedAdam(torch.optim.Optimizer):
             self._uniform = False
         self._segment_table(sel)
         if not sel:
-            return
+            return False
         gt = (AdamGroup * len(self.param_groups))(*[AdamGroup(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
                                                               float(g["weight_decay"])) for g in self.param_groups])
         n = len(self._index)
         check(lib.zsg_adam_step_segments(st.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self._seg_tab.data_ptr(),
                                          len(sel), self._nchunks, gt, len(self.param_groups), float(self.grad_scale),
                                          self._pcount.data_ptr(), self._pcount[n:].data_ptr(), stream_ptr()), "zsg_adam_step_segments")
+        return False
 
     def param_steps(self) -> torch.Tensor:
         """steps taken by every parameter, in flat order (torch.optim.Adam's state[p]['step'])"""

@@ -6,6 +6,7 @@ import pickle
 import logging
 import os
 import time
+from contextlib import nullcontext
 from pathlib import Path
 from typing import Dict, List, Optional
 
@@ -43,6 +44,7 @@ class Learner:
         self.predictions_dir.mkdir(parents=True, exist_ok=True)
         self.logger = logging.getLogger("zsg." + uid)
         self.optimizer, self.lr_scheduler = None, None
+        self.ema = None               # cfg ema_decay > 0: the weight average (ema.ModelEma), built with the optimizer or a loaded checkpoint
         if cfg.get("freeze_bn", False):        # (kept across the mdl.train() of every epoch: ZSGNet.train re-applies it)
             getattr(mdl, "module", mdl).freeze_batchnorm()
         # training batches grouped by image (img_idx): the trunk once per image slot, forward and backward (ZSGNet.shared_training)
@@ -60,9 +62,19 @@ class Learner:
             self.optimizer = self.opt_fn(self.mdl, lr=lr)
         else:
             self.optimizer = self.opt_fn(self.mdl, lr=lr, params=params)
+        if self._ensure_ema() is not None:        # optimizer.step() updates the average from now on
+            self.ema.attach(self.optimizer)
         if self.cfg["use_reduce_lr_plateau"]:     # reference steps it with val accuracy in the default mode='min'
             self.lr_scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, factor=self.cfg["reduce_factor"],
                                                                            patience=self.cfg["patience"])
+
+    def _ensure_ema(self):
+        """the weight average of cfg ema_decay > 0 (None when off), created from the network's current weights on first use"""
+        decay = float(self.cfg.get("ema_decay", 0.0))
+        if decay > 0 and self.ema is None:
+            from .ema import ModelEma
+            self.ema = ModelEma(self.mdl, decay=decay, warmup=bool(self.cfg.get("ema_warmup", False)))
+        return self.ema
 
     # ---- checkpoints (utils.py:440-497) -----------------------------------------------------------------------------
     def save_model_dict(self):
@@ -73,6 +85,9 @@ class Learner:
                 "scheduler_state_dict": self.lr_scheduler.state_dict() if self.lr_scheduler else None,
                 "num_it": self.num_it, "num_epoch": self.num_epoch, "cfgtxt": json.dumps({k: v for k, v in self.cfg.items() if k != "_frozen"}, default=str),
                 "best_met": self.best_met}
+        if self.ema is not None:      # model_state_dict stays the RAW weights (a resume continues their trajectory); the average beside them
+            ckpt["ema_state_dict"] = {k: (v.detach().cpu().contiguous() if isinstance(v, torch.Tensor) else v)
+                                      for k, v in self.ema.state_dict().items()}
         torch.save(ckpt, self.model_file)
 
     def load_model_dict(self, resume_path: str, load_opt: bool = False):
@@ -88,6 +103,11 @@ class Learner:
         net = self.mdl.module if hasattr(self.mdl, "module") else self.mdl
         net.load_state_dict(ckpt["model_state_dict"], strict=self.cfg["strict_load"])
         self.num_it, self.num_epoch, self.best_met = ckpt.get("num_it", 0), ckpt.get("num_epoch", 0), ckpt.get("best_met", 0.0)
+        if self._ensure_ema() is not None:        # the checkpoint's average, else a fresh one of the loaded weights
+            if ckpt.get("ema_state_dict"):
+                self.ema.load_state_dict(ckpt["ema_state_dict"])
+            else:
+                self.ema.reset()
         if load_opt and ckpt.get("optimizer_state_dict"):
             if self.optimizer is None:
                 self.prepare_optimizer(self.cfg["lr"])
@@ -151,8 +171,15 @@ class Learner:
             res["queries_per_s"] = n_qu * zdist.get_world_size() / dt
         return res
 
-    @torch.no_grad()
     def validate(self, dl=None, with_predictions: bool = False):
+        """_validate, on the averaged weights when there is a weight average and cfg ema_eval is set (ModelEma.applied): the returned
+        numbers, and with them the LR scheduler, best_met and the prediction files, then refer to the averaged model."""
+        use_ema = self.ema is not None and self.cfg.get("ema_eval", True)
+        with self.ema.applied() if use_ema else nullcontext():
+            return self._validate(dl, with_predictions)
+
+    @torch.no_grad()
+    def _validate(self, dl=None, with_predictions: bool = False):
         """utils.py:353-391 (eval mode; losses / metrics averaged over batches weighted by batch size).  The sums are
         ALL-reduced: every rank steps ReduceLROnPlateau and gates best_met / checkpoints on the same global numbers (the
         reference reduces to rank 0 only, so its replicas' learning rates can drift apart).
