@@ -385,6 +385,18 @@ int zsg_resize_u8(const uint8_t* src, int32_t H, int32_t W, int32_t C, const int
  * the job in each launch (blocks_x / blocks_y = their totals).  Byte-identical to zsg_resize_u8 (dat_loader.py:98-146, :121). */
 int zsg_resize_u8_batched(const void* jobs_dev, int32_t njobs, int32_t C, int32_t Ho, int32_t Wo, int32_t blocks_x, int32_t blocks_y,
                           void* stream);
+/* Training augmentation of a whole batch (3 channels): `img.crop(box).resize((Wo, Ho))` — the reference's resampling call,
+ * dat_loader.py:121, applied to a window of the raw image — followed by brightness, contrast and saturation jitter, byte-identical to
+ * zsgnet_pytorch_amd.dat_loader.augment_host.  jobs = device array of
+ * {int64 src, tmp, out; int64 x_bounds, x_coef, y_bounds, y_coef; int32 h, w, pitch, x_ksize, y_ksize, blk0_x, blk0_y, pad;
+ *  float brightness, contrast, saturation; int32 pad} (104 bytes): src = the address of the WINDOW's first pixel inside the raw image,
+ * pitch = that image's row pitch in pixels, h / w = the window's sides (the tap tables are built for them), tmp = scratch [h][Wo][3]
+ * (4-byte aligned for dword stores), blk0_x / blk0_y = the first 256-pixel block of the job in launch 1 (h * Wo pixels) / in launches
+ * 2 and 3 (Ho * Wo pixels), blocks_x / blocks_y their totals.  gray_sums: njobs uint32 accumulators (zeroed by launch 1; the mean
+ * gray value contrast blends with is their exact integer sum / (Ho * Wo)); Ho * Wo <= 2^24.  Launch 3 (contrast, saturation; in place)
+ * runs only when do_cs != 0: pass 0 when every job has contrast == saturation == 1. */
+int zsg_augment_u8_batched(const void* jobs_dev, int32_t njobs, int32_t Ho, int32_t Wo, int32_t blocks_x, int32_t blocks_y,
+                           void* gray_sums, int32_t do_cs, void* stream);
 /* Head input BackBone.concat_we (mdl.py:69-104) + head conv0 (mdl.py:216, 514 -> 256, 3x3 pad 1) without ever materialising
  * the concatenated tensor, and without its spatially-constant input channels: the language vector
  * is constant over the image and the grid channels do not depend on the batch index, so only the 256 feature channels

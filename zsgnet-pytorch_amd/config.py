@@ -36,6 +36,10 @@ DEFAULTS: Dict[str, Any] = {
     "ema_decay": 0.0,               # > 0: an exponential moving average of the weights, updated in every optimizer step (ema.ModelEma); 0 = off
     "ema_warmup": False,            # ... its decay ramps up as min(ema_decay, (1 + n) / (10 + n)) over the first updates
     "ema_eval": True,               # ... validation / testing (and with them the LR scheduler, best_met, the prediction files) use the average
+    "aug_crop_min": 1.0,            # < 1 (in (0, 1]): training images are cropped to a random window of this fraction of each side at least, which always holds the box(es) (dat_loader.draw_augment); 1 = off
+    "aug_brightness": 0.0,          # > 0: training images get a brightness factor from U(max(0, 1 - v), 1 + v) (dat_loader.augment_host; on the GPU with gpu_img_resize); 0 = off
+    "aug_contrast": 0.0,            # ... a contrast factor (blend with the image's mean gray value)
+    "aug_saturation": 0.0,          # ... a saturation factor (blend with the pixel's gray value)
     # configs/ds_info.json: where each dataset's images and csv files live (override with --ds_info.<name>.<key>=...)
     "ds_info": {name: {"data_dir": f"./data/{root}", "img_dir": f"./data/{imgs}",
                        **{f"{s}_csv_file": f"./data/{csv}/csv_dir/{f}.csv" for s, f in (("trn", trn), ("val", "val"), ("test", "test"))}}

@@ -17,6 +17,7 @@ What is different, and why:
     undefined for flickr30k_c0/c1, vg_split_*) work: flickr30k* ids get the '.jpg' suffix, everything else is a path.
 """
 import ast
+import collections
 import functools
 import math
 import re
@@ -124,28 +125,24 @@ def resize_tables(in_size: int, out_size: int):
     filterscale = max(scale, 1.0)
     support = 2.0 * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
-    bounds = np.zeros((out_size, 2), np.int32)
-    coef = np.zeros((out_size, ksize), np.int32)
     ss = 1.0 / filterscale
-    for xx in range(out_size):
-        center = 0.0 + (xx + 0.5) * scale
-        xmin = int(center - support + 0.5)
-        if xmin < 0:
-            xmin = 0
-        xmax = int(center + support + 0.5)
-        if xmax > in_size:
-            xmax = in_size
-        xmax -= xmin
-        k = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
-        ww = 0.0
-        for w in k:
-            ww += w
-        if ww != 0.0:
-            k = [w / ww for w in k]
-        bounds[xx] = (xmin, xmax)
-        for x, w in enumerate(k):
-            v = w * (1 << _RESIZE_PRECISION_BITS)
-            coef[xx, x] = int(-0.5 + v) if w < 0 else int(0.5 + v)
+    # every output position at once; per element the SAME double-precision operations in the same order as Pillow's loops
+    # (a random augmentation crop needs two new tables per image: a Python loop per output position cost the consumer thread ~1 ms each)
+    center = 0.0 + (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)                      # (int): truncation
+    cnt = np.minimum((center + support + 0.5).astype(np.int64), in_size) - xmin
+    taps = np.arange(ksize, dtype=np.int64)[None, :]
+    x = np.abs(((taps + xmin[:, None]) - center[:, None] + 0.5) * ss)
+    a = -0.5
+    k = np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1, np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))      # _bicubic
+    k = np.where(taps < cnt[:, None], k, 0.0)
+    ww = np.zeros(out_size, np.float64)
+    for t in range(ksize):                                                               # the sum in tap order, as Pillow adds it
+        ww = ww + k[:, t]
+    k = np.where((ww != 0.0)[:, None], k / np.where(ww != 0.0, ww, 1.0)[:, None], k)
+    v = k * (1 << _RESIZE_PRECISION_BITS)
+    coef = np.where(k < 0, (-0.5 + v).astype(np.int64), (0.5 + v).astype(np.int64)).astype(np.int32)
+    bounds = np.stack([xmin, cnt], 1).astype(np.int32)
     return bounds, coef, ksize
 
 
@@ -157,6 +154,103 @@ def flatten_raw(imgs) -> Tuple[torch.Tensor, torch.Tensor]:
     return torch.cat([im.reshape(-1) for im in imgs]), hw
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# training augmentation: box-safe random crop + colour jitter.  The host definition (exact to the byte); the HIP kernels of
+# csrc/aug.hip (zsg_augment_u8_batched, driven by GpuResizer.resize_flat) reproduce augment_host bit for bit.
+# ---------------------------------------------------------------------------------------------------------------------
+AUG_KEYS = {"aug_crop_min": 1.0, "aug_brightness": 0.0, "aug_contrast": 0.0, "aug_saturation": 0.0}      # the defaults: off
+
+
+def aug_params(cfg) -> Tuple[float, float, float, float]:
+    """the four aug_* keys of cfg (a cfg without them = the defaults), validated: ValueError outside their ranges"""
+    cmin, vb, vc, vs = (float(cfg[k]) if k in cfg else d for k, d in AUG_KEYS.items())
+    if not (0.0 < cmin <= 1.0):
+        raise ValueError(f"aug_crop_min = {cmin}: must lie in (0, 1]")
+    for k, v in (("aug_brightness", vb), ("aug_contrast", vc), ("aug_saturation", vs)):
+        if not (0.0 <= v < math.inf):
+            raise ValueError(f"{k} = {v}: must be >= 0 (and finite)")
+    return cmin, vb, vc, vs
+
+
+def aug_enabled(cfg) -> bool:
+    return aug_params(cfg) != tuple(AUG_KEYS.values())
+
+
+def draw_augment(rng, h: int, w: int, boxes, cfg):
+    """One random augmentation of a decoded h x w image whose queries have the pixel boxes `boxes` ([x1, y1, x2, y2] each): None when
+    the aug_* keys are at their defaults, else (crop, jitter) with crop = (x0, y0, x0 + cw, y0 + ch) integers — inside the image and
+    holding every box (clipped to the image) — and jitter = float32 (brightness, contrast, saturation) factors.  rng: numpy's
+    uniform / randint interface (np.random, a RandomState).  Draw order: cw, ch, x0, y0, then the three factors; a part that is off
+    draws nothing."""
+    cmin, vb, vc, vs = aug_params(cfg)
+    if (cmin, vb, vc, vs) == tuple(AUG_KEYS.values()):
+        return None
+    h, w = int(h), int(w)
+    crop = (0, 0, w, h)
+    if cmin < 1.0:
+        cw = max(1, int(round(w * rng.uniform(cmin, 1.0))))
+        ch = max(1, int(round(h * rng.uniform(cmin, 1.0))))
+        b = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+        xs, ys = np.clip(b[:, [0, 2]], 0, w), np.clip(b[:, [1, 3]], 0, h)
+        X1, X2, Y1, Y2 = int(math.floor(xs.min())), int(math.ceil(xs.max())), int(math.floor(ys.min())), int(math.ceil(ys.max()))
+        cw, ch = min(w, max(cw, X2 - X1, 1)), min(h, max(ch, Y2 - Y1, 1))
+        x0 = int(rng.randint(max(0, X2 - cw), min(X1, w - cw) + 1))           # never empty: cw >= X2 - X1, X2 <= w, cw <= w
+        y0 = int(rng.randint(max(0, Y2 - ch), min(Y1, h - ch) + 1))
+        crop = (x0, y0, x0 + cw, y0 + ch)
+    f = [np.float32(rng.uniform(max(0.0, 1.0 - v), 1.0 + v)) if v > 0 else np.float32(1.0) for v in (vb, vc, vs)]
+    return crop, np.array(f, np.float32)
+
+
+def _resize_pass_host(src: np.ndarray, n_out: int) -> np.ndarray:
+    """one pass of Pillow's 8-bit resampler along axis 0 of uint8 [n_in, m, 3], with resize_tables' integers (an unchanged length:
+    Pillow skips the pass)"""
+    n_in = src.shape[0]
+    if n_in == n_out:
+        return src
+    bounds, coef, ks = resize_tables(n_in, n_out)
+    idx = np.minimum(bounds[:, :1] + np.arange(ks, dtype=np.int32)[None], n_in - 1)      # taps past the count have coefficient 0
+    acc = np.int32(1 << 21) + (src[idx].astype(np.int32) * coef[:, :, None, None]).sum(axis=1, dtype=np.int32)
+    return np.clip(acc >> 22, 0, 255).astype(np.uint8)
+
+
+_GRAY = (np.float32(0.2989), np.float32(0.587), np.float32(0.114))
+
+
+def _gray_host(p: np.ndarray) -> np.ndarray:
+    """trunc((0.2989 r + 0.587 g) + 0.114 b) of float32 [..., 3], every product and sum rounded to fp32"""
+    return np.trunc((_GRAY[0] * p[..., 0] + _GRAY[1] * p[..., 1]) + _GRAY[2] * p[..., 2])
+
+
+def _blend_host(x: np.ndarray, m, f: np.float32) -> np.ndarray:
+    """trunc(clamp(f * x + (1 - f) * m, 0, 255)) in fp32, no fused multiply-add (numpy rounds every operation)"""
+    return np.trunc(np.clip(f * x + (np.float32(1.0) - f) * m, np.float32(0.0), np.float32(255.0)))
+
+
+def augment_host(img_u8_hwc: np.ndarray, crop, jitter, out_hw) -> np.ndarray:
+    """THE definition of the training augmentation: uint8 [h, w, 3] -> uint8 [Ho, Wo, 3].
+    1. Pillow's `img.crop(crop).resize((Wo, Ho))`: the tap tables of the crop's side lengths applied to the window (taps stop at the
+       window's edge, not the image's);
+    2. brightness: blend(x, 0, b);  3. contrast: blend(x, mean, c), mean = the exact integer sum of gray over the image after step 2,
+       divided by Ho * Wo in double precision and rounded once to fp32;  4. saturation: blend(x, gray(pixel after step 3), s);
+    with blend(x, m, f) = trunc(clamp(f * x + (1 - f) * m, 0, 255)) and gray = trunc((0.2989 r + 0.587 g) + 0.114 b), all in fp32 with
+    every product and sum rounded separately.  A factor of exactly 1 is the identity."""
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    a = np.asarray(img_u8_hwc)
+    assert a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3, "augment_host: uint8 [h, w, 3]"
+    x0, y0, x1, y1 = (int(v) for v in crop)
+    if not (0 <= x0 < x1 <= a.shape[1] and 0 <= y0 < y1 <= a.shape[0]):
+        raise ValueError(f"augment_host: crop {(x0, y0, x1, y1)} is not inside the {a.shape[0]} x {a.shape[1]} image")
+    win = a[y0:y1, x0:x1]
+    win = _resize_pass_host(win.transpose(1, 0, 2), Wo).transpose(1, 0, 2)        # horizontal pass first, as Pillow
+    p = _resize_pass_host(win, Ho).astype(np.float32)
+    fb, fc, fs = (np.float32(v) for v in jitter)
+    p = _blend_host(p, np.float32(0.0), fb)
+    mean = np.float32(np.float64(int(_gray_host(p).astype(np.int64).sum())) / np.float64(Ho * Wo))
+    p = _blend_host(p, mean, fc)
+    p = _blend_host(p, _gray_host(p)[..., None], fs)
+    return p.astype(np.uint8)
+
+
 class GpuResizer:
     """Resizes raw uint8 HWC images of ANY size to one [B, H, W, 3] uint8 batch on the GPU (Pillow's two-pass fixed-point bicubic, bit-
     identical to PIL.Image.resize's default filter, dat_loader.py:121).  The tap tables of an axis length are computed once on the host
@@ -165,31 +259,74 @@ class GpuResizer:
 
     def __init__(self, out_hw, device="cuda"):
         self.Ho, self.Wo, self.dev = int(out_hw[0]), int(out_hw[1]), device
-        self._tab = {}
+        self._tab = collections.OrderedDict()          # (axis length in, out) -> device tap tables, least recently used first
         self._tmp = None
+        self._gray = None
         self._jobs_host = None
         import PIL
         if tuple(int(v) for v in PIL.__version__.split(".")[:2]) < (7, 0):      # (Pillow < 7 resizes with NEAREST by default: the two paths would differ)
             raise RuntimeError("GpuResizer reproduces PIL.Image.resize's default filter of Pillow >= 7 (bicubic); found Pillow " + PIL.__version__)
 
-    def _tables(self, n_in, n_out, identity_ok=False):
-        key = (n_in, n_out)
-        if key not in self._tab:
-            if n_in == n_out and not identity_ok:
-                self._tab[key] = None                    # Pillow skips a pass whose size does not change
-            elif n_in == n_out:
-                # the batched launches run both passes for every image: an unchanged axis gets the identity table (one tap, 2^22)
+    TABLE_CACHE = 4096          # device tap tables kept (as resize_tables' lru_cache): crop sides vary per sample
+
+    def _tables(self, n_in, n_out, identity_ok=True):
+        """device tap tables (bounds, coefficients, ksize) of one axis; an axis that keeps its length gets the identity table (one tap,
+        2^22: the batched launches run both passes for every image, Pillow skips that pass — the same bytes)"""
+        self._ensure_tables([(n_in, n_out)])
+        return self._tab[(n_in, n_out)]
+
+    def _ensure_tables(self, keys):
+        """All tables of a batch that are not on the device yet travel in ONE pinned, asynchronous upload (random crops bring two new
+        axis lengths per image).  The cache is bounded: the least recently used tables leave; kernels still queued keep theirs (the
+        caching allocator reuses a freed block only for later work of the same stream)."""
+        new = []
+        for key in dict.fromkeys(keys):
+            if key in self._tab:
+                self._tab.move_to_end(key)
+            else:
+                new.append(key)
+        if not new:
+            return
+        host, parts = [], []
+        for n_in, n_out in new:
+            if n_in == n_out:
                 b = np.stack([np.arange(n_out, dtype=np.int32), np.ones(n_out, np.int32)], 1)
-                c = np.full((n_out, 1), 1 << _RESIZE_PRECISION_BITS, np.int32)
-                self._tab[key] = (torch.from_numpy(b).to(self.dev), torch.from_numpy(c).to(self.dev), 1)
+                c, ks = np.full((n_out, 1), 1 << _RESIZE_PRECISION_BITS, np.int32), 1
             else:
                 b, c, ks = resize_tables(n_in, n_out)
-                self._tab[key] = (torch.from_numpy(b).to(self.dev), torch.from_numpy(c).to(self.dev), ks)
-        return self._tab[key]
+            host += [b.reshape(-1), c.reshape(-1)]
+            parts.append((n_out, ks))
+        buf = torch.from_numpy(np.concatenate(host))
+        dev = (buf.pin_memory() if torch.device(self.dev).type == "cuda" else buf).to(self.dev, non_blocking=True)
+        off = 0
+        for key, (n, ks) in zip(new, parts):
+            while len(self._tab) >= max(self.TABLE_CACHE, 2 * len(keys)):
+                self._tab.popitem(last=False)
+            self._tab[key] = (dev[off:off + 2 * n].view(n, 2), dev[off + 2 * n:off + (2 + ks) * n].view(n, ks), ks)
+            off += (2 + ks) * n
 
-    def resize_flat(self, flat: torch.Tensor, hw, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """flat: uint8 DEVICE tensor holding the raw images back to back; hw: [B, 2] (host) heights / widths.  Returns uint8 [B, Ho, Wo, 3]."""
-        return self._run([(flat.data_ptr() + off, h, w) for off, h, w in self._offsets(hw)], out, keep=flat)
+    def resize_flat(self, flat: torch.Tensor, hw, out: Optional[torch.Tensor] = None, crop=None, jitter=None) -> torch.Tensor:
+        """flat: uint8 DEVICE tensor holding the raw images back to back; hw: [B, 2] (host) heights / widths.  Returns uint8 [B, Ho, Wo, 3].
+        crop ([B, 4] host integers x0, y0, x1, y1 inside each image) and / or jitter ([B, 3] host float32 brightness, contrast,
+        saturation factors): the training augmentation augment_host defines, on the GPU (zsg_augment_u8_batched) — each image's
+        window is resized instead of the whole image, then jittered; a missing one = the whole image / factors 1."""
+        offs = self._offsets(hw)
+        if crop is None and jitter is None:
+            return self._run([(flat.data_ptr() + off, h, w) for off, h, w in offs], out, keep=flat)
+        B = len(offs)
+        crop = [[0, 0, w, h] for _, h, w in offs] if crop is None else (crop.tolist() if torch.is_tensor(crop) else [list(c) for c in crop])
+        jit = np.ones((B, 3), np.float32) if jitter is None else np.asarray(jitter.cpu() if torch.is_tensor(jitter) else jitter, dtype=np.float32).reshape(-1, 3)
+        if len(crop) != B or jit.shape[0] != B:
+            raise ValueError(f"resize_flat: {B} images, {len(crop)} crops, {jit.shape[0]} jitter triples")
+        if not np.isfinite(jit).all() or (jit < 0).any():
+            raise ValueError("resize_flat: jitter factors must be finite and >= 0")
+        items = []
+        for (off, h, w), c in zip(offs, crop):
+            x0, y0, x1, y1 = (int(v) for v in c)
+            if not (0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h):          # checked HERE: the kernels read the window unchecked
+                raise ValueError(f"resize_flat: crop {(x0, y0, x1, y1)} is not inside the {h} x {w} image")
+            items.append((flat.data_ptr() + off + (y0 * w + x0) * 3, y1 - y0, x1 - x0, w))
+        return self._run_aug(items, jit, out)
 
     @staticmethod
     def _offsets(hw):
@@ -210,17 +347,23 @@ class GpuResizer:
             self._tmp = torch.empty(need, dtype=torch.uint8, device=self.dev)
         blob, tmp_off, bx, by = b"", 0, 0, 0
         per_out = self.Ho * self.Wo * 3
+        self._ensure_tables([(w, self.Wo) for _, _, w in items] + [(h, self.Ho) for _, h, _ in items])
         for i, (ptr, h, w) in enumerate(items):
-            tx, ty = self._tables(w, self.Wo, True), self._tables(h, self.Ho, True)
+            tx, ty = self._tab[(w, self.Wo)], self._tab[(h, self.Ho)]
             blob += struct.pack("<qqqqqqqiiiiiiii", ptr, self._tmp.data_ptr() + tmp_off, out.data_ptr() + i * per_out,
                                 tx[0].data_ptr(), tx[1].data_ptr(), ty[0].data_ptr(), ty[1].data_ptr(), h, w, tx[2], ty[2], bx, by, 0, 0)
             tmp_off += h * self.Wo * 3
             bx += (h * self.Wo * 3 + 1023) // 1024
             by += (per_out + 1023) // 1024
-        # job table: pinned host slot -> device, asynchronously; four slots in rotation, each guarded by the event of its last upload
-        # (a slot is rewritten only when that copy has completed: normally four batches ago)
+        jobs = self._upload_jobs(blob, 88)
+        check(lib.zsg_resize_u8_batched(jobs.data_ptr(), B, 3, self.Ho, self.Wo, bx, by, stream_ptr()), "zsg_resize_u8_batched")
+        return out
+
+    def _upload_jobs(self, blob: bytes, stride: int):
+        """job table: pinned host slot -> device, asynchronously; four slots in rotation, each guarded by the event of its last upload
+        (a slot is rewritten only when that copy has completed: normally four batches ago).  Returns the device table."""
         if self._jobs_host is None or self._jobs_host[0].numel() < len(blob):
-            n = max(len(blob), 88 * 256)
+            n = max(len(blob), stride * 256)
             self._jobs_host = [torch.empty(n, dtype=torch.uint8).pin_memory() for _ in range(4)]
             self._jobs_dev = [torch.empty(n, dtype=torch.uint8, device=self.dev) for _ in range(4)]
             self._jobs_ev = [None] * 4
@@ -232,7 +375,35 @@ class GpuResizer:
         self._jobs_dev[k][:len(blob)].copy_(self._jobs_host[k][:len(blob)], non_blocking=True)
         self._jobs_ev[k] = torch.cuda.Event()
         self._jobs_ev[k].record()
-        check(lib.zsg_resize_u8_batched(self._jobs_dev[k].data_ptr(), B, 3, self.Ho, self.Wo, bx, by, stream_ptr()), "zsg_resize_u8_batched")
+        return self._jobs_dev[k]
+
+    def _run_aug(self, items, jit, out):
+        """items: (address of the window's first pixel, window height, window width, row pitch of its image in pixels) per image"""
+        import struct
+        from ._lib import check, lib, stream_ptr
+        B = len(items)
+        if out is None:
+            out = torch.empty(B, self.Ho, self.Wo, 3, dtype=torch.uint8, device=self.dev)
+        need = sum((h * self.Wo * 3 + 3) // 4 * 4 for _, h, _, _ in items)
+        if self._tmp is None or self._tmp.numel() < need:
+            self._tmp = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        if self._gray is None or self._gray.numel() < B:
+            self._gray = torch.zeros(max(B, 64), dtype=torch.int32, device=self.dev)
+        blob, tmp_off, bx, by = b"", 0, 0, 0
+        per_out = self.Ho * self.Wo * 3
+        self._ensure_tables([(w, self.Wo) for _, _, w, _ in items] + [(h, self.Ho) for _, h, _, _ in items])
+        for i, (ptr, h, w, pitch) in enumerate(items):
+            tx, ty = self._tab[(w, self.Wo)], self._tab[(h, self.Ho)]
+            blob += struct.pack("<qqqqqqqiiiiiiiifffi", ptr, self._tmp.data_ptr() + tmp_off, out.data_ptr() + i * per_out,
+                                tx[0].data_ptr(), tx[1].data_ptr(), ty[0].data_ptr(), ty[1].data_ptr(), h, w, pitch, tx[2], ty[2], bx, by, 0,
+                                float(jit[i, 0]), float(jit[i, 1]), float(jit[i, 2]), 0)
+            tmp_off += (h * self.Wo * 3 + 3) // 4 * 4          # every job's scratch starts dword aligned
+            bx += (h * self.Wo + 255) // 256
+            by += (self.Ho * self.Wo + 255) // 256
+        jobs = self._upload_jobs(blob, 104)
+        do_cs = int(bool((jit[:, 1:] != 1.0).any()))           # launch 3 (contrast, saturation) only when some job needs it
+        check(lib.zsg_augment_u8_batched(jobs.data_ptr(), B, self.Ho, self.Wo, bx, by, self._gray.data_ptr(), do_cs, stream_ptr()),
+              "zsg_augment_u8_batched")
         return out
 
     def __call__(self, imgs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -257,6 +428,7 @@ class ImgQuDataset(Dataset):
         gpu_normalise = gpu_normalise or gpu_resize
         self.cfg, self.ds_name, self.split_type, self.gpu_normalise, self.gpu_resize = cfg, ds_name, split_type, gpu_normalise, gpu_resize
         self.embedder = embedder if embedder is not None else get_embedder(cfg)
+        self.augment = split_type == "train" and aug_enabled(cfg)      # training split only: draw_augment per item / per image slot
         self.img_dir = Path(cfg["ds_info"][ds_name]["img_dir"])
         self.phrase_len = PHRASE_LEN
         df = pd.read_csv(csv_file)
@@ -269,35 +441,55 @@ class ImgQuDataset(Dataset):
     def __len__(self):
         return len(self.files)
 
-    def load_image(self, idx: int) -> Tuple[torch.Tensor, int, int]:
-        """the image of row idx as the batch carries it (decoded, resized unless gpu_resize) + its decoded height / width"""
+    def load_image(self, idx: int, boxes=None):
+        """the image of row idx as the batch carries it (decoded, resized unless gpu_resize) + its decoded height / width.
+        boxes (a training dataset with augmentation on): the pixel boxes the crop must keep — one draw_augment from np.random; a worker
+        that resizes applies it (augment_host), with gpu_resize the raw image travels and DevicePrefetcher applies it on the GPU.
+        Returns a fourth value then: the (crop, jitter) drawn."""
         import PIL.Image
         img = PIL.Image.open(self.img_dir / self.files[idx]).convert("RGB")
         h, w = img.height, img.width
         rs = self.cfg["resize_img"]
+        aug = draw_augment(np.random, h, w, boxes, self.cfg) if boxes is not None else None
         if not self.gpu_resize:
-            img = img.resize((rs[0], rs[1]))                      # PIL's default filter, as the reference (dat_loader.py:121)
+            if aug is not None:
+                img = augment_host(np.asarray(img), aug[0], aug[1], (rs[1], rs[0]))
+            else:
+                img = img.resize((rs[0], rs[1]))                  # PIL's default filter, as the reference (dat_loader.py:121)
         a = np.asarray(img)                                       # [H, W, 3] uint8
         if self.gpu_normalise:
             img_t = torch.from_numpy(a.copy())                    # normalised on the GPU (zsg_u8hwc_to_nhwc4)
         else:
             img_t = torch.from_numpy(a.transpose(2, 0, 1).astype(np.float64)).float().div_(255)     # pil2tensor(...).float().div_(255)
-        return img_t, h, w
+        return (img_t, h, w) if boxes is None else (img_t, h, w, aug)
 
-    def query_item(self, idx: int, h: int, w: int) -> Dict[str, torch.Tensor]:
-        """the per-query fields of row idx (everything but the image, whose decoded size h, w scales the box)"""
+    def query_item(self, idx: int, h: int, w: int, crop=None) -> Dict[str, torch.Tensor]:
+        """the per-query fields of row idx (everything but the image, whose decoded size h, w scales the box).  crop (x0, y0, x1, y1):
+        the image was cropped to that window — the box is given relative to it (unclipped) and img_size is the window's, so the
+        identities between annot, orig_annot and img_size the evaluator relies on keep holding."""
         q = self.queries[idx]
         if isinstance(q, list):
             q = str(np.random.choice(q))                          # dat_loader.py:153-154
         q = q.replace("_", " ")
         qvec, qlen = embed_query(self.embedder, q, self.phrase_len)
         x1, y1, x2, y2 = self.boxes[idx]
+        if crop is not None:
+            x0, y0 = int(crop[0]), int(crop[1])
+            h, w = int(crop[3]) - y0, int(crop[2]) - x0
+            x1, y1, x2, y2 = x1 - x0, y1 - y0, x2 - x0, y2 - y0
         target = 2 * np.array([y1 / h, x1 / w, y2 / h, x2 / w]) - 1          # y1x1y2x2 in [-1, 1] (anchors are row, column)
         return {"idxs": torch.tensor(idx).long(), "qvec": torch.from_numpy(qvec),
                 "qlens": torch.tensor(min(qlen, self.phrase_len)), "annot": torch.from_numpy(target).float(),
                 "orig_annot": torch.tensor([x1, y1, x2, y2]).float(), "img_size": torch.tensor([h, w])}
 
     def __getitem__(self, idx: int) -> Dict[str, torch.Tensor]:
+        if self.augment:
+            img_t, h, w, (crop, jitter) = self.load_image(idx, [self.boxes[idx]])
+            item = {"img": img_t}
+            item.update(self.query_item(idx, h, w, crop))
+            if self.gpu_resize:                                   # applied by DevicePrefetcher (GpuResizer.resize_flat), dropped there
+                item["aug_crop"], item["aug_jitter"] = torch.tensor(crop, dtype=torch.int32), torch.from_numpy(jitter)
+            return item
         img_t, h, w = self.load_image(idx)
         item = {"img": img_t}
         item.update(self.query_item(idx, h, w))
@@ -324,16 +516,22 @@ class ImgQuDataset(Dataset):
         """One batch of the grouped TRAINING loader (cfg group_trn_by_image): one image slot per chunk — the rows of a chunk share an image
         file, which is decoded (and resized) once, from the chunk's first row — even if two chunks of one file meet in a batch; the
         queries in chunk order.  Exactly len(chunks) slots, every one used (checked by the collater)."""
-        imgs, items, idx = [], [], []
+        imgs, items, idx, crops, jitters = [], [], [], [], []
         for s, rows in enumerate(chunks):
             if len({self.files[r] for r in rows}) != 1:
                 raise ValueError(f"grouped_train_batch: chunk {s} mixes image files")
-            img_t, h, w = self.load_image(rows[0])
+            crop = None
+            if self.augment:                                      # ONE draw per image slot, from the union of the chunk's boxes
+                img_t, h, w, (crop, jitter) = self.load_image(rows[0], [self.boxes[r] for r in rows])
+                crops.append(crop)
+                jitters.append(jitter)
+            else:
+                img_t, h, w = self.load_image(rows[0])
             imgs.append(img_t)
             for r in rows:
-                items.append(self.query_item(r, h, w))
+                items.append(self.query_item(r, h, w, crop))
                 idx.append(s)
-        return grouped_collater(items, imgs, idx, all_slots_used=True)
+        return grouped_collater(items, imgs, idx, all_slots_used=True, aug=(crops, jitters) if self.augment and self.gpu_resize else None)
 
 
 def collater(batch: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
@@ -348,7 +546,7 @@ def collater(batch: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
             out["img"], out["img_hw"] = flatten_raw([b[k] for b in batch])
             continue
         t = torch.stack([b[k] for b in batch])
-        out[k] = t if (k == "img" and t.dtype == torch.uint8) else t.float()
+        out[k] = t if ((k == "img" and t.dtype == torch.uint8) or k == "aug_crop") else t.float()       # (aug_crop: int32 pixel windows)
     out["qvec"] = out["qvec"][:, :max_qlen]
     if "img_hw" in out:
         out["img_hw"] = out["img_hw"].int()
@@ -356,10 +554,12 @@ def collater(batch: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
 
 
 def grouped_collater(items: List[Dict[str, torch.Tensor]], imgs: List[torch.Tensor], img_idx: List[int],
-                     all_slots_used: bool = False) -> Dict[str, torch.Tensor]:
+                     all_slots_used: bool = False, aug=None) -> Dict[str, torch.Tensor]:
     """collater for queries that share images: `items` carry no image; `imgs` are the distinct images, img_idx[q] the image of query q.
     This is where the index range is checked (on the host, once per batch): the forward reads img_idx on the device only.
-    all_slots_used (training batches): every image slot must be named by some query — train-mode BatchNorm reduces over all slots."""
+    all_slots_used (training batches): every image slot must be named by some query — train-mode BatchNorm reduces over all slots.
+    aug = (crops, jitters), one per image SLOT (gpu_resize training with augmentation): emitted as `aug_crop` int32 [slots, 4] and
+    `aug_jitter` float32 [slots, 3] alongside `img`."""
     if not imgs or len(img_idx) != len(items) or min(img_idx) < 0 or max(img_idx) >= len(imgs):
         raise ValueError(f"grouped_collater: img_idx out of range for {len(imgs)} images / {len(items)} queries")
     if all_slots_used and len(set(img_idx)) != len(imgs):
@@ -372,6 +572,11 @@ def grouped_collater(items: List[Dict[str, torch.Tensor]], imgs: List[torch.Tens
         t = torch.stack(imgs)
         out["img"] = t if t.dtype == torch.uint8 else t.float()
     out["img_idx"] = torch.tensor(img_idx, dtype=torch.long)
+    if aug is not None:
+        if len(aug[0]) != len(imgs) or len(aug[1]) != len(imgs):
+            raise ValueError(f"grouped_collater: {len(imgs)} image slots but {len(aug[0])} crops / {len(aug[1])} jitter triples")
+        out["aug_crop"] = torch.tensor([list(c) for c in aug[0]], dtype=torch.int32)
+        out["aug_jitter"] = torch.from_numpy(np.stack(aug[1]).astype(np.float32))
     return out
 
 
@@ -550,6 +755,8 @@ class DevicePrefetcher:
     """Wraps a loader of pinned host batches: the next batch is copied to the GPU on a side stream while the current one
     is being consumed (HIP copy engine overlaps the training step), and handed over with an event wait."""
 
+    _HOST_ONLY = ("img_hw", "aug_crop", "aug_jitter")        # fields the resizer consumes on the host: not part of the device batch
+
     def __init__(self, loader, device="cuda", resize_hw=None):
         """resize_hw = (H, W): batches whose "img" is raw uint8 HWC (a list of differently sized images, or a stack at another size)
         are resized on the GPU, on the upload stream (GpuResizer)."""
@@ -565,14 +772,15 @@ class DevicePrefetcher:
         if self.stream is None:
             return batch, None
         with torch.cuda.stream(self.stream):
-            dev = {k: v.to(self.device, non_blocking=True) for k, v in batch.items() if torch.is_tensor(v) and k != "img_hw"}
+            dev = {k: v.to(self.device, non_blocking=True) for k, v in batch.items() if torch.is_tensor(v) and k not in self._HOST_ONLY}
             img = batch.get("img")
             hw = batch.get("img_hw")
+            crop, jitter = batch.get("aug_crop"), batch.get("aug_jitter")      # training augmentation: applied by the resizer, not handed on
             if isinstance(img, list):              # (callers that still hand over a list of raw images: flattened here, on this thread)
                 img, hw = flatten_raw(img)
                 dev["img"] = img.pin_memory().to(self.device, non_blocking=True)
             elif hw is None and self.resize_hw and torch.is_tensor(img) and img.dtype == torch.uint8 and img.dim() == 4 \
-                    and tuple(img.shape[1:3]) != self.resize_hw:
+                    and (tuple(img.shape[1:3]) != self.resize_hw or crop is not None):
                 hw = torch.tensor([[img.shape[1], img.shape[2]]] * img.shape[0], dtype=torch.int32)      # a stack at another size
                 dev["img"] = dev["img"].reshape(-1)
             if hw is not None:
@@ -580,7 +788,9 @@ class DevicePrefetcher:
                     raise RuntimeError("DevicePrefetcher: raw images of mixed sizes need resize_hw")
                 if self._resizer is None:
                     self._resizer = GpuResizer(self.resize_hw, self.device)
-                dev["img"] = self._resizer.resize_flat(dev["img"], hw)
+                dev["img"] = self._resizer.resize_flat(dev["img"], hw, crop=crop, jitter=jitter)
+            elif crop is not None:
+                raise RuntimeError("DevicePrefetcher: a batch with aug_crop / aug_jitter needs raw uint8 images and resize_hw")
             ev = torch.cuda.Event()
             ev.record(self.stream)
         return dev, ev
@@ -612,6 +822,7 @@ def get_data(cfg, embedder=None, prefetch: Optional[bool] = None):
     from .synth import DataWrap
     ds_name = cfg["ds_to_use"]
     info = cfg["ds_info"][ds_name]
+    aug_params(cfg)                                          # ValueError for an aug_* key outside its range
     emb = embedder if embedder is not None else get_embedder(cfg)
     gpu = torch.cuda.is_available() and (cfg["gpu_img_normalise"] if "gpu_img_normalise" in cfg else True)
     prefetch = gpu if prefetch is None else prefetch
