@@ -548,10 +548,12 @@ def sort_rank(qlens: torch.Tensor) -> torch.Tensor:
     return rank
 
 
-def query_encoder(sd, qvec, qlens, h0, c0, rank: Optional[torch.Tensor] = None):
+def query_encoder(sd, qvec, qlens, h0, c0, rank: Optional[torch.Tensor] = None, bidirectional: bool = True):
     """[B, 2H] = [h_fwd(len-1) || reverse-cell(x[len-1]; h0[1],c0[1])].
     Reference mdl.py:296-336 with a packed bidirectional nn.LSTM: the backward direction's output at the
-    last valid token is its FIRST step.  h0/c0 [2,B,H] are indexed by *sorted* position."""
+    last valid token is its FIRST step.  h0/c0 [2,B,H] are indexed by *sorted* position.
+    bidirectional=False (cfg use_bidirectional): [B, H] = h_fwd(len-1) alone, h0/c0 [1,B,H]; the `_reverse` keys are
+    not read.  The direction is the caller's statement, never inferred from which keys `sd` happens to hold."""
     B = qvec.shape[0]
     if rank is None:
         rank = sort_rank(qlens)
@@ -563,6 +565,9 @@ def query_encoder(sd, qvec, qlens, h0, c0, rank: Optional[torch.Tensor] = None):
         for t in range(int(lens[b])):
             h, c = lstm_cell(qvec[b:b + 1, t], h, c, sd["lstm.weight_ih_l0"], sd["lstm.weight_hh_l0"],
                              sd["lstm.bias_ih_l0"], sd["lstm.bias_hh_l0"])
+        if not bidirectional:
+            outs.append(h)
+            continue
         hr, _ = lstm_cell(qvec[b:b + 1, int(lens[b]) - 1], h0[1, r:r + 1], c0[1, r:r + 1],
                           sd["lstm.weight_ih_l0_reverse"], sd["lstm.weight_hh_l0_reverse"],
                           sd["lstm.bias_ih_l0_reverse"], sd["lstm.bias_hh_l0_reverse"])
@@ -601,13 +606,13 @@ def head_input(feat, we, use_lang=True, use_img=True):
 
 
 def zsgnet_forward(sd, batch, h0, c0, arch="resnet50", training=True, six_hundred=False, rank=None,
-                   use_lang=True, use_img=True, do_norm=False):
+                   use_lang=True, use_img=True, do_norm=False, bidirectional=True):
     """Reference mdl.py:338-403.  Returns dict(att_out [B,A,1], bbx_out [B,A,4], feat_sizes [L,2], num_f_out [1]).
     The encoder always runs (the blind variants still take the pyramid sizes — and, in train mode, the BatchNorm
     running-statistics update — from it, mdl.py:363-375); do_norm = per-pixel channel L2 normalisation of the maps and
     of the language vector, without epsilon (mdl.py:118-130; not applied to `we` in the language-blind call)."""
     bn = BNState(sd, training)
-    we = query_encoder(sd, batch["qvec"], batch["qlens"], h0, c0, rank)
+    we = query_encoder(sd, batch["qvec"], batch["qlens"], h0, c0, rank, bidirectional)
     if arch == "ssd_vgg":
         feats = ssd_forward(sd, batch["img"], six_hundred)
     else:

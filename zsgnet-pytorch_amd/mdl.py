@@ -36,6 +36,8 @@ from .params import ParamStore, pad4, register_named
 VGG_BASE = [64, 64, "M", 128, 128, "M", 256, 256, 256, "C", 512, 512, 512, "M", 512, 512, 512]     # ssd_vgg.py:174-177
 SSD_EXTRAS = [256, "S", 512, 128, "S", 256, 128, 256, 128, 256]                                          # ssd_vgg.py:179-182
 
+LSTM_DIMS = (32, 64, 128, 256)    # cfg lstm_dim: the widths csrc/lstm.hip instantiates zsg_lstm_fwd / zsg_lstm_bwd for
+
 LIVE_NETS = weakref.WeakSet()      # every ZSGNet alive: optim.clip_grad_norm_ finds a parameter's flat store here
 
 ARCHS = {
@@ -120,6 +122,13 @@ class ZSGNet(nn.Module):
         self.emb_dim = int(cfg["emb_dim"])
         self.bid = bool(cfg["use_bidirectional"])
         self.lstm_dim = int(cfg["lstm_dim"])
+        # (the reference takes any value; here the recurrence is compiled per width, csrc/lstm.hip, and the input projection is an
+        # MFMA GEMM over 4-channel groups, zsg_conv_igemm: refuse before anything is allocated, not with -1 inside the first forward)
+        if self.lstm_dim not in LSTM_DIMS:
+            raise ValueError(f"lstm_dim={self.lstm_dim}: supported values are {', '.join(map(str, LSTM_DIMS))}")
+        if self.emb_dim <= 0 or self.emb_dim % 4:
+            raise ValueError(f"emb_dim={self.emb_dim}: supported values are the positive multiples of 4 "
+                             "(zero-pad the word vectors, e.g. GloVe-50 to 52)")
         self.lstm_out_dim = self.lstm_dim * (self.bid + 1)
         self.use_lang = bool(cfg["use_lang"])
         self.use_img = bool(cfg["use_img"])
