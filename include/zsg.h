@@ -476,10 +476,25 @@ int zsg_lstm_bwd(const float* dwe, int32_t we_ld, int32_t we_off, const float* w
  * Limit: B <= 512 samples per call (one LDS record per sample in the merge kernel); larger batches are rejected with -1
  * (the reference's per-GPU batches are 16-32, BASELINE configs; split a larger batch over calls and sum the losses).
  * ------------------------------------------------------------------------------------------------------------- */
-size_t zsg_loss_workspace_bytes(int32_t B, int32_t A);
+size_t zsg_loss_workspace_bytes(int32_t B, int32_t A);   /* one size for zsg_loss_fwd_bwd and zsg_loss_fwd_bwd_iou */
 int zsg_loss_fwd_bwd(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, float alpha,
                      float gamma, float lamb_reg, float match_thr, int32_t flags, float grad_scale, float* losses,
                      float* grad5, int32_t* match_idx, int32_t* npos, void* ws, size_t ws_bytes, void* stream);
+/* zsg_loss_fwd_bwd with a box IoU term (no counterpart in the reference, whose criterion stops at loss.py:91's smooth-L1; it extends
+ * that criterion, and the pieces are the reference's: the positives of simple_match_anchors anchors.py:153-165, the decode of
+ * reg_params_to_bbox anchors.py:182-197).  For every positive anchor, p = the decoded box, g = annot, eps = 1e-7:
+ *   inter = max(min(p.y2,g.y2) - max(p.y1,g.y1), 0) * (same in x);  union = area(p) + area(g) - inter;  iou = inter / (union + eps);
+ *   ey = max(p.y2,g.y2) - min(p.y1,g.y1), ex likewise;
+ *   iou_kind 1 (giou): L = 1 - iou + (ey ex - union) / (ey ex + eps)
+ *   iou_kind 2 (diou): L = 1 - iou + |centre(p) - centre(g)|^2 / (ey^2 + ex^2 + eps)
+ * iou_ls = mean over samples of (sum of L over the sample's positives / #pos);  loss = lamb_reg box_ls + lamb_iou iou_ls + cls_ls.
+ * losses[4] = (loss, cls_ls, box_ls, iou_ls); grad5 also carries d(lamb_iou iou_ls) / d out5[..,0:4] (through the decode, exp
+ * included; positives only; the classification gradient is that of zsg_loss_fwd_bwd bit for bit).  NaN branch: box_ls, cls_ls or
+ * iou_ls NaN -> the constants of loss.py:128-133, iou_ls = 0, grad5 = 0.  Same launches, limits and workspace as zsg_loss_fwd_bwd. */
+int zsg_loss_fwd_bwd_iou(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, float alpha,
+                         float gamma, float lamb_reg, float match_thr, int32_t flags, float grad_scale, int32_t iou_kind,
+                         float lamb_iou, float* losses, float* grad5, int32_t* match_idx, int32_t* npos, void* ws,
+                         size_t ws_bytes, void* stream);
 
 /* Evaluator.forward, evaluator.py:48-117 (reg_params_to_bbox anchors.py:182-197): arg-max score anchor -> decode ->
  * IoU >= thr.  metrics[2] = (Acc, MaxPos); pred_boxes [B][4] pixels x1y1x2y2; pred_scores [B]; pred_idx [B] int32. */

@@ -1,0 +1,72 @@
+"""Developer tool: device time of the ZSGLoss call (loss + gradient kernels) at B = 16, A = 17460 on a fixed head output, for
+cfg box_iou_loss = none / giou / diou, alternating.  Each call is bracketed by the library's own HIP events (zsg_prof_enable: recorded on
+the stream right before the first and after the last launch of the entry point), so the figure is the kernels and the gaps between them,
+not the Python around them; the median of --calls calls after --warmup, min and max next to it.  One JSON line (--json PATH also writes it).
+--kinds none restricts the set (a tree from before the IoU loss has only that one)."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from oracle import zsg_oracle as O  # noqa: E402
+from zsgnet_pytorch_amd import _lib as L, config, loss  # noqa: E402
+from zsgnet_pytorch_amd.synth import synthetic_batch  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--batch", type=int, default=16)
+ap.add_argument("--calls", type=int, default=60)
+ap.add_argument("--warmup", type=int, default=10)
+ap.add_argument("--kinds", default="none,giou,diou")
+ap.add_argument("--json", default=None)
+args = ap.parse_args()
+B, A = args.batch, 17460
+kinds = args.kinds.split(",")
+
+gen = torch.Generator().manual_seed(7)
+out5 = torch.cat([torch.randn(B, A, 4, generator=gen) * 0.3, torch.randn(B, A, 1, generator=gen) * 1.5 - 3.0], dim=2).cuda().requires_grad_()
+bt = synthetic_batch(B, 8, 8, seed=1)
+out = dict(att_bbx_out=out5, feat_sizes=torch.tensor(O.feat_sizes_for(300, 300)), num_f_out=torch.tensor([6]))
+inp = {"annot": bt["annot"].cuda()}
+lfs = {}
+for k in kinds:
+    c = config.get_cfg() if k == "none" else config.get_cfg(box_iou_loss=k)
+    lfs[k] = loss.get_default_loss(*config.ratios_scales(c), c)
+
+
+def one_call(lf):
+    """device milliseconds of one call"""
+    ents = (L.ProfEntry * 16)()
+    L.lib.zsg_prof_collect(ents, 16)                 # (drop earlier records)
+    lf(out, inp)
+    n = L.lib.zsg_prof_collect(ents, 16)             # (waits for the recorded events)
+    got = {ents[i].name.decode(): (ents[i].launches, ents[i].ms) for i in range(n)}
+    (name, (calls, ms)), = [(k, v) for k, v in got.items() if k.startswith("loss_fwd_bwd")]
+    assert calls == 1, got
+    return ms
+
+
+ms = {k: [] for k in kinds}
+L.lib.zsg_prof_enable(1)
+try:
+    for i in range(args.warmup + args.calls):
+        for k in kinds:                              # alternating: every variant sees the same clock state
+            t = one_call(lfs[k])
+            if i >= args.warmup:
+                ms[k].append(t)
+finally:
+    L.lib.zsg_prof_enable(0)
+npos = lfs[kinds[0]].npos.cpu().tolist()
+res = {"what": "ZSGLoss call, HIP events around the entry point's launches, median of %d calls" % args.calls, "B": B, "A": A,
+       "positives_per_sample_min_max": [min(npos), max(npos)], "stamp": L.lib.zsg_source_stamp().decode()}
+for k in kinds:
+    v = sorted(ms[k])
+    res[k + "_us"] = round(1e3 * v[len(v) // 2], 2)
+    res[k + "_min_max_us"] = [round(1e3 * v[0], 2), round(1e3 * v[-1], 2)]
+line = json.dumps(res)
+print(line)
+if args.json:
+    with open(args.json, "w") as f:
+        f.write(line + "\n")

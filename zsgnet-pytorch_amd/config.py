@@ -40,6 +40,8 @@ DEFAULTS: Dict[str, Any] = {
     "aug_brightness": 0.0,          # > 0: training images get a brightness factor from U(max(0, 1 - v), 1 + v) (dat_loader.augment_host; on the GPU with gpu_img_resize); 0 = off
     "aug_contrast": 0.0,            # ... a contrast factor (blend with the image's mean gray value)
     "aug_saturation": 0.0,          # ... a saturation factor (blend with the pixel's gray value)
+    "box_iou_loss": "none",         # "giou" / "diou": ZSGLoss adds lamb_iou * (that IoU loss of the decoded positive boxes) to the criterion and reports it as iou_ls (zsg_loss_fwd_bwd_iou); "none" = off
+    "lamb_iou": 1.0,                # ... its weight (>= 0); lamb_reg = 0 with it trains on the IoU term alone
     # configs/ds_info.json: where each dataset's images and csv files live (override with --ds_info.<name>.<key>=...)
     "ds_info": {name: {"data_dir": f"./data/{root}", "img_dir": f"./data/{imgs}",
                        **{f"{s}_csv_file": f"./data/{csv}/csv_dir/{f}.csv" for s, f in (("trn", trn), ("val", "val"), ("test", "test"))}}

@@ -297,9 +297,19 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
     }
 }
 
-extern "C" size_t zsg_loss_workspace_bytes(int32_t B, int32_t A) {
+struct LossWsIou {       // LossWs + the sample's box-IoU loss sum (zsg_loss_fwd_bwd_iou); the same 48 bytes
+    double box_sum, cls_sum, iou_sum, row_max, row_lse;
+    int best, npos;
+};
+struct LossPartIou {     // LossPart + the range's box-IoU loss sum
+    double box_sum, cls_sum, iou_sum;
+    int npos, best;
+};
+
+extern "C" size_t zsg_loss_workspace_bytes(int32_t B, int32_t A) {   // covers both entry points (the records of the IoU one are the larger)
     (void)A;
-    return (size_t)B * (sizeof(LossWs) + LS_CHUNKS * (sizeof(ArgMax) + sizeof(LossPart)));
+    static_assert(sizeof(LossWsIou) == sizeof(LossWs) && sizeof(LossPartIou) >= sizeof(LossPart), "workspace records");
+    return (size_t)B * (sizeof(LossWsIou) + LS_CHUNKS * (sizeof(ArgMax) + sizeof(LossPartIou)));
 }
 
 extern "C" int zsg_loss_fwd_bwd(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, float alpha, float gamma,
@@ -327,6 +337,309 @@ extern "C" int zsg_loss_fwd_bwd(const float* out5, const float* annot, const flo
                        flags, grad_scale, (const LossWs*)rec, chunked ? (const LossPart*)parts : (const LossPart*)nullptr, losses, grad5,
                        match_idx, npos);
     ZSG_CHECK_LAUNCH("loss_fwd_bwd");
+    return 0;
+}
+
+// ---- box IoU loss: a GIoU / DIoU term next to the smooth-L1 term (zsg_loss_fwd_bwd_iou) ----------------------------------
+// The kernels below are loss_stats_kernel / loss_part_kernel / loss_grad_kernel with that term added inside their anchor loops (the
+// same launches, loss_argmax_kernel is shared); the kernels above are what ZSGLoss runs when the term is off, and are not touched.
+// For a positive anchor: p = the decoded box (decode_box's expressions), g = the annotation,
+//   inter = max(min(p.y2, g.y2) - max(p.y1, g.y1), 0) * (same in x),  union = area(p) + area(g) - inter,  iou = inter / (union + eps),
+//   ey, ex = the sides of the smallest box enclosing both,
+//   giou:  L = 1 - iou + (ey ex - union) / (ey ex + eps)          diou:  L = 1 - iou + |centre(p) - centre(g)|^2 / (ey^2 + ex^2 + eps)
+// iou_loss_terms returns L and dL / d(r0..r3): the derivative with respect to (y1, x1, y2, x2) written out by hand, then through the
+// decode (d/dr0 = ah (dy1 + dy2), d/dr2 = h / 2 (dy2 - dy1), likewise in x).  At an exact tie of a min / max the zero side is taken.
+// It is evaluated in fp64 from the fp32 inputs: the derivative of inter / union is a difference of near-equal products, and only the
+// few positive anchors of a sample come here, so the extra cost does not show.  Negative anchors never enter the sum (a select, not
+// the multiply of the smooth-L1 term): a NaN in a negative anchor's regression output reaches box_ls only.
+#define IOU_EPS 1e-7
+__device__ __forceinline__ double iou_loss_terms(const float* __restrict__ o5, const f32x4 an, const f32x4 bx, int kind, double d[4]) {
+    const double acy = ((double)an[0] + (double)an[2]) / 2., acx = ((double)an[1] + (double)an[3]) / 2.;
+    const double ah = (double)an[2] - (double)an[0], aw = (double)an[3] - (double)an[1];
+    const double cy = ah * (double)o5[0] + acy, cx = aw * (double)o5[1] + acx;
+    const double h = exp((double)o5[2]) * ah, w = exp((double)o5[3]) * aw;
+    const double y1 = cy - h / 2., x1 = cx - w / 2., y2 = cy + h / 2., x2 = cx + w / 2.;
+    const double g0 = bx[0], g1 = bx[1], g2 = bx[2], g3 = bx[3];
+    const double ry = fmin(y2, g2) - fmax(y1, g0), rx = fmin(x2, g3) - fmax(x1, g1);
+    const double iy = fmax(ry, 0.), ix = fmax(rx, 0.);
+    const double inter = iy * ix;
+    const double ph = y2 - y1, pw = x2 - x1;
+    const double uni = ph * pw + (g2 - g0) * (g3 - g1) - inter;
+    const double ue = uni + IOU_EPS;
+    const double iou = inter / ue;
+    const double ey = fmax(y2, g2) - fmin(y1, g0), ex = fmax(x2, g3) - fmin(x1, g1);
+    // per coordinate k of (y1, x1, y2, x2): d inter, d area(p), d ey, d ex
+    const double di[4] = {(ry > 0. && y1 > g0) ? -ix : 0., (rx > 0. && x1 > g1) ? -iy : 0.,
+                          (ry > 0. && y2 < g2) ? ix : 0., (rx > 0. && x2 < g3) ? iy : 0.};
+    const double da[4] = {-pw, -ph, pw, ph};
+    const double dey[4] = {y1 < g0 ? -1. : 0., 0., y2 > g2 ? 1. : 0., 0.};
+    const double dex[4] = {0., x1 < g1 ? -1. : 0., 0., x2 > g3 ? 1. : 0.};
+    double L, dp[4];
+    if (kind == 1) {
+        const double C = ey * ex, ce = C + IOU_EPS;
+        L = 1. - iou + (C - uni) / ce;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double dU = da[k] - di[k], dC = dey[k] * ex + dex[k] * ey;
+            dp[k] = ((dC - dU) * ce - (C - uni) * dC) / (ce * ce) - (di[k] * ue - inter * dU) / (ue * ue);
+        }
+    } else {
+        const double qy = (y1 + y2) / 2. - (g0 + g2) / 2., qx = (x1 + x2) / 2. - (g1 + g3) / 2.;
+        const double rho2 = qy * qy + qx * qx, D = ey * ey + ex * ex + IOU_EPS;
+        L = 1. - iou + rho2 / D;
+        const double dq[4] = {qy, qx, qy, qx};                      // d rho2: 2 q * (1 / 2)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double dU = da[k] - di[k], dD = 2. * (ey * dey[k] + ex * dex[k]);
+            dp[k] = (dq[k] * D - rho2 * dD) / (D * D) - (di[k] * ue - inter * dU) / (ue * ue);
+        }
+    }
+    d[0] = ah * (dp[0] + dp[2]);
+    d[1] = aw * (dp[1] + dp[3]);
+    d[2] = (h / 2.) * (dp[2] - dp[0]);
+    d[3] = (w / 2.) * (dp[3] - dp[1]);
+    return L;
+}
+
+// pass 1, one block per sample (loss_stats_kernel + the IoU sum)
+__global__ __launch_bounds__(LS_THREADS) void loss_stats_iou_kernel(const float* __restrict__ out5, const float* __restrict__ annot,
+                                                                    const float* __restrict__ anchors, int A, float alpha, float gamma,
+                                                                    float thr, int flags, int iou_kind, LossWsIou* __restrict__ ws) {
+    __shared__ ArgMax sm_a[LS_THREADS / 64];
+    __shared__ double sm_d[LS_THREADS / 64];
+    const int b = blockIdx.x;
+    const bool use_focal = flags & 1, use_multi = flags & 2, use_softmax = flags & 4;
+    const f32x4 bx = *(const f32x4*)(annot + 4 * b);
+    const float* o = out5 + (size_t)b * A * 5;
+
+    ArgMax m = {-INFINITY, 0x7fffffff};
+    for (int a = threadIdx.x; a < A; a += LS_THREADS) {
+        const float v = iou_exact(bx, *(const f32x4*)(anchors + 4 * a));
+        if (v > m.v) { m.v = v; m.i = a; }
+    }
+    m = block_argmax(m, sm_a);
+    const int best = m.i == 0x7fffffff ? 0 : m.i;
+
+    double row_max = 0, row_lse = 0;
+    if (use_softmax) {
+        float mx = -INFINITY;
+        for (int a = threadIdx.x; a < A; a += LS_THREADS) mx = fmaxf(mx, o[a * 5 + 4]);
+        ArgMax t = {mx, 0};
+        t = block_argmax(t, sm_a);
+        double se = 0;
+        for (int a = threadIdx.x; a < A; a += LS_THREADS) se += exp((double)o[a * 5 + 4] - (double)t.v);
+        se = block_sum_d(se, sm_d);
+        row_max = t.v;
+        row_lse = (double)t.v + log(se);
+    }
+
+    double box = 0, cls = 0, iou = 0;
+    int cnt = 0;
+    for (int a = threadIdx.x; a < A; a += LS_THREADS) {
+        const f32x4 an = *(const f32x4*)(anchors + 4 * a);
+        const float v = iou_exact(bx, an);
+        const bool pos = (use_multi && v > thr) || a == best;
+        const float t = pos ? 1.f : 0.f;
+        cnt += pos;
+        float d[4];
+        const float s = box_terms(o + a * 5, an, bx, d);
+        box += (double)(s * t);
+        if (pos) {
+            double di[4];
+            iou += iou_loss_terms(o + a * 5, an, bx, iou_kind, di);
+        }
+        const float x = o[a * 5 + 4];
+        if (!use_softmax) {
+            const float bce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+            float w = 1.f;
+            if (use_focal) {
+                const float p = 1.0f / (1.0f + expf(-x));
+                w = focal_pow(t * (1.f - p) + (1.f - t) * p, gamma) * ((1.f - t) * alpha + t * (1.f - alpha));
+            }
+            cls += (double)(w * bce);
+        }
+    }
+    box = block_sum_d(box, sm_d);
+    cls = block_sum_d(cls, sm_d);
+    iou = block_sum_d(iou, sm_d);
+    const int npos = (int)(block_sum_d((double)cnt, sm_d) + 0.5);
+    if (threadIdx.x == 0) {
+        if (use_softmax) cls = row_lse - (double)o[best * 5 + 4];
+        LossWsIou r;
+        r.box_sum = box; r.cls_sum = cls; r.iou_sum = iou; r.row_max = row_max; r.row_lse = row_lse; r.best = best; r.npos = npos;
+        ws[b] = r;
+    }
+}
+
+// chunked pass 1b (loss_part_kernel + the IoU sum); pass 1a is loss_argmax_kernel itself
+__global__ __launch_bounds__(256) void loss_part_iou_kernel(const float* __restrict__ out5, const float* __restrict__ annot,
+                                                            const float* __restrict__ anchors, int A, float alpha, float gamma, float thr,
+                                                            int flags, int iou_kind, const ArgMax* __restrict__ amax,
+                                                            LossPartIou* __restrict__ parts) {
+    __shared__ double sm_d[4];
+    const bool use_focal = flags & 1, use_multi = flags & 2;
+    const int b = blockIdx.y, per = (A + LS_CHUNKS - 1) / LS_CHUNKS;
+    const int a0 = blockIdx.x * per, a1 = min(A, a0 + per);
+    const f32x4 bx = *(const f32x4*)(annot + 4 * b);
+    const float* o = out5 + (size_t)b * A * 5;
+    ArgMax m = amax[b * LS_CHUNKS];
+    for (int c = 1; c < LS_CHUNKS; ++c) m = argmax_merge(m, amax[b * LS_CHUNKS + c]);
+    const int best = m.i == 0x7fffffff ? 0 : m.i;
+    double box = 0, cls = 0, iou = 0;
+    int cnt = 0;
+    for (int a = a0 + threadIdx.x; a < a1; a += 256) {
+        const f32x4 an = *(const f32x4*)(anchors + 4 * a);
+        const float v = iou_exact(bx, an);
+        const bool pos = (use_multi && v > thr) || a == best;
+        const float t = pos ? 1.f : 0.f;
+        cnt += pos;
+        float d[4];
+        const float s = box_terms(o + a * 5, an, bx, d);
+        box += (double)(s * t);
+        if (pos) {
+            double di[4];
+            iou += iou_loss_terms(o + a * 5, an, bx, iou_kind, di);
+        }
+        const float x = o[a * 5 + 4];
+        const float bce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+        float w = 1.f;
+        if (use_focal) {
+            const float p = 1.0f / (1.0f + expf(-x));
+            w = focal_pow(t * (1.f - p) + (1.f - t) * p, gamma) * ((1.f - t) * alpha + t * (1.f - alpha));
+        }
+        cls += (double)(w * bce);
+    }
+    box = block_sum_d(box, sm_d);
+    cls = block_sum_d(cls, sm_d);
+    iou = block_sum_d(iou, sm_d);
+    const int npos = (int)(block_sum_d((double)cnt, sm_d) + 0.5);
+    if (threadIdx.x == 0) {
+        LossPartIou r;
+        r.box_sum = box; r.cls_sum = cls; r.iou_sum = iou; r.npos = npos; r.best = best;
+        parts[b * LS_CHUNKS + blockIdx.x] = r;
+    }
+}
+
+// pass 2 (loss_grad_kernel + the IoU term): losses[4] = (loss, cls_ls, box_ls, iou_ls); a NaN in any of the three parts gives the
+// constants, iou_ls = 0 and an exactly zero gradient (also at the anchor that holds the NaN).
+__global__ __launch_bounds__(256) void loss_grad_iou_kernel(const float* __restrict__ out5, const float* __restrict__ annot,
+                                                            const float* __restrict__ anchors, int B, int A, float alpha, float gamma,
+                                                            float lamb, float thr, int flags, float grad_scale, int iou_kind, float lamb_iou,
+                                                            const LossWsIou* __restrict__ ws_in, const LossPartIou* __restrict__ parts,
+                                                            float* __restrict__ losses, float* __restrict__ grad5,
+                                                            int* __restrict__ match_idx, int* __restrict__ npos_out) {
+    const bool use_focal = flags & 1, use_multi = flags & 2, use_softmax = flags & 4;
+    const int b = blockIdx.y;
+    __shared__ LossWsIou ws[LS_MAX_B];
+    for (int k = threadIdx.x; k < B; k += blockDim.x) {
+        LossWsIou r;
+        if (parts) {                                     // merge the sample's range records in range order
+            r.box_sum = r.cls_sum = r.iou_sum = r.row_max = r.row_lse = 0;
+            r.npos = 0;
+            for (int c = 0; c < LS_CHUNKS; ++c) {
+                const LossPartIou q = parts[k * LS_CHUNKS + c];
+                r.box_sum += q.box_sum;
+                r.cls_sum += q.cls_sum;
+                r.iou_sum += q.iou_sum;
+                r.npos += q.npos;
+            }
+            r.best = parts[k * LS_CHUNKS].best;
+        } else {
+            r = ws_in[k];
+        }
+        ws[k] = r;
+    }
+    __syncthreads();
+    double box = 0, cls = 0, iou = 0;
+    long long npos_all = 0;
+    for (int k = 0; k < B; ++k) {
+        box += ws[k].box_sum / (double)ws[k].npos;
+        iou += ws[k].iou_sum / (double)ws[k].npos;
+        cls += ws[k].cls_sum;
+        npos_all += ws[k].npos;
+    }
+    box /= (double)B;
+    iou /= (double)B;
+    cls /= (double)npos_all;
+    const bool bad = (box != box) || (cls != cls) || (iou != iou);
+    if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) {
+        const double bl = bad ? 0.01 : box, cl = bad ? 1.0 : cls, il = bad ? 0.0 : iou;
+        losses[0] = (float)(lamb * bl + lamb_iou * il + cl);
+        losses[1] = (float)cl;
+        losses[2] = (float)bl;
+        losses[3] = (float)il;
+    }
+    const LossWsIou me = ws[b];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        match_idx[b] = me.best;
+        if (npos_out) npos_out[b] = me.npos;
+    }
+    if (!grad5) return;
+    const f32x4 bx = *(const f32x4*)(annot + 4 * b);
+    const float* o = out5 + (size_t)b * A * 5;
+    float* g = grad5 + (size_t)b * A * 5;
+    const float kbox = bad ? 0.f : grad_scale * lamb / ((float)B * (float)me.npos);
+    const float kiou = bad ? 0.f : grad_scale * lamb_iou / ((float)B * (float)me.npos);
+    const float kcls = bad ? 0.f : grad_scale / (float)npos_all;
+    for (int a = blockIdx.x * blockDim.x + threadIdx.x; a < A; a += gridDim.x * blockDim.x) {
+        const f32x4 an = *(const f32x4*)(anchors + 4 * a);
+        const float v = iou_exact(bx, an);
+        const bool pos = (use_multi && v > thr) || a == me.best;
+        const float t = pos ? 1.f : 0.f;
+        float d[4];
+        box_terms(o + a * 5, an, bx, d);
+        if (pos && !bad) {                               // (bad: zeros, not 0 * NaN — the NaN may sit in this very anchor)
+            double di[4];
+            iou_loss_terms(o + a * 5, an, bx, iou_kind, di);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[a * 5 + k] = kbox * d[k] + kiou * (float)di[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[a * 5 + k] = 0.f;
+        }
+        const float x = o[a * 5 + 4];
+        float ga;
+        if (use_softmax) {
+            ga = (float)exp((double)x - me.row_lse) - (a == me.best ? 1.f : 0.f);
+        } else {
+            const float p = 1.0f / (1.0f + expf(-x));
+            float w = 1.f;
+            if (use_focal) w = focal_pow(t * (1.f - p) + (1.f - t) * p, gamma) * ((1.f - t) * alpha + t * (1.f - alpha));
+            ga = w * (p - t);
+        }
+        g[a * 5 + 4] = bad ? 0.f : kcls * ga;
+    }
+}
+
+extern "C" int zsg_loss_fwd_bwd_iou(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, float alpha,
+                                    float gamma, float lamb_reg, float match_thr, int32_t flags, float grad_scale, int32_t iou_kind,
+                                    float lamb_iou, float* losses, float* grad5, int32_t* match_idx, int32_t* npos, void* ws,
+                                    size_t ws_bytes, void* stream) {
+    ZSG_REQUIRE(out5 && annot && anchors && losses && match_idx && ws && B > 0 && A > 0, "loss_fwd_bwd_iou: bad argument");
+    ZSG_REQUIRE(!((flags & 4) && (flags & 2)), "loss_fwd_bwd_iou: use_softmax requires use_multi == False (loss.py:107)");
+    ZSG_REQUIRE(iou_kind == 1 || iou_kind == 2, "loss_fwd_bwd_iou: iou_kind=%d is neither 1 (giou) nor 2 (diou)", iou_kind);
+    ZSG_REQUIRE(lamb_iou >= 0.f, "loss_fwd_bwd_iou: lamb_iou must not be negative");
+    if (ws_bytes < zsg_loss_workspace_bytes(B, A)) ZSG_FAIL(-2, "loss_fwd_bwd_iou: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("loss_fwd_bwd_iou", st, 0, (double)B * A * 5 * 4 * 3);
+    ZSG_REQUIRE(B <= LS_MAX_B, "loss_fwd_bwd_iou: B=%d exceeds %d", B, LS_MAX_B);
+    LossWsIou* rec = (LossWsIou*)ws;
+    LossPartIou* parts = (LossPartIou*)(rec + B);
+    ArgMax* amax = (ArgMax*)(parts + (size_t)B * LS_CHUNKS);
+    const bool chunked = !(flags & 4) && A >= 4 * LS_CHUNKS;      // as zsg_loss_fwd_bwd
+    if (chunked) {
+        ZSG_LAUNCH(loss_argmax_kernel, dim3(LS_CHUNKS, B), dim3(256), 0, st, annot, anchors, A, amax);
+        ZSG_LAUNCH(loss_part_iou_kernel, dim3(LS_CHUNKS, B), dim3(256), 0, st, out5, annot, anchors, A, alpha, gamma, match_thr, flags,
+                           iou_kind, (const ArgMax*)amax, parts);
+    } else {
+        ZSG_LAUNCH(loss_stats_iou_kernel, dim3(B), dim3(LS_THREADS), 0, st, out5, annot, anchors, A, alpha, gamma, match_thr, flags,
+                           iou_kind, rec);
+    }
+    const int chunks = min(32, cdiv(A, 256));
+    ZSG_LAUNCH(loss_grad_iou_kernel, dim3(chunks, B), dim3(256), 0, st, out5, annot, anchors, B, A, alpha, gamma, lamb_reg, match_thr,
+                       flags, grad_scale, iou_kind, lamb_iou, (const LossWsIou*)rec,
+                       chunked ? (const LossPartIou*)parts : (const LossPartIou*)nullptr, losses, grad5, match_idx, npos);
+    ZSG_CHECK_LAUNCH("loss_fwd_bwd_iou");
     return 0;
 }
 

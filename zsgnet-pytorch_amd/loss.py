@@ -50,7 +50,8 @@ class _LossFn(torch.autograd.Function):
     def forward(ctx, out5, mod, annot):
         B, A, _ = out5.shape
         dev = out5.device
-        losses = torch.empty(3, device=dev)
+        kind = mod.iou_kind                 # 0: the reference's criterion; 1 / 2: + lamb_iou * GIoU / DIoU loss (zsg_loss_fwd_bwd_iou)
+        losses = torch.empty(4 if kind else 3, device=dev)
         # Where d(loss)/d(out5) goes: straight into the incoming-gradient buffer of the network plan that produced out5 (ZSGNet.forward
         # attaches it), already scaled by 1 / world under data parallelism (the reducer SUMs) — the backward then needs no launch of
         # its own when the upstream gradient is the constant 1.  Only the FIRST loss applied to an output may take the buffer.
@@ -72,17 +73,23 @@ class _LossFn(torch.autograd.Function):
         wsb = lib.zsg_loss_workspace_bytes(B, A)
         ws = torch.empty((wsb + 7) // 8, dtype=torch.float64, device=dev)
         flags = (1 if mod.use_focal else 0) | (2 if mod.use_multi else 0) | (4 if mod.use_softmax else 0)
-        check(lib.zsg_loss_fwd_bwd(out5.data_ptr(), annot.data_ptr(), mod.anchs.data_ptr(), B, A, mod.alpha, float(mod.gamma),
-                                   float(mod.lamb_reg), float(mod.cfg["matching_threshold"]), flags, scale, losses.data_ptr(),
-                                   grad5.data_ptr(), mod.match_idx.data_ptr(), mod.npos.data_ptr(), ws.data_ptr(), wsb,
-                                   stream_ptr()), "zsg_loss_fwd_bwd")
+        if kind:
+            check(lib.zsg_loss_fwd_bwd_iou(out5.data_ptr(), annot.data_ptr(), mod.anchs.data_ptr(), B, A, mod.alpha, float(mod.gamma),
+                                           float(mod.lamb_reg), float(mod.cfg["matching_threshold"]), flags, scale, kind,
+                                           float(mod.lamb_iou), losses.data_ptr(), grad5.data_ptr(), mod.match_idx.data_ptr(),
+                                           mod.npos.data_ptr(), ws.data_ptr(), wsb, stream_ptr()), "zsg_loss_fwd_bwd_iou")
+        else:
+            check(lib.zsg_loss_fwd_bwd(out5.data_ptr(), annot.data_ptr(), mod.anchs.data_ptr(), B, A, mod.alpha, float(mod.gamma),
+                                       float(mod.lamb_reg), float(mod.cfg["matching_threshold"]), flags, scale, losses.data_ptr(),
+                                       grad5.data_ptr(), mod.match_idx.data_ptr(), mod.npos.data_ptr(), ws.data_ptr(), wsb,
+                                       stream_ptr()), "zsg_loss_fwd_bwd")
         ctx.fast, ctx.scale, ctx.plan = fast, scale, plan
         if fast:
             ctx.grad5 = grad5                 # (the plan's own buffer: not a saved tensor — the plan enforces one backward per forward)
         else:
             ctx.save_for_backward(grad5)
         mod._last_losses = losses
-        # (a view of the 3-float result, not a copy: one dependent launch less between the loss kernels and the backward)
+        # (a view of the 3- or 4-float result, not a copy: one dependent launch less between the loss kernels and the backward)
         return losses.narrow(0, 0, 1).view(())
 
     @staticmethod
@@ -97,7 +104,10 @@ class _LossFn(torch.autograd.Function):
 
 
 class ZSGLoss(nn.Module):
-    """Criterion to be minimised (reference loss.py:11-143).  forward(out, inp) -> {'loss','cls_ls','box_ls'}."""
+    """Criterion to be minimised (reference loss.py:11-143).  forward(out, inp) -> {'loss','cls_ls','box_ls'}.
+    cfg box_iou_loss = "giou" / "diou" adds lamb_iou * (that IoU loss of the decoded boxes of the positive anchors) and the key 'iou_ls'."""
+
+    IOU_KINDS = {"none": 0, "giou": 1, "diou": 2}
 
     def __init__(self, ratios, scales, cfg):
         super().__init__()
@@ -106,7 +116,13 @@ class ZSGLoss(nn.Module):
         self.alpha, self.gamma = cfg["alpha"], cfg["gamma"]
         self.use_focal, self.use_softmax, self.use_multi = cfg["use_focal"], cfg["use_softmax"], cfg["use_multi"]
         self.lamb_reg = cfg["lamb_reg"]
-        self.loss_keys = ["loss", "cls_ls", "box_ls"]
+        kind, self.lamb_iou = cfg.get("box_iou_loss", "none"), cfg.get("lamb_iou", 1.0)
+        if kind not in self.IOU_KINDS:
+            raise ValueError(f"box_iou_loss={kind!r}: expected one of {sorted(self.IOU_KINDS)}")
+        if not self.lamb_iou >= 0:
+            raise ValueError(f"lamb_iou={self.lamb_iou}: must not be negative")
+        self.iou_kind = self.IOU_KINDS[kind]
+        self.loss_keys = ["loss", "cls_ls", "box_ls"] + (["iou_ls"] if self.iou_kind else [])
         self.anchs = None
         self.get_anchors = partial(create_anchors, ratios=self.ratios, scales=self.scales, flatten=True)
 
@@ -127,7 +143,10 @@ class ZSGLoss(nn.Module):
         if loss.requires_grad:
             loss = loss.as_subclass(_LossScalar)      # (stays attached to the autograd graph; see _LossScalar)
         ls = self._last_losses
-        return {"loss": loss, "cls_ls": ls[1], "box_ls": ls[2]}
+        res = {"loss": loss, "cls_ls": ls[1], "box_ls": ls[2]}
+        if self.iou_kind:
+            res["iou_ls"] = ls[3]
+        return res
 
 
 def get_default_loss(ratios, scales, cfg):
