@@ -592,6 +592,51 @@ int zsg_adam_step_ema(float* p, const float* g, float* m, float* v, int64_t n, f
 /* Exchanges the contents of two disjoint buffers of n > 0 floats in one pass (16 B per element); overlapping ranges return -1. */
 int zsg_swap_f32(float* a, float* b, int64_t n, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Fused optimizer steps with a choice of rule (csrc/optim.hip), in the three launch shapes of the Adam block above.  Each rule follows
+ * torch's single-tensor implementation and replaces one optimizer.step() of
+ *     ZSG_OPT_ADAM   torch.optim.Adam(lr, betas, eps, weight_decay, amsgrad)      coupled decay g += wd * p
+ *     ZSG_OPT_ADAMW  torch.optim.AdamW(lr, betas, eps, weight_decay, amsgrad)     decoupled decay p *= 1 - lr * wd, then Adam on the raw g
+ *     ZSG_OPT_SGD    torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)
+ *                    g += wd * p;  buf = g on the parameter's FIRST step, else momentum * buf + (1 - dampening) * g;
+ *                    p -= lr * (nesterov ? g + momentum * buf : buf);  momentum == 0: p -= lr * g, no buffer
+ * over one flat buffer instead of one update per parameter tensor.  flags: ZSG_OPT_AMSGRAD (Adam / AdamW only) keeps
+ * vmax = max(vmax, v) and divides by sqrt(vmax) / sqrt(bc2) + eps.  One call uses one rule; groups differ in hyperparameters only.
+ *
+ * Buffers (fp32, n elements each, 16-byte aligned, zero-initialised by the caller before the first step, disjoint):
+ *     Adam / AdamW   s0 = m (exp_avg), s1 = v (exp_avg_sq), s2 = vmax (max_exp_avg_sq) with ZSG_OPT_AMSGRAD, else not read (NULL is legal)
+ *     SGD            s0 = the momentum buffer when some group has momentum != 0, else not read (NULL is legal); s1, s2 not read
+ * A parameter's first step is decided on the device from the counter the kernel reads (t == 1; the per-segment counter on the segmented
+ * path): a parameter that joins later starts its momentum buffer from its first gradient, whatever the buffer holds.
+ * HBM traffic per parameter: Adam / AdamW 28 B, with amsgrad 36 B, SGD with momentum 20 B, plain SGD 12 B; + 8 B with the average riding.
+ * Rule ZSG_OPT_ADAM without flags gives the bits of zsg_adam_step / _ema / _segments; AdamW with weight_decay == 0 gives Adam's bits.
+ * A NULL required pointer, a misaligned buffer, ngroups outside 1..ZSG_ADAM_MAX_GROUPS, ema_w outside [0, 1], nesterov without
+ * momentum or with dampening, an unknown algo or flag: -1 before anything is launched (zsg_last_error names the argument).
+ * ------------------------------------------------------------------------------------------------------------- */
+#define ZSG_OPT_ADAM 0
+#define ZSG_OPT_ADAMW 1
+#define ZSG_OPT_SGD 2
+#define ZSG_OPT_AMSGRAD 1          /* flags */
+typedef struct zsg_optim_group {
+    float lr, beta1, beta2, eps, weight_decay;          /* (the fields of zsg_adam_group; beta1, beta2, eps unused by SGD) */
+    float momentum, dampening;                          /* SGD */
+    int32_t nesterov;                                   /* SGD: 0 / 1 */
+} zsg_optim_group;
+/* One launch over p[0:n] (16-byte accesses plus a tail of n % 4).  hp: ONE hyperparameter set on the host, passed to the kernel by value.
+ * step_count: device int32[2] as zsg_adam_step's ([0] = steps taken, [1] = the completion ticket): no host round trip, capturable. */
+int zsg_optim_step(int32_t algo, int32_t flags, float* p, const float* g, float* s0, float* s1, float* s2, int64_t n,
+                   const zsg_optim_group* hp, float grad_scale, int32_t* step_count, void* stream);
+/* The same launch with the weight average riding: ema <- the rule of "Weight EMA" on the p this step stores.  p, the state and step_count
+ * come out bit-identical to zsg_optim_step, ema bit-identical to zsg_ema_update on the post-step p. */
+int zsg_optim_step_ema(int32_t algo, int32_t flags, float* p, const float* g, float* s0, float* s1, float* s2, int64_t n,
+                       const zsg_optim_group* hp, float grad_scale, int32_t* step_count, float* ema, float ema_w, void* stream);
+/* The step over listed segments: segs / nseg / nchunks, counters and ticket exactly as zsg_adam_step_segments takes them (the same DEVICE
+ * table, which zsg_grad_norm / zsg_grad_scale read too); groups: a HOST table of ngroups sets, passed by value.  Nothing outside the
+ * listed ranges is read or written, in p or in any state buffer.  One segment in one group gives the bits of zsg_optim_step. */
+int zsg_optim_step_segments(int32_t algo, int32_t flags, float* p, const float* g, float* s0, float* s1, float* s2,
+                            const zsg_adam_seg* segs, int32_t nseg, int32_t nchunks, const zsg_optim_group* groups, int32_t ngroups,
+                            float grad_scale, int32_t* counters, int32_t* ticket, void* stream);
+
 int zsg_memset_f32(float* p, int64_t n, float value, void* stream);
 
 /* Wave priority of the kernels of the step's dependent chain (convolutions forward / data gradient, BatchNorm passes, the small

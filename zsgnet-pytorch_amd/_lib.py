@@ -46,6 +46,15 @@ class AdamGroup(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)]
 
 
+OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2          # ZSG_OPT_*: the rule of zsg_optim_step / _ema / _segments
+OPT_AMSGRAD = 1                               # ... its flag ZSG_OPT_AMSGRAD
+
+
+class OptimGroup(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("momentum", C.c_float), ("dampening", C.c_float), ("nesterov", C.c_int32)]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -153,6 +162,9 @@ SIGNATURES = {
     "zsg_ema_update": (I32, [P, P, I64, P, P, I64, F32, P]),
     "zsg_adam_step_ema": (I32, [P, P, P, P, I64, F32, F32, F32, F32, F32, F32, P, P, F32, P]),
     "zsg_swap_f32": (I32, [P, P, I64, P]),
+    "zsg_optim_step": (I32, [I32, I32, P, P, P, P, P, I64, C.POINTER(OptimGroup), F32, P, P]),
+    "zsg_optim_step_ema": (I32, [I32, I32, P, P, P, P, P, I64, C.POINTER(OptimGroup), F32, P, P, F32, P]),
+    "zsg_optim_step_segments": (I32, [I32, I32, P, P, P, P, P, P, I32, I32, C.POINTER(OptimGroup), I32, F32, P, P, P]),
     "zsg_memset_f32": (I32, [P, I64, F32, P]),
     "zsg_set_stream_workspace": (I32, [P, P, SZ]),
     "zsg_set_main_priority": (I32, [I32]),

@@ -8,7 +8,11 @@ from typing import Any, Dict
 DEFAULTS: Dict[str, Any] = {
     # configs/cfg.json:1-43
     "ds_to_use": "refclef", "bs": 16, "nw": 4, "bsv": 16, "nwv": 4, "lr": 1e-4, "devices": 0, "opt_fn": "Adam",
-    "opt_fn_params": {"betas": [0.9, 0.99]}, "do_norm": False, "use_same_atb": True, "mdl_to_use": "retina",
+    # opt_fn: "Adam" / "AdamW" / "SGD" (optim.make_opt_fn); opt_fn_params: the keys of all three, each rule takes its own (betas, eps, amsgrad:
+    # Adam / AdamW; momentum, dampening, nesterov: SGD; weight_decay: all).  The reference has betas alone (cfg.json)
+    "opt_fn_params": {"betas": [0.9, 0.99], "eps": 1e-8, "weight_decay": 0.0, "amsgrad": False, "momentum": 0.0, "dampening": 0.0,
+                      "nesterov": False},
+    "do_norm": False, "use_same_atb": True, "mdl_to_use": "retina",
     "resize_img": [300, 300], "tmp_path": "./tmp", "use_multi": True, "use_focal": True, "use_softmax": False,
     "alpha": 0.25, "gamma": 2, "ratios": "[1/2, 1, 2]", "scales": "[1, 2**(1/3), 2**(2/3)]", "scale_factor": 4,
     "emb_dim": 300, "matching_threshold": 0.6, "epochs": 10, "use_bidirectional": True, "lstm_dim": 128,

@@ -7,8 +7,9 @@ The average is three buffers of the network's own layouts: `flat` (store.flat), 
 in fp32; the first update after construction / reset() is a copy (w = 1).  The update count is a host integer and w travels by value: no
 device read-back, no synchronisation.
 
-update() is one zsg_ema_update launch over both float buffers.  attach(FusedAdam) makes optimizer.step() do it: inside the single Adam
-launch (zsg_adam_step_ema, + one small launch for the statistics), or — when the step goes through zsg_adam_step_segments (frozen
+update() is one zsg_ema_update launch over both float buffers.  attach(optimizer) — any optim.FusedOptimizer: FusedAdam, FusedAdamW,
+FusedSGD — makes optimizer.step() do it: inside the single step launch (zsg_adam_step_ema / zsg_optim_step_ema, + one small launch for
+the statistics), or — when the step goes through the segmented launch (zsg_adam_step_segments / zsg_optim_step_segments: frozen
 parameters, parameter groups) — as update() over the WHOLE flat buffer after the step, so that a parameter that was trained and later
 frozen keeps converging to its value.  applied() exchanges the buffers' contents with the network's (zsg_swap_f32): inside, the network
 is the averaged model for every plan (the eval plans refold BatchNorm from store.flat on each forward); on exit everything is restored
@@ -90,10 +91,11 @@ class ModelEma:
         self._update(self._next_weight())
 
     def attach(self, optimizer):
-        """From now on optimizer.step() (a FusedAdam of the same network) updates the average itself."""
-        from .optim import FusedAdam
-        if not isinstance(optimizer, FusedAdam) or optimizer.net is not self.net:
-            raise ValueError("ModelEma.attach: the optimizer is not a FusedAdam of this ModelEma's network")
+        """From now on optimizer.step() (a FusedAdam / FusedAdamW / FusedSGD of the same network) updates the average itself."""
+        from .optim import FusedOptimizer
+        if not isinstance(optimizer, FusedOptimizer) or optimizer.net is not self.net:
+            raise ValueError("ModelEma.attach: the optimizer is not a FusedAdam of this ModelEma's network, nor another optim.FusedOptimizer "
+                             "(FusedAdamW, FusedSGD) of it")
         if optimizer._ema not in (None, self):
             raise ValueError("ModelEma.attach: the optimizer already updates another average")
         self.detach()
@@ -118,7 +120,7 @@ class ModelEma:
     @contextmanager
     def applied(self):
         """Inside, the network IS the averaged model (weights, BatchNorm statistics, num_batches_tracked exchanged in place: every launch
-        plan keeps its pointers); on exit the raw weights and the average are back, bit for bit.  FusedAdam.step, update() and a nested
+        plan keeps its pointers); on exit the raw weights and the average are back, bit for bit.  The optimizer's step, update() and a nested
         applied() raise RuntimeError inside."""
         self._check_launch("applied")
         with torch.no_grad():

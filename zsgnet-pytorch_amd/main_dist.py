@@ -8,7 +8,6 @@ key or a type mismatch is an assertion (extended_config.py:78-88).  Accepts the 
 as torchrun's LOCAL_RANK.  Data: synthetic batches (cfg.synthetic) — the CSV datasets are not available offline."""
 import os
 import sys
-from functools import partial
 
 import torch
 
@@ -38,7 +37,7 @@ def learner_init(uid: str, cfg):
     from .evaluator import get_default_eval
     from .loss import get_default_loss
     from .mdl import get_default_net
-    from .optim import FusedAdam
+    from .optim import make_opt_fn
     from .trainer import Learner
     device = torch.device(cfg["device"])
     if cfg["synthetic"]:
@@ -62,7 +61,7 @@ def learner_init(uid: str, cfg):
                                             broadcast_buffers=True, find_unused_parameters=True)
     loss_fn = get_default_loss(ratios, scales, cfg)
     eval_fn = get_default_eval(ratios, scales, cfg)
-    opt_fn = partial(FusedAdam, betas=(0.9, 0.99))
+    opt_fn = make_opt_fn(cfg)          # cfg opt_fn / opt_fn_params: FusedAdam(betas=(0.9, 0.99)) by default
     return Learner(uid=uid, data=data, mdl=mdl, loss_fn=loss_fn, opt_fn=opt_fn, eval_fn=eval_fn, device=device, cfg=cfg)
 
 

@@ -1,25 +1,33 @@
-"""Fused Adam over the model's flat parameter buffer (reference: torch.optim.Adam(betas=(0.9,0.99)), main_dist.py:50,
-stepped at utils.py:413).  One HIP launch updates all 37.6 M parameters (28 B/param of HBM traffic) instead of ~170
-per-tensor updates; the step counter lives on the device.
+"""Fused optimizers over the model's flat parameter buffer: FusedAdam (reference: torch.optim.Adam(betas=(0.9,0.99)), main_dist.py:50,
+stepped at utils.py:413), FusedAdamW and FusedSGD (torch.optim.AdamW / SGD).  One HIP launch updates all 37.6 M parameters (Adam: 28 B/param
+of HBM traffic) instead of ~170 per-tensor updates; the step counter lives on the device.  make_opt_fn(cfg) builds the one cfg opt_fn /
+opt_fn_params name.  FusedOptimizer is what they share; the rule is the only thing a subclass adds.
 
-Fine-tuning (torch.optim semantics): `params=` takes the model's parameters or a list of group dicts with their own lr / betas /
-eps / weight_decay (add_param_group too).  A parameter is stepped only when it is in some group AND its p.grad is not None — a
-frozen parameter (requires_grad=False: the backward leaves its p.grad at None) keeps its value and moments bit for bit.  With one
-group and every parameter stepped, the step is the single zsg_adam_step launch; otherwise zsg_adam_step_segments updates the
-listed parameters only, with per-group hyperparameters and per-parameter step counters (torch's state['step']).
+Fine-tuning (torch.optim semantics): `params=` takes the model's parameters or a list of group dicts with their own hyperparameters (the
+per-group keys torch takes for that optimizer; add_param_group too).  A parameter is stepped only when it is in some group AND its p.grad is
+not None — a frozen parameter (requires_grad=False: the backward leaves its p.grad at None) keeps its value and state bit for bit.  With one
+group and every parameter stepped, the step is the single launch (zsg_adam_step for plain FusedAdam, zsg_optim_step for every other rule);
+otherwise zsg_adam_step_segments / zsg_optim_step_segments updates the listed parameters only, with per-group hyperparameters and
+per-parameter step counters (torch's state['step']; a parameter's first step starts SGD's momentum buffer from its gradient).
+
+State: FusedAdam / FusedAdamW m, v (+ vmax with amsgrad=True); FusedSGD momentum_buffer once some group has momentum != 0, else nothing.
+state_dict()['zsg'] holds them with the counters and — for everything but plain FusedAdam, whose keys are m, v, step, steps — the rule's
+name 'algo'; load_state_dict refuses another rule's state.  (A momentum switched on after a parameter's first step starts from a zero
+buffer, where torch would start from the gradient: the two differ only with dampening != 0.)
 
 clip_grad_norm_ is torch.nn.utils.clip_grad_norm_ over the same flat gradient buffer: two HIP launches (zsg_grad_norm, zsg_grad_scale)
-through the segment table the segmented Adam step uses, with no host round trip.
+through the segment table the segmented step uses, with no host round trip.
 
-A weight average (ema.ModelEma.attach) rides in the step: inside the single launch (zsg_adam_step_ema), or as one zsg_ema_update over the
-whole flat buffer behind the segmented step.  Which one follows from the path the step takes; nothing else selects it."""
+A weight average (ema.ModelEma.attach) rides in the step: inside the single launch (zsg_adam_step_ema / zsg_optim_step_ema), or as one
+zsg_ema_update over the whole flat buffer behind the segmented step.  Which one follows from the path the step takes; nothing else selects it."""
 import ctypes as C
 import math
 
 import torch
 
 from . import mdl
-from ._lib import ADAM_CHUNK, ADAM_MAX_GROUPS, AdamGroup, AdamSeg, check, lib, stream_ptr
+from ._lib import (ADAM_CHUNK, ADAM_MAX_GROUPS, OPT_ADAM, OPT_ADAMW, OPT_AMSGRAD, OPT_SGD, AdamGroup, AdamSeg, OptimGroup, check, lib,
+                   stream_ptr)
 
 
 def segment_table(net, key):
@@ -39,16 +47,22 @@ def segment_table(net, key):
     return tab, chunk
 
 
-class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, model, lr=1e-4, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, grad_scale=1.0, params=None):
+class FusedOptimizer(torch.optim.Optimizer):
+    """What the fused optimizers share: the parameter index into the flat store, parameter groups, zero_grad, which parameters a step
+    updates and their segment table, the step counters (one while every step updates every parameter, one per parameter once a step
+    leaves some out), the weight average's hook in step(), the checkpoint's frame.  A subclass names its rule (NAME, ALGO), the group
+    keys it takes (HYPER), its state buffers (_buffers) and one hyperparameter set of the C ABI (_group)."""
+    NAME = None            # the rule's name in checkpoints and cfg opt_fn: 'Adam' / 'AdamW' / 'SGD'
+    ALGO = None            # ZSG_OPT_*
+    HYPER = ()             # group keys load_state_dict restores
+
+    def __init__(self, model, defaults, grad_scale=1.0, params=None):
         net = model.module if hasattr(model, "module") else model
         self.net = net
         plist = net._ordered_params()
         self._index = {id(p): i for i, p in enumerate(plist)}
-        super().__init__(plist if params is None else params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        super().__init__(plist if params is None else params, defaults)
         flat = net.store.flat
-        self.m = torch.zeros_like(flat)
-        self.v = torch.zeros_like(flat)
         self._step2 = torch.zeros(2, dtype=torch.int32, device=flat.device)      # [steps taken, the update kernel's completion ticket]
         self.step_count = self._step2[:1]
         self.grad_scale = grad_scale
@@ -65,14 +79,19 @@ class FusedAdam(torch.optim.Optimizer):
         ps = [ps] if isinstance(ps, torch.Tensor) else list(ps)
         param_group = dict(param_group, params=ps)          # (an iterator is consumed here once)
         index = self.__dict__.get("_index", {})
+        name = type(self).__name__
         for p in ps:
             if id(p) not in index:
                 shape = tuple(p.shape) if isinstance(p, torch.Tensor) else type(p).__name__
-                raise ValueError(f"FusedAdam: a tensor of shape {shape} is not a parameter of the model's flat parameter store; "
+                raise ValueError(f"{name}: a tensor of shape {shape} is not a parameter of the model's flat parameter store; "
                                  "only the model's own parameters (model.parameters() or a subset) can be optimised")
         if len(self.param_groups) >= ADAM_MAX_GROUPS:
-            raise ValueError(f"FusedAdam: at most {ADAM_MAX_GROUPS} parameter groups are supported")
+            raise ValueError(f"{name}: at most {ADAM_MAX_GROUPS} parameter groups are supported")
+        self._check_group(param_group)
         super().add_param_group(param_group)
+
+    def _check_group(self, group):
+        """a ValueError for a group dict this rule cannot honour (its keys not in the dict take the defaults)"""
 
     def zero_grad(self, set_to_none: bool = False):
         """One memset of the flat gradient buffer; the p.grad views stay (backward accumulates into them).  With
@@ -98,7 +117,7 @@ class FusedAdam(torch.optim.Optimizer):
         return tuple(sorted((idx[id(p)], gi) for gi, g in enumerate(groups) for p in g["params"] if p.grad is not None))
 
     def _segment_table(self, key):
-        """device segment table of zsg_adam_step_segments for `key` (rebuilt only when the stepped set or the groups change)"""
+        """device segment table of the segmented step for `key` (rebuilt only when the stepped set or the groups change)"""
         if key == self._seg_key:
             return
         self._seg_tab, self._nchunks = segment_table(self.net, key)
@@ -107,7 +126,8 @@ class FusedAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         if self.net.__dict__.get("_ema_applied") is not None:
-            raise RuntimeError("FusedAdam.step inside ModelEma.applied(): the network holds the averaged weights, not the trained ones")
+            raise RuntimeError(f"{type(self).__name__}.step inside ModelEma.applied(): the network holds the averaged weights, not the "
+                               "trained ones")
         ema = self._ema
         if ema is None:
             self._step(None, 0.0)
@@ -115,13 +135,12 @@ class FusedAdam(torch.optim.Optimizer):
         ema._check_launch("attach: step")
         w = ema._next_weight()
         if self._step(ema, w):
-            ema._update(w, stats_only=True)       # the parameters' average rode in the Adam launch: the BatchNorm statistics remain
+            ema._update(w, stats_only=True)       # the parameters' average rode in the step's launch: the BatchNorm statistics remain
         else:
             ema._update(w)                        # segmented step: the whole flat buffer, frozen parameters included
 
     def _step(self, ema, ema_w):
-        """the Adam update; True when the single launch took the weight average `ema` along (zsg_adam_step_ema)"""
-        st = self.net.store
+        """the update; True when the single launch took the weight average `ema` along"""
         self.net.join_weight_readers()          # (a forward without backward may still be reading the weights on the side stream)
         sel = self._stepped()
         if sel is None and self._seg and self._uniform:
@@ -130,15 +149,8 @@ class FusedAdam(torch.optim.Optimizer):
             self._pcount.zero_()
             self._seg = False
         if sel is None and not self._seg:
-            g = self.param_groups[0]
-            hp = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(self.grad_scale))
-            if ema is not None:
-                check(lib.zsg_adam_step_ema(st.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), st.flat.numel(), *hp,
-                                            self.step_count.data_ptr(), ema.flat.data_ptr(), ema_w, stream_ptr()), "zsg_adam_step_ema")
-                return True
-            check(lib.zsg_adam_step(st.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), st.flat.numel(), *hp,
-                                    self.step_count.data_ptr(), stream_ptr()), "zsg_adam_step")
-            return False
+            self._launch_flat(self.param_groups[0], ema, ema_w)
+            return ema is not None
         if sel is None:
             sel = tuple((i, 0) for i in range(len(self._index)))
         if not self._seg:                        # the counts move to the per-parameter counters
@@ -149,37 +161,87 @@ class FusedAdam(torch.optim.Optimizer):
         if len(sel) < len(self._index):
             self._uniform = False
         self._segment_table(sel)
-        if not sel:
-            return False
-        gt = (AdamGroup * len(self.param_groups))(*[AdamGroup(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                                                              float(g["weight_decay"])) for g in self.param_groups])
-        n = len(self._index)
-        check(lib.zsg_adam_step_segments(st.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self._seg_tab.data_ptr(),
-                                         len(sel), self._nchunks, gt, len(self.param_groups), float(self.grad_scale),
-                                         self._pcount.data_ptr(), self._pcount[n:].data_ptr(), stream_ptr()), "zsg_adam_step_segments")
+        if sel:
+            self._launch_segments(len(sel))
         return False
 
+    # ---- the launches (zsg_optim_step / _ema / _segments with this rule) -----------------------------------------------------------
+    def _flags(self) -> int:
+        return 0
+
+    def _buffers(self):
+        """{checkpoint key: state buffer} in the C ABI's order s0, s1, s2 (allocated ones only)"""
+        return {}
+
+    def _group(self, g) -> OptimGroup:
+        raise NotImplementedError
+
+    def _state_ptrs(self):
+        ptrs = [b.data_ptr() for b in self._buffers().values()]
+        return ptrs + [None] * (3 - len(ptrs))
+
+    def _launch_flat(self, g, ema, ema_w):
+        st = self.net.store
+        head = (self.ALGO, self._flags(), st.flat.data_ptr(), st.grad.data_ptr(), *self._state_ptrs(), st.flat.numel(), C.byref(self._group(g)),
+                float(self.grad_scale), self.step_count.data_ptr())
+        if ema is not None:
+            check(lib.zsg_optim_step_ema(*head, ema.flat.data_ptr(), ema_w, stream_ptr()), "zsg_optim_step_ema")
+        else:
+            check(lib.zsg_optim_step(*head, stream_ptr()), "zsg_optim_step")
+
+    def _launch_segments(self, nseg):
+        st, n, groups = self.net.store, len(self._index), self.param_groups
+        gt = (OptimGroup * len(groups))(*[self._group(g) for g in groups])
+        check(lib.zsg_optim_step_segments(self.ALGO, self._flags(), st.flat.data_ptr(), st.grad.data_ptr(), *self._state_ptrs(),
+                                          self._seg_tab.data_ptr(), nseg, self._nchunks, gt, len(groups), float(self.grad_scale),
+                                          self._pcount.data_ptr(), self._pcount[n:].data_ptr(), stream_ptr()), "zsg_optim_step_segments")
+
     def param_steps(self) -> torch.Tensor:
-        """steps taken by every parameter, in flat order (torch.optim.Adam's state[p]['step'])"""
+        """steps taken by every parameter, in flat order (torch.optim's state[p]['step'])"""
         n = len(self._index)
         return (self._pcount[:n] if self._seg else self._step2[:1].expand(n)).clone()
 
+    # ---- checkpoints ----------------------------------------------------------------------------------------------------------------
+    def _describe(self) -> str:
+        return self.NAME
+
+    def _saved_meta(self):
+        """what state_dict()['zsg'] holds beside the buffers and counters"""
+        return dict(algo=self._describe())
+
     def state_dict(self):
         d = super().state_dict()
-        d["zsg"] = dict(m=self.m, v=self.v, step=self.step_count, steps=self.param_steps())
+        d["zsg"] = dict(self._saved_meta(), **self._buffers(), step=self.step_count, steps=self.param_steps())
         return d
 
+    def _load_buffers(self, z, saved):
+        """copies the saved buffers in; a ValueError when one this rule needs is missing"""
+        for k, b in self._buffers().items():
+            if k not in z:
+                raise ValueError(f"{type(self).__name__}.load_state_dict: the saved {saved} state has no '{k}' buffer, which "
+                                 f"{self._describe()} needs")
+            b.copy_(z[k])
+
     def load_state_dict(self, sd):
-        """Restores the moments / step counters AND the param_groups (lr as left by the scheduler, betas, eps, weight decay).
-        A state saved before per-parameter counters existed (one 'step') gives its count to every parameter.
-        A plain torch.optim.Adam state dict (a reference checkpoint) has per-parameter OIHW moments that do not map onto
-        the flat OHWI buffer: refuse it loudly instead of silently restarting the moments."""
+        """Restores the state buffers / step counters AND the param_groups' hyperparameters (lr as left by the scheduler, ...).
+        A state saved before per-parameter counters existed (one 'step') gives its count to every parameter.  The state of another rule
+        (or one without a buffer this rule needs) is a ValueError naming both.  A plain torch.optim state dict (a reference checkpoint)
+        has per-parameter OIHW tensors that do not map onto the flat OHWI buffer: refuse it loudly instead of silently restarting."""
+        name = type(self).__name__
         z = sd.get("zsg")
         if z is None:
-            raise ValueError("FusedAdam.load_state_dict: no 'zsg' entry — this is not a FusedAdam state (a torch.optim.Adam "
+            raise ValueError(f"{name}.load_state_dict: no 'zsg' entry — this is not a {name} state (a torch.optim.{self.NAME} "
                              "state of the reference cannot be mapped onto the flat parameter buffer); resume with load_opt=False")
-        self.m.copy_(z["m"])
-        self.v.copy_(z["v"])
+        saved = z.get("algo", "Adam")          # (a state from before the rule was recorded is FusedAdam's)
+        if saved != self._describe():
+            raise ValueError(f"{name}.load_state_dict: the saved state belongs to {saved}, this optimizer is {self._describe()}; "
+                             "resume with load_opt=False, or build the optimizer the checkpoint was written by (cfg opt_fn / opt_fn_params)")
+        groups = self.param_groups
+        for g, gs in zip(groups, sd.get("param_groups", [])):
+            for k in self.HYPER:
+                if k in gs:
+                    g[k] = gs[k]
+        self._load_buffers(z, saved)
         steps = z.get("steps")
         n = len(self._index)
         self._pcount.zero_()
@@ -191,11 +253,131 @@ class FusedAdam(torch.optim.Optimizer):
             cnt = z["step"] if steps is None or steps.numel() != n else steps.reshape(-1)[:1]
             self.step_count.copy_(cnt.to(self.step_count.dtype))
             self._seg, self._uniform = False, True
-        saved = sd.get("param_groups", [])
-        for g, gs in zip(self.param_groups, saved):
-            for k in ("lr", "betas", "eps", "weight_decay"):
-                if k in gs:
-                    g[k] = gs[k]
+
+
+class FusedAdam(FusedOptimizer):
+    """torch.optim.Adam.  Without amsgrad it launches zsg_adam_step / zsg_adam_step_ema / zsg_adam_step_segments (csrc/adam.hip), with it
+    the general entry points (csrc/optim.hip) and a third state buffer `vmax`."""
+    NAME, ALGO, HYPER = "Adam", OPT_ADAM, ("lr", "betas", "eps", "weight_decay")
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, grad_scale=1.0, params=None, amsgrad=False):
+        self.amsgrad = bool(amsgrad)
+        super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), grad_scale, params)
+        flat = self.net.store.flat
+        self.m = torch.zeros_like(flat)
+        self.v = torch.zeros_like(flat)
+        self.vmax = torch.zeros_like(flat) if self.amsgrad else None
+
+    def _check_group(self, group):
+        if "amsgrad" in group and bool(group["amsgrad"]) != self.amsgrad:
+            raise ValueError(f"{type(self).__name__}: amsgrad is a property of the optimizer (amsgrad={self.amsgrad}), not of a parameter "
+                             "group: one optimizer uses one update rule")
+
+    def _flags(self):
+        return OPT_AMSGRAD if self.amsgrad else 0
+
+    def _describe(self):
+        return self.NAME + (" with amsgrad" if self.amsgrad else "")
+
+    def _buffers(self):
+        return dict(m=self.m, v=self.v, vmax=self.vmax) if self.amsgrad else dict(m=self.m, v=self.v)
+
+    def _group(self, g):
+        return OptimGroup(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), 0.0, 0.0, 0)
+
+    def _legacy(self):
+        """the launches of csrc/adam.hip: plain Adam (what this class was before it had a base)"""
+        return type(self) is FusedAdam and not self.amsgrad
+
+    def _saved_meta(self):
+        return {} if self._legacy() else super()._saved_meta()
+
+    def _launch_flat(self, g, ema, ema_w):
+        if not self._legacy():
+            return super()._launch_flat(g, ema, ema_w)
+        st = self.net.store
+        hp = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(self.grad_scale))
+        if ema is not None:
+            check(lib.zsg_adam_step_ema(st.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), st.flat.numel(), *hp,
+                                        self.step_count.data_ptr(), ema.flat.data_ptr(), ema_w, stream_ptr()), "zsg_adam_step_ema")
+        else:
+            check(lib.zsg_adam_step(st.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), st.flat.numel(), *hp,
+                                    self.step_count.data_ptr(), stream_ptr()), "zsg_adam_step")
+
+    def _launch_segments(self, nseg):
+        if not self._legacy():
+            return super()._launch_segments(nseg)
+        st, n = self.net.store, len(self._index)
+        gt = (AdamGroup * len(self.param_groups))(*[AdamGroup(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                                                              float(g["weight_decay"])) for g in self.param_groups])
+        check(lib.zsg_adam_step_segments(st.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self._seg_tab.data_ptr(),
+                                         nseg, self._nchunks, gt, len(self.param_groups), float(self.grad_scale),
+                                         self._pcount.data_ptr(), self._pcount[n:].data_ptr(), stream_ptr()), "zsg_adam_step_segments")
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW: the decay is p *= 1 - lr * weight_decay ahead of the Adam update of the unmodified gradient."""
+    NAME, ALGO = "AdamW", OPT_ADAMW
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, grad_scale=1.0, params=None):
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, params=params, amsgrad=amsgrad)
+
+
+def _check_nesterov(nesterov, momentum, dampening):
+    if nesterov and (momentum <= 0 or dampening != 0):
+        raise ValueError("Nesterov momentum requires a momentum and zero dampening")          # (torch.optim.SGD's message)
+
+
+class FusedSGD(FusedOptimizer):
+    """torch.optim.SGD with momentum, dampening, weight decay and Nesterov momentum.  The momentum buffer exists once some group has
+    momentum != 0 (plain SGD allocates nothing); a parameter's first step sets its part to the gradient, as torch creates it."""
+    NAME, ALGO, HYPER = "SGD", OPT_SGD, ("lr", "momentum", "dampening", "weight_decay", "nesterov")
+
+    def __init__(self, model, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0, params=None):
+        self.momentum_buffer = None
+        super().__init__(model, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov), grad_scale,
+                         params)
+        self._ensure_buffer()
+
+    def _check_group(self, group):
+        d = self.defaults
+        _check_nesterov(group.get("nesterov", d["nesterov"]), group.get("momentum", d["momentum"]), group.get("dampening", d["dampening"]))
+
+    def _ensure_buffer(self):
+        if self.momentum_buffer is None and any(float(g["momentum"]) != 0 for g in self.param_groups):
+            self.momentum_buffer = torch.zeros_like(self.net.store.flat)
+
+    def _buffers(self):
+        self._ensure_buffer()          # (a group added, or a momentum set, after construction)
+        return {} if self.momentum_buffer is None else dict(momentum_buffer=self.momentum_buffer)
+
+    def _group(self, g):
+        return OptimGroup(float(g["lr"]), 0.0, 0.0, 0.0, float(g["weight_decay"]), float(g["momentum"]), float(g["dampening"]),
+                          1 if g["nesterov"] else 0)
+
+
+OPT_FNS = {"Adam": FusedAdam, "AdamW": FusedAdamW, "SGD": FusedSGD}          # cfg opt_fn
+OPT_FN_PARAMS = dict(betas=[0.9, 0.99], eps=1e-8, weight_decay=0.0, amsgrad=False, momentum=0.0, dampening=0.0, nesterov=False)
+
+
+def make_opt_fn(cfg):
+    """The optimizer factory of cfg opt_fn / opt_fn_params (reference main_dist.py:50: partial(torch.optim.Adam, betas=(0.9, 0.99))): a
+    callable (model, lr=..., params=...) as trainer.Learner expects.  Keys of opt_fn_params that the chosen rule does not have are
+    ignored, except that amsgrad or non-default betas with SGD are a ValueError (who sets them expects an effect)."""
+    from functools import partial
+    name = cfg["opt_fn"]
+    if name not in OPT_FNS:
+        raise ValueError(f"opt_fn {name!r} is not supported: one of {', '.join(OPT_FNS)}")
+    hp = dict(OPT_FN_PARAMS, **cfg.get("opt_fn_params", {}))
+    if name == "SGD":
+        if hp["amsgrad"] or [float(b) for b in hp["betas"]] != OPT_FN_PARAMS["betas"]:
+            raise ValueError("opt_fn SGD has no amsgrad and no betas (opt_fn_params.amsgrad / opt_fn_params.betas are set): choose Adam or "
+                             "AdamW, or leave them at their defaults")
+        _check_nesterov(hp["nesterov"], float(hp["momentum"]), float(hp["dampening"]))
+        return partial(FusedSGD, momentum=float(hp["momentum"]), dampening=float(hp["dampening"]), weight_decay=float(hp["weight_decay"]),
+                       nesterov=bool(hp["nesterov"]))
+    return partial(OPT_FNS[name], betas=tuple(float(b) for b in hp["betas"]), eps=float(hp["eps"]), weight_decay=float(hp["weight_decay"]),
+                   amsgrad=bool(hp["amsgrad"]))
 
 
 # ---- gradient-norm clipping ---------------------------------------------------------------------------------------------------------
