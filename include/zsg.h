@@ -476,7 +476,7 @@ int zsg_lstm_bwd(const float* dwe, int32_t we_ld, int32_t we_off, const float* w
  * Limit: B <= 512 samples per call (one LDS record per sample in the merge kernel); larger batches are rejected with -1
  * (the reference's per-GPU batches are 16-32, BASELINE configs; split a larger batch over calls and sum the losses).
  * ------------------------------------------------------------------------------------------------------------- */
-size_t zsg_loss_workspace_bytes(int32_t B, int32_t A);   /* one size for zsg_loss_fwd_bwd and zsg_loss_fwd_bwd_iou */
+size_t zsg_loss_workspace_bytes(int32_t B, int32_t A);   /* one size for zsg_loss_fwd_bwd, zsg_loss_fwd_bwd_iou and zsg_loss_fwd_bwd_q */
 int zsg_loss_fwd_bwd(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, float alpha,
                      float gamma, float lamb_reg, float match_thr, int32_t flags, float grad_scale, float* losses,
                      float* grad5, int32_t* match_idx, int32_t* npos, void* ws, size_t ws_bytes, void* stream);
@@ -495,6 +495,25 @@ int zsg_loss_fwd_bwd_iou(const float* out5, const float* annot, const float* anc
                          float gamma, float lamb_reg, float match_thr, int32_t flags, float grad_scale, int32_t iou_kind,
                          float lamb_iou, float* losses, float* grad5, int32_t* match_idx, int32_t* npos, void* ws,
                          size_t ws_bytes, void* stream);
+/* zsg_loss_fwd_bwd_iou with an IoU-aware classification target (no counterpart in the reference, whose att logit is trained against the
+ * hard 0 / 1 positives mask alone, loss.py:73-87 and :111-125).  x = the att logit, s = sigmoid(x), m = the positives mask exactly as
+ * above, q = m ? iou : 0 with iou the very iou defined above for the decoded box of the anchor (evaluated for every positive also when
+ * iou_kind = 0), held constant: no gradient flows through q into the box channels.  BCE(x, q) = max(x,0) - x q + log1p(exp(-|x|)).
+ *   cls_kind 0 (none): the classification term of zsg_loss_fwd_bwd
+ *   cls_kind 1 (qfl):  l = |q - s|^gamma BCE(x, q) for every anchor                    (Quality Focal Loss, Li et al. 2020)
+ *   cls_kind 2 (vfl):  l = q BCE(x, q) at positives, alpha s^gamma BCE(x, 0) at negatives   (Varifocal Loss, Zhang et al. 2021)
+ * cls_ls = sum of l over all samples and anchors / sum of m (loss.py:125's normaliser); its gradient is the true derivative of l with
+ * respect to x, through the modulating factor (unlike the focal weights of loss.py:118, which are detached).  cls_kind 1 / 2 need
+ * flags bit0 set, bit2 clear and gamma >= 1 (else -1).  iou_kind: 0 (no IoU term, iou_ls = 0), 1, 2.
+ * losses[5] = (loss, cls_ls, box_ls, iou_ls, pos_iou), pos_iou = mean over samples of (sum of q over the sample's positives / #pos).
+ * With cls_kind = 0, losses[0:4], grad5, match_idx and npos are those of zsg_loss_fwd_bwd (iou_kind 0) / zsg_loss_fwd_bwd_iou bit for
+ * bit (outside the NaN branch).  NaN branch: box_ls, cls_ls or iou_ls NaN -> the constants of loss.py:128-133, iou_ls = pos_iou = 0
+ * and grad5 = +0 everywhere, for every cls_kind and iou_kind (zsg_loss_fwd_bwd writes 0 * derivative there: a -0 or a NaN may remain).
+ * Same launches, limits and workspace as zsg_loss_fwd_bwd. */
+int zsg_loss_fwd_bwd_q(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, float alpha, float gamma,
+                       float lamb_reg, float match_thr, int32_t flags, float grad_scale, int32_t iou_kind, float lamb_iou,
+                       int32_t cls_kind, float* losses, float* grad5, int32_t* match_idx, int32_t* npos, void* ws, size_t ws_bytes,
+                       void* stream);
 
 /* Evaluator.forward, evaluator.py:48-117 (reg_params_to_bbox anchors.py:182-197): arg-max score anchor -> decode ->
  * IoU >= thr.  metrics[2] = (Acc, MaxPos); pred_boxes [B][4] pixels x1y1x2y2; pred_scores [B]; pred_idx [B] int32. */

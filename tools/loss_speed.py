@@ -1,8 +1,9 @@
 """Developer tool: device time of the ZSGLoss call (loss + gradient kernels) at B = 16, A = 17460 on a fixed head output, for
-cfg box_iou_loss = none / giou / diou, alternating.  Each call is bracketed by the library's own HIP events (zsg_prof_enable: recorded on
+cfg box_iou_loss = none / giou / diou and (--cls) cfg cls_quality = qfl / vfl, alternating call by call with none.  Each call is bracketed by the library's own HIP events (zsg_prof_enable: recorded on
 the stream right before the first and after the last launch of the entry point), so the figure is the kernels and the gaps between them,
 not the Python around them; the median of --calls calls after --warmup, min and max next to it.  One JSON line (--json PATH also writes it).
---kinds none restricts the set (a tree from before the IoU loss has only that one)."""
+--kinds none restricts the set (a tree from before the IoU loss has only that one); --cls qfl,vfl adds those variants (each with
+box_iou_loss none; "qfl+giou" names a box IoU loss next to it)."""
 import argparse
 import json
 import os
@@ -20,10 +21,11 @@ ap.add_argument("--batch", type=int, default=16)
 ap.add_argument("--calls", type=int, default=60)
 ap.add_argument("--warmup", type=int, default=10)
 ap.add_argument("--kinds", default="none,giou,diou")
+ap.add_argument("--cls", default="", help="comma list of cls_quality variants timed next to --kinds: qfl, vfl, qfl+giou, ...")
 ap.add_argument("--json", default=None)
 args = ap.parse_args()
 B, A = args.batch, 17460
-kinds = args.kinds.split(",")
+kinds = args.kinds.split(",") + [k for k in args.cls.split(",") if k]
 
 gen = torch.Generator().manual_seed(7)
 out5 = torch.cat([torch.randn(B, A, 4, generator=gen) * 0.3, torch.randn(B, A, 1, generator=gen) * 1.5 - 3.0], dim=2).cuda().requires_grad_()
@@ -32,7 +34,10 @@ out = dict(att_bbx_out=out5, feat_sizes=torch.tensor(O.feat_sizes_for(300, 300))
 inp = {"annot": bt["annot"].cuda()}
 lfs = {}
 for k in kinds:
-    c = config.get_cfg() if k == "none" else config.get_cfg(box_iou_loss=k)
+    if k.split("+")[0] in ("qfl", "vfl"):
+        c = config.get_cfg(cls_quality=k.split("+")[0], box_iou_loss=(k.split("+") + ["none"])[1])
+    else:
+        c = config.get_cfg() if k == "none" else config.get_cfg(box_iou_loss=k)
     lfs[k] = loss.get_default_loss(*config.ratios_scales(c), c)
 
 

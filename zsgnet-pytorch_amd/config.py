@@ -46,6 +46,7 @@ DEFAULTS: Dict[str, Any] = {
     "aug_saturation": 0.0,          # ... a saturation factor (blend with the pixel's gray value)
     "box_iou_loss": "none",         # "giou" / "diou": ZSGLoss adds lamb_iou * (that IoU loss of the decoded positive boxes) to the criterion and reports it as iou_ls (zsg_loss_fwd_bwd_iou); "none" = off
     "lamb_iou": 1.0,                # ... its weight (>= 0); lamb_reg = 0 with it trains on the IoU term alone
+    "cls_quality": "none",          # "qfl" / "vfl": the att logit is trained towards the IoU of the anchor's decoded box with the annotation (Quality Focal / Varifocal loss, zsg_loss_fwd_bwd_q) and ZSGLoss also reports pos_iou; needs use_focal, no use_softmax, gamma >= 1; "none" = the reference's focal term
     # configs/ds_info.json: where each dataset's images and csv files live (override with --ds_info.<name>.<key>=...)
     "ds_info": {name: {"data_dir": f"./data/{root}", "img_dir": f"./data/{imgs}",
                        **{f"{s}_csv_file": f"./data/{csv}/csv_dir/{f}.csv" for s, f in (("trn", trn), ("val", "val"), ("test", "test"))}}

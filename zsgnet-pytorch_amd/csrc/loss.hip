@@ -306,10 +306,20 @@ struct LossPartIou {     // LossPart + the range's box-IoU loss sum
     int npos, best;
 };
 
-extern "C" size_t zsg_loss_workspace_bytes(int32_t B, int32_t A) {   // covers both entry points (the records of the IoU one are the larger)
+struct LossWsQ {         // LossWsIou with the sum of the positives' quality targets in the place of row_max (which pass 2 never reads)
+    double box_sum, cls_sum, iou_sum, q_sum, row_lse;
+    int best, npos;
+};
+struct LossPartQ {       // LossPartIou + the range's sum of quality targets: the largest range record
+    double box_sum, cls_sum, iou_sum, q_sum;
+    int npos, best;
+};
+
+extern "C" size_t zsg_loss_workspace_bytes(int32_t B, int32_t A) {   // covers the three entry points (the records of the quality one are the largest)
     (void)A;
-    static_assert(sizeof(LossWsIou) == sizeof(LossWs) && sizeof(LossPartIou) >= sizeof(LossPart), "workspace records");
-    return (size_t)B * (sizeof(LossWsIou) + LS_CHUNKS * (sizeof(ArgMax) + sizeof(LossPartIou)));
+    static_assert(sizeof(LossWsIou) == sizeof(LossWs) && sizeof(LossWsQ) == sizeof(LossWs), "workspace records");
+    static_assert(sizeof(LossPartQ) >= sizeof(LossPartIou) && sizeof(LossPartIou) >= sizeof(LossPart), "workspace records");
+    return (size_t)B * (sizeof(LossWsQ) + LS_CHUNKS * (sizeof(ArgMax) + sizeof(LossPartQ)));
 }
 
 extern "C" int zsg_loss_fwd_bwd(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, float alpha, float gamma,
@@ -640,6 +650,301 @@ extern "C" int zsg_loss_fwd_bwd_iou(const float* out5, const float* annot, const
                        flags, grad_scale, iou_kind, lamb_iou, (const LossWsIou*)rec,
                        chunked ? (const LossPartIou*)parts : (const LossPartIou*)nullptr, losses, grad5, match_idx, npos);
     ZSG_CHECK_LAUNCH("loss_fwd_bwd_iou");
+    return 0;
+}
+
+// ---- IoU-aware classification targets: Quality Focal / Varifocal loss (zsg_loss_fwd_bwd_q) ----------------------------------
+// The three kernels below are the IoU-loss kernels above with the classification term exchanged (the same launches, loss_argmax_kernel
+// is shared); the kernels above are what the two older entry points run and are not touched.  With x the att logit, s = sigmoid(x),
+// m the positives mask and q = m ? iou(decoded box, annotation) : 0 (the iou of iou_loss_terms, the same fp64 expressions in the same
+// order: bit-equal to it), a constant for the derivative, BCE(x, q) = max(x, 0) - x q + log1p(exp(-|x|)):
+//   cls_kind 1 (qfl):  l = |q - s|^gamma BCE(x, q)                                      every anchor
+//   cls_kind 2 (vfl):  l = q BCE(x, q)  (positives),   alpha s^gamma BCE(x, 0)  (negatives)
+// and dl/dx is the true derivative, through the modulating factor (d BCE / dx = s - q, ds/dx = s (1 - s)):
+//   d/dx |q - s|^gamma BCE = sign(s - q) |s - q|^(gamma - 1) (gamma s (1 - s) BCE + (s - q)^2)
+// Both summands inside the bracket are >= 0: nothing cancels except in s - q itself, where the derivative is small; fp32 as the
+// focal term.  cls_kind 0 is the focal / plain / softmax term of the kernels above, expression for expression; iou_kind 0 leaves
+// the IoU loss out (iou_ls = 0).  q is evaluated for every positive in all cases: its per-sample mean is losses[4] (pos_iou).
+__device__ __forceinline__ double decoded_iou(const float* __restrict__ o5, const f32x4 an, const f32x4 bx) {
+    const double acy = ((double)an[0] + (double)an[2]) / 2., acx = ((double)an[1] + (double)an[3]) / 2.;
+    const double ah = (double)an[2] - (double)an[0], aw = (double)an[3] - (double)an[1];
+    const double cy = ah * (double)o5[0] + acy, cx = aw * (double)o5[1] + acx;
+    const double h = exp((double)o5[2]) * ah, w = exp((double)o5[3]) * aw;
+    const double y1 = cy - h / 2., x1 = cx - w / 2., y2 = cy + h / 2., x2 = cx + w / 2.;
+    const double g0 = bx[0], g1 = bx[1], g2 = bx[2], g3 = bx[3];
+    const double ry = fmin(y2, g2) - fmax(y1, g0), rx = fmin(x2, g3) - fmax(x1, g1);
+    const double iy = fmax(ry, 0.), ix = fmax(rx, 0.);
+    const double inter = iy * ix;
+    const double ph = y2 - y1, pw = x2 - x1;
+    const double uni = ph * pw + (g2 - g0) * (g3 - g1) - inter;
+    return inter / (uni + IOU_EPS);
+}
+
+// l and dl/dx of one anchor for cls_kind 1 / 2 (q = 0 at a negative anchor)
+__device__ __forceinline__ float quality_terms(float x, float q, bool pos, int cls_kind, float alpha, float gamma, float* dx) {
+    const float p = 1.0f / (1.0f + expf(-x));
+    const float bce = fmaxf(x, 0.f) - x * q + log1pf(expf(-fabsf(x)));
+    if (cls_kind == 2 && pos) {
+        *dx = q * (p - q);
+        return q * bce;
+    }
+    const float d = p - q, ad = fabsf(d);
+    const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    const float w = cls_kind == 2 ? alpha : 1.f;
+    *dx = w * sg * focal_pow(ad, gamma - 1.f) * (gamma * p * (1.f - p) * bce + d * d);
+    return w * focal_pow(ad, gamma) * bce;
+}
+
+struct QSums {
+    double box, cls, iou, q;
+    int cnt;
+};
+// one anchor of pass 1: the loop body of loss_stats_iou_kernel / loss_part_iou_kernel with q and the exchanged classification term
+__device__ __forceinline__ void q_pass1_anchor(QSums& s, const float* __restrict__ o, const float* __restrict__ anchors, const f32x4 bx,
+                                               int a, int best, float alpha, float gamma, float thr, int flags, int iou_kind, int cls_kind) {
+    const bool use_focal = flags & 1, use_multi = flags & 2, use_softmax = flags & 4;
+    const f32x4 an = *(const f32x4*)(anchors + 4 * a);
+    const float v = iou_exact(bx, an);
+    const bool pos = (use_multi && v > thr) || a == best;
+    const float t = pos ? 1.f : 0.f;
+    s.cnt += pos;
+    float d[4];
+    const float sl1 = box_terms(o + a * 5, an, bx, d);
+    s.box += (double)(sl1 * t);
+    float q = 0.f;
+    if (pos) {
+        double di[4];
+        if (iou_kind) s.iou += iou_loss_terms(o + a * 5, an, bx, iou_kind, di);
+        const double qd = decoded_iou(o + a * 5, an, bx);
+        s.q += qd;
+        q = (float)qd;
+    }
+    const float x = o[a * 5 + 4];
+    if (cls_kind) {
+        float dx;
+        s.cls += (double)quality_terms(x, q, pos, cls_kind, alpha, gamma, &dx);
+    } else if (!use_softmax) {
+        const float bce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+        float w = 1.f;
+        if (use_focal) {
+            const float p = 1.0f / (1.0f + expf(-x));
+            w = focal_pow(t * (1.f - p) + (1.f - t) * p, gamma) * ((1.f - t) * alpha + t * (1.f - alpha));
+        }
+        s.cls += (double)(w * bce);
+    }
+}
+
+// pass 1, one block per sample (loss_stats_iou_kernel + q)
+__global__ __launch_bounds__(LS_THREADS) void loss_stats_q_kernel(const float* __restrict__ out5, const float* __restrict__ annot,
+                                                                  const float* __restrict__ anchors, int A, float alpha, float gamma,
+                                                                  float thr, int flags, int iou_kind, int cls_kind,
+                                                                  LossWsQ* __restrict__ ws) {
+    __shared__ ArgMax sm_a[LS_THREADS / 64];
+    __shared__ double sm_d[LS_THREADS / 64];
+    const int b = blockIdx.x;
+    const bool use_softmax = flags & 4;
+    const f32x4 bx = *(const f32x4*)(annot + 4 * b);
+    const float* o = out5 + (size_t)b * A * 5;
+
+    ArgMax m = {-INFINITY, 0x7fffffff};
+    for (int a = threadIdx.x; a < A; a += LS_THREADS) {
+        const float v = iou_exact(bx, *(const f32x4*)(anchors + 4 * a));
+        if (v > m.v) { m.v = v; m.i = a; }
+    }
+    m = block_argmax(m, sm_a);
+    const int best = m.i == 0x7fffffff ? 0 : m.i;
+
+    double row_lse = 0;
+    if (use_softmax) {
+        float mx = -INFINITY;
+        for (int a = threadIdx.x; a < A; a += LS_THREADS) mx = fmaxf(mx, o[a * 5 + 4]);
+        ArgMax t = {mx, 0};
+        t = block_argmax(t, sm_a);
+        double se = 0;
+        for (int a = threadIdx.x; a < A; a += LS_THREADS) se += exp((double)o[a * 5 + 4] - (double)t.v);
+        se = block_sum_d(se, sm_d);
+        row_lse = (double)t.v + log(se);
+    }
+
+    QSums s = {0, 0, 0, 0, 0};
+    for (int a = threadIdx.x; a < A; a += LS_THREADS) q_pass1_anchor(s, o, anchors, bx, a, best, alpha, gamma, thr, flags, iou_kind, cls_kind);
+    const double box = block_sum_d(s.box, sm_d);
+    double cls = block_sum_d(s.cls, sm_d);
+    const double iou = block_sum_d(s.iou, sm_d);
+    const double qs = block_sum_d(s.q, sm_d);
+    const int npos = (int)(block_sum_d((double)s.cnt, sm_d) + 0.5);
+    if (threadIdx.x == 0) {
+        if (use_softmax) cls = row_lse - (double)o[best * 5 + 4];
+        LossWsQ r;
+        r.box_sum = box; r.cls_sum = cls; r.iou_sum = iou; r.q_sum = qs; r.row_lse = row_lse; r.best = best; r.npos = npos;
+        ws[b] = r;
+    }
+}
+
+// chunked pass 1b (loss_part_iou_kernel + q); pass 1a is loss_argmax_kernel itself
+__global__ __launch_bounds__(256) void loss_part_q_kernel(const float* __restrict__ out5, const float* __restrict__ annot,
+                                                          const float* __restrict__ anchors, int A, float alpha, float gamma, float thr,
+                                                          int flags, int iou_kind, int cls_kind, const ArgMax* __restrict__ amax,
+                                                          LossPartQ* __restrict__ parts) {
+    __shared__ double sm_d[4];
+    const int b = blockIdx.y, per = (A + LS_CHUNKS - 1) / LS_CHUNKS;
+    const int a0 = blockIdx.x * per, a1 = min(A, a0 + per);
+    const f32x4 bx = *(const f32x4*)(annot + 4 * b);
+    const float* o = out5 + (size_t)b * A * 5;
+    ArgMax m = amax[b * LS_CHUNKS];
+    for (int c = 1; c < LS_CHUNKS; ++c) m = argmax_merge(m, amax[b * LS_CHUNKS + c]);
+    const int best = m.i == 0x7fffffff ? 0 : m.i;
+    QSums s = {0, 0, 0, 0, 0};
+    for (int a = a0 + threadIdx.x; a < a1; a += 256) q_pass1_anchor(s, o, anchors, bx, a, best, alpha, gamma, thr, flags, iou_kind, cls_kind);
+    const double box = block_sum_d(s.box, sm_d);
+    const double cls = block_sum_d(s.cls, sm_d);
+    const double iou = block_sum_d(s.iou, sm_d);
+    const double qs = block_sum_d(s.q, sm_d);
+    const int npos = (int)(block_sum_d((double)s.cnt, sm_d) + 0.5);
+    if (threadIdx.x == 0) {
+        LossPartQ r;
+        r.box_sum = box; r.cls_sum = cls; r.iou_sum = iou; r.q_sum = qs; r.npos = npos; r.best = best;
+        parts[b * LS_CHUNKS + blockIdx.x] = r;
+    }
+}
+
+// pass 2 (loss_grad_iou_kernel + q): losses[5] = (loss, cls_ls, box_ls, iou_ls, pos_iou); a NaN in any of the three loss parts gives
+// the constants, iou_ls = pos_iou = 0 and an exactly zero gradient (also at the anchor that holds the NaN).
+__global__ __launch_bounds__(256) void loss_grad_q_kernel(const float* __restrict__ out5, const float* __restrict__ annot,
+                                                          const float* __restrict__ anchors, int B, int A, float alpha, float gamma,
+                                                          float lamb, float thr, int flags, float grad_scale, int iou_kind, float lamb_iou,
+                                                          int cls_kind, const LossWsQ* __restrict__ ws_in,
+                                                          const LossPartQ* __restrict__ parts, float* __restrict__ losses,
+                                                          float* __restrict__ grad5, int* __restrict__ match_idx,
+                                                          int* __restrict__ npos_out) {
+    const bool use_focal = flags & 1, use_multi = flags & 2, use_softmax = flags & 4;
+    const int b = blockIdx.y;
+    __shared__ LossWsQ ws[LS_MAX_B];
+    for (int k = threadIdx.x; k < B; k += blockDim.x) {
+        LossWsQ r;
+        if (parts) {                                     // merge the sample's range records in range order
+            r.box_sum = r.cls_sum = r.iou_sum = r.q_sum = r.row_lse = 0;
+            r.npos = 0;
+            for (int c = 0; c < LS_CHUNKS; ++c) {
+                const LossPartQ q = parts[k * LS_CHUNKS + c];
+                r.box_sum += q.box_sum;
+                r.cls_sum += q.cls_sum;
+                r.iou_sum += q.iou_sum;
+                r.q_sum += q.q_sum;
+                r.npos += q.npos;
+            }
+            r.best = parts[k * LS_CHUNKS].best;
+        } else {
+            r = ws_in[k];
+        }
+        ws[k] = r;
+    }
+    __syncthreads();
+    double box = 0, cls = 0, iou = 0, qm = 0;
+    long long npos_all = 0;
+    for (int k = 0; k < B; ++k) {
+        box += ws[k].box_sum / (double)ws[k].npos;
+        iou += ws[k].iou_sum / (double)ws[k].npos;
+        qm += ws[k].q_sum / (double)ws[k].npos;
+        cls += ws[k].cls_sum;
+        npos_all += ws[k].npos;
+    }
+    box /= (double)B;
+    iou /= (double)B;
+    qm /= (double)B;
+    cls /= (double)npos_all;
+    const bool bad = (box != box) || (cls != cls) || (iou != iou);
+    if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) {
+        const double bl = bad ? 0.01 : box, cl = bad ? 1.0 : cls, il = bad ? 0.0 : iou;
+        losses[0] = (float)(lamb * bl + lamb_iou * il + cl);
+        losses[1] = (float)cl;
+        losses[2] = (float)bl;
+        losses[3] = (float)il;
+        losses[4] = (float)(bad ? 0.0 : qm);
+    }
+    const LossWsQ me = ws[b];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        match_idx[b] = me.best;
+        if (npos_out) npos_out[b] = me.npos;
+    }
+    if (!grad5) return;
+    const f32x4 bx = *(const f32x4*)(annot + 4 * b);
+    const float* o = out5 + (size_t)b * A * 5;
+    float* g = grad5 + (size_t)b * A * 5;
+    const float kbox = bad ? 0.f : grad_scale * lamb / ((float)B * (float)me.npos);
+    const float kiou = bad ? 0.f : grad_scale * lamb_iou / ((float)B * (float)me.npos);
+    const float kcls = bad ? 0.f : grad_scale / (float)npos_all;
+    for (int a = blockIdx.x * blockDim.x + threadIdx.x; a < A; a += gridDim.x * blockDim.x) {
+        const f32x4 an = *(const f32x4*)(anchors + 4 * a);
+        const float v = iou_exact(bx, an);
+        const bool pos = (use_multi && v > thr) || a == me.best;
+        const float t = pos ? 1.f : 0.f;
+        float d[4];
+        box_terms(o + a * 5, an, bx, d);
+        float q = 0.f;
+        if (pos && !bad) {                               // (bad: zeros, not 0 * NaN — the NaN may sit in this very anchor)
+            if (iou_kind) {
+                double di[4];
+                iou_loss_terms(o + a * 5, an, bx, iou_kind, di);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) g[a * 5 + k] = kbox * d[k] + kiou * (float)di[k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) g[a * 5 + k] = kbox * d[k];
+            }
+            if (cls_kind) q = (float)decoded_iou(o + a * 5, an, bx);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[a * 5 + k] = 0.f;
+        }
+        const float x = o[a * 5 + 4];
+        float ga;
+        if (cls_kind) {
+            quality_terms(x, q, pos, cls_kind, alpha, gamma, &ga);
+        } else if (use_softmax) {
+            ga = (float)exp((double)x - me.row_lse) - (a == me.best ? 1.f : 0.f);
+        } else {
+            const float p = 1.0f / (1.0f + expf(-x));
+            float w = 1.f;
+            if (use_focal) w = focal_pow(t * (1.f - p) + (1.f - t) * p, gamma) * ((1.f - t) * alpha + t * (1.f - alpha));
+            ga = w * (p - t);
+        }
+        g[a * 5 + 4] = bad ? 0.f : kcls * ga;
+    }
+}
+
+extern "C" int zsg_loss_fwd_bwd_q(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, float alpha,
+                                  float gamma, float lamb_reg, float match_thr, int32_t flags, float grad_scale, int32_t iou_kind,
+                                  float lamb_iou, int32_t cls_kind, float* losses, float* grad5, int32_t* match_idx, int32_t* npos,
+                                  void* ws, size_t ws_bytes, void* stream) {
+    ZSG_REQUIRE(out5 && annot && anchors && losses && match_idx && ws && B > 0 && A > 0, "loss_fwd_bwd_q: bad argument");
+    ZSG_REQUIRE(!((flags & 4) && (flags & 2)), "loss_fwd_bwd_q: use_softmax requires use_multi == False (loss.py:107)");
+    ZSG_REQUIRE(iou_kind >= 0 && iou_kind <= 2, "loss_fwd_bwd_q: iou_kind=%d is none of 0 (none), 1 (giou), 2 (diou)", iou_kind);
+    ZSG_REQUIRE(lamb_iou >= 0.f, "loss_fwd_bwd_q: lamb_iou must not be negative");
+    ZSG_REQUIRE(cls_kind >= 0 && cls_kind <= 2, "loss_fwd_bwd_q: cls_kind=%d is none of 0 (none), 1 (qfl), 2 (vfl)", cls_kind);
+    ZSG_REQUIRE(!cls_kind || ((flags & 1) && !(flags & 4)), "loss_fwd_bwd_q: cls_kind=%d needs use_focal and no use_softmax", cls_kind);
+    ZSG_REQUIRE(!cls_kind || gamma >= 1.f, "loss_fwd_bwd_q: cls_kind=%d needs gamma >= 1 (the derivative is singular at sigmoid = q below)", cls_kind);
+    if (ws_bytes < zsg_loss_workspace_bytes(B, A)) ZSG_FAIL(-2, "loss_fwd_bwd_q: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("loss_fwd_bwd_q", st, 0, (double)B * A * 5 * 4 * 3);
+    ZSG_REQUIRE(B <= LS_MAX_B, "loss_fwd_bwd_q: B=%d exceeds %d", B, LS_MAX_B);
+    LossWsQ* rec = (LossWsQ*)ws;
+    LossPartQ* parts = (LossPartQ*)(rec + B);
+    ArgMax* amax = (ArgMax*)(parts + (size_t)B * LS_CHUNKS);
+    const bool chunked = !(flags & 4) && A >= 4 * LS_CHUNKS;      // as zsg_loss_fwd_bwd
+    if (chunked) {
+        ZSG_LAUNCH(loss_argmax_kernel, dim3(LS_CHUNKS, B), dim3(256), 0, st, annot, anchors, A, amax);
+        ZSG_LAUNCH(loss_part_q_kernel, dim3(LS_CHUNKS, B), dim3(256), 0, st, out5, annot, anchors, A, alpha, gamma, match_thr, flags,
+                           iou_kind, cls_kind, (const ArgMax*)amax, parts);
+    } else {
+        ZSG_LAUNCH(loss_stats_q_kernel, dim3(B), dim3(LS_THREADS), 0, st, out5, annot, anchors, A, alpha, gamma, match_thr, flags,
+                           iou_kind, cls_kind, rec);
+    }
+    const int chunks = min(32, cdiv(A, 256));
+    ZSG_LAUNCH(loss_grad_q_kernel, dim3(chunks, B), dim3(256), 0, st, out5, annot, anchors, B, A, alpha, gamma, lamb_reg, match_thr,
+                       flags, grad_scale, iou_kind, lamb_iou, cls_kind, (const LossWsQ*)rec,
+                       chunked ? (const LossPartQ*)parts : (const LossPartQ*)nullptr, losses, grad5, match_idx, npos);
+    ZSG_CHECK_LAUNCH("loss_fwd_bwd_q");
     return 0;
 }
 

@@ -51,7 +51,8 @@ class _LossFn(torch.autograd.Function):
         B, A, _ = out5.shape
         dev = out5.device
         kind = mod.iou_kind                 # 0: the reference's criterion; 1 / 2: + lamb_iou * GIoU / DIoU loss (zsg_loss_fwd_bwd_iou)
-        losses = torch.empty(4 if kind else 3, device=dev)
+        cls_kind = mod.cls_kind             # 0: the reference's classification term; 1 / 2: QFL / VFL on the IoU target (zsg_loss_fwd_bwd_q)
+        losses = torch.empty(5 if cls_kind else (4 if kind else 3), device=dev)
         # Where d(loss)/d(out5) goes: straight into the incoming-gradient buffer of the network plan that produced out5 (ZSGNet.forward
         # attaches it), already scaled by 1 / world under data parallelism (the reducer SUMs) — the backward then needs no launch of
         # its own when the upstream gradient is the constant 1.  Only the FIRST loss applied to an output may take the buffer.
@@ -73,7 +74,12 @@ class _LossFn(torch.autograd.Function):
         wsb = lib.zsg_loss_workspace_bytes(B, A)
         ws = torch.empty((wsb + 7) // 8, dtype=torch.float64, device=dev)
         flags = (1 if mod.use_focal else 0) | (2 if mod.use_multi else 0) | (4 if mod.use_softmax else 0)
-        if kind:
+        if cls_kind:
+            check(lib.zsg_loss_fwd_bwd_q(out5.data_ptr(), annot.data_ptr(), mod.anchs.data_ptr(), B, A, mod.alpha, float(mod.gamma),
+                                         float(mod.lamb_reg), float(mod.cfg["matching_threshold"]), flags, scale, kind,
+                                         float(mod.lamb_iou), cls_kind, losses.data_ptr(), grad5.data_ptr(), mod.match_idx.data_ptr(),
+                                         mod.npos.data_ptr(), ws.data_ptr(), wsb, stream_ptr()), "zsg_loss_fwd_bwd_q")
+        elif kind:
             check(lib.zsg_loss_fwd_bwd_iou(out5.data_ptr(), annot.data_ptr(), mod.anchs.data_ptr(), B, A, mod.alpha, float(mod.gamma),
                                            float(mod.lamb_reg), float(mod.cfg["matching_threshold"]), flags, scale, kind,
                                            float(mod.lamb_iou), losses.data_ptr(), grad5.data_ptr(), mod.match_idx.data_ptr(),
@@ -89,7 +95,7 @@ class _LossFn(torch.autograd.Function):
         else:
             ctx.save_for_backward(grad5)
         mod._last_losses = losses
-        # (a view of the 3- or 4-float result, not a copy: one dependent launch less between the loss kernels and the backward)
+        # (a view of the 3- to 5-float result, not a copy: one dependent launch less between the loss kernels and the backward)
         return losses.narrow(0, 0, 1).view(())
 
     @staticmethod
@@ -105,9 +111,12 @@ class _LossFn(torch.autograd.Function):
 
 class ZSGLoss(nn.Module):
     """Criterion to be minimised (reference loss.py:11-143).  forward(out, inp) -> {'loss','cls_ls','box_ls'}.
-    cfg box_iou_loss = "giou" / "diou" adds lamb_iou * (that IoU loss of the decoded boxes of the positive anchors) and the key 'iou_ls'."""
+    cfg box_iou_loss = "giou" / "diou" adds lamb_iou * (that IoU loss of the decoded boxes of the positive anchors) and the key 'iou_ls'.
+    cfg cls_quality = "qfl" / "vfl" trains the att logit towards the IoU of the anchor's decoded box with the annotation (Quality Focal /
+    Varifocal loss in the place of the focal term) and adds the key 'pos_iou', the mean of that target over the positives (no gradient)."""
 
     IOU_KINDS = {"none": 0, "giou": 1, "diou": 2}
+    CLS_KINDS = {"none": 0, "qfl": 1, "vfl": 2}
 
     def __init__(self, ratios, scales, cfg):
         super().__init__()
@@ -122,7 +131,18 @@ class ZSGLoss(nn.Module):
         if not self.lamb_iou >= 0:
             raise ValueError(f"lamb_iou={self.lamb_iou}: must not be negative")
         self.iou_kind = self.IOU_KINDS[kind]
-        self.loss_keys = ["loss", "cls_ls", "box_ls"] + (["iou_ls"] if self.iou_kind else [])
+        quality = cfg.get("cls_quality", "none")
+        if quality not in self.CLS_KINDS:
+            raise ValueError(f"cls_quality={quality!r}: expected one of {sorted(self.CLS_KINDS)}")
+        self.cls_kind = self.CLS_KINDS[quality]
+        if self.cls_kind:
+            if self.use_softmax:
+                raise ValueError(f"cls_quality={quality!r} is defined on the sigmoid branch: use_softmax must be False")
+            if not self.use_focal:
+                raise ValueError(f"cls_quality={quality!r} replaces the focal term: use_focal must be True")
+            if not self.gamma >= 1:
+                raise ValueError(f"cls_quality={quality!r} needs gamma >= 1 (gamma={self.gamma}: the derivative is singular where sigmoid = target)")
+        self.loss_keys = ["loss", "cls_ls", "box_ls"] + (["iou_ls"] if self.iou_kind else []) + (["pos_iou"] if self.cls_kind else [])
         self.anchs = None
         self.get_anchors = partial(create_anchors, ratios=self.ratios, scales=self.scales, flatten=True)
 
@@ -146,6 +166,8 @@ class ZSGLoss(nn.Module):
         res = {"loss": loss, "cls_ls": ls[1], "box_ls": ls[2]}
         if self.iou_kind:
             res["iou_ls"] = ls[3]
+        if self.cls_kind:
+            res["pos_iou"] = ls[4]
         return res
 
 
