@@ -476,7 +476,7 @@ int zsg_lstm_bwd(const float* dwe, int32_t we_ld, int32_t we_off, const float* w
  * Limit: B <= 512 samples per call (one LDS record per sample in the merge kernel); larger batches are rejected with -1
  * (the reference's per-GPU batches are 16-32, BASELINE configs; split a larger batch over calls and sum the losses).
  * ------------------------------------------------------------------------------------------------------------- */
-size_t zsg_loss_workspace_bytes(int32_t B, int32_t A);   /* one size for zsg_loss_fwd_bwd, zsg_loss_fwd_bwd_iou and zsg_loss_fwd_bwd_q */
+size_t zsg_loss_workspace_bytes(int32_t B, int32_t A);   /* one size for zsg_loss_fwd_bwd, _iou, _q and _m */
 int zsg_loss_fwd_bwd(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, float alpha,
                      float gamma, float lamb_reg, float match_thr, int32_t flags, float grad_scale, float* losses,
                      float* grad5, int32_t* match_idx, int32_t* npos, void* ws, size_t ws_bytes, void* stream);
@@ -514,6 +514,32 @@ int zsg_loss_fwd_bwd_q(const float* out5, const float* annot, const float* ancho
                        float lamb_reg, float match_thr, int32_t flags, float grad_scale, int32_t iou_kind, float lamb_iou,
                        int32_t cls_kind, float* losses, float* grad5, int32_t* match_idx, int32_t* npos, void* ws, size_t ws_bytes,
                        void* stream);
+/* zsg_loss_fwd_bwd_q on a positives mask made beforehand (ZSGLoss.forward with cfg matcher = "atss"; no counterpart in the reference,
+ * whose positives are simple_match_anchors' fixed rule, anchors.py:153-165 as called at loss.py:73-87).  pos_mask [B][A] uint8: anchor a
+ * of sample b is positive where pos_mask[b][a] != 0 or a is the sample's arg-max IoU anchor (lowest index, as above: every sample keeps a
+ * positive, match_idx and the NaN branch keep their meaning).  flags bit1 (use_multi) and match_thr are not consulted.  Everything else
+ * is zsg_loss_fwd_bwd_q's: the sums and their order, grad_scale, losses[5], match_idx, npos, the limits, the workspace
+ * (zsg_loss_workspace_bytes) and the launches.  Given the mask of the fixed rule it returns zsg_loss_fwd_bwd_q's bits. */
+int zsg_loss_fwd_bwd_m(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, float alpha, float gamma,
+                       float lamb_reg, float match_thr, int32_t flags, float grad_scale, int32_t iou_kind, float lamb_iou,
+                       int32_t cls_kind, const uint8_t* pos_mask, float* losses, float* grad5, int32_t* match_idx, int32_t* npos,
+                       void* ws, size_t ws_bytes, void* stream);
+/* ATSS anchor assignment (Adaptive Training Sample Selection, Zhang et al. 2020) — ZSGLoss.forward with cfg matcher = "atss", in the
+ * place of simple_match_anchors anchors.py:153-165; the mask goes to zsg_loss_fwd_bwd_m.  One annotation g = annot[b] per sample.
+ * level_off [L + 1] int32 in HOST memory (read before anything is launched): pyramid level l owns the anchors
+ * [level_off[l], level_off[l + 1]) of create_anchors' flattened order, level_off[0] = 0, level_off[L] = A, strictly ascending.
+ * All fp32, in this order, no contraction:
+ *   acy = (a.y1 + a.y2) / 2, acx = (a.x1 + a.x2) / 2;  gcy, gcx likewise;  d(a) = (acy - gcy)(acy - gcy) + (acx - gcx)(acx - gcx)
+ *   C = per level the min(topk, n_l) anchors with the smallest key (d, index), lexicographic; ordered by level, then by rank
+ *   v(a) = IoU(g, a) exactly as zsg_loss_fwd_bwd's;  t = mean(v over C) + std(v over C): fp64 from the fp32 values, summed in the order
+ *   of C, mean = sum v / |C|, std = sqrt(sum (v - mean)^2 / (|C| - 1)), 0 for |C| = 1
+ *   positive: (a in C and (double)v(a) >= t and g.y1 < acy < g.y2 and g.x1 < acx < g.x2)  or  a == the arg-max IoU anchor of the sample
+ * pos_mask [B][A] uint8: every byte is written, 0 or 1.  thr [B] double = t (may be null).  cand [B][8 * 16] int32 = C in its order,
+ * -1 behind it (may be null).  Two launches, no atomics, no host synchronisation, the same bits on every run.
+ * Limits (else -1, nothing launched): 1 <= L <= 8, 1 <= topk <= 16, B <= 512, level_off as above. */
+size_t zsg_match_atss_workspace_bytes(int32_t B, int32_t L);
+int zsg_match_atss(const float* annot, const float* anchors, const int32_t* level_off, int32_t L, int32_t B, int32_t A, int32_t topk,
+                   uint8_t* pos_mask, double* thr, int32_t* cand, void* ws, size_t ws_bytes, void* stream);
 
 /* Evaluator.forward, evaluator.py:48-117 (reg_params_to_bbox anchors.py:182-197): arg-max score anchor -> decode ->
  * IoU >= thr.  metrics[2] = (Acc, MaxPos); pred_boxes [B][4] pixels x1y1x2y2; pred_scores [B]; pred_idx [B] int32. */

@@ -3,7 +3,9 @@ cfg box_iou_loss = none / giou / diou and (--cls) cfg cls_quality = qfl / vfl, a
 the stream right before the first and after the last launch of the entry point), so the figure is the kernels and the gaps between them,
 not the Python around them; the median of --calls calls after --warmup, min and max next to it.  One JSON line (--json PATH also writes it).
 --kinds none restricts the set (a tree from before the IoU loss has only that one); --cls qfl,vfl adds those variants (each with
-box_iou_loss none; "qfl+giou" names a box IoU loss next to it)."""
+box_iou_loss none; "qfl+giou" names a box IoU loss next to it); --matcher iou,atss times every variant under both anchor assignments
+(cfg matcher; the atss rows are named "atss", "atss+giou", "atss+qfl+giou", ... and are the sum of the two bracketed entry points,
+zsg_match_atss and zsg_loss_fwd_bwd_m)."""
 import argparse
 import json
 import os
@@ -22,10 +24,12 @@ ap.add_argument("--calls", type=int, default=60)
 ap.add_argument("--warmup", type=int, default=10)
 ap.add_argument("--kinds", default="none,giou,diou")
 ap.add_argument("--cls", default="", help="comma list of cls_quality variants timed next to --kinds: qfl, vfl, qfl+giou, ...")
+ap.add_argument("--matcher", default="iou", help="comma list of cfg matcher values every variant is timed under: iou, atss")
 ap.add_argument("--json", default=None)
 args = ap.parse_args()
 B, A = args.batch, 17460
-kinds = args.kinds.split(",") + [k for k in args.cls.split(",") if k]
+base = args.kinds.split(",") + [k for k in args.cls.split(",") if k]
+kinds = [k if m == "iou" else (m if k == "none" else m + "+" + k) for m in args.matcher.split(",") for k in base]
 
 gen = torch.Generator().manual_seed(7)
 out5 = torch.cat([torch.randn(B, A, 4, generator=gen) * 0.3, torch.randn(B, A, 1, generator=gen) * 1.5 - 3.0], dim=2).cuda().requires_grad_()
@@ -34,10 +38,16 @@ out = dict(att_bbx_out=out5, feat_sizes=torch.tensor(O.feat_sizes_for(300, 300))
 inp = {"annot": bt["annot"].cuda()}
 lfs = {}
 for k in kinds:
-    if k.split("+")[0] in ("qfl", "vfl"):
-        c = config.get_cfg(cls_quality=k.split("+")[0], box_iou_loss=(k.split("+") + ["none"])[1])
-    else:
-        c = config.get_cfg() if k == "none" else config.get_cfg(box_iou_loss=k)
+    parts = k.split("+")
+    kw = {}
+    if parts[0] == "atss":
+        kw["matcher"] = parts.pop(0)
+    for p in parts:
+        if p in ("qfl", "vfl"):
+            kw["cls_quality"] = p
+        elif p != "none":
+            kw["box_iou_loss"] = p
+    c = config.get_cfg(**kw)
     lfs[k] = loss.get_default_loss(*config.ratios_scales(c), c)
 
 
@@ -48,9 +58,9 @@ def one_call(lf):
     lf(out, inp)
     n = L.lib.zsg_prof_collect(ents, 16)             # (waits for the recorded events)
     got = {ents[i].name.decode(): (ents[i].launches, ents[i].ms) for i in range(n)}
-    (name, (calls, ms)), = [(k, v) for k, v in got.items() if k.startswith("loss_fwd_bwd")]
-    assert calls == 1, got
-    return ms
+    mine = [v for k, v in got.items() if k.startswith(("loss_fwd_bwd", "match_atss"))]
+    assert len(mine) == (2 if lf.matcher == "atss" else 1) and all(calls == 1 for calls, _ in mine), got
+    return sum(ms for _, ms in mine)
 
 
 ms = {k: [] for k in kinds}
@@ -64,8 +74,11 @@ try:
 finally:
     L.lib.zsg_prof_enable(0)
 npos = lfs[kinds[0]].npos.cpu().tolist()
+npos_atss = [lf.npos.cpu().tolist() for k, lf in lfs.items() if lf.matcher == "atss"][:1]
 res = {"what": "ZSGLoss call, HIP events around the entry point's launches, median of %d calls" % args.calls, "B": B, "A": A,
        "positives_per_sample_min_max": [min(npos), max(npos)], "stamp": L.lib.zsg_source_stamp().decode()}
+if npos_atss:
+    res["positives_per_sample_min_max_atss"] = [min(npos_atss[0]), max(npos_atss[0])]
 for k in kinds:
     v = sorted(ms[k])
     res[k + "_us"] = round(1e3 * v[len(v) // 2], 2)

@@ -150,6 +150,9 @@ SIGNATURES = {
     "zsg_loss_fwd_bwd": (I32, [P, P, P, I32, I32, F32, F32, F32, F32, I32, F32, P, P, P, P, P, SZ, P]),
     "zsg_loss_fwd_bwd_iou": (I32, [P, P, P, I32, I32, F32, F32, F32, F32, I32, F32, I32, F32, P, P, P, P, P, SZ, P]),
     "zsg_loss_fwd_bwd_q": (I32, [P, P, P, I32, I32, F32, F32, F32, F32, I32, F32, I32, F32, I32, P, P, P, P, P, SZ, P]),
+    "zsg_loss_fwd_bwd_m": (I32, [P, P, P, I32, I32, F32, F32, F32, F32, I32, F32, I32, F32, I32, P, P, P, P, P, P, SZ, P]),
+    "zsg_match_atss_workspace_bytes": (SZ, [I32, I32]),
+    "zsg_match_atss": (I32, [P, P, P, I32, I32, I32, I32, P, P, P, P, SZ, P]),
     "zsg_eval_workspace_bytes": (SZ, [I32]),
     "zsg_eval": (I32, [P, P, P, P, I32, I32, F32, P, P, P, P, P, P, P]),
     "zsg_eval_topk_workspace_bytes": (SZ, [I32, I32, I32, I32]),

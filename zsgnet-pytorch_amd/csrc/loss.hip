@@ -699,13 +699,17 @@ struct QSums {
     double box, cls, iou, q;
     int cnt;
 };
-// one anchor of pass 1: the loop body of loss_stats_iou_kernel / loss_part_iou_kernel with q and the exchanged classification term
+// one anchor of pass 1: the loop body of loss_stats_iou_kernel / loss_part_iou_kernel with q and the exchanged classification term.
+// MASK = false: the reference's fixed rule for the positives, the expression of the kernels above.  MASK = true (zsg_loss_fwd_bwd_m): pm,
+// the sample's row of a positives mask made beforehand (zsg_match_atss), decides; use_multi and thr are not consulted.
+template <bool MASK>
 __device__ __forceinline__ void q_pass1_anchor(QSums& s, const float* __restrict__ o, const float* __restrict__ anchors, const f32x4 bx,
-                                               int a, int best, float alpha, float gamma, float thr, int flags, int iou_kind, int cls_kind) {
+                                               int a, int best, float alpha, float gamma, float thr, int flags, int iou_kind, int cls_kind,
+                                               const uint8_t* __restrict__ pm) {
     const bool use_focal = flags & 1, use_multi = flags & 2, use_softmax = flags & 4;
     const f32x4 an = *(const f32x4*)(anchors + 4 * a);
-    const float v = iou_exact(bx, an);
-    const bool pos = (use_multi && v > thr) || a == best;
+    const float v = iou_exact(bx, an);                   // (unused with a mask)
+    const bool pos = MASK ? (pm[a] != 0 || a == best) : ((use_multi && v > thr) || a == best);
     const float t = pos ? 1.f : 0.f;
     s.cnt += pos;
     float d[4];
@@ -734,11 +738,17 @@ __device__ __forceinline__ void q_pass1_anchor(QSums& s, const float* __restrict
     }
 }
 
-// pass 1, one block per sample (loss_stats_iou_kernel + q)
+// pass 1, one block per sample (loss_stats_iou_kernel + q).  The three kernels end in a parameter pack that is either empty
+// (zsg_loss_fwd_bwd_q: the kernel's arguments and its code are what they were without the pack) or one const uint8_t* pos_mask [B][A]
+// (zsg_loss_fwd_bwd_m).
+__device__ __forceinline__ const uint8_t* mask_arg() { return nullptr; }
+__device__ __forceinline__ const uint8_t* mask_arg(const uint8_t* p) { return p; }
+template <typename... M>
 __global__ __launch_bounds__(LS_THREADS) void loss_stats_q_kernel(const float* __restrict__ out5, const float* __restrict__ annot,
                                                                   const float* __restrict__ anchors, int A, float alpha, float gamma,
                                                                   float thr, int flags, int iou_kind, int cls_kind,
-                                                                  LossWsQ* __restrict__ ws) {
+                                                                  LossWsQ* __restrict__ ws, M... pos_mask) {
+    constexpr bool MASK = sizeof...(M) != 0;
     __shared__ ArgMax sm_a[LS_THREADS / 64];
     __shared__ double sm_d[LS_THREADS / 64];
     const int b = blockIdx.x;
@@ -766,8 +776,10 @@ __global__ __launch_bounds__(LS_THREADS) void loss_stats_q_kernel(const float* _
         row_lse = (double)t.v + log(se);
     }
 
+    const uint8_t* pm = MASK ? mask_arg(pos_mask...) + (size_t)b * A : nullptr;
     QSums s = {0, 0, 0, 0, 0};
-    for (int a = threadIdx.x; a < A; a += LS_THREADS) q_pass1_anchor(s, o, anchors, bx, a, best, alpha, gamma, thr, flags, iou_kind, cls_kind);
+    for (int a = threadIdx.x; a < A; a += LS_THREADS)
+        q_pass1_anchor<MASK>(s, o, anchors, bx, a, best, alpha, gamma, thr, flags, iou_kind, cls_kind, pm);
     const double box = block_sum_d(s.box, sm_d);
     double cls = block_sum_d(s.cls, sm_d);
     const double iou = block_sum_d(s.iou, sm_d);
@@ -782,10 +794,12 @@ __global__ __launch_bounds__(LS_THREADS) void loss_stats_q_kernel(const float* _
 }
 
 // chunked pass 1b (loss_part_iou_kernel + q); pass 1a is loss_argmax_kernel itself
+template <typename... M>
 __global__ __launch_bounds__(256) void loss_part_q_kernel(const float* __restrict__ out5, const float* __restrict__ annot,
                                                           const float* __restrict__ anchors, int A, float alpha, float gamma, float thr,
                                                           int flags, int iou_kind, int cls_kind, const ArgMax* __restrict__ amax,
-                                                          LossPartQ* __restrict__ parts) {
+                                                          LossPartQ* __restrict__ parts, M... pos_mask) {
+    constexpr bool MASK = sizeof...(M) != 0;
     __shared__ double sm_d[4];
     const int b = blockIdx.y, per = (A + LS_CHUNKS - 1) / LS_CHUNKS;
     const int a0 = blockIdx.x * per, a1 = min(A, a0 + per);
@@ -794,8 +808,10 @@ __global__ __launch_bounds__(256) void loss_part_q_kernel(const float* __restric
     ArgMax m = amax[b * LS_CHUNKS];
     for (int c = 1; c < LS_CHUNKS; ++c) m = argmax_merge(m, amax[b * LS_CHUNKS + c]);
     const int best = m.i == 0x7fffffff ? 0 : m.i;
+    const uint8_t* pm = MASK ? mask_arg(pos_mask...) + (size_t)b * A : nullptr;
     QSums s = {0, 0, 0, 0, 0};
-    for (int a = a0 + threadIdx.x; a < a1; a += 256) q_pass1_anchor(s, o, anchors, bx, a, best, alpha, gamma, thr, flags, iou_kind, cls_kind);
+    for (int a = a0 + threadIdx.x; a < a1; a += 256)
+        q_pass1_anchor<MASK>(s, o, anchors, bx, a, best, alpha, gamma, thr, flags, iou_kind, cls_kind, pm);
     const double box = block_sum_d(s.box, sm_d);
     const double cls = block_sum_d(s.cls, sm_d);
     const double iou = block_sum_d(s.iou, sm_d);
@@ -810,13 +826,15 @@ __global__ __launch_bounds__(256) void loss_part_q_kernel(const float* __restric
 
 // pass 2 (loss_grad_iou_kernel + q): losses[5] = (loss, cls_ls, box_ls, iou_ls, pos_iou); a NaN in any of the three loss parts gives
 // the constants, iou_ls = pos_iou = 0 and an exactly zero gradient (also at the anchor that holds the NaN).
+template <typename... M>
 __global__ __launch_bounds__(256) void loss_grad_q_kernel(const float* __restrict__ out5, const float* __restrict__ annot,
                                                           const float* __restrict__ anchors, int B, int A, float alpha, float gamma,
                                                           float lamb, float thr, int flags, float grad_scale, int iou_kind, float lamb_iou,
                                                           int cls_kind, const LossWsQ* __restrict__ ws_in,
                                                           const LossPartQ* __restrict__ parts, float* __restrict__ losses,
                                                           float* __restrict__ grad5, int* __restrict__ match_idx,
-                                                          int* __restrict__ npos_out) {
+                                                          int* __restrict__ npos_out, M... pos_mask) {
+    constexpr bool MASK = sizeof...(M) != 0;
     const bool use_focal = flags & 1, use_multi = flags & 2, use_softmax = flags & 4;
     const int b = blockIdx.y;
     __shared__ LossWsQ ws[LS_MAX_B];
@@ -874,10 +892,11 @@ __global__ __launch_bounds__(256) void loss_grad_q_kernel(const float* __restric
     const float kbox = bad ? 0.f : grad_scale * lamb / ((float)B * (float)me.npos);
     const float kiou = bad ? 0.f : grad_scale * lamb_iou / ((float)B * (float)me.npos);
     const float kcls = bad ? 0.f : grad_scale / (float)npos_all;
+    const uint8_t* pm = MASK ? mask_arg(pos_mask...) + (size_t)b * A : nullptr;
     for (int a = blockIdx.x * blockDim.x + threadIdx.x; a < A; a += gridDim.x * blockDim.x) {
         const f32x4 an = *(const f32x4*)(anchors + 4 * a);
-        const float v = iou_exact(bx, an);
-        const bool pos = (use_multi && v > thr) || a == me.best;
+        const float v = iou_exact(bx, an);               // (unused with a mask)
+        const bool pos = MASK ? (pm[a] != 0 || a == me.best) : ((use_multi && v > thr) || a == me.best);
         const float t = pos ? 1.f : 0.f;
         float d[4];
         box_terms(o + a * 5, an, bx, d);
@@ -913,6 +932,30 @@ __global__ __launch_bounds__(256) void loss_grad_q_kernel(const float* __restric
     }
 }
 
+// the launches of zsg_loss_fwd_bwd_q (no mask argument) and zsg_loss_fwd_bwd_m (M = const uint8_t*) after their argument checks
+template <typename... M>
+static void loss_q_launch(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, float alpha, float gamma,
+                          float lamb_reg, float match_thr, int32_t flags, float grad_scale, int32_t iou_kind, float lamb_iou,
+                          int32_t cls_kind, float* losses, float* grad5, int32_t* match_idx, int32_t* npos, void* ws, hipStream_t st,
+                          M... pos_mask) {
+    LossWsQ* rec = (LossWsQ*)ws;
+    LossPartQ* parts = (LossPartQ*)(rec + B);
+    ArgMax* amax = (ArgMax*)(parts + (size_t)B * LS_CHUNKS);
+    const bool chunked = !(flags & 4) && A >= 4 * LS_CHUNKS;      // as zsg_loss_fwd_bwd
+    if (chunked) {
+        ZSG_LAUNCH(loss_argmax_kernel, dim3(LS_CHUNKS, B), dim3(256), 0, st, annot, anchors, A, amax);
+        ZSG_LAUNCH(loss_part_q_kernel<M...>, dim3(LS_CHUNKS, B), dim3(256), 0, st, out5, annot, anchors, A, alpha, gamma, match_thr, flags,
+                           iou_kind, cls_kind, (const ArgMax*)amax, parts, pos_mask...);
+    } else {
+        ZSG_LAUNCH(loss_stats_q_kernel<M...>, dim3(B), dim3(LS_THREADS), 0, st, out5, annot, anchors, A, alpha, gamma, match_thr, flags,
+                           iou_kind, cls_kind, rec, pos_mask...);
+    }
+    const int chunks = min(32, cdiv(A, 256));
+    ZSG_LAUNCH(loss_grad_q_kernel<M...>, dim3(chunks, B), dim3(256), 0, st, out5, annot, anchors, B, A, alpha, gamma, lamb_reg, match_thr,
+                       flags, grad_scale, iou_kind, lamb_iou, cls_kind, (const LossWsQ*)rec,
+                       chunked ? (const LossPartQ*)parts : (const LossPartQ*)nullptr, losses, grad5, match_idx, npos, pos_mask...);
+}
+
 extern "C" int zsg_loss_fwd_bwd_q(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, float alpha,
                                   float gamma, float lamb_reg, float match_thr, int32_t flags, float grad_scale, int32_t iou_kind,
                                   float lamb_iou, int32_t cls_kind, float* losses, float* grad5, int32_t* match_idx, int32_t* npos,
@@ -928,23 +971,185 @@ extern "C" int zsg_loss_fwd_bwd_q(const float* out5, const float* annot, const f
     hipStream_t st = (hipStream_t)stream;
     ZSG_PROF("loss_fwd_bwd_q", st, 0, (double)B * A * 5 * 4 * 3);
     ZSG_REQUIRE(B <= LS_MAX_B, "loss_fwd_bwd_q: B=%d exceeds %d", B, LS_MAX_B);
-    LossWsQ* rec = (LossWsQ*)ws;
-    LossPartQ* parts = (LossPartQ*)(rec + B);
-    ArgMax* amax = (ArgMax*)(parts + (size_t)B * LS_CHUNKS);
-    const bool chunked = !(flags & 4) && A >= 4 * LS_CHUNKS;      // as zsg_loss_fwd_bwd
-    if (chunked) {
-        ZSG_LAUNCH(loss_argmax_kernel, dim3(LS_CHUNKS, B), dim3(256), 0, st, annot, anchors, A, amax);
-        ZSG_LAUNCH(loss_part_q_kernel, dim3(LS_CHUNKS, B), dim3(256), 0, st, out5, annot, anchors, A, alpha, gamma, match_thr, flags,
-                           iou_kind, cls_kind, (const ArgMax*)amax, parts);
-    } else {
-        ZSG_LAUNCH(loss_stats_q_kernel, dim3(B), dim3(LS_THREADS), 0, st, out5, annot, anchors, A, alpha, gamma, match_thr, flags,
-                           iou_kind, cls_kind, rec);
-    }
-    const int chunks = min(32, cdiv(A, 256));
-    ZSG_LAUNCH(loss_grad_q_kernel, dim3(chunks, B), dim3(256), 0, st, out5, annot, anchors, B, A, alpha, gamma, lamb_reg, match_thr,
-                       flags, grad_scale, iou_kind, lamb_iou, cls_kind, (const LossWsQ*)rec,
-                       chunked ? (const LossPartQ*)parts : (const LossPartQ*)nullptr, losses, grad5, match_idx, npos);
+    loss_q_launch(out5, annot, anchors, B, A, alpha, gamma, lamb_reg, match_thr, flags, grad_scale, iou_kind, lamb_iou, cls_kind, losses,
+                  grad5, match_idx, npos, ws, st);
     ZSG_CHECK_LAUNCH("loss_fwd_bwd_q");
+    return 0;
+}
+
+// zsg_loss_fwd_bwd_q on a positives mask made beforehand (zsg_match_atss): the instantiations of its three kernels that take the mask, the same
+// launches on both paths.  An anchor is positive where pos_mask[b][a] != 0 or it is the sample's arg-max IoU anchor; flags bit1
+// (use_multi) and match_thr are not consulted.  The sums, the NaN rule, grad_scale, losses[5], match_idx and npos are those of _q.
+extern "C" int zsg_loss_fwd_bwd_m(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, float alpha,
+                                  float gamma, float lamb_reg, float match_thr, int32_t flags, float grad_scale, int32_t iou_kind,
+                                  float lamb_iou, int32_t cls_kind, const uint8_t* pos_mask, float* losses, float* grad5,
+                                  int32_t* match_idx, int32_t* npos, void* ws, size_t ws_bytes, void* stream) {
+    ZSG_REQUIRE(out5 && annot && anchors && pos_mask && losses && match_idx && ws && B > 0 && A > 0, "loss_fwd_bwd_m: bad argument");
+    ZSG_REQUIRE(!((flags & 4) && (flags & 2)), "loss_fwd_bwd_m: use_softmax requires use_multi == False (loss.py:107)");
+    ZSG_REQUIRE(iou_kind >= 0 && iou_kind <= 2, "loss_fwd_bwd_m: iou_kind=%d is none of 0 (none), 1 (giou), 2 (diou)", iou_kind);
+    ZSG_REQUIRE(lamb_iou >= 0.f, "loss_fwd_bwd_m: lamb_iou must not be negative");
+    ZSG_REQUIRE(cls_kind >= 0 && cls_kind <= 2, "loss_fwd_bwd_m: cls_kind=%d is none of 0 (none), 1 (qfl), 2 (vfl)", cls_kind);
+    ZSG_REQUIRE(!cls_kind || ((flags & 1) && !(flags & 4)), "loss_fwd_bwd_m: cls_kind=%d needs use_focal and no use_softmax", cls_kind);
+    ZSG_REQUIRE(!cls_kind || gamma >= 1.f, "loss_fwd_bwd_m: cls_kind=%d needs gamma >= 1 (the derivative is singular at sigmoid = q below)", cls_kind);
+    if (ws_bytes < zsg_loss_workspace_bytes(B, A)) ZSG_FAIL(-2, "loss_fwd_bwd_m: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("loss_fwd_bwd_m", st, 0, (double)B * A * 5 * 4 * 3);
+    ZSG_REQUIRE(B <= LS_MAX_B, "loss_fwd_bwd_m: B=%d exceeds %d", B, LS_MAX_B);
+    loss_q_launch(out5, annot, anchors, B, A, alpha, gamma, lamb_reg, match_thr, flags, grad_scale, iou_kind, lamb_iou, cls_kind, losses,
+                  grad5, match_idx, npos, ws, st, pos_mask);
+    ZSG_CHECK_LAUNCH("loss_fwd_bwd_m");
+    return 0;
+}
+
+// ---- ATSS anchor assignment (zsg_match_atss): the positives mask that zsg_loss_fwd_bwd_m consumes ------------------------------------
+// Adaptive Training Sample Selection (Zhang et al. 2020) for one annotation g per sample, over the L pyramid levels of the anchor list
+// (level l owns the indices [level_off[l], level_off[l + 1])); every step fp32 in this order (the file is compiled without contraction):
+//   acy = (a.y1 + a.y2) / 2, acx likewise; gcy, gcx likewise;  d(a) = (acy - gcy)(acy - gcy) + (acx - gcx)(acx - gcx)
+//   candidates C: per level the min(topk, n_l) anchors with the smallest key (d, index), lexicographic (the n anchors of a cell share
+//                 their centre: the lower index wins), ordered by level, then by rank
+//   v(a) = iou_exact(g, a);  t = mean(v over C) + std(v over C), fp64 from the fp32 values, summed in the order of C, the unbiased
+//                 std (0 for one candidate): mean = sum v / |C|,  std = sqrt(sum (v - mean)^2 / (|C| - 1))
+//   positive: (a in C and (double)v(a) >= t and g.y1 < acy < g.y2 and g.x1 < acx < g.x2)  or  a == the arg-max IoU anchor (lowest index)
+// Two launches, no atomics, fixed orders: the same bits on every run.
+//   atss_select_kernel, (L, B) blocks: the arg-max IoU of the level, then up to topk block-wide arg-min passes over the level, each taking
+//     the smallest key greater than the winner before it (no marks), and records (index, v) per slot; unused slots get index -1.
+//   atss_mask_kernel, (ranges of ATSS_TILE anchors, B) blocks: the <= 128 records of the sample into LDS, t by one thread, the range's
+//     flags in LDS (one thread per candidate tests and sets its own), then EVERY byte of the range of pos_mask is written, 0 or 1.
+#define ATSS_MAX_L 8
+#define ATSS_MAX_K 16
+#define ATSS_TILE 1024
+struct AtssCand {
+    int idx;
+    float v;
+};
+struct AtssLevels {      // the level table, by value: level_off is a host array, checked before anything is launched
+    int off[ATSS_MAX_L + 1];
+};
+
+extern "C" size_t zsg_match_atss_workspace_bytes(int32_t B, int32_t L) {   // per (sample, level): ATSS_MAX_K slot records + the level's arg-max
+    return (size_t)B * L * (ATSS_MAX_K * sizeof(AtssCand) + sizeof(ArgMax));
+}
+
+__global__ __launch_bounds__(LS_THREADS) void atss_select_kernel(const float* __restrict__ annot, const float* __restrict__ anchors,
+                                                                 AtssLevels lv, int topk, AtssCand* __restrict__ cand,
+                                                                 ArgMax* __restrict__ lmax) {
+    __shared__ ArgMax sm_a[LS_THREADS / 64];
+    const int l = blockIdx.x, b = blockIdx.y, L = gridDim.x;
+    const int lo = lv.off[l], hi = lv.off[l + 1];
+    const f32x4 bx = *(const f32x4*)(annot + 4 * b);
+    const float gcy = (bx[0] + bx[2]) / 2.f, gcx = (bx[1] + bx[3]) / 2.f;
+
+    ArgMax m = {-INFINITY, 0x7fffffff};
+    for (int a = lo + threadIdx.x; a < hi; a += LS_THREADS) {
+        const float v = iou_exact(bx, *(const f32x4*)(anchors + 4 * a));
+        if (v > m.v) { m.v = v; m.i = a; }
+    }
+    m = block_argmax(m, sm_a);
+    if (threadIdx.x == 0) lmax[b * L + l] = m;
+
+    AtssCand* out = cand + ((size_t)b * L + l) * ATSS_MAX_K;
+    float pd = -INFINITY;                                // the winner before: every key (d, a) is greater than (-inf, -1)
+    int pi = -1;
+    bool more = true;
+    for (int r = 0; r < ATSS_MAX_K; ++r) {
+        AtssCand rec = {-1, 0.f};
+        if (more && r < topk) {                          // (block-uniform)
+            ArgMax w = {-INFINITY, 0x7fffffff};          // the arg-max of -d with the lowest index = the lexicographic minimum of (d, a)
+            for (int a = lo + threadIdx.x; a < hi; a += LS_THREADS) {
+                const f32x4 an = *(const f32x4*)(anchors + 4 * a);
+                const float acy = (an[0] + an[2]) / 2.f, acx = (an[1] + an[3]) / 2.f;
+                const float dy = acy - gcy, dx = acx - gcx;
+                const float d = dy * dy + dx * dx;
+                if ((d > pd || (d == pd && a > pi)) && -d > w.v) { w.v = -d; w.i = a; }
+            }
+            w = block_argmax(w, sm_a);
+            more = w.i != 0x7fffffff;                    // the level is used up (n_l < topk)
+            if (more) {
+                pd = -w.v;
+                pi = w.i;
+                rec.idx = w.i;
+                rec.v = iou_exact(bx, *(const f32x4*)(anchors + 4 * w.i));
+            }
+        }
+        if (threadIdx.x == 0) out[r] = rec;
+    }
+}
+
+__global__ __launch_bounds__(256) void atss_mask_kernel(const float* __restrict__ annot, const float* __restrict__ anchors, int A, int L,
+                                                        const AtssCand* __restrict__ cand, const ArgMax* __restrict__ lmax,
+                                                        uint8_t* __restrict__ pos_mask, double* __restrict__ thr_out,
+                                                        int* __restrict__ cand_out) {
+    __shared__ AtssCand sc[ATSS_MAX_L * ATSS_MAX_K];
+    __shared__ uint8_t flag[ATSS_TILE];
+    __shared__ double s_thr;
+    __shared__ int s_best;
+    const int b = blockIdx.y, t = threadIdx.x;
+    const int a0 = blockIdx.x * ATSS_TILE, a1 = min(A, a0 + ATSS_TILE);
+    const int nrec = L * ATSS_MAX_K;
+    if (t < nrec) sc[t] = cand[(size_t)b * nrec + t];
+    for (int i = t; i < ATSS_TILE; i += 256) flag[i] = 0;
+    __syncthreads();
+    if (t == 0) {
+        int n = 0;
+        double sum = 0;
+        for (int k = 0; k < nrec; ++k)
+            if (sc[k].idx >= 0) { sum += (double)sc[k].v; ++n; }
+        const double mean = sum / (double)n;
+        double ss = 0;
+        for (int k = 0; k < nrec; ++k)
+            if (sc[k].idx >= 0) { const double e = (double)sc[k].v - mean; ss += e * e; }
+        s_thr = mean + (n > 1 ? sqrt(ss / (double)(n - 1)) : 0.0);
+        ArgMax m = lmax[b * L];
+        for (int l = 1; l < L; ++l) m = argmax_merge(m, lmax[b * L + l]);
+        s_best = m.i == 0x7fffffff ? 0 : m.i;            // as the loss kernels
+        if (blockIdx.x == 0) {
+            if (thr_out) thr_out[b] = s_thr;
+            if (cand_out) {                              // C in its order, -1 behind it
+                int c = 0;
+                for (int k = 0; k < nrec; ++k)
+                    if (sc[k].idx >= 0) cand_out[b * (ATSS_MAX_L * ATSS_MAX_K) + c++] = sc[k].idx;
+                for (; c < ATSS_MAX_L * ATSS_MAX_K; ++c) cand_out[b * (ATSS_MAX_L * ATSS_MAX_K) + c] = -1;
+            }
+        }
+    }
+    __syncthreads();
+    if (t < nrec) {
+        const int a = sc[t].idx;
+        if (a >= a0 && a < a1) {
+            const f32x4 bx = *(const f32x4*)(annot + 4 * b);
+            const f32x4 an = *(const f32x4*)(anchors + 4 * a);
+            const float acy = (an[0] + an[2]) / 2.f, acx = (an[1] + an[3]) / 2.f;
+            const bool inside = bx[0] < acy && acy < bx[2] && bx[1] < acx && acx < bx[3];
+            if (inside && (double)sc[t].v >= s_thr) flag[a - a0] = 1;
+        }
+    }
+    if (t == 0 && s_best >= a0 && s_best < a1) flag[s_best - a0] = 1;     // (may meet a candidate's own write of the same 1)
+    __syncthreads();
+    for (int i = t; a0 + i < a1; i += 256) pos_mask[(size_t)b * A + a0 + i] = flag[i];
+}
+
+extern "C" int zsg_match_atss(const float* annot, const float* anchors, const int32_t* level_off, int32_t L, int32_t B, int32_t A,
+                              int32_t topk, uint8_t* pos_mask, double* thr, int32_t* cand, void* ws, size_t ws_bytes, void* stream) {
+    ZSG_REQUIRE(annot && anchors && level_off && pos_mask && ws && B > 0 && A > 0, "match_atss: bad argument");
+    ZSG_REQUIRE(L >= 1 && L <= ATSS_MAX_L, "match_atss: L=%d levels, expected 1..%d", L, ATSS_MAX_L);
+    ZSG_REQUIRE(topk >= 1 && topk <= ATSS_MAX_K, "match_atss: topk=%d, expected 1..%d", topk, ATSS_MAX_K);
+    ZSG_REQUIRE(B <= LS_MAX_B, "match_atss: B=%d exceeds %d", B, LS_MAX_B);
+    AtssLevels lv;
+    ZSG_REQUIRE(level_off[0] == 0, "match_atss: level_off[0]=%d, expected 0", level_off[0]);
+    for (int l = 0; l <= ATSS_MAX_L; ++l) lv.off[l] = level_off[l < L ? l : L];
+    for (int l = 0; l < L; ++l)
+        ZSG_REQUIRE(level_off[l + 1] > level_off[l], "match_atss: level_off[%d]=%d is not above level_off[%d]=%d", l + 1, level_off[l + 1], l,
+                    level_off[l]);
+    ZSG_REQUIRE(level_off[L] == A, "match_atss: level_off[%d]=%d, expected A=%d", L, level_off[L], A);
+    if (ws_bytes < zsg_match_atss_workspace_bytes(B, L)) ZSG_FAIL(-2, "match_atss: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("match_atss", st, 0, (double)B * A * 16 * (topk + 1));
+    AtssCand* recs = (AtssCand*)ws;
+    ArgMax* lmax = (ArgMax*)(recs + (size_t)B * L * ATSS_MAX_K);
+    ZSG_LAUNCH(atss_select_kernel, dim3(L, B), dim3(LS_THREADS), 0, st, annot, anchors, lv, topk, recs, lmax);
+    ZSG_LAUNCH(atss_mask_kernel, dim3(cdiv(A, ATSS_TILE), B), dim3(256), 0, st, annot, anchors, A, L, (const AtssCand*)recs,
+                       (const ArgMax*)lmax, pos_mask, thr, cand);
+    ZSG_CHECK_LAUNCH("match_atss");
     return 0;
 }
 

@@ -52,7 +52,8 @@ class _LossFn(torch.autograd.Function):
         dev = out5.device
         kind = mod.iou_kind                 # 0: the reference's criterion; 1 / 2: + lamb_iou * GIoU / DIoU loss (zsg_loss_fwd_bwd_iou)
         cls_kind = mod.cls_kind             # 0: the reference's classification term; 1 / 2: QFL / VFL on the IoU target (zsg_loss_fwd_bwd_q)
-        losses = torch.empty(5 if cls_kind else (4 if kind else 3), device=dev)
+        atss = mod.matcher == "atss"        # the positives come from zsg_match_atss's mask (zsg_loss_fwd_bwd_m) instead of the fixed IoU rule
+        losses = torch.empty(5 if (cls_kind or atss) else (4 if kind else 3), device=dev)
         # Where d(loss)/d(out5) goes: straight into the incoming-gradient buffer of the network plan that produced out5 (ZSGNet.forward
         # attaches it), already scaled by 1 / world under data parallelism (the reducer SUMs) — the backward then needs no launch of
         # its own when the upstream gradient is the constant 1.  Only the FIRST loss applied to an output may take the buffer.
@@ -74,7 +75,22 @@ class _LossFn(torch.autograd.Function):
         wsb = lib.zsg_loss_workspace_bytes(B, A)
         ws = torch.empty((wsb + 7) // 8, dtype=torch.float64, device=dev)
         flags = (1 if mod.use_focal else 0) | (2 if mod.use_multi else 0) | (4 if mod.use_softmax else 0)
-        if cls_kind:
+        if atss:
+            assert mod.level_off is not None and int(mod.level_off[-1]) == A, "matcher='atss' needs the level table of these anchors (set_anchors)"
+            L = mod.level_off.numel() - 1
+            mod.pos_mask = torch.empty((B, A), dtype=torch.uint8, device=dev)
+            mod.atss_thr = torch.empty(B, dtype=torch.float64, device=dev)
+            mwsb = lib.zsg_match_atss_workspace_bytes(B, L)
+            mws = torch.empty((mwsb + 7) // 8, dtype=torch.float64, device=dev)
+            check(lib.zsg_match_atss(annot.data_ptr(), mod.anchs.data_ptr(), mod.level_off.data_ptr(), L, B, A, int(mod.atss_topk),
+                                     mod.pos_mask.data_ptr(), mod.atss_thr.data_ptr(), None, mws.data_ptr(), mwsb, stream_ptr()),
+                  "zsg_match_atss")
+            check(lib.zsg_loss_fwd_bwd_m(out5.data_ptr(), annot.data_ptr(), mod.anchs.data_ptr(), B, A, mod.alpha, float(mod.gamma),
+                                         float(mod.lamb_reg), float(mod.cfg["matching_threshold"]), flags, scale, kind,
+                                         float(mod.lamb_iou), cls_kind, mod.pos_mask.data_ptr(), losses.data_ptr(), grad5.data_ptr(),
+                                         mod.match_idx.data_ptr(), mod.npos.data_ptr(), ws.data_ptr(), wsb, stream_ptr()),
+                  "zsg_loss_fwd_bwd_m")
+        elif cls_kind:
             check(lib.zsg_loss_fwd_bwd_q(out5.data_ptr(), annot.data_ptr(), mod.anchs.data_ptr(), B, A, mod.alpha, float(mod.gamma),
                                          float(mod.lamb_reg), float(mod.cfg["matching_threshold"]), flags, scale, kind,
                                          float(mod.lamb_iou), cls_kind, losses.data_ptr(), grad5.data_ptr(), mod.match_idx.data_ptr(),
@@ -113,10 +129,14 @@ class ZSGLoss(nn.Module):
     """Criterion to be minimised (reference loss.py:11-143).  forward(out, inp) -> {'loss','cls_ls','box_ls'}.
     cfg box_iou_loss = "giou" / "diou" adds lamb_iou * (that IoU loss of the decoded boxes of the positive anchors) and the key 'iou_ls'.
     cfg cls_quality = "qfl" / "vfl" trains the att logit towards the IoU of the anchor's decoded box with the annotation (Quality Focal /
-    Varifocal loss in the place of the focal term) and adds the key 'pos_iou', the mean of that target over the positives (no gradient)."""
+    Varifocal loss in the place of the focal term) and adds the key 'pos_iou', the mean of that target over the positives (no gradient).
+    cfg matcher = "atss" exchanges the fixed IoU rule for the positives with ATSS (zsg_match_atss, INTEGRATION.md "Anchor assignment");
+    the mask of the last call stays in .pos_mask [B, A] uint8 and the per-sample thresholds in .atss_thr [B] float64."""
 
     IOU_KINDS = {"none": 0, "giou": 1, "diou": 2}
     CLS_KINDS = {"none": 0, "qfl": 1, "vfl": 2}
+    MATCHERS = ("iou", "atss")
+    MAX_LEVELS, MAX_TOPK = 8, 16            # zsg_match_atss's limits
 
     def __init__(self, ratios, scales, cfg):
         super().__init__()
@@ -142,9 +162,32 @@ class ZSGLoss(nn.Module):
                 raise ValueError(f"cls_quality={quality!r} replaces the focal term: use_focal must be True")
             if not self.gamma >= 1:
                 raise ValueError(f"cls_quality={quality!r} needs gamma >= 1 (gamma={self.gamma}: the derivative is singular where sigmoid = target)")
+        self.matcher, self.atss_topk = cfg.get("matcher", "iou"), cfg.get("atss_topk", 9)
+        if self.matcher not in self.MATCHERS:
+            raise ValueError(f"matcher={self.matcher!r}: expected one of {sorted(self.MATCHERS)}")
+        if self.matcher == "atss":
+            if not self.use_multi:
+                raise ValueError("matcher='atss' selects several positives per sample: use_multi must be True")
+            if self.use_softmax:
+                raise ValueError("matcher='atss' is defined on the sigmoid branch: use_softmax must be False")
+            if not (isinstance(self.atss_topk, int) and 1 <= self.atss_topk <= self.MAX_TOPK):
+                raise ValueError(f"atss_topk={self.atss_topk!r}: expected an integer in 1 .. {self.MAX_TOPK}")
         self.loss_keys = ["loss", "cls_ls", "box_ls"] + (["iou_ls"] if self.iou_kind else []) + (["pos_iou"] if self.cls_kind else [])
         self.anchs = None
+        self.level_off = None                    # int32 [levels + 1] in host memory: the anchor index ranges of the pyramid levels (set_anchors)
         self.get_anchors = partial(create_anchors, ratios=self.ratios, scales=self.scales, flatten=True)
+
+    def set_anchors(self, anchs: torch.Tensor, feat_sizes) -> None:
+        """the anchors [A, 4] (device, fp32, create_anchors' flattened order) together with the level table of the pyramid they were
+        built from: feat_sizes = the (h, w) of every level, each level holding h * w * len(ratios) * len(scales) anchors"""
+        n = len(self.ratios) * len(self.scales)
+        sizes = [int(h) * int(w) * n for h, w in (feat_sizes.tolist() if torch.is_tensor(feat_sizes) else feat_sizes)]
+        if not 1 <= len(sizes) <= self.MAX_LEVELS:
+            raise ValueError(f"feat_sizes: {len(sizes)} pyramid levels, expected 1 .. {self.MAX_LEVELS}")
+        if min(sizes) < 1 or sum(sizes) != anchs.shape[0]:
+            raise ValueError(f"feat_sizes: the levels hold {sizes} = {sum(sizes)} anchors, the anchor list has {anchs.shape[0]}")
+        self.anchs = anchs
+        self.level_off = torch.tensor([0] + sizes, dtype=torch.int64).cumsum(0).to(torch.int32)
 
     def forward(self, out: Dict[str, torch.Tensor], inp: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         annot = inp["annot"].contiguous().float()
@@ -157,7 +200,7 @@ class ZSGLoss(nn.Module):
             fs = out["feat_sizes"]
             if "num_f_out" in out and out["num_f_out"].numel() > 1:
                 fs = fs[:int(out["num_f_out"][0])]
-            self.anchs = self.get_anchors(fs, device=out5.device)
+            self.set_anchors(self.get_anchors(fs, device=out5.device), fs)
         assert self.anchs.shape[0] == out5.shape[1], "anchor count does not match the network output"
         loss = _LossFn.apply(out5, self, annot)
         if loss.requires_grad:
