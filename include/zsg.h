@@ -191,6 +191,37 @@ int zsg_conv_wino_bnb_tail(const zsg_conv_desc* d, const float* src, const float
 int zsg_conv_wino_bnb(const zsg_conv_desc* d, const float* src, const float* U, float* out, const float* add_src,
                       const float* bn_x, const float* bn_mean, const float* bn_invstd, const uint8_t* bn_relu_mask,
                       float* partials, void* stream);
+/* ---------------------------------------------------------------------------------------------------------------
+ * Reduced-precision INFERENCE convolution (eval_dtype = "bf16"; csrc/igemm_bf16.hip): zsg_conv_igemm's descriptor, gather and epilogue
+ * on v_mfma_f32_32x32x16_bf16.  Same call sites as zsg_conv_igemm, forward only, behind a BatchNorm fold (zsg_bn_fold) — the
+ * reference has no counterpart (it evaluates in fp32, or under torch.autocast where the user asks for it).
+ * Numerical contract:
+ *   - activations (src, add_src, out) and bias are fp32 in memory; every src element is rounded to bf16 by the operand loader,
+ *     round-to-nearest-even, exactly as torch.Tensor.to(torch.bfloat16): +-0 and +-inf are preserved, NaN stays NaN, a finite value
+ *     above the largest bf16 becomes inf.  The weights are rounded once, by the same rule, by zsg_pack_w_bf16_batched.
+ *   - fp32 subnormals go through the hardware conversion (v_cvt_pk_bf16_f32) like every other value: they round to a bf16 subnormal or
+ *     to zero under the kernel's denormal mode; no test pins this down.
+ *   - every product of two bf16 values is exact in fp32; products are accumulated in fp32 by the MFMA in a fixed K order (tap-major,
+ *     channels ascending, 64 per K tile; the order inside one MFMA is the hardware's).  No split-K, no stream-K, no atomics: the same
+ *     input gives the same bits on every run and for every tile hint the order of K tiles is the same.
+ *   - epilogue in fp32, in zsg_conv_igemm's order: acc + bias[n] + add_src[.], then ReLU.  add_src may alias out.
+ * Supported: C % 4 == 0 (a half group at C % 8 == 4 is zero-filled), any N (N = 45 with out_ld = 45 takes the 4-byte epilogue), any row
+ * count, up to ZSG_MAX_SEG segments, strides, dilation, tap tables.  d->wC / wc0 / wt_ld are NOT read: the weight operand is the packed
+ * image uint16 [N][wR*wS][C8], C8 = roundup(d->C, 8).  tile_hint: 0 = the library heuristic (igemm's: fewest rounds of 256 blocks x
+ * tile area, smaller tiles favoured), else BM | BN << 8 out of 64x64, 128x64, 128x128.
+ * Not supported (-1, nothing launched, zsg_last_error names the argument): merge_x, epi_flags, tile_hint split_k > 1, stream-K bits
+ * (28-29) or variant bits 24-27.  There is no mask_src and no bn_partials operand.
+ * zsg_conv_igemm_bf16_supported: 1 when zsg_conv_igemm_bf16 accepts the descriptor (and its tile_hint), else 0 — the host asks at
+ * lowering time and keeps the fp32 launch instead of failing inside a forward. */
+int zsg_conv_igemm_bf16(const zsg_conv_desc* d, const float* src, const uint16_t* wt_packed, float* out, const float* bias,
+                        const float* add_src, void* stream);
+int32_t zsg_conv_igemm_bf16_supported(const zsg_conv_desc* d);
+/* Every bf16 weight image of an eval plan in ONE launch.  jobs: device array of { int64 src, dst (absolute device addresses); int32 N,
+ * T, wC, wc0, C, C8, blk0, pad }: fp32 OHWI source element (n, t, c) at n*T*wC + t*wC + wc0 + c (wc0 + C <= wC: a channel window, what
+ * head conv0's feature GEMM needs), destination uint16 [N][T][C8] with C8 = roundup(C, 8), 16-byte aligned, channels C..C8-1 zero;
+ * blk0 = running sum of ceil(N*T*C8/8 / 256); total_blocks = the final sum.  Rounding: the contract above. */
+int zsg_pack_w_bf16_batched(const void* jobs_dev, int32_t njobs, int32_t total_blocks, void* stream);
+
 /* elements of the transformed image of a C -> N 3x3 filter: [ceil(C/8)][16][roundup(N,64)][8] */
 int64_t zsg_wino_u_elems(int32_t C, int32_t N);
 /* U = G g G^T for every job in ONE launch.  jobs: device array of { int64 src, dst (absolute device addresses);

@@ -3,12 +3,22 @@
 images per batch; without --images the one-image-per-query path, as before.
 --topk K [--pre-nms N] [--queries Q]: the evaluator call alone, on a fixed [Q, 17460, 5] head output: eval_topk = 1 (zsg_eval only) against
 eval_topk = K in eval mode (zsg_eval + zsg_eval_topk), alternating; device events around groups of calls, the median per call of each, one
-JSON line (--json PATH also writes it to a file)."""
+JSON line (--json PATH also writes it to a file).
+--dtype fp32|bf16: cfg eval_dtype of the network (the forward paths; --topk times no network)."""
 import argparse
 import json
 import os
 import sys
 import time
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32", help="eval_dtype: operand precision of the eval plan's convolutions")
+ap.add_argument("--images", type=int, default=None, help="distinct images per batch (shared-image plan); default: one image per query")
+ap.add_argument("--queries", type=int, default=16, help="queries per batch")
+ap.add_argument("--topk", type=int, default=None, help="time the evaluator call with and without the top-k launch (K boxes per query)")
+ap.add_argument("--pre-nms", type=int, default=128, help="with --topk: candidates per query that enter the NMS")
+ap.add_argument("--json", default=None, help="with --topk: also write the result line to this file")
+args = ap.parse_args()          # (before the heavy imports: --help and a bad value answer at once)
 
 import torch
 
@@ -16,15 +26,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from zsgnet_pytorch_amd import config, evaluator, loss, mdl
 from zsgnet_pytorch_amd.synth import synthetic_batch, synthetic_shared_batch
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--images", type=int, default=None, help="distinct images per batch (shared-image plan); default: one image per query")
-ap.add_argument("--queries", type=int, default=16, help="queries per batch")
-ap.add_argument("--topk", type=int, default=None, help="time the evaluator call with and without the top-k launch (K boxes per query)")
-ap.add_argument("--pre-nms", type=int, default=128, help="with --topk: candidates per query that enter the NMS")
-ap.add_argument("--json", default=None, help="with --topk: also write the result line to this file")
-args = ap.parse_args()
 Q = args.queries
-cfg = config.get_cfg()
+cfg = config.get_cfg(eval_dtype=args.dtype)
 
 
 def time_topk():
@@ -83,6 +86,6 @@ with torch.no_grad():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / 50
 if args.images is None:
-    print(f"eval: {1e3 * dt:.3f} ms per batch of {Q} -> {Q / dt:.0f} img/s")
+    print(f"eval [{args.dtype}]: {1e3 * dt:.3f} ms per batch of {Q} -> {Q / dt:.0f} img/s")
 else:
-    print(f"eval (shared): {1e3 * dt:.3f} ms per batch of {Q} queries over {args.images} images -> {Q / dt:.0f} queries/s")
+    print(f"eval (shared) [{args.dtype}]: {1e3 * dt:.3f} ms per batch of {Q} queries over {args.images} images -> {Q / dt:.0f} queries/s")

@@ -71,6 +71,9 @@ SIGNATURES = {
     "zsg_source_stamp": (C.c_char_p, []),
     "zsg_set_deterministic": (I32, [I32]),
     "zsg_conv_igemm": (I32, [DP, P, P, P, P, P, P, P, P]),
+    "zsg_conv_igemm_bf16": (I32, [DP, P, P, P, P, P, P]),
+    "zsg_conv_igemm_bf16_supported": (I32, [DP]),
+    "zsg_pack_w_bf16_batched": (I32, [P, I32, I32, P]),
     "zsg_comm_unique_id": (I32, [P]),
     "zsg_comm_init": (I32, [C.POINTER(P), P, I32, I32]),
     "zsg_comm_allreduce_bucket": (I32, [P, P, I64, P]),

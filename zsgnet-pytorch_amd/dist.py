@@ -284,7 +284,8 @@ class DistributedDataParallel(nn.Module):
             if get_rank() == 0:
                 Bi, Q, H, W, Tp = geo
                 self.module._plan_for(Bi, H, W, Tp, Q=Q)          # (cached: lowers only when this (Bi, Q) / bucket is new)
-        elif get_rank() == 0 and (tuple(geo) + (self.module.training,)) not in self.module._plans:
+        elif get_rank() == 0 and (self.module._eval_key(*geo[:4]) if (not self.module.training and hasattr(self.module, "_eval_key"))
+                                  else tuple(geo) + (self.module.training,)) not in self.module._plans:
             self.module._plan_for(*geo[:4])
         payload = [dict(ops._TUNE_CACHE) if get_rank() == 0 else None]
         dist.broadcast_object_list(payload, src=0, group=self.group)

@@ -18,6 +18,7 @@ keep working while no autograd graph is built per layer.
 import ctypes as _ct
 import math
 import os
+import struct as _struct
 import types
 import weakref
 from dataclasses import dataclass, field
@@ -36,6 +37,7 @@ from .params import ParamStore, pad4, register_named
 VGG_BASE = [64, 64, "M", 128, 128, "M", 256, 256, 256, "C", 512, 512, 512, "M", 512, 512, 512]     # ssd_vgg.py:174-177
 SSD_EXTRAS = [256, "S", 512, 128, "S", 256, 128, 256, 128, 256]                                          # ssd_vgg.py:179-182
 
+EVAL_DTYPES = ("fp32", "bf16")    # cfg eval_dtype / ZSGNet.eval_precision: operand precision of the eval plans' convolutions
 LSTM_DIMS = (32, 64, 128, 256)    # cfg lstm_dim: the widths csrc/lstm.hip instantiates zsg_lstm_fwd / zsg_lstm_bwd for
 
 LIVE_NETS = weakref.WeakSet()      # every ZSGNet alive: optim.clip_grad_norm_ finds a parameter's flat store here
@@ -161,6 +163,7 @@ class ZSGNet(nn.Module):
         self._sync_bn_group = None     # process group of the synchronized BatchNorm collectives (sync_batchnorm), None: per-rank statistics
         self._sync_bn_conf = None      # (process group it was made for, force) of that group
         self.debug = False
+        self._eval_dtype = "fp32"      # operand precision of the eval plans' convolutions (eval_precision)
         LIVE_NETS.add(self)
 
     # ------------------------------------------------------------------------------------------------------
@@ -315,7 +318,8 @@ class ZSGNet(nn.Module):
     def _apply(self, fn, recurse=True):
         flat = fn(self.store.flat)
         if flat.dtype != torch.float32:
-            raise TypeError("zsgnet-pytorch_amd computes in fp32 only (fp32 MFMA); dtype conversion is not supported")
+            raise TypeError("zsgnet-pytorch_amd keeps its parameters and activations in fp32; dtype conversion is not supported "
+                            "(reduced-precision inference: ZSGNet.eval_precision('bf16') / cfg eval_dtype)")
         self.store.flat = flat
         self.store.grad = torch.zeros_like(flat)
         self._rmv = fn(self._rmv)
@@ -546,6 +550,24 @@ class ZSGNet(nn.Module):
         self._shared_train = bool(enable)
         return self
 
+    def eval_precision(self, dtype: str = "fp32") -> "ZSGNet":
+        """Operand precision of the convolutions of the EVAL plans: "fp32" (default: what every plan lowered before) or "bf16" — every
+        convolution behind the stem runs on bf16 MFMA (zsg_conv_igemm_bf16: fp32 activations rounded by the operand loader, weights packed
+        once per forward, fp32 accumulation and epilogue); the stem, the query encoder, the language map, pooling, upsampling and
+        l2norm stay fp32.  Train-mode plans are untouched.  The eval plan cache is keyed by the dtype, so switching back and forth
+        reuses plans."""
+        if dtype not in EVAL_DTYPES:
+            raise ValueError(f"eval_dtype={dtype!r}: expected one of {', '.join(EVAL_DTYPES)}")
+        self._eval_dtype = dtype
+        return self
+
+    def _eval_key(self, B, H, W, T, Q: Optional[int] = None) -> Tuple:
+        """plan-cache key of an eval plan; the default dtype keeps the key it always had"""
+        dt = () if self._eval_dtype == "fp32" else (self._eval_dtype,)
+        if Q is not None:
+            return (B, Q, H, W, T, "shared") + dt + (False,)
+        return (B, H, W, T) + dt + (False,)
+
     def _refuse_sync_shared(self, inp) -> None:
         """sync_batchnorm + a shared training batch is out of scope: refused before any collective of the forward is issued (the
         data-parallel wrapper calls this ahead of its buffer broadcast)"""
@@ -572,19 +594,19 @@ class ZSGNet(nn.Module):
         if Q is not None:
             # eval-only plan of Q queries over B (bucketed) images; the cache of these is bounded: least recently used first out
             assert not self.training
-            key = (B, Q, H, W, T, "shared", False)
+            key = self._eval_key(B, H, W, T, Q)
             if key in self._plans:
                 self._plans[key] = self._plans.pop(key)         # (most recently used last)
             else:
-                old = [k for k in self._plans if len(k) == 7 and k[5] == "shared"]
+                old = [k for k in self._plans if len(k) in (7, 8) and k[5] == "shared"]      # (of every eval dtype: one bound)
                 for k in old[:max(0, len(old) + 1 - SHARED_PLANS_MAX)]:
                     del self._plans[k]
-                self._plans[key] = _Plan(self, B, H, W, T, False, Q=Q)
+                self._plans[key] = _Plan(self, B, H, W, T, False, Q=Q, dtype=self._eval_dtype)
             return self._plans[key]
         if not self.training:
-            key = (B, H, W, T, False)
+            key = self._eval_key(B, H, W, T)
             if key not in self._plans:
-                self._plans[key] = _Plan(self, B, H, W, T, False)
+                self._plans[key] = _Plan(self, B, H, W, T, False, dtype=self._eval_dtype)
             return self._plans[key]
         fz, fb, sb = self._frozen_key(), self._frozen_bn_key(), self._sync_bn_key()
         key = (B, H, W, T, fz, fb, sb, True)
@@ -726,8 +748,13 @@ class _Plan:
     """Static lowering of ZSGNet for one (B, H, W, T, training) geometry."""
 
     def __init__(self, net: ZSGNet, B: int, H: int, W: int, T: int, training: bool, frozen=frozenset(), frozen_bn=frozenset(),
-                 sync_bn=frozenset(), Q: Optional[int] = None):
+                 sync_bn=frozenset(), Q: Optional[int] = None, dtype: str = "fp32"):
         self.net, self.B, self.H, self.W, self.T, self.training = net, B, H, W, T, training
+        # eval plans only (ZSGNet.eval_precision): every convolution zsg_conv_igemm_bf16 supports is lowered to it; their weights are
+        # packed to bf16 by ONE zsg_pack_w_bf16_batched launch per forward (behind the BatchNorm fold, whose output it reads)
+        assert dtype in EVAL_DTYPES and not (training and dtype != "fp32")
+        self.bf16 = dtype == "bf16"
+        self.pack_jobs, self.pack_blocks, self.pack_keep, self.pack_jobs_dev = [], 0, [], None
         # Q: a shared-image plan (ZSGNet._forward_shared) — the image trunk up to conv0's feature GEMM is lowered at batch B (image
         # slots), the query encoder and everything behind zsg_head_shared_conv0 at batch Q; every other plan has one batch, Q == B.  A
         # shared TRAINING plan (ZSGNet.shared_training) has exactly B slots, all used; its backward turns the gradient of h1 [Q] into
@@ -815,6 +842,9 @@ class _Plan:
             import struct
             blob = b"".join(struct.pack("<qqqqqiiii", *j) for j in self.fold_jobs)
             self.fold_jobs_dev = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(self.dev)
+        if self.pack_jobs:
+            blob = b"".join(_struct.pack("<qqiiiiiiii", *j) for j in self.pack_jobs)
+            self.pack_jobs_dev = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(self.dev)
 
     # ---- allocation helpers --------------------------------------------------------------------------------
     def _buf(self, n, dtype=torch.float32):
@@ -932,6 +962,29 @@ class _Plan:
         self._tunables.append(d)
         return r
 
+    def _bf16_conv(self, d, src_buf, w_src: torch.Tensor, wC: int, wc0: int, out_buf, bias, add_src, what: str, lane: int = 0) -> bool:
+        """Lower the convolution `d` to zsg_conv_igemm_bf16 when this is a bf16 eval plan and the library takes the descriptor (else
+        False: the caller lowers the fp32 launch).  w_src: the fp32 OHWI weight (raw parameter storage or a folded copy) whose channel
+        window [wc0, wc0 + d.C) of wC is packed to uint16 [N][taps][C8]; the job joins the plan's one pack launch and the image is
+        filled once now, so that the tuner times real data."""
+        if not self.bf16 or self.training or not lib.zsg_conv_igemm_bf16_supported(_ct.byref(d)):
+            return False
+        T, c8 = d.wR * d.wS, (d.C + 7) // 8 * 8
+        assert wc0 + d.C <= wC and w_src.numel() >= d.N * T * wC
+        wp = self._buf(d.N * T * c8, dtype=torch.int16)
+        job = (w_src.data_ptr(), wp.data_ptr(), d.N, T, wC, wc0, d.C, c8)
+        one = torch.frombuffer(bytearray(_struct.pack("<qqiiiiiiii", *job, 0, 0)), dtype=torch.uint8).to(self.dev)
+        nblk = (d.N * T * c8 // 8 + 255) // 256
+        check(lib.zsg_pack_w_bf16_batched(one.data_ptr(), 1, nblk, stream_ptr()), "pack_w_bf16")
+        torch.cuda.current_stream().synchronize()          # (`one` is freed on return)
+        self.pack_jobs.append(job + (self.pack_blocks, 0))
+        self.pack_blocks += nblk
+        self.pack_keep.append(w_src)
+        args = (src_buf, wp, out_buf, bias, add_src)
+        self._tune("igemm", lib.zsg_conv_igemm_bf16, d, args, stream_ptr())
+        self.fwd.add(lib.zsg_conv_igemm_bf16, d, *args, what=what + "+bf16", lane=lane)
+        return True
+
     def _wino_u(self, src_ptr: int, N: int, Cred: int, row_ld: int, tap_ld: int, flip: int):
         """Transformed filter image of one 3x3 convolution (+ a one-off transform so that the tuner times real data);
         the job joins the program's batched transform only if the Winograd kernel wins the tuning."""
@@ -1000,6 +1053,12 @@ class _Plan:
         wt = self.P(L.name + ".weight")
         if pend is not None:
             return self._conv_bnpre(L, src, out, d, wt, pend, bn_fuse)
+        if self._bf16_conv(d, rd.buf, wt, L.cpad, 0, out.buf, bias, None, L.name, lane=self._lane):
+            # (an eval plan has no backward: the tape entry only keeps the callers' bookkeeping — _head_stack pops it — in step)
+            out.bn_chunks, out.bn_inline, out.needs_mask, out.requires_grad = 0, None, relu, self._conv_rg(L, src)
+            src._consumed = True
+            self.tape.append(lambda: None)
+            return out
         wargs = None
         if wino_ok(L.k, L.stride, L.pad, L.dil) and not L.merge_x and wino_mode() != "0":
             U, job = self._wino_u(wt.data_ptr(), L.cout, L.cpad, L.k * L.k * L.cpad, L.cpad, 0)
@@ -1163,6 +1222,8 @@ class _Plan:
         d = fwd_desc(x, out, L.cpad, L.cout, L.k, L.stride, L.pad, L.dil, wC=L.cpad, relu=relu, merge_x=L.merge_x)
         wt, bias = self.fold_arena[w_off:w_off + n_w], self.fold_arena[b_off:b_off + L.cout]
         args = (x.buf, wt, out.buf, bias, residual.buf if residual is not None else None, None, None)
+        if self._bf16_conv(d, x.buf, wt, L.cpad, 0, out.buf, bias, args[4], L.name + "+bn"):
+            return out
         wargs = None
         if wino_ok(L.k, L.stride, L.pad, L.dil) and not L.merge_x and wino_mode() != "0":
             U, job = self._wino_u(wt.data_ptr(), L.cout, L.cpad, L.k * L.k * L.cpad, L.cpad, 0)
@@ -2177,15 +2238,17 @@ class _Plan:
             d0 = fwd_desc(Fp, Y, Cf, 256, 3, 1, 1, 1, wC=cp, wc0=0, relu=False)
             a0 = (Fp.buf, self.P(W0n), Y.buf, None, None, None, None)
             wargs = None
-            if wino_mode() != "0":
+            bf0 = self._bf16_conv(d0, Fp.buf, self.P(W0n), cp, 0, Y.buf, None, None, L0.name + ".feat")
+            if not bf0 and wino_mode() != "0":
                 U0, job0 = self._wino_u(self.P(W0n).data_ptr(), 256, Cf, 9 * cp, cp, 0)
                 wargs = (Fp.buf, U0) + a0[2:]
-            self._tune("igemm", lib.zsg_conv_igemm, d0, a0, stream_ptr(), wino_args=wargs)
-            if d0.use_wino:
-                self.wino_jobs["fwd"].add(*job0)
-                self.fwd.add(lib.zsg_conv_wino, d0, *wargs, what=L0.name + ".feat")
-            else:
-                self.fwd.add(lib.zsg_conv_igemm, d0, *a0, what=L0.name + ".feat")
+            if not bf0:
+                self._tune("igemm", lib.zsg_conv_igemm, d0, a0, stream_ptr(), wino_args=wargs)
+                if d0.use_wino:
+                    self.wino_jobs["fwd"].add(*job0)
+                    self.fwd.add(lib.zsg_conv_wino, d0, *wargs, what=L0.name + ".feat")
+                else:
+                    self.fwd.add(lib.zsg_conv_igemm, d0, *a0, what=L0.name + ".feat")
             hw = torch.tensor([v for hw_ in sizes for v in hw_], dtype=torch.int32)
             self.fwd.add(lib.zsg_head_shared_conv0, Y.buf, self.in_idx, 1, self.P(L0.name + ".bias"), G.buf if G is not None else None,
                          V.buf if V is not None else None, self.B, B, len(sizes), hw, 256, h1.buf, what=L0.name + ".shared")
@@ -2217,15 +2280,17 @@ class _Plan:
             d0 = fwd_desc(Fp, h1, Cf, 256, 3, 1, 1, 1, wC=cp, wc0=0, relu=True)
             a0 = (Fp.buf, self.P(W0n), h1.buf, self.P(L0.name + ".bias"), lmap.buf if lmap is not None else None, None, None)
             wargs = None
-            if wino_mode() != "0":
+            bf0 = self._bf16_conv(d0, Fp.buf, self.P(W0n), cp, 0, h1.buf, a0[3], a0[4], L0.name)
+            if not bf0 and wino_mode() != "0":
                 U0, job0 = self._wino_u(self.P(W0n).data_ptr(), 256, Cf, 9 * cp, cp, 0)
                 wargs = (Fp.buf, U0) + a0[2:]
-            self._tune("igemm", lib.zsg_conv_igemm, d0, a0, stream_ptr(), wino_args=wargs)
-            if d0.use_wino:
-                self.wino_jobs["fwd"].add(*job0)
-                self.fwd.add(lib.zsg_conv_wino, d0, *wargs, what=L0.name)
-            else:
-                self.fwd.add(lib.zsg_conv_igemm, d0, *a0, what=L0.name)
+            if not bf0:
+                self._tune("igemm", lib.zsg_conv_igemm, d0, a0, stream_ptr(), wino_args=wargs)
+                if d0.use_wino:
+                    self.wino_jobs["fwd"].add(*job0)
+                    self.fwd.add(lib.zsg_conv_wino, d0, *wargs, what=L0.name)
+                else:
+                    self.fwd.add(lib.zsg_conv_igemm, d0, *a0, what=L0.name)
         else:                             # image-blind: h1 = relu(lmap + bias), an affine map with scale 1
             one, zero = self._buf(256) + 1.0, self._buf(256)
             self.fwd.add(lib.zsg_bn_apply, lmap.buf, h1.rows(), 256, zero, one, one, self.P(L0.name + ".bias"), None, 1, h1.buf, None,
@@ -2409,6 +2474,8 @@ class _Plan:
         if not self.training and self.fold_jobs:       # the weights may have changed since the last eval forward: refold (one launch)
             check(lib.zsg_bn_fold(net.store.flat.data_ptr(), net._rm.data_ptr(), net._rv.data_ptr(), 1e-5, self.fold_jobs_dev.data_ptr(),
                                   len(self.fold_jobs), self.fold_rows, self.fold_arena.data_ptr(), stream_ptr()), "bn_fold")
+        if self.pack_jobs:       # bf16 eval plan: the packed weight images, from the parameters and the fold just made (one launch)
+            check(lib.zsg_pack_w_bf16_batched(self.pack_jobs_dev.data_ptr(), len(self.pack_jobs), self.pack_blocks, stream_ptr()), "pack_w_bf16")
         if u8:
             check(lib.zsg_u8hwc_to_nhwc4(img.data_ptr(), n_img * self.H * self.W, self.fwd.calls[self.img_slot][1][5], stream_ptr()), "u8hwc_to_nhwc4")
         else:
@@ -2591,6 +2658,7 @@ def get_default_net(num_anchors=1, cfg=None):
     kind = cfg["mdl_to_use"]
     arch = cfg["resnet_arch"] if "resnet_arch" in cfg else "resnet50"
     net = ZSGNet(kind, num_anchors, cfg=cfg, arch=arch)
+    net.eval_precision(cfg["eval_dtype"] if "eval_dtype" in cfg else "fp32")          # (raises on anything but fp32 / bf16)
     path = cfg["pretrained_path"] if "pretrained_path" in cfg else ""
     if path:
         n = load_pretrained_encoder(net, path)

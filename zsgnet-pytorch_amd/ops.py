@@ -832,9 +832,10 @@ def autotune_conv(kind: str, fn, d: ConvDesc, args: Sequence, stream: int, ws_by
     if no_tune:
         return 0
     _check_table_arch()
-    add_src, mask = (args[4], args[5]) if kind == "igemm" else (None, None)
+    bf16 = fn is lib.zsg_conv_igemm_bf16          # (d, src, packed weights, out, bias, add_src): no mask operand
+    add_src, mask = (args[4], None if bf16 else args[5]) if kind == "igemm" else (None, None)
     key = _sig(kind, d, (add_src is not None, mask is not None, add_src is not None and add_src is args[2], split_penalty_ms > 0,
-                         mode if wino_args is not None else "", deterministic(), "fp32", fn.__name__,
+                         mode if wino_args is not None else "", deterministic(), "bf16" if bf16 else "fp32", fn.__name__,
                          os.environ.get("ZSG_PW", "1") != "0" and not (d.merge_x and os.environ.get("ZSG_MX", "1") == "0"),
                          allow_sk and os.environ.get("ZSG_SK", "1") != "0"))
     d._tune_key = key
@@ -844,7 +845,10 @@ def autotune_conv(kind: str, fn, d: ConvDesc, args: Sequence, stream: int, ws_by
         return v
     rows = sum(d.B * d.seg[i].rows_y * d.seg[i].rows_x for i in range(d.nseg))
     cands = []
-    if kind == "igemm":
+    if bf16:
+        # the bf16 eval entry: its tile hints are all there is (no split-K, stream-K, Winograd or streaming variants)
+        cands = [tile_hint(64, 64, 1), tile_hint(128, 64, 1)] + ([tile_hint(128, 128, 1)] if d.N > 64 else [])
+    elif kind == "igemm":
         tiles = [(64, 64), (128, 64)] + ([(128, 128)] if d.N > 64 else [])
         s0 = d.seg[0]
         dense = (d.nseg == 1 and not d.relu and d.out_ld == d.N and s0.osy == 1 and s0.osx == 1 and s0.out_W == s0.rows_x
