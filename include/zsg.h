@@ -222,6 +222,54 @@ int32_t zsg_conv_igemm_bf16_supported(const zsg_conv_desc* d);
  * blk0 = running sum of ceil(N*T*C8/8 / 256); total_blocks = the final sum.  Rounding: the contract above. */
 int zsg_pack_w_bf16_batched(const void* jobs_dev, int32_t njobs, int32_t total_blocks, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * bf16 ACTIVATION STORAGE for inference (eval_dtype = "bf16_act"; csrc/igemm_bf16.hip, csrc/bf16_act.hip).  Everything "bf16" has;
+ * in addition the activations between the stem's max-pool and the heads' last convolution are stored as bf16 (uint16 elements, the
+ * same NHWC / packed-pyramid layouts, the same ELEMENT offsets and leading dimensions as the fp32 plan).  Contract:
+ *   - Rounding: a value is rounded exactly once, when it is stored; round-to-nearest-even, the rule above (Tensor.to(torch.bfloat16)).
+ *   - Arithmetic: everything is computed in fp32 from the widened inputs (widening is exact) — bias, residual add, ReLU, max,
+ *     upsample-add, the l2 norm, the shared conv0 sum — in the order of the fp32 kernels.  The convolution's operand loader rounds an
+ *     fp32 activation to bf16 anyway, so a convolution fed a bf16 activation sees the operand bits the "bf16" plan's sees for the same
+ *     fp32 value; results differ only where an fp32 activation was consumed in fp32 (residual add_src, upsample_add, l2norm, ReLU,
+ *     the average pool).
+ *   - fp32 in memory: the image and the stem convolution's output, the LSTM and the language vector, the language-map operands V, G
+ *     and lmap (lmap enters conv0 as an fp32 add_src), the shared-image plan's per-slot accumulator Y, and the network's outputs (the
+ *     heads' final convolutions read bf16 and write fp32).  Training plans never see any of this.
+ *
+ * zsg_conv_igemm_bf16_io: zsg_conv_igemm_bf16 with the storage format of each activation operand chosen by io_flags:
+ *     ZSG_IO_SRC_BF16 = 1 (src is uint16), ZSG_IO_OUT_BF16 = 2 (out is uint16), ZSG_IO_ADD_BF16 = 4 (add_src is uint16).
+ *   io_flags = 0 is zsg_conv_igemm_bf16 (same kernel, same bits).  With SRC_BF16 the loader converts nothing: an 8-channel group is one
+ *   16-byte load when src_ld and every segment's src_off / src_bstride are multiples of 8 and src is 16-byte aligned, else two 8-byte
+ *   halves (C = 36 with src_ld = 36; src 8-byte aligned); the C % 8 == 4 tail is zero-filled either way.  With OUT_BF16 the epilogue
+ *   rounds and stores 8-byte groups of 4 channels (2-byte stores where N / out_ld / the offsets are not multiples of 4: N = 45).
+ *   add_src may alias out when both have the same format.  Same K order, same refusals as zsg_conv_igemm_bf16; in addition: io_flags
+ *   outside 0..7, ADD_BF16 without add_src, a src that is not 8-byte aligned (SRC_BF16), add_src aliasing out in another format.
+ * zsg_conv_igemm_bf16_io_supported: what the DESCRIPTOR and the flag word decide of that (the pointers are the entry's business). */
+#define ZSG_IO_SRC_BF16 1
+#define ZSG_IO_OUT_BF16 2
+#define ZSG_IO_ADD_BF16 4
+int zsg_conv_igemm_bf16_io(const zsg_conv_desc* d, const void* src, const uint16_t* wt_packed, void* out, const float* bias,
+                           const void* add_src, int32_t io_flags, void* stream);
+int32_t zsg_conv_igemm_bf16_io_supported(const zsg_conv_desc* d, int32_t io_flags);
+/* Element-wise kernels of such a plan (forward only; the fp32 kernel of the same name on the widened inputs, rounded once).
+ * zsg_maxpool_fwd_bf16: x fp32 (x_bf16 = 0: the stem's output) or bf16, out bf16, no index output; NaN propagates.  C % 4 == 0. */
+int zsg_maxpool_fwd_bf16(const void* x, int32_t x_bf16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k, int32_t s, int32_t p,
+                         int32_t Ho, int32_t Wo, uint16_t* out, void* stream);
+/* out = a + nearest-upsampled p (zsg_upsample_add_fwd's index rule), all bf16.  C % 4 == 0. */
+int zsg_upsample_add_fwd_bf16(const uint16_t* a, const uint16_t* p, int32_t B, int32_t Hs, int32_t Ws, int32_t Hd, int32_t Wd, int32_t C,
+                              uint16_t* out, void* stream);
+/* out = fmaxf(x, 0) (a NaN becomes 0, as zsg_relu_fwd).  n % 4 == 0. */
+int zsg_relu_fwd_bf16(const uint16_t* x, int64_t n, uint16_t* out, void* stream);
+/* mean over HW pixels: the pixel-ascending fp32 sum of zsg_avgpool_fwd, divided, rounded. */
+int zsg_avgpool_fwd_bf16(const uint16_t* x, int32_t B, int32_t HW, int32_t C, uint16_t* out, void* stream);
+/* zsg_head_shared_conv0 with h1 stored as bf16: Y, bias, G, V fp32, the same summation order ((Y + G) + (taps + bias)), ReLU, one
+ * rounding; an img_idx outside [0, Bi) gives NaN rows. */
+int zsg_head_shared_conv0_bf16(const float* Y, const void* img_idx, int32_t idx_i64, const float* bias, const float* G, const float* V,
+                               int32_t Bi, int32_t Q, int32_t nlev, const int32_t* hw, int32_t N, uint16_t* out, void* stream);
+/* The cast pair (any n, any element alignment): what a bf16_act plan puts around an operation that has no bf16 form (l2norm). */
+int zsg_cast_f32_bf16(const float* x, int64_t n, uint16_t* out, void* stream);
+int zsg_cast_bf16_f32(const uint16_t* x, int64_t n, float* out, void* stream);
+
 /* elements of the transformed image of a C -> N 3x3 filter: [ceil(C/8)][16][roundup(N,64)][8] */
 int64_t zsg_wino_u_elems(int32_t C, int32_t N);
 /* U = G g G^T for every job in ONE launch.  jobs: device array of { int64 src, dst (absolute device addresses);

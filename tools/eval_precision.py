@@ -1,6 +1,6 @@
-"""Developer tool: how far the bf16 eval plan (cfg eval_dtype = "bf16", ZSGNet.eval_precision) lands from the fp32 eval plan of the SAME
+"""Developer tool: how far the bf16 and bf16_act eval plans (cfg eval_dtype, ZSGNet.eval_precision) land from the fp32 eval plan of the SAME
 weights.  ResNet-50 FPN 300x300, B = 16 (--arch / --hw / --batch change it), oracle.seeded_state_dict(arch, 1), a synthetic batch.
-Prints, for bf16 against fp32: max and mean |delta| of the box channels and of the att channel relative to max|fp32| of those
+Prints, for bf16 against fp32 (the keys it always had) and for bf16_act against fp32 (the same keys with the prefix "act_"): max and mean |delta| of the box channels and of the att channel relative to max|fp32| of those
 channels, the share of queries whose evaluator pred_idx agrees, and both Acc values — one JSON line (--json PATH also writes it to a
 file)."""
 import argparse
@@ -35,18 +35,22 @@ r, s = config.ratios_scales(cfg)
 ev = evaluator.get_default_eval(r, s, cfg).eval()
 res = {}
 with torch.no_grad():
-    for dtype in ("fp32", "bf16"):
+    for dtype in ("fp32", "bf16", "bf16_act"):
         out = net.eval_precision(dtype)(bt)
         em = ev(out, bt)
         torch.cuda.synchronize()
         res[dtype] = (out["att_bbx_out"].double().cpu(), ev.pred_idx.cpu().clone(), float(em["Acc"]))
-a, b = res["fp32"][0], res["bf16"][0]
-box, att = (b[..., :4] - a[..., :4]).abs(), (b[..., 4] - a[..., 4]).abs()
+a = res["fp32"][0]
 sb, sa = float(a[..., :4].abs().max()), float(a[..., 4].abs().max())
-line = json.dumps({"what": "bf16 eval plan against the fp32 eval plan of the same weights, relative to max|fp32| per channel group",
-                   "arch": args.arch, "hw": args.hw, "B": args.batch,
-                   "box_max": float(box.max()) / sb, "box_mean": float(box.mean()) / sb, "att_max": float(att.max()) / sa, "att_mean": float(att.mean()) / sa,
-                   "pred_idx_agree": float((res["fp32"][1] == res["bf16"][1]).float().mean()), "acc_fp32": res["fp32"][2], "acc_bf16": res["bf16"][2]})
+rec = {"what": "bf16 / bf16_act (act_*) eval plans against the fp32 eval plan of the same weights, relative to max|fp32| per channel group",
+       "arch": args.arch, "hw": args.hw, "B": args.batch, "acc_fp32": res["fp32"][2]}
+for dtype, pre in (("bf16", ""), ("bf16_act", "act_")):
+    b = res[dtype][0]
+    box, att = (b[..., :4] - a[..., :4]).abs(), (b[..., 4] - a[..., 4]).abs()
+    rec.update({pre + "box_max": float(box.max()) / sb, pre + "box_mean": float(box.mean()) / sb, pre + "att_max": float(att.max()) / sa,
+                pre + "att_mean": float(att.mean()) / sa, pre + "pred_idx_agree": float((res["fp32"][1] == res[dtype][1]).float().mean()),
+                "acc_" + dtype: res[dtype][2]})
+line = json.dumps(rec)
 print(line)
 if args.json:
     with open(args.json, "w") as f:

@@ -4,7 +4,7 @@ images per batch; without --images the one-image-per-query path, as before.
 --topk K [--pre-nms N] [--queries Q]: the evaluator call alone, on a fixed [Q, 17460, 5] head output: eval_topk = 1 (zsg_eval only) against
 eval_topk = K in eval mode (zsg_eval + zsg_eval_topk), alternating; device events around groups of calls, the median per call of each, one
 JSON line (--json PATH also writes it to a file).
---dtype fp32|bf16: cfg eval_dtype of the network (the forward paths; --topk times no network)."""
+--dtype fp32|bf16|bf16_act: cfg eval_dtype of the network (the forward paths; --topk times no network)."""
 import argparse
 import json
 import os
@@ -12,7 +12,9 @@ import sys
 import time
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32", help="eval_dtype: operand precision of the eval plan's convolutions")
+ap.add_argument("--dtype", choices=("fp32", "bf16", "bf16_act"), default="fp32",
+                help="eval_dtype: operand precision of the eval plan's convolutions (bf16_act: bf16 activation storage as well)")
+ap.add_argument("--per-kernel", action="store_true", help="also print the per-launch device times of one forward and the plan's bytes")
 ap.add_argument("--images", type=int, default=None, help="distinct images per batch (shared-image plan); default: one image per query")
 ap.add_argument("--queries", type=int, default=16, help="queries per batch")
 ap.add_argument("--topk", type=int, default=None, help="time the evaluator call with and without the top-k launch (K boxes per query)")
@@ -85,6 +87,14 @@ with torch.no_grad():
         out = net(bt); lf(out, bt); ev(out, bt)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / 50
+plan = next(reversed(net._plans.values()))
+print(f"plan bytes [{args.dtype}]: {plan.bytes} ({plan.bytes / 2**20:.1f} MiB), {len(plan.fwd.calls)} launches")
+if args.per_kernel:
+    from zsgnet_pytorch_amd._lib import stream_ptr
+    torch.cuda.synchronize()
+    rows = plan.fwd.profile(stream_ptr())
+    for r_ in rows:
+        print("  ", r_)
 if args.images is None:
     print(f"eval [{args.dtype}]: {1e3 * dt:.3f} ms per batch of {Q} -> {Q / dt:.0f} img/s")
 else:

@@ -74,6 +74,15 @@ SIGNATURES = {
     "zsg_conv_igemm_bf16": (I32, [DP, P, P, P, P, P, P]),
     "zsg_conv_igemm_bf16_supported": (I32, [DP]),
     "zsg_pack_w_bf16_batched": (I32, [P, I32, I32, P]),
+    "zsg_conv_igemm_bf16_io": (I32, [DP, P, P, P, P, P, I32, P]),
+    "zsg_conv_igemm_bf16_io_supported": (I32, [DP, I32]),
+    "zsg_maxpool_fwd_bf16": (I32, [P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, P]),
+    "zsg_upsample_add_fwd_bf16": (I32, [P, P, I32, I32, I32, I32, I32, I32, P, P]),
+    "zsg_relu_fwd_bf16": (I32, [P, I64, P, P]),
+    "zsg_avgpool_fwd_bf16": (I32, [P, I32, I32, I32, P, P]),
+    "zsg_head_shared_conv0_bf16": (I32, [P, P, I32, P, P, P, I32, I32, I32, P, I32, P, P]),
+    "zsg_cast_f32_bf16": (I32, [P, I64, P, P]),
+    "zsg_cast_bf16_f32": (I32, [P, I64, P, P]),
     "zsg_comm_unique_id": (I32, [P]),
     "zsg_comm_init": (I32, [C.POINTER(P), P, I32, I32]),
     "zsg_comm_allreduce_bucket": (I32, [P, P, I64, P]),

@@ -1,4 +1,14 @@
-// igemm_bf16.hip — the eval-only implicit-GEMM convolution on bf16 MFMA (eval_dtype = "bf16"), NHWC fp32 x packed bf16 weights, gfx950.
+// igemm_bf16.hip — the eval-only implicit-GEMM convolution on bf16 MFMA (eval_dtype = "bf16" / "bf16_act"), NHWC x packed bf16 weights, gfx950.
+//
+// Two entries, one kernel template.  zsg_conv_igemm_bf16: activations fp32 in memory (the text below).  zsg_conv_igemm_bf16_io: each of src /
+// out / add_src is fp32 or bf16 in memory (io_flags, the template parameter IO; IO = 0 is the first entry's kernel, instruction for
+// instruction the same source path).  With a bf16 src the loader converts nothing: the 8-channel group of a tile row is ONE 16-byte buffer
+// load where src_ld and the segment offsets are multiples of 8, else two 8-byte loads (C = 36, src_ld = 36: rows are only 8-byte aligned),
+// each half bounds-checked as the fp32 halves are, so the C % 8 == 4 tail zero-fills.  The group goes global -> registers -> LDS like the
+// fp32 one (the same one-stage prefetch, half the registers); a direct global -> LDS load was NOT built or timed.  With a bf16 out the
+// epilogue rounds once (bf16.h: the packer's conversion) and stores 8-byte groups of 4 channels, or 2 bytes per lane on the scalar path.
+// What was timed on the bf16 storage path is in profiles/bf16act_eval_time.txt (whole eval forwards and their per-kernel times; no
+// micro-benchmark of the loader alone).
 //
 // Same GEMM view, descriptor and epilogue as igemm.hip (rows = (segment, b, y, x), n = output channel, K = taps x C walked tap-major):
 //      Out[row][n] = relu( sum_{taps} sum_{c<C} bf16(Src[gather(row, tap)][c]) * Wp[n][tap][c]  + bias[n] + add_src[row][n] )
@@ -24,7 +34,7 @@
 // same input gives the same bits on every run.
 #include <stdlib.h>
 
-#include "common.h"
+#include "bf16.h"
 
 ZSG_DEFINE_PRIO_FLAG()
 
@@ -32,16 +42,6 @@ ZSG_DEFINE_PRIO_FLAG()
 #define BF_LDR 72               // bf16 elements per LDS tile row (144 B)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// fp32 -> bf16, round-to-nearest-even; +-0, +-inf preserved, NaN stays NaN, a finite value above the largest bf16 becomes inf.  One
-// function for the packer and the activation loader: both operands are rounded by the same rule.
-__device__ __forceinline__ unsigned bf16_pack2(float lo, float hi) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 
 // ---- weight packer ------------------------------------------------------------------------------------------------------------
 struct BfPackJob {
@@ -92,21 +92,25 @@ struct BfSegDev {
 };
 
 struct BfParams {
-    const float* src;
+    const void* src;            // fp32, or bf16 with BF_SRC16
     const uint16_t* wt;         // packed [N][T][C8]
-    float* out;
+    void* out;                  // fp32, or bf16 with BF_OUT16
     const float* bias;
-    const float* add_src;
+    const void* add_src;        // fp32, or bf16 with BF_ADD16 (may alias out when both are bf16)
     int C, C8, N, src_ld, out_ld, wS, T, relu, nseg;
     int m_tiles, n_tiles;
     int remap;                  // XCD-aware tile order (only when every segment carries the same amount of K work)
-    int vec;                    // 16-byte epilogue allowed (alignment of every operand checked on the host)
+    int vec;                    // 4-channel epilogue groups allowed (alignment of every operand checked on the host)
     double alg_bytes;           // host only
     BfSegDev seg[ZSG_MAX_SEG];
 };
 
 // BM x BN block tile, 4 waves (2 x 2), each wave TM x TN MFMA tiles of 32x32.  Two blocks per CU (at most 256 registers per lane).
-template <int BM, int BN>
+// IO: the storage formats of src / out / add_src (BF_SRC16 | BF_OUT16 | BF_ADD16); IO = 0 is the fp32-in-memory kernel of eval_dtype = "bf16".
+// BF_SRC8 (with BF_SRC16): the two-halves loader.  A compile-time choice: a run-time branch around the loads made the compiler wait for
+// them where the paths join, i.e. in front of the MFMAs they are meant to fly under.
+#define BF_SRC8 8
+template <int BM, int BN, int IO>
 __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
     ZSG_SET_MAIN_PRIO();
     constexpr int WM = 2, WN = 2, NT = 256;
@@ -177,8 +181,11 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
     const rsrc_t rsrc_a = make_rsrc(p.src);
     const rsrc_t rsrc_b = make_rsrc(p.wt);
     int cc = 0, jx = 0, jy = 0;          // K-iteration counters of the NEXT tile to load (wave-uniform)
-    f32x4 ra[RA][2];
+    constexpr bool S16 = (IO & BF_SRC16) != 0;
+    f32x4 ra[S16 ? 1 : RA][2];           // fp32 source: two 4-channel halves, converted on the way to LDS
+    u32x4 rh[S16 ? RA : 1];              // bf16 source: the group as it lies in memory
     u32x4 rb[RB];
+    bool hi_dead = false;                // the staged group's upper half lies past C (set by load_tile, applied by store_tile)
     // live == false (past the last K tile): every lane gets an out-of-range offset — the loads still issue and return zeros
     auto load_tile = [&](bool live) {
         const int wr = sg.ty.w0 + jy * sg.ty.wstep;
@@ -187,14 +194,27 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
         const int dxx = jx * sg.tx.dstep;
         const int koff = cc * BF_BK + 8 * g;
         const bool k0 = live & (koff < Cdim), k1 = live & (koff + 4 < Cdim);      // the two 4-channel halves of this thread's group
+        hi_dead = !k1;
         const int tap = (dyy * srcW + dxx) * src_ld + koff;
 #pragma unroll
         for (int j = 0; j < RA; ++j) {
             const int yy = a_by[j] + dyy, xx = a_bx[j] + dxx;
             const bool ok = ((unsigned)yy < (unsigned)srcH) & ((unsigned)xx < (unsigned)srcW);
-            const unsigned o = 4u * (unsigned)(a_off[j] + tap);
-            ra[j][0] = buf_load4(rsrc_a, (ok & k0) ? o : ZSG_OOB);
-            ra[j][1] = buf_load4(rsrc_a, (ok & k1) ? o + 16u : ZSG_OOB);
+            if constexpr (S16) {
+                const unsigned o = 2u * (unsigned)(a_off[j] + tap);
+                if constexpr (!(IO & BF_SRC8)) {      // one 16-byte load; a C % 8 == 4 tail's upper half (it lies inside the row's padding) is
+                                                      // dropped in store_tile: touching the loaded value here would wait for the load in front of the MFMAs
+                    rh[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, (int)((ok & k0) ? o : ZSG_OOB), 0, 0);
+                } else {                 // rows that are only 8-byte aligned (src_ld % 8 == 4): two halves, each bounds-checked by itself
+                    const u32x2 lo = __builtin_amdgcn_raw_buffer_load_b64(rsrc_a, (int)((ok & k0) ? o : ZSG_OOB), 0, 0);
+                    const u32x2 hi = __builtin_amdgcn_raw_buffer_load_b64(rsrc_a, (int)((ok & k1) ? o + 8u : ZSG_OOB), 0, 0);
+                    rh[j] = u32x4{lo[0], lo[1], hi[0], hi[1]};
+                }
+            } else {
+                const unsigned o = 4u * (unsigned)(a_off[j] + tap);
+                ra[j][0] = buf_load4(rsrc_a, (ok & k0) ? o : ZSG_OOB);
+                ra[j][1] = buf_load4(rsrc_a, (ok & k1) ? o + 16u : ZSG_OOB);
+            }
         }
         const int wtap = (wr * p.wS + ws_) * p.C8 + koff;
         const bool kb = live & (koff < p.C8);
@@ -214,9 +234,15 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
         __bf16* b = Bs + buf * BN * LDR;
 #pragma unroll
         for (int j = 0; j < RA; ++j) {
-            const u32x4 v = {bf16_pack2(ra[j][0][0], ra[j][0][1]), bf16_pack2(ra[j][0][2], ra[j][0][3]),
-                             bf16_pack2(ra[j][1][0], ra[j][1][1]), bf16_pack2(ra[j][1][2], ra[j][1][3])};
-            *(u32x4*)(a + (r0 + RP * j) * LDR + 8 * g) = v;
+            if constexpr (S16) {
+                u32x4 v = rh[j];
+                if (hi_dead) v[2] = v[3] = 0u;
+                *(u32x4*)(a + (r0 + RP * j) * LDR + 8 * g) = v;
+            } else {
+                const u32x4 v = {bf16_pack2(ra[j][0][0], ra[j][0][1]), bf16_pack2(ra[j][0][2], ra[j][0][3]),
+                                 bf16_pack2(ra[j][1][0], ra[j][1][1]), bf16_pack2(ra[j][1][2], ra[j][1][3])};
+                *(u32x4*)(a + (r0 + RP * j) * LDR + 8 * g) = v;
+            }
         }
 #pragma unroll
         for (int j = 0; j < RB; ++j) *(u32x4*)(b + (r0 + RP * j) * LDR + 8 * g) = rb[j];
@@ -288,12 +314,16 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
                 if (ro < 0) continue;
                 const size_t o = (size_t)ro + n;
                 f32x4 v = *(const f32x4*)(ct + row * LDC + 4 * cg) + bv;
-                if (p.add_src) v += *(const f32x4*)(p.add_src + o);
+                if (p.add_src) {
+                    if constexpr (IO & BF_ADD16) v += bf16_widen4(*(const u32x2*)((const uint16_t*)p.add_src + o));
+                    else v += *(const f32x4*)((const float*)p.add_src + o);
+                }
                 if (p.relu) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
                 }
-                *(f32x4*)(p.out + o) = v;
+                if constexpr (IO & BF_OUT16) *(u32x2*)((uint16_t*)p.out + o) = bf16_pack4(v);      // rounded once, here
+                else *(f32x4*)((float*)p.out + o) = v;
             }
         }
     } else {
@@ -311,9 +341,13 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
                     if (ro >= 0 && nok) {
                         const size_t o = (size_t)ro + n;
                         float v = acc[i][j][e] + bv;
-                        if (p.add_src) v += p.add_src[o];
+                        if (p.add_src) {
+                            if constexpr (IO & BF_ADD16) v += bf16_widen1(((const uint16_t*)p.add_src)[o]);
+                            else v += ((const float*)p.add_src)[o];
+                        }
                         if (p.relu) v = fmaxf(v, 0.f);
-                        p.out[o] = v;
+                        if constexpr (IO & BF_OUT16) ((uint16_t*)p.out)[o] = bf16_round1(v);
+                        else ((float*)p.out)[o] = v;
                     }
                 }
             }
@@ -383,7 +417,20 @@ extern "C" int32_t zsg_conv_igemm_bf16_supported(const zsg_conv_desc* d) {
     return bf16_check(d, &bm, &bn) == nullptr ? 1 : 0;
 }
 
-template <int BM, int BN>
+// What the storage formats add to bf16_check.  A bf16 source needs what the 8-byte half loads need (C, src_ld and the segment offsets
+// multiples of 4: bf16_check's own conditions, which the fp32 loader needs for its 16-byte halves); a bf16 output or add_src of any
+// leading dimension is served by the scalar epilogue.  So only the flag word itself can be refused here.
+static const char* bf16_io_check(const zsg_conv_desc* d, int32_t io, int* BM, int* BN) {
+    if (io < 0 || io > (BF_SRC16 | BF_OUT16 | BF_ADD16)) return "io_flags (SRC_BF16 = 1 | OUT_BF16 = 2 | ADD_BF16 = 4)";
+    return bf16_check(d, BM, BN);
+}
+
+extern "C" int32_t zsg_conv_igemm_bf16_io_supported(const zsg_conv_desc* d, int32_t io_flags) {
+    int bm = 0, bn = 0;
+    return bf16_io_check(d, io_flags, &bm, &bn) == nullptr ? 1 : 0;
+}
+
+template <int BM, int BN, int IO>
 static int launch_bf16(const BfParams& p, hipStream_t st, double flops, const char* kname) {
     const size_t lds = (size_t)2 * (BM + BN) * BF_LDR * sizeof(uint16_t) + BM * sizeof(int);
     static bool attr_done[ZSG_MAX_DEV] = {};      // per device; idempotent (a benign race sets it twice)
@@ -391,23 +438,34 @@ static int launch_bf16(const BfParams& p, hipStream_t st, double flops, const ch
     (void)hipGetDevice(&dev);
     ZSG_REQUIRE(dev >= 0 && dev < ZSG_MAX_DEV, "igemm_bf16: device %d", dev);
     if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN, IO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) ZSG_FAIL(-3, "igemm_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_done[dev] = true;
     }
     ZSG_PROF(kname, st, flops, p.alg_bytes);
-    ZSG_LAUNCH((igemm_bf16_kernel<BM, BN>), dim3(p.m_tiles * p.n_tiles), dim3(256), lds, st, p);
+    ZSG_LAUNCH((igemm_bf16_kernel<BM, BN, IO>), dim3(p.m_tiles * p.n_tiles), dim3(256), lds, st, p);
     ZSG_CHECK_LAUNCH("igemm_bf16");
     return 0;
 }
 
-extern "C" int zsg_conv_igemm_bf16(const zsg_conv_desc* d, const float* src, const uint16_t* wt_packed, float* out, const float* bias,
-                                   const float* add_src, void* stream) {
-    ZSG_REQUIRE(d && src && wt_packed && out, "conv_igemm_bf16: null argument");
+template <int IO>
+static int launch_bf16_tile(int BM, int BN, const BfParams& p, hipStream_t st, double fl, const char* n64, const char* n128x64, const char* n128) {
+    if (BM == 128 && BN == 128) return launch_bf16<128, 128, IO>(p, st, fl, n128);
+    if (BM == 128 && BN == 64) return launch_bf16<128, 64, IO>(p, st, fl, n128x64);
+    return launch_bf16<64, 64, IO>(p, st, fl, n64);
+}
+
+static int conv_bf16_run(const char* who, const zsg_conv_desc* d, const void* src, const uint16_t* wt_packed, void* out, const float* bias,
+                         const void* add_src, int32_t io, void* stream) {
+    ZSG_REQUIRE(d && src && wt_packed && out, "%s: null argument", who);
     int BM = 64, BN = 64;
-    const char* why = bf16_check(d, &BM, &BN);
-    ZSG_REQUIRE(why == nullptr, "conv_igemm_bf16: unsupported: %s", why);
-    ZSG_REQUIRE((((uintptr_t)src | (uintptr_t)wt_packed) & 15) == 0, "conv_igemm_bf16: src / wt_packed not 16-byte aligned");
+    const char* why = bf16_io_check(d, io, &BM, &BN);
+    ZSG_REQUIRE(why == nullptr, "%s: unsupported: %s", who, why);
+    ZSG_REQUIRE(!(io & BF_ADD16) || add_src, "%s: ADD_BF16 without add_src", who);
+    const bool s16 = (io & BF_SRC16) != 0, o16 = (io & BF_OUT16) != 0, a16 = (io & BF_ADD16) != 0;
+    ZSG_REQUIRE((((uintptr_t)src & (s16 ? 7 : 15)) | ((uintptr_t)wt_packed & 15)) == 0, "%s: src / wt_packed not aligned (16 bytes; a bf16 src: 8)", who);
+    ZSG_REQUIRE(((uintptr_t)out & (o16 ? 1 : 3)) == 0 && ((uintptr_t)add_src & (a16 ? 1 : 3)) == 0, "%s: out / add_src not element-aligned", who);
+    ZSG_REQUIRE(add_src != out || a16 == o16, "%s: add_src aliases out in another format", who);
     BfParams p;
     memset(&p, 0, sizeof(p));
     p.src = src; p.wt = wt_packed; p.out = out; p.bias = bias; p.add_src = add_src;
@@ -434,15 +492,58 @@ extern "C" int zsg_conv_igemm_bf16(const zsg_conv_desc* d, const float* src, con
     for (int s = 1; s < d->nseg; ++s)
         if (d->seg[s].ty.n * d->seg[s].tx.n != d->seg[0].ty.n * d->seg[0].tx.n) p.remap = 0;
     {
+        // 4-channel groups in the epilogue: 16 bytes of fp32, 8 bytes of bf16
         bool v = (d->out_ld % 4) == 0 && (d->N % 4) == 0;
         for (int s = 0; s < d->nseg; ++s) v = v && (d->seg[s].out_off % 4) == 0 && (d->seg[s].out_bstride % 4) == 0;
-        const uintptr_t al = (uintptr_t)out | (uintptr_t)bias | (uintptr_t)add_src;
-        p.vec = (v && (al & 15) == 0) ? 1 : 0;
+        const uintptr_t al = ((uintptr_t)out & (o16 ? 7 : 15)) | ((uintptr_t)bias & 15) | ((uintptr_t)add_src & (a16 ? 7 : 15));
+        p.vec = (v && al == 0) ? 1 : 0;
     }
-    // algorithmic bytes: fp32 activations in and out, the filter at 2 bytes per element
-    p.alg_bytes = zsg_conv_alg_bytes(d, add_src != nullptr) - 2.0 * (double)d->N * d->seg[0].ty.n * d->seg[0].tx.n * d->C;
+    int kio = io;                // the kernel's template word: the flags + the loader width of a bf16 source
+    if (s16) {
+        bool w = (d->src_ld % 8) == 0 && ((uintptr_t)src & 15) == 0;
+        for (int s = 0; s < d->nseg; ++s) w = w && (d->seg[s].src_off % 8) == 0 && (d->seg[s].src_bstride % 8) == 0;
+        if (!w) kio |= BF_SRC8;
+    }
+    // algorithmic bytes: the activations at their storage width, the filter at 2 bytes per element
+    {
+        double in_e = 0, out_e = 0;
+        for (int s = 0; s < d->nseg; ++s) {
+            in_e += (double)d->B * d->seg[s].src_H * d->seg[s].src_W * d->C;
+            out_e += (double)d->B * d->seg[s].rows_y * d->seg[s].rows_x * d->N;
+        }
+        p.alg_bytes = zsg_conv_alg_bytes(d, add_src != nullptr) - 2.0 * (double)d->N * d->seg[0].ty.n * d->seg[0].tx.n * d->C
+                      - (s16 ? 2.0 * in_e : 0.0) - (o16 ? 2.0 * out_e : 0.0) - ((a16 && add_src) ? 2.0 * out_e : 0.0);
+    }
     hipStream_t st = (hipStream_t)stream;
-    if (BM == 128 && BN == 128) return launch_bf16<128, 128>(p, st, fl, "igemm_bf16_kernel<128, 128>");
-    if (BM == 128 && BN == 64) return launch_bf16<128, 64>(p, st, fl, "igemm_bf16_kernel<128, 64>");
-    return launch_bf16<64, 64>(p, st, fl, "igemm_bf16_kernel<64, 64>");
+    // (the fp32-in-memory kernel keeps the profile names it had; the others carry their flag word, "h" = the two-halves loader)
+#define BF_CASE(k, suf)                                                                                                                      \
+    case k:                                                                                                                                  \
+        return launch_bf16_tile<k>(BM, BN, p, st, fl, "igemm_bf16_kernel<64, 64" suf ">", "igemm_bf16_kernel<128, 64" suf ">",                \
+                                   "igemm_bf16_kernel<128, 128" suf ">");
+    switch (kio) {
+        BF_CASE(0, "")
+        BF_CASE(1, ", 1")
+        BF_CASE(2, ", 2")
+        BF_CASE(3, ", 3")
+        BF_CASE(4, ", 4")
+        BF_CASE(5, ", 5")
+        BF_CASE(6, ", 6")
+        BF_CASE(7, ", 7")
+        BF_CASE(9, ", 1h")
+        BF_CASE(11, ", 3h")
+        BF_CASE(13, ", 5h")
+        BF_CASE(15, ", 7h")
+    }
+#undef BF_CASE
+    ZSG_FAIL(-1, "%s: io_flags %d", who, io);
+}
+
+extern "C" int zsg_conv_igemm_bf16(const zsg_conv_desc* d, const float* src, const uint16_t* wt_packed, float* out, const float* bias,
+                                   const float* add_src, void* stream) {
+    return conv_bf16_run("conv_igemm_bf16", d, src, wt_packed, out, bias, add_src, 0, stream);
+}
+
+extern "C" int zsg_conv_igemm_bf16_io(const zsg_conv_desc* d, const void* src, const uint16_t* wt_packed, void* out, const float* bias,
+                                      const void* add_src, int32_t io_flags, void* stream) {
+    return conv_bf16_run("conv_igemm_bf16_io", d, src, wt_packed, out, bias, add_src, io_flags, stream);
 }

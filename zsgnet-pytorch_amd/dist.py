@@ -301,6 +301,11 @@ class DistributedDataParallel(nn.Module):
             self._sync_buffers()
         return self.module(inp)
 
+    def eval_precision(self, dtype: str = "fp32"):
+        """ZSGNet.eval_precision of the wrapped network ("fp32" | "bf16" | "bf16_act"): eval plans are per rank, nothing is communicated"""
+        self.module.eval_precision(dtype)
+        return self
+
     def close(self):
         """Releases the native communicator (its RCCL communicator, stream and events); the wrapper is unusable afterwards."""
         if self.comm is not None:

@@ -37,7 +37,7 @@ from .params import ParamStore, pad4, register_named
 VGG_BASE = [64, 64, "M", 128, 128, "M", 256, 256, 256, "C", 512, 512, 512, "M", 512, 512, 512]     # ssd_vgg.py:174-177
 SSD_EXTRAS = [256, "S", 512, 128, "S", 256, 128, 256, 128, 256]                                          # ssd_vgg.py:179-182
 
-EVAL_DTYPES = ("fp32", "bf16")    # cfg eval_dtype / ZSGNet.eval_precision: operand precision of the eval plans' convolutions
+EVAL_DTYPES = ("fp32", "bf16", "bf16_act")    # cfg eval_dtype / ZSGNet.eval_precision: operand precision of the eval plans' convolutions (+ bf16 activation storage)
 LSTM_DIMS = (32, 64, 128, 256)    # cfg lstm_dim: the widths csrc/lstm.hip instantiates zsg_lstm_fwd / zsg_lstm_bwd for
 
 LIVE_NETS = weakref.WeakSet()      # every ZSGNet alive: optim.clip_grad_norm_ finds a parameter's flat store here
@@ -105,6 +105,11 @@ class Act(TView):
         self.gfilled = False
         self.needs_mask = False
         self.requires_grad = True
+
+    @property
+    def b16(self) -> bool:
+        """stored as bf16 (a bf16_act eval plan); the layout is in ELEMENTS either way"""
+        return self.buf.dtype == torch.bfloat16
 
     def lvl(self, i) -> "Act":
         a = Act(self.buf, self.B, self.C, self.ld, [self.levels[i]], f"{self.name}[{i}]")
@@ -554,8 +559,10 @@ class ZSGNet(nn.Module):
         """Operand precision of the convolutions of the EVAL plans: "fp32" (default: what every plan lowered before) or "bf16" — every
         convolution behind the stem runs on bf16 MFMA (zsg_conv_igemm_bf16: fp32 activations rounded by the operand loader, weights packed
         once per forward, fp32 accumulation and epilogue); the stem, the query encoder, the language map, pooling, upsampling and
-        l2norm stay fp32.  Train-mode plans are untouched.  The eval plan cache is keyed by the dtype, so switching back and forth
-        reuses plans."""
+        l2norm stay fp32 — or "bf16_act": "bf16", and the activations between the stem's max-pool and the heads' last convolution are STORED
+        as bf16 (half the activation bytes of the plan; each value rounded once where it is stored, all arithmetic fp32: include/zsg.h), the
+        stem's output, the query encoder, the language maps, the shared plan's accumulator and the outputs stay fp32.  Train-mode plans are
+        untouched.  The eval plan cache is keyed by the dtype, so switching back and forth reuses plans."""
         if dtype not in EVAL_DTYPES:
             raise ValueError(f"eval_dtype={dtype!r}: expected one of {', '.join(EVAL_DTYPES)}")
         self._eval_dtype = dtype
@@ -753,7 +760,12 @@ class _Plan:
         # eval plans only (ZSGNet.eval_precision): every convolution zsg_conv_igemm_bf16 supports is lowered to it; their weights are
         # packed to bf16 by ONE zsg_pack_w_bf16_batched launch per forward (behind the BatchNorm fold, whose output it reads)
         assert dtype in EVAL_DTYPES and not (training and dtype != "fp32")
-        self.bf16 = dtype == "bf16"
+        self.bf16 = dtype in ("bf16", "bf16_act")
+        # bf16_act: the activations behind the stem are 16-bit buffers (adt), the convolutions go through zsg_conv_igemm_bf16_io with the
+        # flags their operands' dtypes imply, the element-wise launches through csrc/bf16_act.hip; an operation without a bf16 form is
+        # wrapped in casts (_f32 / _via_f32)
+        self.act16 = dtype == "bf16_act"
+        self.adt = torch.bfloat16 if self.act16 else torch.float32
         self.pack_jobs, self.pack_blocks, self.pack_keep, self.pack_jobs_dev = [], 0, [], None
         # Q: a shared-image plan (ZSGNet._forward_shared) — the image trunk up to conv0's feature GEMM is lowered at batch B (image
         # slots), the query encoder and everything behind zsg_head_shared_conv0 at batch Q; every other plan has one batch, Q == B.  A
@@ -852,23 +864,59 @@ class _Plan:
         self.bytes += t.numel() * t.element_size()
         return t
 
-    def act(self, name, B, H, W, C, ld=None, requires_grad=True) -> Act:
+    def act(self, name, B, H, W, C, ld=None, requires_grad=True, dtype=torch.float32) -> Act:
         ld = ld or C
-        a = Act(self._buf(B * H * W * ld), B, C, ld, [Level(0, H, W, H * W * ld)], name)
+        a = Act(self._buf(B * H * W * ld, dtype=dtype), B, C, ld, [Level(0, H, W, H * W * ld)], name)
         a.requires_grad = requires_grad
         self.acts[name] = a
         return a
 
-    def packed(self, name, B, sizes, C, ld=None) -> Act:
+    def packed(self, name, B, sizes, C, ld=None, dtype=torch.float32) -> Act:
         """pyramid levels packed level-major in one buffer"""
         ld = ld or C
         lv, off = [], 0
         for (h, w) in sizes:
             lv.append(Level(off, h, w, h * w * ld))
             off += B * h * w * ld
-        a = Act(self._buf(off), B, C, ld, lv, name)
+        a = Act(self._buf(off, dtype=dtype), B, C, ld, lv, name)
         self.acts[name] = a
         return a
+
+    # ---- bf16_act: casts around an operation that has no bf16 form ------------------------------------------------------------
+    @staticmethod
+    def _span(a: Act) -> Tuple[int, int]:
+        """(first element, element count) of the buffer region an activation owns: one level of a packed buffer, or all of it"""
+        if len(a.levels) == 1:
+            return a.levels[0].off, a.B * a.levels[0].bstride
+        return 0, a.buf.numel()
+
+    def _twin32(self, a: Act) -> Act:
+        """an fp32 buffer with the element layout of the bf16 activation `a` (same offsets: descriptors built on `a` stay valid)"""
+        t = Act(self._buf(a.buf.numel()), a.B, a.C, a.ld, a.levels, a.name + ".f32")
+        t.requires_grad = a.requires_grad
+        return t
+
+    def _f32(self, a: Optional[Act], lane: int = 0) -> Optional[Act]:
+        """`a` itself when it is fp32, else its fp32 copy (one zsg_cast_bf16_f32 launch)"""
+        if a is None or not a.b16:
+            return a
+        t = self._twin32(a)
+        o, n = self._span(a)
+        self.fwd.add(lib.zsg_cast_bf16_f32, a.buf[o:], n, t.buf[o:], what="cast f32<-" + a.name, lane=lane)
+        return t
+
+    def _via_f32(self, src: Optional[Act], out: Act, add: Optional[Act] = None, lane: int = 0):
+        """(src, out, add) as fp32 Acts for an fp32-only launch + finish(): the launch that rounds the fp32 result into the bf16 `out`.
+        Identities when nothing is bf16."""
+        s32, a32 = self._f32(src, lane), self._f32(add, lane)
+        if not out.b16:
+            return s32, out, a32, lambda: None
+        o32 = self._twin32(out)
+
+        def finish():
+            o, n = self._span(out)
+            self.fwd.add(lib.zsg_cast_f32_bf16, o32.buf[o:], n, out.buf[o:], what="cast bf16<-" + out.name, lane=lane)
+        return s32, o32, a32, finish
 
     def like(self, a: Act, name=None) -> Act:
         if len(a.levels) == 1:           # a level of a packed buffer gets a compact twin, not a copy of the whole pack
@@ -967,7 +1015,14 @@ class _Plan:
         False: the caller lowers the fp32 launch).  w_src: the fp32 OHWI weight (raw parameter storage or a folded copy) whose channel
         window [wc0, wc0 + d.C) of wC is packed to uint16 [N][taps][C8]; the job joins the plan's one pack launch and the image is
         filled once now, so that the tuner times real data."""
-        if not self.bf16 or self.training or not lib.zsg_conv_igemm_bf16_supported(_ct.byref(d)):
+        if not self.bf16 or self.training:
+            return False
+        b16 = lambda t: t is not None and t.dtype == torch.bfloat16
+        io = (1 if b16(src_buf) else 0) | (2 if b16(out_buf) else 0) | (4 if b16(add_src) else 0)      # SRC_BF16 | OUT_BF16 | ADD_BF16
+        if self.act16:
+            if not lib.zsg_conv_igemm_bf16_io_supported(_ct.byref(d), io):
+                return False
+        elif not lib.zsg_conv_igemm_bf16_supported(_ct.byref(d)):
             return False
         T, c8 = d.wR * d.wS, (d.C + 7) // 8 * 8
         assert wc0 + d.C <= wC and w_src.numel() >= d.N * T * wC
@@ -981,6 +1036,10 @@ class _Plan:
         self.pack_blocks += nblk
         self.pack_keep.append(w_src)
         args = (src_buf, wp, out_buf, bias, add_src)
+        if self.act16:
+            self._tune("igemm", lib.zsg_conv_igemm_bf16_io, d, args + (io,), stream_ptr())
+            self.fwd.add(lib.zsg_conv_igemm_bf16_io, d, *args, io, what=what + f"+bf16io{io}", lane=lane)
+            return True
         self._tune("igemm", lib.zsg_conv_igemm_bf16, d, args, stream_ptr())
         self.fwd.add(lib.zsg_conv_igemm_bf16, d, *args, what=what + "+bf16", lane=lane)
         return True
@@ -1037,7 +1096,7 @@ class _Plan:
             lv = src.levels
             assert len(lv) == 1
             out = self.act(name or L.name, src.B, conv_out(lv[0].H, L.k, L.stride, L.pad, L.dil),
-                           conv_out(lv[0].W, L.k, L.stride, L.pad, L.dil), L.cout)
+                           conv_out(lv[0].W, L.k, L.stride, L.pad, L.dil), L.cout, dtype=torch.float32 if L.merge_x else self.adt)
         d = fwd_desc(src, out, L.cpad, L.cout, L.k, L.stride, L.pad, L.dil, wC=L.cpad, relu=relu, merge_x=L.merge_x)
         bias = self.P(L.name + ".bias") if L.bias else None
         rd = src
@@ -1058,6 +1117,13 @@ class _Plan:
             out.bn_chunks, out.bn_inline, out.needs_mask, out.requires_grad = 0, None, relu, self._conv_rg(L, src)
             src._consumed = True
             self.tape.append(lambda: None)
+            return out
+        if src.b16 or out.b16:
+            # bf16_act, a convolution the bf16 entry refuses: the fp32 lowering between casts
+            s32, o32, _, finish = self._via_f32(src, out, lane=self._lane)
+            self.conv(L, s32, relu=relu, out=o32, bn_fuse=bn_fuse)
+            finish()
+            out.bn_chunks, out.bn_inline, out.needs_mask, out.requires_grad = 0, None, relu, o32.requires_grad
             return out
         wargs = None
         if wino_ok(L.k, L.stride, L.pad, L.dil) and not L.merge_x and wino_mode() != "0":
@@ -1218,12 +1284,20 @@ class _Plan:
                                b_off, self.fold_rows, L.cout, L.k * L.k * L.cpad, Lb.index))
         self.fold_rows += L.cout
         lv = x.levels[0]
-        out = self.act(name or Lb.name, x.B, conv_out(lv.H, L.k, L.stride, L.pad, L.dil), conv_out(lv.W, L.k, L.stride, L.pad, L.dil), L.cout)
+        out = self.act(name or Lb.name, x.B, conv_out(lv.H, L.k, L.stride, L.pad, L.dil), conv_out(lv.W, L.k, L.stride, L.pad, L.dil), L.cout,
+                       dtype=torch.float32 if L.merge_x else self.adt)       # (the stem convolution's output stays fp32)
         d = fwd_desc(x, out, L.cpad, L.cout, L.k, L.stride, L.pad, L.dil, wC=L.cpad, relu=relu, merge_x=L.merge_x)
         wt, bias = self.fold_arena[w_off:w_off + n_w], self.fold_arena[b_off:b_off + L.cout]
         args = (x.buf, wt, out.buf, bias, residual.buf if residual is not None else None, None, None)
         if self._bf16_conv(d, x.buf, wt, L.cpad, 0, out.buf, bias, args[4], L.name + "+bn"):
             return out
+        if x.b16 or out.b16 or (residual is not None and residual.b16):
+            # bf16_act, a convolution the bf16 entry refuses: the fp32 launch below between casts
+            x32, o32, r32, finish = self._via_f32(x, out, residual)
+            args = (x32.buf, wt, o32.buf, bias, r32.buf if r32 is not None else None, None, None)
+            x, real_out, out = x32, out, o32
+        else:
+            real_out, finish = out, (lambda: None)
         wargs = None
         if wino_ok(L.k, L.stride, L.pad, L.dil) and not L.merge_x and wino_mode() != "0":
             U, job = self._wino_u(wt.data_ptr(), L.cout, L.cpad, L.k * L.k * L.cpad, L.cpad, 0)
@@ -1234,7 +1308,8 @@ class _Plan:
             self.fwd.add(lib.zsg_conv_wino, d, *wargs, what=L.name + "+bn")
         else:
             self.fwd.add(lib.zsg_conv_igemm, d, *args, what=L.name + "+bn")
-        return out
+        finish()
+        return real_out
 
     def _wt(self, L: ConvL, cred: int) -> torch.Tensor:
         """transposed weight image [cpad][k*k][cred] for the data gradient (a slice of one arena); all images are
@@ -1622,9 +1697,13 @@ class _Plan:
                 x = self._lower_stem_fused(C[e + "conv1"], BN[e + "bn1"], x0, H1, W1, H2, W2)
             else:
                 a = self.conv_bn(C[e + "conv1"], BN[e + "bn1"], x0, True, name="stem.a", yname="stem.y")
-                x = self.act("pool", B, H2, W2, 64)
-                idx = self._buf((B * H2 * W2 * 64 + 3) // 4)      # uint8 indices, stored in a float-sized buffer
-                self.fwd.add(lib.zsg_maxpool_fwd, a.buf, B, H1, W1, 64, 3, 2, 1, H2, W2, x.buf, idx, what="maxpool")
+                x = self.act("pool", B, H2, W2, 64, dtype=self.adt)
+                if self.act16:                                    # fp32 stem output -> bf16 (no indices: nothing runs backward)
+                    idx = None
+                    self.fwd.add(lib.zsg_maxpool_fwd_bf16, a.buf, int(a.b16), B, H1, W1, 64, 3, 2, 1, H2, W2, x.buf, what="maxpool")
+                else:
+                    idx = self._buf((B * H2 * W2 * 64 + 3) // 4)      # uint8 indices, stored in a float-sized buffer
+                    self.fwd.add(lib.zsg_maxpool_fwd, a.buf, B, H1, W1, 64, 3, 2, 1, H2, W2, x.buf, idx, what="maxpool")
                 pool_in, pool_out = a, x
 
                 def pool_back():
@@ -1854,10 +1933,14 @@ class _Plan:
                 o -= 1
             return o
         Ho, Wo = osz(l.H), osz(l.W)
-        out = self.act(name, x.B, Ho, Wo, x.C)
+        out = self.act(name, x.B, Ho, Wo, x.C, dtype=self.adt)
         out.requires_grad = x.requires_grad
-        idx = self._buf((x.B * Ho * Wo * x.C + 3) // 4)
-        self.fwd.add(lib.zsg_maxpool_fwd, x.buf, x.B, l.H, l.W, x.C, k, s, p, Ho, Wo, out.buf, idx, what=name)
+        if self.act16:
+            idx = None
+            self.fwd.add(lib.zsg_maxpool_fwd_bf16, x.buf, int(x.b16), x.B, l.H, l.W, x.C, k, s, p, Ho, Wo, out.buf, what=name)
+        else:
+            idx = self._buf((x.B * Ho * Wo * x.C + 3) // 4)
+            self.fwd.add(lib.zsg_maxpool_fwd, x.buf, x.B, l.H, l.W, x.C, k, s, p, Ho, Wo, out.buf, idx, what=name)
 
         def back():
             if out.grad is None:
@@ -1873,10 +1956,13 @@ class _Plan:
         l = x.levels[0]
         rows = x.B * l.H * l.W
         if out is None:
-            out = self.act(name, x.B, l.H, l.W, x.C)
+            out = self.act(name, x.B, l.H, l.W, x.C, dtype=x.buf.dtype)
         out.requires_grad = x.requires_grad
         nrm = self._buf(rows)
-        self.fwd.add(lib.zsg_l2norm_fwd, self.base(x), rows, x.C, self.base(out), nrm, what=name, lane=lane)
+        # (bf16_act: no bf16 form — the fp32 kernel between casts; identities in every other plan)
+        x32, o32, _, finish = self._via_f32(x, out, lane=lane)
+        self.fwd.add(lib.zsg_l2norm_fwd, self.base(x32), rows, x.C, self.base(o32), nrm, what=name, lane=lane)
+        finish()
 
         def back():
             if out.grad is None:
@@ -1953,7 +2039,7 @@ class _Plan:
     def _pyramid(self, sizes) -> List[Act]:
         """The head's input features: all pyramid levels packed level-major in ONE buffer (so every head convolution is
         one grouped launch); the producers write their level in place."""
-        self.Fpack = self.packed("head.feat_raw" if self.net.do_norm else "head.feat", self.B, sizes, 256)
+        self.Fpack = self.packed("head.feat_raw" if self.net.do_norm else "head.feat", self.B, sizes, 256, dtype=self.adt)
         lv = [self.Fpack.lvl(i) for i in range(len(sizes))]
         for i, a in enumerate(lv):
             a.name = f"feat{i}"
@@ -2025,10 +2111,10 @@ class _Plan:
         f = "backbone.fpn."
         with self.on_side_stream():
             p6 = self.conv(C[f + "P6"], c5, out=o6)
-            r6 = self.act("r6", B, p6.levels[0].H, p6.levels[0].W, 256)
+            r6 = self.act("r6", B, p6.levels[0].H, p6.levels[0].W, 256, dtype=self.adt)
             r6.requires_grad = p6.requires_grad
             n6 = r6.buf.numel()
-            self.fwd.add(lib.zsg_relu_fwd, self.base(p6), n6, r6.buf, what="relu(p6)", lane=self._lane)
+            self.fwd.add(lib.zsg_relu_fwd_bf16 if self.act16 else lib.zsg_relu_fwd, self.base(p6), n6, r6.buf, what="relu(p6)", lane=self._lane)
 
             def relu_back():
                 if r6.grad is None:
@@ -2043,7 +2129,8 @@ class _Plan:
             l7 = p7.levels[0]
             p8 = o8
             p8.requires_grad = p7.requires_grad
-            self.fwd.add(lib.zsg_avgpool_fwd, self.base(p7), B, l7.H * l7.W, 256, self.base(p8), what="avgpool", lane=self._lane)
+            self.fwd.add(lib.zsg_avgpool_fwd_bf16 if self.act16 else lib.zsg_avgpool_fwd, self.base(p7), B, l7.H * l7.W, 256, self.base(p8),
+                         what="avgpool", lane=self._lane)
 
             def avg_back():
                 if p8.grad is None:
@@ -2056,10 +2143,11 @@ class _Plan:
 
     def _upsample_add(self, a: Act, p: Act, name: str, join: bool = False) -> Act:
         la, lp = a.levels[0], p.levels[0]
-        out = self.act(name, a.B, la.H, la.W, a.C)
+        out = self.act(name, a.B, la.H, la.W, a.C, dtype=self.adt)
         out.requires_grad = a.requires_grad or p.requires_grad
-        self.fwd.add(lib.zsg_upsample_add_fwd, a.buf, p.buf, a.B, lp.H, lp.W, la.H, la.W, a.C, out.buf, what=name,
-                     lane=2 if (join and self.training) else 0)
+        assert a.b16 == p.b16 == out.b16
+        self.fwd.add(lib.zsg_upsample_add_fwd_bf16 if self.act16 else lib.zsg_upsample_add_fwd, a.buf, p.buf, a.B, lp.H, lp.W, la.H, la.W, a.C,
+                     out.buf, what=name, lane=2 if (join and self.training) else 0)
 
         def back():
             if out.grad is None:
@@ -2137,7 +2225,7 @@ class _Plan:
             self.Fpack.requires_grad = feat_rg
         heads_in = feats                         # the Acts whose .grad conv0's data gradient fills
         if net.do_norm and Cf:
-            hc.Fp = self.packed("head.feat", self.B, sizes, 256)
+            hc.Fp = self.packed("head.feat", self.B, sizes, 256, dtype=self.adt)
             hc.Fp.requires_grad = feat_rg
             heads_in = [self.l2norm(f, f"featnorm{i}", out=hc.Fp.lvl(i)) for i, f in enumerate(feats)]
         if net.do_norm and Cw:
@@ -2212,7 +2300,7 @@ class _Plan:
         W0n = L0.name + ".weight"
         cp = L0.cpad
         assert cp == Cf + Cw + Cg
-        h1 = self.packed(prefix + ".h1", B, sizes, 256)
+        h1 = self.packed(prefix + ".h1", B, sizes, 256, dtype=self.adt)
         # conv0 sees [features | language vector (constant over the image) | grid (constant over the batch)] (or a subset,
         # mdl.py:363-375): only the features go through the big implicit GEMM; the rest enters as an additive map
         #   lmap[b][p][n] = G[p][n] + sum_{tap valid at p} V[b][n*9+tap],  V = W0[:, :, :, lang] . we[b],  G = conv(grid, W0[..., grid])
@@ -2239,9 +2327,11 @@ class _Plan:
             a0 = (Fp.buf, self.P(W0n), Y.buf, None, None, None, None)
             wargs = None
             bf0 = self._bf16_conv(d0, Fp.buf, self.P(W0n), cp, 0, Y.buf, None, None, L0.name + ".feat")
+            if not bf0 and Fp.b16:           # (bf16_act and the bf16 entry refuses: the fp32 launch on a cast copy of the features)
+                a0 = (self._f32(Fp).buf,) + a0[1:]
             if not bf0 and wino_mode() != "0":
                 U0, job0 = self._wino_u(self.P(W0n).data_ptr(), 256, Cf, 9 * cp, cp, 0)
-                wargs = (Fp.buf, U0) + a0[2:]
+                wargs = (a0[0], U0) + a0[2:]
             if not bf0:
                 self._tune("igemm", lib.zsg_conv_igemm, d0, a0, stream_ptr(), wino_args=wargs)
                 if d0.use_wino:
@@ -2250,7 +2340,7 @@ class _Plan:
                 else:
                     self.fwd.add(lib.zsg_conv_igemm, d0, *a0, what=L0.name + ".feat")
             hw = torch.tensor([v for hw_ in sizes for v in hw_], dtype=torch.int32)
-            self.fwd.add(lib.zsg_head_shared_conv0, Y.buf, self.in_idx, 1, self.P(L0.name + ".bias"), G.buf if G is not None else None,
+            self.fwd.add(lib.zsg_head_shared_conv0_bf16 if h1.b16 else lib.zsg_head_shared_conv0, Y.buf, self.in_idx, 1, self.P(L0.name + ".bias"), G.buf if G is not None else None,
                          V.buf if V is not None else None, self.B, B, len(sizes), hw, 256, h1.buf, what=L0.name + ".shared")
         elif Cw or Cg:
             # None of this depends on the image: in training it runs on the side stream right behind the query encoder (the
@@ -2281,9 +2371,13 @@ class _Plan:
             a0 = (Fp.buf, self.P(W0n), h1.buf, self.P(L0.name + ".bias"), lmap.buf if lmap is not None else None, None, None)
             wargs = None
             bf0 = self._bf16_conv(d0, Fp.buf, self.P(W0n), cp, 0, h1.buf, a0[3], a0[4], L0.name)
+            finish0 = lambda: None
+            if not bf0 and (Fp.b16 or h1.b16):      # (bf16_act and the bf16 entry refuses: the fp32 launch between casts)
+                f32_, h32, _, finish0 = self._via_f32(Fp, h1)
+                a0 = (f32_.buf, a0[1], h32.buf) + a0[3:]
             if not bf0 and wino_mode() != "0":
                 U0, job0 = self._wino_u(self.P(W0n).data_ptr(), 256, Cf, 9 * cp, cp, 0)
-                wargs = (Fp.buf, U0) + a0[2:]
+                wargs = (a0[0], U0) + a0[2:]
             if not bf0:
                 self._tune("igemm", lib.zsg_conv_igemm, d0, a0, stream_ptr(), wino_args=wargs)
                 if d0.use_wino:
@@ -2291,10 +2385,13 @@ class _Plan:
                     self.fwd.add(lib.zsg_conv_wino, d0, *wargs, what=L0.name)
                 else:
                     self.fwd.add(lib.zsg_conv_igemm, d0, *a0, what=L0.name)
+                finish0()
         else:                             # image-blind: h1 = relu(lmap + bias), an affine map with scale 1
             one, zero = self._buf(256) + 1.0, self._buf(256)
-            self.fwd.add(lib.zsg_bn_apply, lmap.buf, h1.rows(), 256, zero, one, one, self.P(L0.name + ".bias"), None, 1, h1.buf, None,
+            _, h32, _, finish0 = self._via_f32(None, h1)          # (bf16_act: zsg_bn_apply writes fp32; rounded into h1 by a cast)
+            self.fwd.add(lib.zsg_bn_apply, lmap.buf, h1.rows(), 256, zero, one, one, self.P(L0.name + ".bias"), None, 1, h32.buf, None,
                          what=L0.name)
+            finish0()
         h1.needs_mask = True
         w0t, b0t = self.trains(W0n), self.trains(L0.name + ".bias")
         we_rg = bool(Cw) and we.requires_grad
@@ -2361,7 +2458,7 @@ class _Plan:
         self.tape.append(head0_back)
         hs = [h1]
         for i in range(1, 5):
-            nxt = self.packed(f"{prefix}.h{i + 1}", B, sizes, 256)
+            nxt = self.packed(f"{prefix}.h{i + 1}", B, sizes, 256, dtype=self.adt)
             self.conv(C[f"{prefix}.{i}.0"], hs[-1], relu=True, out=nxt)      # backward via the tape
             hs.append(nxt)
         L5 = C[prefix + ".5"]
@@ -2658,7 +2755,7 @@ def get_default_net(num_anchors=1, cfg=None):
     kind = cfg["mdl_to_use"]
     arch = cfg["resnet_arch"] if "resnet_arch" in cfg else "resnet50"
     net = ZSGNet(kind, num_anchors, cfg=cfg, arch=arch)
-    net.eval_precision(cfg["eval_dtype"] if "eval_dtype" in cfg else "fp32")          # (raises on anything but fp32 / bf16)
+    net.eval_precision(cfg["eval_dtype"] if "eval_dtype" in cfg else "fp32")          # (raises on anything but fp32 / bf16 / bf16_act)
     path = cfg["pretrained_path"] if "pretrained_path" in cfg else ""
     if path:
         n = load_pretrained_encoder(net, path)

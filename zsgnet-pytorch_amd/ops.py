@@ -832,10 +832,12 @@ def autotune_conv(kind: str, fn, d: ConvDesc, args: Sequence, stream: int, ws_by
     if no_tune:
         return 0
     _check_table_arch()
-    bf16 = fn is lib.zsg_conv_igemm_bf16          # (d, src, packed weights, out, bias, add_src): no mask operand
+    io = fn is lib.zsg_conv_igemm_bf16_io         # (... add_src, io_flags): the storage formats are part of the key, through the name field
+    bf16 = io or fn is lib.zsg_conv_igemm_bf16    # (d, src, packed weights, out, bias, add_src): no mask operand
     add_src, mask = (args[4], None if bf16 else args[5]) if kind == "igemm" else (None, None)
     key = _sig(kind, d, (add_src is not None, mask is not None, add_src is not None and add_src is args[2], split_penalty_ms > 0,
-                         mode if wino_args is not None else "", deterministic(), "bf16" if bf16 else "fp32", fn.__name__,
+                         mode if wino_args is not None else "", deterministic(), "bf16" if bf16 else "fp32",
+                         fn.__name__ + (":io%d" % args[5] if io else ""),
                          os.environ.get("ZSG_PW", "1") != "0" and not (d.merge_x and os.environ.get("ZSG_MX", "1") == "0"),
                          allow_sk and os.environ.get("ZSG_SK", "1") != "0"))
     d._tune_key = key
