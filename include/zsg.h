@@ -121,6 +121,36 @@ int zsg_conv_wgrad(const zsg_conv_desc* d, const float* src, const float* dy, fl
                    size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Reduced-precision TRAINING weight gradient (wgrad_dtype = "bf16"; csrc/wgrad_bf16.hip): zsg_conv_wgrad's descriptor (the forward
+ * descriptor), dw layout with the wC / wc0 / wt_ld window, accumulate flag and workspace rule (zsg_conv_wgrad_workspace_bytes serves
+ * both entries) on v_mfma_f32_32x32x16_bf16.  Same GEMM: M = output channel, N = (tap, c) tap-major, K = pixel rows of dy.  The
+ * reference has no counterpart (autograd's fp32 weight gradient, or torch.autocast where the user asks for it).
+ * Numerical contract:
+ *   - src, dy and dw are fp32 in memory.  Every src and dy element is rounded to bf16 on its way into the matrix operand,
+ *     round-to-nearest-even, exactly as torch.Tensor.to(torch.bfloat16) (the conversion of zsg_conv_igemm_bf16: +-0 and +-inf preserved,
+ *     NaN stays NaN, a finite value above the largest bf16 becomes inf).
+ *   - a tap outside the image, a pixel row beyond a segment's last and a column beyond N / ncols contribute exactly +0: memory there is
+ *     never read (out-of-range buffer loads), and the channels N..out_ld-1 of a padded dy row (N = 45 in 48-wide rows) are replaced by
+ *     +0 before the conversion — their values never enter an MFMA, so 0 * NaN cannot happen.
+ *   - every product of two bf16 values is exact in fp32; products are accumulated in fp32 by the MFMA.  K tiles are 32 pixel rows and
+ *     never straddle a segment; a K slice accumulates its tiles in ascending pixel-row order (the order inside one MFMA is the
+ *     hardware's).
+ *   - with more than one K slice, the slices go to the workspace as fp32 slabs [splits][N][ncols] and are summed in a fixed order by the
+ *     slab reduction of zsg_conv_wgrad, which applies the window and accumulate; with one slice the kernel writes dw itself and honours
+ *     both.  accumulate == 0 never reads dw.  No atomics: the same input and the same tile_hint give the same bits on every run.
+ *   - tile_hint: 0 = the heuristic (128-wide tiles where N / ncols exceed 64; two blocks per CU, at most 64 slices, at least two K
+ *     tiles per slice), else BM | BN << 8 | splits << 16 with BM, BN out of {64, 128} and splits in 1..255 (clipped to half the K
+ *     tiles).  Workspace too small for the slices: -2.
+ * Not supported (-1, nothing launched, zsg_last_error names the argument; zsg_conv_wgrad_bf16_supported returns 0): merge_x (the
+ * stem: C = 4), out_ld % 4 != 0 or dy offsets that are not multiples of 4, an image stride >= 2^23 elements (the fp32 entry's wide
+ * fallback), tile_hint variant bits 24-27 and the BN field 255.  All other limits are zsg_conv_wgrad's.
+ * zsg_conv_wgrad_bf16_supported: 1 when zsg_conv_wgrad_bf16 accepts the descriptor (and its tile_hint), else 0 — the host asks at
+ * lowering time and keeps the fp32 launch instead of failing inside a backward. */
+int zsg_conv_wgrad_bf16(const zsg_conv_desc* d, const float* src, const float* dy, float* dw, int32_t accumulate, void* ws,
+                        size_t ws_bytes, void* stream);
+int32_t zsg_conv_wgrad_bf16_supported(const zsg_conv_desc* d);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Winograd F(2x2,3x3) convolution on fp32 MFMA: the 3x3 / stride 1 / pad 1 convolutions (forward and data gradient)
  * of the same call sites as zsg_conv_igemm — fpn_resnet.py:73-74,92-94 (Bottleneck.conv2), :141-152 (P*_2),
  * mdl.py:211-219 (the shared head) — at 4 instead of 9 multiply-adds per (pixel, cin, cout), still fp32 throughout

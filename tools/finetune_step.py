@@ -28,6 +28,13 @@ and direction on top of the gradient buckets.
 Adam launch: zsg_adam_step_ema + the statistics' zsg_ema_update), update() after an unattached step (one zsg_ema_update over both
 buffers), and the out-of-tree way, torch._foreach_lerp_ over clones of the ~170 strided parameter views.
 
+    python tools/finetune_step.py --wgrad-bf16 [--out profiles/wgrad_bf16_step.json]
+
+--wgrad-bf16 measures the convolution weight gradients on bf16 MFMA (ZSGNet.wgrad_precision("bf16"): zsg_conv_wgrad_bf16) against the
+fp32 plan, everything trainable.  Each variant also reports its weight-gradient kernel class per kernel (zsg_prof_*: the library's
+per-launch events over a few steps on one stream): wgrad_kernel / wino_wgrad_kernel / wgrad_bf16_kernel instantiations and
+wgrad_reduce_kernel, with launches and ms per step, TFLOP/s and algorithmic bytes per launch.
+
 host_enqueue_ms_per_step: host time to enqueue a step (starting from an idle GPU; equal
 to the GPU's ms_per_step when the host, not the GPU, sets the pace).  --only NAME[,NAME] runs the named variants alone (profiling).
 """
@@ -74,10 +81,56 @@ EMA_VARIANTS = {
 }
 EMA_DECAY = 0.999
 # (DistributedDataParallel with forced collectives, synchronized BatchNorm)
+# cfg wgrad_dtype of the variant's network
+WGRAD_VARIANTS = {
+    "fp32": "fp32",
+    "bf16_wgrad": "bf16",
+}
 SYNC_VARIANTS = {
     "ddp_forced": False,
     "ddp_forced_sync_bn": True,
 }
+
+
+WGRAD_KERNELS = ("wgrad_kernel", "wino_wgrad_kernel", "wgrad_bf16_kernel", "wgrad_reduce_kernel")
+
+
+def wgrad_class(step_fn, nprof=4):
+    """the weight-gradient kernel class of one variant, per kernel, taken with the library's own per-launch events (zsg_prof_*, as
+    bench.py's roofline leg and tools/eval_speed.py --per-kernel do): nprof steps with every launch alone on the GPU (one stream), so a
+    kernel's time is its own.  Rows are per kernel instantiation: launches and ms per step, TFLOP/s of the direct-form work, algorithmic
+    bytes per launch and the rate they amount to; wgrad_reduce_kernel is listed on its own."""
+    from zsgnet_pytorch_amd._lib import ProfEntry, lib
+    keep = ops.SIDE_STREAM
+    ops.SIDE_STREAM = False
+    try:
+        step_fn()
+        torch.cuda.synchronize()
+        lib.zsg_prof_enable(1)
+        for _ in range(nprof):
+            step_fn()
+        torch.cuda.synchronize()
+        lib.zsg_prof_enable(0)
+    finally:
+        ops.SIDE_STREAM = keep
+    arr = (ProfEntry * 256)()
+    n = lib.zsg_prof_collect(arr, 256)
+    rows, total = [], 0.0
+    for i in range(n):
+        e = arr[i]
+        name = e.name.decode()
+        total += e.ms / nprof
+        if name.split("<")[0] not in WGRAD_KERNELS:
+            continue
+        rows.append(dict(kernel=name, launches_per_step=e.launches / nprof, ms_per_step=round(e.ms / nprof, 4),
+                         us_per_launch=round(1e3 * e.ms / e.launches, 2),
+                         tflops=round(e.flops / (e.ms * 1e9), 1) if e.flops > 0 else None,
+                         alg_mbytes_per_launch=round(e.bytes / e.launches / 2 ** 20, 2) if e.bytes > 0 else None,
+                         alg_gbps=round(e.bytes / (e.ms * 1e6), 1) if e.bytes > 0 else None))
+    rows.sort(key=lambda r: -r["ms_per_step"])
+    return dict(wgrad_class_ms=round(sum(r["ms_per_step"] for r in rows), 4),
+                wgrad_reduce_ms=round(sum(r["ms_per_step"] for r in rows if r["kernel"].startswith("wgrad_reduce")), 4),
+                all_kernels_ms=round(total, 4), wgrad_kernels=rows)
 
 
 def main():
@@ -91,6 +144,7 @@ def main():
     ap.add_argument("--clip", action="store_true")
     ap.add_argument("--sync-bn", action="store_true")
     ap.add_argument("--ema", action="store_true")
+    ap.add_argument("--wgrad-bf16", action="store_true")
     ap.add_argument("--only", default="", help="comma-separated variant names to run (e.g. one variant under rocprofv3)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
@@ -110,19 +164,22 @@ def main():
     sd = None
     runs = {}
     if a.sync_bn:
-        variants = {k: ((), False, None, v, None) for k, v in SYNC_VARIANTS.items()}
+        variants = {k: ((), False, None, v, None, "fp32") for k, v in SYNC_VARIANTS.items()}
+    elif a.wgrad_bf16:
+        variants = {k: ((), False, None, None, None, v) for k, v in WGRAD_VARIANTS.items()}
     elif a.ema:
-        variants = {k: ((), False, None, None, v) for k, v in EMA_VARIANTS.items()}
+        variants = {k: ((), False, None, None, v, "fp32") for k, v in EMA_VARIANTS.items()}
     elif a.clip:
-        variants = {k: ((), False, c, None, None) for k, c in CLIP_VARIANTS.items()}
+        variants = {k: ((), False, c, None, None, "fp32") for k, c in CLIP_VARIANTS.items()}
     elif a.frozen_bn:
-        variants = {k: (v[0], v[1], None, None, None) for k, v in BN_VARIANTS.items()}
+        variants = {k: (v[0], v[1], None, None, None, "fp32") for k, v in BN_VARIANTS.items()}
     else:
-        variants = {k: (v, False, None, None, None) for k, v in VARIANTS.items()}
+        variants = {k: (v, False, None, None, None, "fp32") for k, v in VARIANTS.items()}
     if a.only:
         variants = {k: v for k, v in variants.items() if k in a.only.split(",")}
-    for name, (prefixes, bn_frozen, clip, sync_bn, ema) in variants.items():
+    for name, (prefixes, bn_frozen, clip, sync_bn, ema, wgrad_dtype) in variants.items():
         net = mdl.get_default_net(9, cfg)
+        net.wgrad_precision(wgrad_dtype)
         if sd is None:
             sd = {k: v.clone() for k, v in net.state_dict().items()}
         net.load_state_dict(sd)
@@ -194,6 +251,8 @@ def main():
         if v["clip"] is not None:
             res["variants"][name].update(clip=v["clip"][0], max_norm=v["clip"][1], last_grad_norm=round(float(v["norm"]), 6),
                                          engaged=float(v["norm"]) > v["clip"][1])
+        if a.wgrad_bf16:
+            res["variants"][name].update(wgrad_dtype=net._wgrad_dtype, **wgrad_class(lambda: step(v)))
         if v["ema"] is not None:
             res["variants"][name].update(ema=v["ema"], ema_decay=EMA_DECAY)
             if "avg" in v:

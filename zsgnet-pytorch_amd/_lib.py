@@ -115,6 +115,8 @@ SIGNATURES = {
     "zsg_wino_weights": (I32, [P, I32, I32, P]),
     "zsg_conv_wgrad_workspace_bytes": (SZ, [DP]),
     "zsg_conv_wgrad": (I32, [DP, P, P, P, I32, P, SZ, P]),
+    "zsg_conv_wgrad_bf16": (I32, [DP, P, P, P, I32, P, SZ, P]),
+    "zsg_conv_wgrad_bf16_supported": (I32, [DP]),
     "zsg_conv_wgrad_wino_workspace_bytes": (SZ, [DP]),
     "zsg_conv_wgrad_wino": (I32, [DP, P, P, P, I32, P, SZ, P]),
     "zsg_conv_wgrad_wino_batched": (I32, [DP, I32, P, P, P, I32, P, SZ, P]),

@@ -277,6 +277,8 @@ class DistributedDataParallel(nn.Module):
             key += (self.module._frozen_bn_key(),)       # (frozen BatchNorm layers lower other launches: tuned anew, broadcast anew)
         if self.module.training and hasattr(self.module, "_sync_bn_key"):
             key += (self.module._sync_bn_key(),)         # (so do synchronized ones: no in-kernel statistics finalize)
+        if self.module.training and getattr(self.module, "_wgrad_dtype", "fp32") != "fp32":
+            key += (("wgrad", self.module._wgrad_dtype),)    # (bf16 weight gradients are tuned under their own entries)
         if key in self._tuned:
             return
         self._tuned.add(key)
@@ -304,6 +306,11 @@ class DistributedDataParallel(nn.Module):
     def eval_precision(self, dtype: str = "fp32"):
         """ZSGNet.eval_precision of the wrapped network ("fp32" | "bf16" | "bf16_act"): eval plans are per rank, nothing is communicated"""
         self.module.eval_precision(dtype)
+        return self
+
+    def wgrad_precision(self, dtype: str = "fp32"):
+        """ZSGNet.wgrad_precision of the wrapped network ("fp32" | "bf16"): the gradients stay fp32, so buckets and collectives are unchanged"""
+        self.module.wgrad_precision(dtype)
         return self
 
     def close(self):

@@ -37,6 +37,7 @@ from .params import ParamStore, pad4, register_named
 VGG_BASE = [64, 64, "M", 128, 128, "M", 256, 256, 256, "C", 512, 512, 512, "M", 512, 512, 512]     # ssd_vgg.py:174-177
 SSD_EXTRAS = [256, "S", 512, 128, "S", 256, 128, 256, 128, 256]                                          # ssd_vgg.py:179-182
 
+WGRAD_DTYPES = ("fp32", "bf16")               # cfg wgrad_dtype / ZSGNet.wgrad_precision: operand precision of the training plans' convolution weight gradients
 EVAL_DTYPES = ("fp32", "bf16", "bf16_act")    # cfg eval_dtype / ZSGNet.eval_precision: operand precision of the eval plans' convolutions (+ bf16 activation storage)
 LSTM_DIMS = (32, 64, 128, 256)    # cfg lstm_dim: the widths csrc/lstm.hip instantiates zsg_lstm_fwd / zsg_lstm_bwd for
 
@@ -169,6 +170,7 @@ class ZSGNet(nn.Module):
         self._sync_bn_conf = None      # (process group it was made for, force) of that group
         self.debug = False
         self._eval_dtype = "fp32"      # operand precision of the eval plans' convolutions (eval_precision)
+        self._wgrad_dtype = "fp32"     # operand precision of the training plans' convolution weight gradients (wgrad_precision)
         LIVE_NETS.add(self)
 
     # ------------------------------------------------------------------------------------------------------
@@ -568,6 +570,33 @@ class ZSGNet(nn.Module):
         self._eval_dtype = dtype
         return self
 
+    def wgrad_precision(self, dtype: str = "fp32") -> "ZSGNet":
+        """Operand precision of the convolution weight gradients of the TRAINING plans: "fp32" (default: what every plan lowered before,
+        launch for launch) or "bf16" — every weight gradient that goes through _Plan.wgrad and that zsg_conv_wgrad_bf16 accepts runs on
+        bf16 MFMA (src and dy rounded by the operand loader, fp32 accumulation, the fp32 slab reduction; include/zsg.h).  The forward, the
+        loss, every data gradient, the stem's weight gradient and the directly lowered small ones (LSTM projections, head conv0's language
+        / grid columns) stay fp32: everything but those weight gradients keeps the fp32 plan's bits.  Eval plans ignore the switch.  The
+        precision is part of a training plan's identity: switching drops the training plans of the other precision."""
+        if dtype not in WGRAD_DTYPES:
+            raise ValueError(f"wgrad_dtype={dtype!r}: expected one of {', '.join(WGRAD_DTYPES)}")
+        self._wgrad_dtype = dtype
+        return self
+
+    def _wgrad_key(self) -> Tuple:
+        """what the weight-gradient precision adds to a training plan's key, in front of its trailing fields (_plan_for reads those by
+        position from the end and the leading ones by index): nothing for fp32, whose key stays what it always was"""
+        return () if self._wgrad_dtype == "fp32" else (("wgrad", self._wgrad_dtype),)
+
+    @staticmethod
+    def _key_wgrad(k: Tuple) -> str:
+        """the weight-gradient precision of a training plan's key"""
+        return next((e[1] for e in k[7:-1] if isinstance(e, tuple) and e[0] == "wgrad"), "fp32")
+
+    @staticmethod
+    def _key_shared(k: Tuple):
+        """("shared", Q) of a shared-image training plan's key, else None"""
+        return next((e for e in k[7:-1] if isinstance(e, tuple) and e[0] == "shared"), None)
+
     def _eval_key(self, B, H, W, T, Q: Optional[int] = None) -> Tuple:
         """plan-cache key of an eval plan; the default dtype keeps the key it always had"""
         dt = () if self._eval_dtype == "fp32" else (self._eval_dtype,)
@@ -588,15 +617,16 @@ class ZSGNet(nn.Module):
             # shared-image training plan: exactly B image slots and Q queries.  One (B, Q) at a time: a new one, like a new trainable set,
             # drops the shared training plans of the old (activation buffers must not pile up)
             fz, fb, sb = self._frozen_key(), self._frozen_bn_key(), self._sync_bn_key()
-            key = (B, H, W, T, fz, fb, sb, ("shared", Q), True)
+            key = (B, H, W, T, fz, fb, sb, ("shared", Q)) + self._wgrad_key() + (True,)
             if key not in self._plans:
-                for k in [k for k in self._plans if k[-1] and ((k[4], k[5], k[6]) != (fz, fb, sb) or (len(k) == 9 and (k[0], k[7][1]) != (B, Q)))]:
+                for k in [k for k in self._plans if k[-1] and ((k[4], k[5], k[6]) != (fz, fb, sb) or self._key_wgrad(k) != self._wgrad_dtype
+                                                               or (self._key_shared(k) is not None and (k[0], self._key_shared(k)[1]) != (B, Q)))]:
                     old = self._plans.pop(k)
                     if old._prep_pending:
                         torch.cuda.current_stream().wait_event(old._prep_ev)
                 bn_names = list(self.bns)
                 self._plans[key] = _Plan(self, B, H, W, T, True, frozen={self._param_names[i] for i in fz},
-                                         frozen_bn={bn_names[i] for i in fb}, Q=Q)
+                                         frozen_bn={bn_names[i] for i in fb}, Q=Q, wgrad_dtype=self._wgrad_dtype)
             return self._plans[key]
         if Q is not None:
             # eval-only plan of Q queries over B (bucketed) images; the cache of these is bounded: least recently used first out
@@ -616,17 +646,17 @@ class ZSGNet(nn.Module):
                 self._plans[key] = _Plan(self, B, H, W, T, False, dtype=self._eval_dtype)
             return self._plans[key]
         fz, fb, sb = self._frozen_key(), self._frozen_bn_key(), self._sync_bn_key()
-        key = (B, H, W, T, fz, fb, sb, True)
+        key = (B, H, W, T, fz, fb, sb) + self._wgrad_key() + (True,)
         if key not in self._plans:
             # a new trainable set, frozen-BatchNorm set or synchronized-BatchNorm set: the training plans of the old one go (gradual
             # unfreezing must not pile up activation buffers)
-            for k in [k for k in self._plans if k[-1] and (k[4], k[5], k[6]) != (fz, fb, sb)]:
+            for k in [k for k in self._plans if k[-1] and ((k[4], k[5], k[6]) != (fz, fb, sb) or self._key_wgrad(k) != self._wgrad_dtype)]:
                 old = self._plans.pop(k)
                 if old._prep_pending:           # (its side-stream weight preparation may still be reading the weights)
                     torch.cuda.current_stream().wait_event(old._prep_ev)
             bn_names = list(self.bns)
             self._plans[key] = _Plan(self, B, H, W, T, True, frozen={self._param_names[i] for i in fz},
-                                     frozen_bn={bn_names[i] for i in fb}, sync_bn={bn_names[i] for i in sb})
+                                     frozen_bn={bn_names[i] for i in fb}, sync_bn={bn_names[i] for i in sb}, wgrad_dtype=self._wgrad_dtype)
         return self._plans[key]
 
     def _forward_shared(self, inp: Dict[str, Any]) -> Dict[str, Any]:
@@ -755,8 +785,11 @@ class _Plan:
     """Static lowering of ZSGNet for one (B, H, W, T, training) geometry."""
 
     def __init__(self, net: ZSGNet, B: int, H: int, W: int, T: int, training: bool, frozen=frozenset(), frozen_bn=frozenset(),
-                 sync_bn=frozenset(), Q: Optional[int] = None, dtype: str = "fp32"):
+                 sync_bn=frozenset(), Q: Optional[int] = None, dtype: str = "fp32", wgrad_dtype: str = "fp32"):
         self.net, self.B, self.H, self.W, self.T, self.training = net, B, H, W, T, training
+        # training plans only (ZSGNet.wgrad_precision): the weight gradients that go through wgrad() are lowered to zsg_conv_wgrad_bf16
+        assert wgrad_dtype in WGRAD_DTYPES
+        self.wgrad_bf16 = training and wgrad_dtype == "bf16"
         # eval plans only (ZSGNet.eval_precision): every convolution zsg_conv_igemm_bf16 supports is lowered to it; their weights are
         # packed to bf16 by ONE zsg_pack_w_bf16_batched launch per forward (behind the BatchNorm fold, whose output it reads)
         assert dtype in EVAL_DTYPES and not (training and dtype != "fp32")
@@ -1355,7 +1388,7 @@ class _Plan:
             return
         if self.trains(L.name + ".weight"):
             dw = fwd_desc(src, dy, L.cpad, L.cout, L.k, L.stride, L.pad, L.dil, wC=L.cpad)
-            self.wgrad(dw, src, dy, L.name + ".weight", "wgrad:" + L.name)
+            self.wgrad(dw, src, dy, L.name + ".weight", "wgrad:" + L.name, merge_x=L.merge_x)
         if L.bias and self.trains(L.name + ".bias"):
             base = dy.levels[0].off
             self.bwd.add(lib.zsg_colsum, dy.buf[base:], 1, 0, dy.rows(), dy.ld, 0, L.cout, self.G(L.name + ".bias"), 1,
@@ -1363,19 +1396,33 @@ class _Plan:
         if src.requires_grad:
             self.dgrad(L, dy, src, n=L.cpad, completes_bn=completes_bn)
 
-    def wgrad(self, d, src: Act, dy: Act, pname: str, what: str):
+    def wgrad(self, d, src: Act, dy: Act, pname: str, what: str, merge_x: bool = False):
         """weight gradient of one parameter, accumulated into the flat gradient buffer (every parameter has exactly one
         wgrad launch per backward; the shared head's pyramid levels are segments of that one launch).  The autotuner's
-        trial launches write a scratch image, never the gradient buffer."""
+        trial launches write a scratch image, never the gradient buffer.  merge_x: the layer's forward descriptor is a merge_x one (the
+        network's first convolution, C = 4) — the weight-gradient descriptor does not carry the flag, the bf16 entry is asked with it."""
         gw = self.G(pname)
         args = (src.buf, dy.buf, gw, 1, self.wg_ws, self.wg_ws_bytes)
         targs = (src.buf, dy.buf, self.tune_dw, 0, self.wg_ws, self.wg_ws_bytes)
         s0 = d.seg[0]
         wino = (d.wR == 3 and d.wS == 3 and s0.sy == 1 and s0.ty.d0 == -1 and s0.ty.dstep == 1 and not d.merge_x
                 and dy.ld % 4 == 0 and wino_mode() != "0")       # 3x3 / stride 1 / pad 1: Winograd F(3x3,2x2) candidates
+        if self.wgrad_bf16 and self._wgrad_bf16_ok(d, merge_x):
+            # wgrad_dtype = "bf16": the same launch on bf16 MFMA (one direct kernel for 1x1 and 3x3: no Winograd candidates)
+            self._tune("wgrad", lib.zsg_conv_wgrad_bf16, d, targs, stream_ptr(), self.wg_ws_bytes)
+            self.bwd.add(lib.zsg_conv_wgrad_bf16, d, *args, what=what + "+bf16", lane=1)
+            self._wg_log.append((len(self.bwd.calls) - 1, d, src, dy, gw, pname, what + "+bf16"))
+            return
         self._tune("wgrad", lib.zsg_conv_wgrad, d, targs, stream_ptr(), self.wg_ws_bytes, wino_args=targs if wino else None)
         self.bwd.add(lib.zsg_conv_wgrad_wino if d.use_wino else lib.zsg_conv_wgrad, d, *args, what=what, lane=1)
         self._wg_log.append((len(self.bwd.calls) - 1, d, src, dy, gw, pname, what))
+
+    @staticmethod
+    def _wgrad_bf16_ok(d, merge_x: bool = False) -> bool:
+        """zsg_conv_wgrad_bf16_supported on the convolution's descriptor with the forward descriptor's merge_x flag"""
+        dq = type(d).from_buffer_copy(d)
+        dq.merge_x = int(bool(merge_x))
+        return bool(lib.zsg_conv_wgrad_bf16_supported(_ct.byref(dq)))
 
     def dgrad(self, L: ConvL, dy: Act, src: Act, n: int, row0: int = 0, dx: Optional[Act] = None, completes_bn: bool = False):
         """dx (+)= dgrad(dy) for input channels [row0, row0+n) of L; applies src's ReLU mask when required."""
@@ -2756,6 +2803,7 @@ def get_default_net(num_anchors=1, cfg=None):
     arch = cfg["resnet_arch"] if "resnet_arch" in cfg else "resnet50"
     net = ZSGNet(kind, num_anchors, cfg=cfg, arch=arch)
     net.eval_precision(cfg["eval_dtype"] if "eval_dtype" in cfg else "fp32")          # (raises on anything but fp32 / bf16 / bf16_act)
+    net.wgrad_precision(cfg["wgrad_dtype"] if "wgrad_dtype" in cfg else "fp32")       # (raises on anything but fp32 / bf16)
     path = cfg["pretrained_path"] if "pretrained_path" in cfg else ""
     if path:
         n = load_pretrained_encoder(net, path)

@@ -808,6 +808,23 @@ def igemm_partial_rows(d: ConvDesc) -> int:
     return n
 
 
+def wgrad_bf16_cands(N: int, ncols: int, rows: int, ws_bytes: int) -> list:
+    """tile hints the tuner times for zsg_conv_wgrad_bf16 (N output channels, ncols = taps x C weight columns, rows = pixel rows of dy):
+    the entry's four tiles (a 128-wide side only where the GEMM side exceeds 64) x the fp32 branch's split targets, clipped to two
+    32-row K tiles per slice and to the workspace.  No 256-column tile (BN 255), no variant bits, no Winograd."""
+    cands = []
+    for bm in ((64, 128) if N > 64 else (64,)):
+        for bn in ((64, 128) if ncols > 64 else (64,)):
+            nmn = ((N + bm - 1) // bm) * ((ncols + bn - 1) // bn)
+            seen = set()
+            for target in (256, 384, 512, 768, 1024, 2048):
+                sp = max(1, min(target // nmn, rows // 64, 255))
+                if sp not in seen and sp * N * ncols * 4 <= ws_bytes:
+                    seen.add(sp)
+                    cands.append(tile_hint(bm, bn, sp))
+    return cands
+
+
 def autotune_conv(kind: str, fn, d: ConvDesc, args: Sequence, stream: int, ws_bytes: int = 0, split_penalty_ms: float = 0.0,
                   wino_args: Optional[Sequence] = None, wino_fn=None, allow_sk: bool = True) -> int:
     """Pick d.tile_hint for `fn(d, *args, stream)` (kind: 'igemm' | 'wgrad') by timing the candidates on the real
@@ -876,6 +893,8 @@ def autotune_conv(kind: str, fn, d: ConvDesc, args: Sequence, stream: int, ws_by
                         cands.append(tile_hint(64, 64, sp, 1) | K64_FLAG)
                     if blocks64 * sp < 256:
                         cands.append(tile_hint(128, 64, sp))
+    elif fn is lib.zsg_conv_wgrad_bf16:
+        cands = wgrad_bf16_cands(d.N, d.seg[0].ty.n * d.seg[0].tx.n * d.C, rows, ws_bytes)
     else:
         ncols = d.seg[0].ty.n * d.seg[0].tx.n * d.C
         for bm in ((64, 128) if d.N > 64 else (64,)):
