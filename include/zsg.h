@@ -251,6 +251,29 @@ int32_t zsg_conv_igemm_bf16_supported(const zsg_conv_desc* d);
  * head conv0's feature GEMM needs), destination uint16 [N][T][C8] with C8 = roundup(C, 8), 16-byte aligned, channels C..C8-1 zero;
  * blk0 = running sum of ceil(N*T*C8/8 / 256); total_blocks = the final sum.  Rounding: the contract above. */
 int zsg_pack_w_bf16_batched(const void* jobs_dev, int32_t njobs, int32_t total_blocks, void* stream);
+/* ---------------------------------------------------------------------------------------------------------------
+ * Reduced-precision TRAINING convolution of the pyramid and the heads (train_dtype = "bf16_head"; csrc/igemm_bf16.hip): the forward
+ * convolutions and the data gradients of layers without BatchNorm.  zsg_conv_igemm_bf16_m is zsg_conv_igemm_bf16 (fp32 in memory) plus
+ * zsg_conv_igemm's last epilogue term, the ReLU mask of a data gradient.
+ * Numerical contract: zsg_conv_igemm_bf16's, word for word (src rounded to bf16 by the loader, round-to-nearest-even; weights rounded
+ * once by zsg_pack_w_bf16_batched; exact products, fp32 accumulation in the fixed tap-major K order; no split-K, no stream-K, no
+ * atomics: the same input gives the same bits on every run), and the epilogue in zsg_conv_igemm's order:
+ *       v = acc + bias[n] + add_src[o];  if relu: v = max(v, 0);  out[o] = mask_src[o] > 0 ? v : 0
+ *   - mask_src is fp32, indexed with the OUTPUT offsets (the forward activation whose gradient out is, rebased by the caller where
+ *     the two live at different offsets); an element passes where mask_src > 0: -0.0, +0.0, negative values and NaN give +0.0,
+ *     whatever v is (a select, not a product: an inf or NaN in a masked position does not spread).
+ *   - mask_src == NULL launches zsg_conv_igemm_bf16's kernel: the same bits.  The mask is a compile-time variant of the kernel, so the
+ *     kernels of the entries without it are the instructions they were.
+ *   - add_src may alias out; mask_src must not alias out.  mask_src 16-byte aligned takes the 16-byte epilogue with out / bias / add_src,
+ *     else the 4-byte one.
+ * For a data gradient the weight operand is the packed image of the TRANSPOSED filter [n][wR*wS][cred] (zsg_transpose_w_batched, then
+ * zsg_pack_w_bf16_batched with N = n, T = wR*wS, wC = C = cred): dy is rounded by the loader, the transposed weights by the packer.
+ * Supported / not supported: zsg_conv_igemm_bf16's lists (one check, bf16_check); there is no bn_partials operand and no epi_flags:
+ * a data gradient that carries a BatchNorm's backward sums stays fp32.
+ * zsg_conv_igemm_bf16_m_supported: 1 when zsg_conv_igemm_bf16_m accepts the descriptor (and its tile_hint), else 0. */
+int zsg_conv_igemm_bf16_m(const zsg_conv_desc* d, const float* src, const uint16_t* wt_packed, float* out, const float* bias,
+                          const float* add_src, const float* mask_src, void* stream);
+int32_t zsg_conv_igemm_bf16_m_supported(const zsg_conv_desc* d);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * bf16 ACTIVATION STORAGE for inference (eval_dtype = "bf16_act"; csrc/igemm_bf16.hip, csrc/bf16_act.hip).  Everything "bf16" has;

@@ -35,6 +35,15 @@ fp32 plan, everything trainable.  Each variant also reports its weight-gradient 
 per-launch events over a few steps on one stream): wgrad_kernel / wino_wgrad_kernel / wgrad_bf16_kernel instantiations and
 wgrad_reduce_kernel, with launches and ms per step, TFLOP/s and algorithmic bytes per launch.
 
+    python tools/finetune_step.py --train-bf16-head [--wgrad-bf16] [--out profiles/train_bf16_head_step.json]
+
+--train-bf16-head measures the forward convolutions and data gradients of the pyramid and the heads on bf16 MFMA
+(ZSGNet.train_precision("bf16_head"): zsg_conv_igemm_bf16 / zsg_conv_igemm_bf16_m) against the fp32 plan, everything trainable; together
+with --wgrad-bf16 four variants alternate: fp32, bf16_head, bf16_wgrad, both.  Each variant also reports, from per-launch events of its
+four programs replayed on one stream (ops.Program.profile), the forward and data-gradient launches of those layers (the Winograd /
+implicit-GEMM launches of the fp32 plan, the bf16 launches that replace them, the laterals' data gradients that stay fp32), the pack
+launches and the Winograd filter transforms.
+
 host_enqueue_ms_per_step: host time to enqueue a step (starting from an idle GPU; equal
 to the GPU's ms_per_step when the host, not the GPU, sets the pace).  --only NAME[,NAME] runs the named variants alone (profiling).
 """
@@ -86,6 +95,13 @@ WGRAD_VARIANTS = {
     "fp32": "fp32",
     "bf16_wgrad": "bf16",
 }
+# (cfg wgrad_dtype, cfg train_dtype) of the variant's network: --train-bf16-head alone runs the first two
+TRAIN_VARIANTS = {
+    "fp32": ("fp32", "fp32"),
+    "bf16_head": ("fp32", "bf16_head"),
+    "bf16_wgrad": ("bf16", "fp32"),
+    "bf16_head_bf16_wgrad": ("bf16", "bf16_head"),
+}
 SYNC_VARIANTS = {
     "ddp_forced": False,
     "ddp_forced_sync_bn": True,
@@ -133,6 +149,45 @@ def wgrad_class(step_fn, nprof=4):
                 all_kernels_ms=round(total, 4), wgrad_kernels=rows)
 
 
+def head_class(v, nprof=3):
+    """the launches train_dtype = "bf16_head" replaces, of one variant, from per-launch events: the plan's four programs replayed nprof
+    times on one stream (every launch alone on the GPU) right after a step, so every buffer holds that step's operands.  Per class the
+    launch count and the ms per step; the rows name every launch."""
+    net = v["net"]
+    plan = [p for k, p in net._plans.items() if k[-1]][0]
+    st = torch.cuda.current_stream().cuda_stream
+    acc = {}
+    for _ in range(nprof):
+        for tag, prog in (("fwd-prep", plan.prep_u), ("fwd", plan.fwd), ("bwd-prep", plan.prep), ("bwd", plan.bwd)):
+            for i, (what, fname, ms) in enumerate(prog.profile(st)):
+                k = (tag, i, what, fname)
+                acc[k] = acc.get(k, 0.0) + ms / nprof
+    convs = ("zsg_conv_igemm", "zsg_conv_wino", "zsg_conv_igemm_bf16", "zsg_conv_igemm_bf16_m")
+    cls = {}
+    for (tag, i, what, fname), ms in acc.items():
+        base = what[:-len("+bf16")] if what.endswith("+bf16") else what
+        c = None
+        if fname == "zsg_pack_w_bf16_batched":
+            c = "pack_" + ("fwd" if tag == "fwd-prep" else "bwd")
+        elif fname == "zsg_wino_weights":
+            c = "wino_filter_transforms_" + ("fwd" if tag in ("fwd-prep", "fwd") else "bwd")
+        elif tag == "fwd" and fname in convs and base.startswith(mdl.BF16_HEAD_PREFIXES):
+            c = "head_fwd_" + ("bf16" if "bf16" in fname else ("wino" if "wino" in fname else "igemm"))
+        elif tag == "bwd" and fname in convs and base.startswith("dgrad:") and base[6:].startswith(mdl.BF16_HEAD_PREFIXES):
+            c = "head_dgrad_" + ("bf16" if "bf16" in fname else ("wino" if "wino" in fname else "igemm"))
+        if c is not None:
+            e = cls.setdefault(c, dict(launches=0, ms_per_step=0.0, rows=[]))
+            e["launches"] += 1
+            e["ms_per_step"] += ms
+            e["rows"].append([what, fname, round(ms * 1e3, 1)])
+    for e in cls.values():
+        e["ms_per_step"] = round(e["ms_per_step"], 4)
+    tot = lambda pre: round(sum(e["ms_per_step"] for c, e in cls.items() if c.startswith(pre)), 4)
+    return dict(head_fwd_ms=tot("head_fwd_"), head_dgrad_ms=tot("head_dgrad_"), pack_ms=tot("pack_"), wino_filter_transforms_ms=tot("wino_filter"),
+                fwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "fwd"), 4),
+                bwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "bwd"), 4), head_classes=cls)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -145,6 +200,7 @@ def main():
     ap.add_argument("--sync-bn", action="store_true")
     ap.add_argument("--ema", action="store_true")
     ap.add_argument("--wgrad-bf16", action="store_true")
+    ap.add_argument("--train-bf16-head", action="store_true")
     ap.add_argument("--only", default="", help="comma-separated variant names to run (e.g. one variant under rocprofv3)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
@@ -164,22 +220,24 @@ def main():
     sd = None
     runs = {}
     if a.sync_bn:
-        variants = {k: ((), False, None, v, None, "fp32") for k, v in SYNC_VARIANTS.items()}
+        variants = {k: ((), False, None, v, None, "fp32", "fp32") for k, v in SYNC_VARIANTS.items()}
+    elif a.train_bf16_head:
+        variants = {k: ((), False, None, None, None, v[0], v[1]) for k, v in TRAIN_VARIANTS.items() if a.wgrad_bf16 or v[0] == "fp32"}
     elif a.wgrad_bf16:
-        variants = {k: ((), False, None, None, None, v) for k, v in WGRAD_VARIANTS.items()}
+        variants = {k: ((), False, None, None, None, v, "fp32") for k, v in WGRAD_VARIANTS.items()}
     elif a.ema:
-        variants = {k: ((), False, None, None, v, "fp32") for k, v in EMA_VARIANTS.items()}
+        variants = {k: ((), False, None, None, v, "fp32", "fp32") for k, v in EMA_VARIANTS.items()}
     elif a.clip:
-        variants = {k: ((), False, c, None, None, "fp32") for k, c in CLIP_VARIANTS.items()}
+        variants = {k: ((), False, c, None, None, "fp32", "fp32") for k, c in CLIP_VARIANTS.items()}
     elif a.frozen_bn:
-        variants = {k: (v[0], v[1], None, None, None, "fp32") for k, v in BN_VARIANTS.items()}
+        variants = {k: (v[0], v[1], None, None, None, "fp32", "fp32") for k, v in BN_VARIANTS.items()}
     else:
-        variants = {k: (v, False, None, None, None, "fp32") for k, v in VARIANTS.items()}
+        variants = {k: (v, False, None, None, None, "fp32", "fp32") for k, v in VARIANTS.items()}
     if a.only:
         variants = {k: v for k, v in variants.items() if k in a.only.split(",")}
-    for name, (prefixes, bn_frozen, clip, sync_bn, ema, wgrad_dtype) in variants.items():
+    for name, (prefixes, bn_frozen, clip, sync_bn, ema, wgrad_dtype, train_dtype) in variants.items():
         net = mdl.get_default_net(9, cfg)
-        net.wgrad_precision(wgrad_dtype)
+        net.wgrad_precision(wgrad_dtype).train_precision(train_dtype)
         if sd is None:
             sd = {k: v.clone() for k, v in net.state_dict().items()}
         net.load_state_dict(sd)
@@ -205,7 +263,8 @@ def main():
 
     def step(v):
         v["opt"].zero_grad()
-        lf(v["model"](bt), bt)["loss"].backward()
+        v["out"] = v["model"](bt)            # (kept: the forward program's output slot points at it until the next forward)
+        lf(v["out"], bt)["loss"].backward()
         if v["clip"] is not None:
             kind, max_norm = v["clip"]
             fn = optim.clip_grad_norm_ if kind == "fused" else torch.nn.utils.clip_grad_norm_
@@ -243,6 +302,8 @@ def main():
         res["variants"][name] = dict(ms_per_step=round(statistics.median(v["ms"]), 4), round_medians=[round(x, 4) for x in v["ms"]],
                                      host_enqueue_ms_per_step=round(statistics.median(v["host_ms"]), 4),
                                      bwd_launches=len(plan.bwd.calls), prep_launches=len(plan.prep.calls),
+                                     fwd_launches=len(plan.fwd.calls), fwd_prep_launches=len(plan.prep_u.calls),
+                                     fwd_prep=[c[2] for c in plan.prep_u.calls],
                                      stepped_params=sum(p.numel() for p in net.parameters() if p.grad is not None),
                                      frozen_tensors=sum(1 for p in net.parameters() if not p.requires_grad),
                                      frozen_bn_layers=len(net._frozen_bn_key()),
@@ -251,7 +312,9 @@ def main():
         if v["clip"] is not None:
             res["variants"][name].update(clip=v["clip"][0], max_norm=v["clip"][1], last_grad_norm=round(float(v["norm"]), 6),
                                          engaged=float(v["norm"]) > v["clip"][1])
-        if a.wgrad_bf16:
+        if a.train_bf16_head:
+            res["variants"][name].update(train_dtype=net._train_dtype, wgrad_dtype=net._wgrad_dtype, **head_class(v))
+        elif a.wgrad_bf16:
             res["variants"][name].update(wgrad_dtype=net._wgrad_dtype, **wgrad_class(lambda: step(v)))
         if v["ema"] is not None:
             res["variants"][name].update(ema=v["ema"], ema_decay=EMA_DECAY)

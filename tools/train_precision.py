@@ -1,8 +1,10 @@
-"""Developer tool (a report, not a test): what bf16 weight gradients (cfg wgrad_dtype / ZSGNet.wgrad_precision("bf16")) do to a short
-training run.  N Adam steps on seeded synthetic batches, once with wgrad_dtype = fp32 and once with bf16, from the SAME initial weights
-and the same batches; prints both loss curves and the relative L2 distance of the final weights.
+"""Developer tool (a report, not a test): what the reduced-precision TRAINING switches do to a short training run — bf16 weight gradients
+(cfg wgrad_dtype / ZSGNet.wgrad_precision("bf16")), the bf16 forward and data gradients of the pyramid and the heads (cfg train_dtype /
+ZSGNet.train_precision("bf16_head")), or both.  N Adam steps on seeded synthetic batches, once in fp32 and once with the switch, from the
+SAME initial weights and the same batches; prints both loss curves, the distance of the first step's gradients (same weights, same batch:
+the rounding's alone) and the relative L2 distance of the final weights.
 
-    python tools/train_precision.py [--steps 30] [--arch resnet50] [--size 300] [--bs 16] [--lr 1e-4] [--batches 4]
+    python tools/train_precision.py [--switch wgrad|train|both] [--steps 30] [--arch resnet50] [--size 300] [--bs 16] [--lr 1e-4] [--batches 4]
 
 ZSG_DETERMINISTIC=1 is set, so the fp32 run is reproducible and the distance is the bf16 rounding's alone."""
 import argparse
@@ -17,6 +19,7 @@ from zsgnet_pytorch_amd import config, loss, mdl, optim  # noqa: E402
 from zsgnet_pytorch_amd.synth import synthetic_batch  # noqa: E402
 
 ap = argparse.ArgumentParser()
+ap.add_argument("--switch", default="wgrad", choices=("wgrad", "train", "both"))
 ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--arch", default="resnet50")
 ap.add_argument("--size", type=int, default=300)
@@ -24,6 +27,10 @@ ap.add_argument("--bs", type=int, default=16)
 ap.add_argument("--lr", type=float, default=1e-4)
 ap.add_argument("--batches", type=int, default=4, help="distinct synthetic batches, visited round-robin")
 a = ap.parse_args()
+
+# (label, wgrad_dtype, train_dtype) of the two runs
+ON = dict(wgrad=("bf16-wgrad", "bf16", "fp32"), train=("bf16_head", "fp32", "bf16_head"), both=("bf16_head+bf16-wgrad", "bf16", "bf16_head"))[a.switch]
+RUNS = (("fp32", "fp32", "fp32"), ON)
 
 torch.cuda.set_device(0)
 cfg = config.get_cfg(resnet_arch=a.arch, bs=a.bs, resize_img=[a.size, a.size])
@@ -34,33 +41,43 @@ for i in range(a.batches):
     bt = {k: v.cuda() for k, v in synthetic_batch(a.bs, a.size, a.size, seed=100 + i).items()}
     bt["h0"], bt["c0"] = torch.zeros(2, a.bs, 128), torch.zeros(2, a.bs, 128)
     batches.append(bt)
-sd, curves, final = None, {}, {}
+sd, curves, final, g0, names, spans = None, {}, {}, {}, None, None
 w_init = None
-for dtype in mdl.WGRAD_DTYPES:
+for label, wdt, tdt in RUNS:
     torch.manual_seed(1234)
     net = mdl.get_default_net(9, cfg)
     if sd is None:
         sd = {k: v.clone() for k, v in net.state_dict().items()}
     net.load_state_dict(sd)
-    net.to("cuda").train().wgrad_precision(dtype)
+    net.to("cuda").train().wgrad_precision(wdt).train_precision(tdt)
     if w_init is None:
         w_init = net.store.flat.detach().double().cpu()
+        names, spans = list(net._param_names), {n: (net.store.entries[n].offset, net.store.entries[n].size) for n in net._param_names}
     opt = optim.FusedAdam(net, lr=a.lr, betas=(0.9, 0.99))
-    curves[dtype] = []
+    curves[label] = []
     for it in range(a.steps):
         bt = batches[it % len(batches)]
         opt.zero_grad()
         ls = lf(net(bt), bt)["loss"].mean()
         ls.backward()
+        if it == 0:
+            g0[label] = net.store.grad.detach().double().cpu()
         opt.step()
-        curves[dtype].append(float(ls))
+        curves[label].append(float(ls))
     torch.cuda.synchronize()
-    final[dtype] = net.store.flat.detach().double().cpu()
-print(f"train_precision: {a.arch} {a.size}x{a.size} B={a.bs}, {a.steps} Adam steps (lr {a.lr:g}) over {a.batches} synthetic batches")
-print("step   loss fp32     loss bf16-wgrad   difference")
-for it, (x, y) in enumerate(zip(curves["fp32"], curves["bf16"])):
+    final[label] = net.store.flat.detach().double().cpu()
+on = ON[0]
+print(f"train_precision: {a.arch} {a.size}x{a.size} B={a.bs}, {a.steps} Adam steps (lr {a.lr:g}) over {a.batches} synthetic batches; fp32 against {on}")
+print(f"step   loss fp32     loss {on}   difference")
+for it, (x, y) in enumerate(zip(curves["fp32"], curves[on])):
     print(f"{it:4d}   {x:.6f}    {y:.6f}        {y - x:+.2e}")
-d = final["bf16"] - final["fp32"]
+ga, gb = g0["fp32"], g0[on]
+print(f"first step's gradient (same weights, same batch): ||g - g_fp32||_2 / ||g_fp32||_2 = {float((gb - ga).norm() / ga.norm()):.3e}, "
+      f"cosine = {float((ga * gb).sum() / (ga.norm() * gb.norm())):.6f}")
+per = sorted(((float((gb[o:o + n] - ga[o:o + n]).norm() / ga[o:o + n].norm()), nm) for nm, (o, n) in spans.items() if float(ga[o:o + n].norm()) > 0), reverse=True)
+print("  largest per-parameter distances: " + ", ".join(f"{nm} {v:.2e}" for v, nm in per[:5]) + f"; median {per[len(per) // 2][0]:.2e}; bit-equal parameters: "
+      f"{sum(1 for nm, (o, n) in spans.items() if torch.equal(ga[o:o + n], gb[o:o + n]))} of {len(spans)}")
+d = final[on] - final["fp32"]
 moved = float((final["fp32"] - w_init).norm())
-print(f"distance travelled by the fp32 run: ||w_fp32 - w_init||_2 = {moved:.3e}; ||w_bf16 - w_fp32||_2 / that = {float(d.norm()) / moved:.3e}")
-print(f"final weights: ||w_bf16 - w_fp32||_2 / ||w_fp32||_2 = {float(d.norm() / final['fp32'].norm()):.3e}, max |difference| = {float(d.abs().max()):.3e}")
+print(f"distance travelled by the fp32 run: ||w_fp32 - w_init||_2 = {moved:.3e}; ||w - w_fp32||_2 / that = {float(d.norm()) / moved:.3e}")
+print(f"final weights: ||w - w_fp32||_2 / ||w_fp32||_2 = {float(d.norm() / final['fp32'].norm()):.3e}, max |difference| = {float(d.abs().max()):.3e}")

@@ -1,6 +1,9 @@
 // igemm_bf16.hip — the eval-only implicit-GEMM convolution on bf16 MFMA (eval_dtype = "bf16" / "bf16_act"), NHWC x packed bf16 weights, gfx950.
 //
-// Two entries, one kernel template.  zsg_conv_igemm_bf16: activations fp32 in memory (the text below).  zsg_conv_igemm_bf16_io: each of src /
+// Three entries, one kernel template.  zsg_conv_igemm_bf16: activations fp32 in memory (the text below).  zsg_conv_igemm_bf16_m (the
+// training plans of train_dtype = "bf16_head": forward convolutions and data gradients of the pyramid and the heads): the same, plus
+// igemm.hip's last epilogue term, the ReLU mask of a data gradient (mask_src, the template parameter MK: a compile-time variant of the
+// IO = 0 kernel, so the kernels without it keep their code; mask_src == NULL launches the first entry's kernel).  zsg_conv_igemm_bf16_io: each of src /
 // out / add_src is fp32 or bf16 in memory (io_flags, the template parameter IO; IO = 0 is the first entry's kernel, instruction for
 // instruction the same source path).  With a bf16 src the loader converts nothing: the 8-channel group of a tile row is ONE 16-byte buffer
 // load where src_ld and the segment offsets are multiples of 8, else two 8-byte loads (C = 36, src_ld = 36: rows are only 8-byte aligned),
@@ -103,15 +106,18 @@ struct BfParams {
     int vec;                    // 4-channel epilogue groups allowed (alignment of every operand checked on the host)
     double alg_bytes;           // host only
     BfSegDev seg[ZSG_MAX_SEG];
+    const float* mask_src;      // MK kernels only: fp32, indexed like out (behind the segments: the other kernels' argument offsets stay)
 };
 
 // BM x BN block tile, 4 waves (2 x 2), each wave TM x TN MFMA tiles of 32x32.  Two blocks per CU (at most 256 registers per lane).
 // IO: the storage formats of src / out / add_src (BF_SRC16 | BF_OUT16 | BF_ADD16); IO = 0 is the fp32-in-memory kernel of eval_dtype = "bf16".
 // BF_SRC8 (with BF_SRC16): the two-halves loader.  A compile-time choice: a run-time branch around the loads made the compiler wait for
 // them where the paths join, i.e. in front of the MFMAs they are meant to fly under.
+// MK (with IO = 0): the epilogue's last term, out = v * (mask_src[same index] > 0) behind the ReLU — a data gradient into a ReLU's input.
 #define BF_SRC8 8
-template <int BM, int BN, int IO>
+template <int BM, int BN, int IO, bool MK = false>
 __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
+    static_assert(!MK || IO == 0, "the mask variant is built for fp32 storage only");
     ZSG_SET_MAIN_PRIO();
     constexpr int WM = 2, WN = 2, NT = 256;
     constexpr int KG = BF_BK / 8;        // threads (8-channel groups) per tile row
@@ -322,6 +328,11 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
                 }
+                if constexpr (MK) {
+                    const f32x4 m = *(const f32x4*)(p.mask_src + o);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = (m[e] > 0.f) ? v[e] : 0.f;
+                }
                 if constexpr (IO & BF_OUT16) *(u32x2*)((uint16_t*)p.out + o) = bf16_pack4(v);      // rounded once, here
                 else *(f32x4*)((float*)p.out + o) = v;
             }
@@ -346,6 +357,7 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
                             else v += ((const float*)p.add_src)[o];
                         }
                         if (p.relu) v = fmaxf(v, 0.f);
+                        if constexpr (MK) v = (p.mask_src[o] > 0.f) ? v : 0.f;
                         if constexpr (IO & BF_OUT16) ((uint16_t*)p.out)[o] = bf16_round1(v);
                         else ((float*)p.out)[o] = v;
                     }
@@ -430,7 +442,12 @@ extern "C" int32_t zsg_conv_igemm_bf16_io_supported(const zsg_conv_desc* d, int3
     return bf16_io_check(d, io_flags, &bm, &bn) == nullptr ? 1 : 0;
 }
 
-template <int BM, int BN, int IO>
+extern "C" int32_t zsg_conv_igemm_bf16_m_supported(const zsg_conv_desc* d) {
+    int bm = 0, bn = 0;
+    return bf16_check(d, &bm, &bn) == nullptr ? 1 : 0;
+}
+
+template <int BM, int BN, int IO, bool MK = false>
 static int launch_bf16(const BfParams& p, hipStream_t st, double flops, const char* kname) {
     const size_t lds = (size_t)2 * (BM + BN) * BF_LDR * sizeof(uint16_t) + BM * sizeof(int);
     static bool attr_done[ZSG_MAX_DEV] = {};      // per device; idempotent (a benign race sets it twice)
@@ -438,26 +455,28 @@ static int launch_bf16(const BfParams& p, hipStream_t st, double flops, const ch
     (void)hipGetDevice(&dev);
     ZSG_REQUIRE(dev >= 0 && dev < ZSG_MAX_DEV, "igemm_bf16: device %d", dev);
     if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN, IO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN, IO, MK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) ZSG_FAIL(-3, "igemm_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_done[dev] = true;
     }
     ZSG_PROF(kname, st, flops, p.alg_bytes);
-    ZSG_LAUNCH((igemm_bf16_kernel<BM, BN, IO>), dim3(p.m_tiles * p.n_tiles), dim3(256), lds, st, p);
+    ZSG_LAUNCH((igemm_bf16_kernel<BM, BN, IO, MK>), dim3(p.m_tiles * p.n_tiles), dim3(256), lds, st, p);
     ZSG_CHECK_LAUNCH("igemm_bf16");
     return 0;
 }
 
-template <int IO>
+template <int IO, bool MK = false>
 static int launch_bf16_tile(int BM, int BN, const BfParams& p, hipStream_t st, double fl, const char* n64, const char* n128x64, const char* n128) {
-    if (BM == 128 && BN == 128) return launch_bf16<128, 128, IO>(p, st, fl, n128);
-    if (BM == 128 && BN == 64) return launch_bf16<128, 64, IO>(p, st, fl, n128x64);
-    return launch_bf16<64, 64, IO>(p, st, fl, n64);
+    if (BM == 128 && BN == 128) return launch_bf16<128, 128, IO, MK>(p, st, fl, n128);
+    if (BM == 128 && BN == 64) return launch_bf16<128, 64, IO, MK>(p, st, fl, n128x64);
+    return launch_bf16<64, 64, IO, MK>(p, st, fl, n64);
 }
 
 static int conv_bf16_run(const char* who, const zsg_conv_desc* d, const void* src, const uint16_t* wt_packed, void* out, const float* bias,
-                         const void* add_src, int32_t io, void* stream) {
+                         const void* add_src, int32_t io, void* stream, const float* mask_src = nullptr) {
     ZSG_REQUIRE(d && src && wt_packed && out, "%s: null argument", who);
+    ZSG_REQUIRE(!mask_src || io == 0, "%s: mask_src with io_flags %d (fp32 storage only)", who, io);
+    ZSG_REQUIRE(((uintptr_t)mask_src & 3) == 0, "%s: mask_src not element-aligned", who);
     int BM = 64, BN = 64;
     const char* why = bf16_io_check(d, io, &BM, &BN);
     ZSG_REQUIRE(why == nullptr, "%s: unsupported: %s", who, why);
@@ -468,7 +487,7 @@ static int conv_bf16_run(const char* who, const zsg_conv_desc* d, const void* sr
     ZSG_REQUIRE(add_src != out || a16 == o16, "%s: add_src aliases out in another format", who);
     BfParams p;
     memset(&p, 0, sizeof(p));
-    p.src = src; p.wt = wt_packed; p.out = out; p.bias = bias; p.add_src = add_src;
+    p.src = src; p.wt = wt_packed; p.out = out; p.bias = bias; p.add_src = add_src; p.mask_src = mask_src;
     p.C = d->C; p.C8 = (d->C + 7) / 8 * 8; p.N = d->N; p.src_ld = d->src_ld; p.out_ld = d->out_ld; p.wS = d->wS; p.T = d->wR * d->wS;
     p.relu = d->relu; p.nseg = d->nseg;
     int tiles = 0;
@@ -495,7 +514,7 @@ static int conv_bf16_run(const char* who, const zsg_conv_desc* d, const void* sr
         // 4-channel groups in the epilogue: 16 bytes of fp32, 8 bytes of bf16
         bool v = (d->out_ld % 4) == 0 && (d->N % 4) == 0;
         for (int s = 0; s < d->nseg; ++s) v = v && (d->seg[s].out_off % 4) == 0 && (d->seg[s].out_bstride % 4) == 0;
-        const uintptr_t al = ((uintptr_t)out & (o16 ? 7 : 15)) | ((uintptr_t)bias & 15) | ((uintptr_t)add_src & (a16 ? 7 : 15));
+        const uintptr_t al = ((uintptr_t)out & (o16 ? 7 : 15)) | ((uintptr_t)bias & 15) | ((uintptr_t)add_src & (a16 ? 7 : 15)) | ((uintptr_t)mask_src & 15);
         p.vec = (v && al == 0) ? 1 : 0;
     }
     int kio = io;                // the kernel's template word: the flags + the loader width of a bf16 source
@@ -515,6 +534,13 @@ static int conv_bf16_run(const char* who, const zsg_conv_desc* d, const void* sr
                       - (s16 ? 2.0 * in_e : 0.0) - (o16 ? 2.0 * out_e : 0.0) - ((a16 && add_src) ? 2.0 * out_e : 0.0);
     }
     hipStream_t st = (hipStream_t)stream;
+    if (mask_src) {              // (the mask reads 4 more bytes per output element)
+        double out_e = 0;
+        for (int s = 0; s < d->nseg; ++s) out_e += (double)d->B * d->seg[s].rows_y * d->seg[s].rows_x * d->N;
+        p.alg_bytes += 4.0 * out_e;
+        return launch_bf16_tile<0, true>(BM, BN, p, st, fl, "igemm_bf16_kernel<64, 64, 0, m>", "igemm_bf16_kernel<128, 64, 0, m>",
+                                         "igemm_bf16_kernel<128, 128, 0, m>");
+    }
     // (the fp32-in-memory kernel keeps the profile names it had; the others carry their flag word, "h" = the two-halves loader)
 #define BF_CASE(k, suf)                                                                                                                      \
     case k:                                                                                                                                  \
@@ -541,6 +567,11 @@ static int conv_bf16_run(const char* who, const zsg_conv_desc* d, const void* sr
 extern "C" int zsg_conv_igemm_bf16(const zsg_conv_desc* d, const float* src, const uint16_t* wt_packed, float* out, const float* bias,
                                    const float* add_src, void* stream) {
     return conv_bf16_run("conv_igemm_bf16", d, src, wt_packed, out, bias, add_src, 0, stream);
+}
+
+extern "C" int zsg_conv_igemm_bf16_m(const zsg_conv_desc* d, const float* src, const uint16_t* wt_packed, float* out, const float* bias,
+                                     const float* add_src, const float* mask_src, void* stream) {
+    return conv_bf16_run("conv_igemm_bf16_m", d, src, wt_packed, out, bias, add_src, 0, stream, mask_src);
 }
 
 extern "C" int zsg_conv_igemm_bf16_io(const zsg_conv_desc* d, const void* src, const uint16_t* wt_packed, void* out, const float* bias,

@@ -279,6 +279,8 @@ class DistributedDataParallel(nn.Module):
             key += (self.module._sync_bn_key(),)         # (so do synchronized ones: no in-kernel statistics finalize)
         if self.module.training and getattr(self.module, "_wgrad_dtype", "fp32") != "fp32":
             key += (("wgrad", self.module._wgrad_dtype),)    # (bf16 weight gradients are tuned under their own entries)
+        if self.module.training and getattr(self.module, "_train_dtype", "fp32") != "fp32":
+            key += (("train", self.module._train_dtype),)    # (so are the bf16 forward convolutions / data gradients of the pyramid and the heads)
         if key in self._tuned:
             return
         self._tuned.add(key)
@@ -311,6 +313,12 @@ class DistributedDataParallel(nn.Module):
     def wgrad_precision(self, dtype: str = "fp32"):
         """ZSGNet.wgrad_precision of the wrapped network ("fp32" | "bf16"): the gradients stay fp32, so buckets and collectives are unchanged"""
         self.module.wgrad_precision(dtype)
+        return self
+
+    def train_precision(self, dtype: str = "fp32"):
+        """ZSGNet.train_precision of the wrapped network ("fp32" | "bf16_head"): activations and gradients stay fp32 in memory, so buckets
+        and collectives are unchanged"""
+        self.module.train_precision(dtype)
         return self
 
     def close(self):

@@ -39,6 +39,8 @@ SSD_EXTRAS = [256, "S", 512, 128, "S", 256, 128, 256, 128, 256]                 
 
 WGRAD_DTYPES = ("fp32", "bf16")               # cfg wgrad_dtype / ZSGNet.wgrad_precision: operand precision of the training plans' convolution weight gradients
 EVAL_DTYPES = ("fp32", "bf16", "bf16_act")    # cfg eval_dtype / ZSGNet.eval_precision: operand precision of the eval plans' convolutions (+ bf16 activation storage)
+TRAIN_DTYPES = ("fp32", "bf16_head")         # cfg train_dtype / ZSGNet.train_precision: operand precision of the training plans' forward convolutions and data gradients ("bf16_head": the pyramid and the heads; "bf16" is left free for a whole-network version)
+BF16_HEAD_PREFIXES = ("backbone.fpn.", "att_reg_box.", "att_box.", "reg_box.")     # the layers train_dtype = "bf16_head" covers: no BatchNorm among them
 LSTM_DIMS = (32, 64, 128, 256)    # cfg lstm_dim: the widths csrc/lstm.hip instantiates zsg_lstm_fwd / zsg_lstm_bwd for
 
 LIVE_NETS = weakref.WeakSet()      # every ZSGNet alive: optim.clip_grad_norm_ finds a parameter's flat store here
@@ -171,6 +173,7 @@ class ZSGNet(nn.Module):
         self.debug = False
         self._eval_dtype = "fp32"      # operand precision of the eval plans' convolutions (eval_precision)
         self._wgrad_dtype = "fp32"     # operand precision of the training plans' convolution weight gradients (wgrad_precision)
+        self._train_dtype = "fp32"     # operand precision of the training plans' forward convolutions / data gradients (train_precision)
         LIVE_NETS.add(self)
 
     # ------------------------------------------------------------------------------------------------------
@@ -582,6 +585,30 @@ class ZSGNet(nn.Module):
         self._wgrad_dtype = dtype
         return self
 
+    def train_precision(self, dtype: str = "fp32") -> "ZSGNet":
+        """Operand precision of the forward convolutions and data gradients of the TRAINING plans: "fp32" (default: what every plan
+        lowered before, launch for launch) or "bf16_head" — the convolutions of the pyramid (backbone.fpn.*) and of the head stacks, which
+        contain no BatchNorm, run on bf16 MFMA in the forward (zsg_conv_igemm_bf16: fp32 activations rounded by the operand loader, the
+        weights packed by one launch per forward, fp32 accumulation, bias / add / ReLU epilogue) and in the data gradient
+        (zsg_conv_igemm_bf16_m: the same with the ReLU-mask epilogue, on the packed transposed filter), except where the data gradient
+        lands in a BatchNorm output (the laterals P*_1 and P6: it may carry that BatchNorm's backward sums, which are fp32 only).  The
+        encoder, the query encoder, the language / grid maps, every weight gradient (wgrad_precision decides those) and every activation
+        in memory stay fp32.  Eval plans ignore the switch.  The precision is part of a training plan's identity: switching drops the
+        training plans of the other precision."""
+        if dtype not in TRAIN_DTYPES:
+            raise ValueError(f"train_dtype={dtype!r}: expected one of {', '.join(TRAIN_DTYPES)}")
+        self._train_dtype = dtype
+        return self
+
+    def _train_key(self) -> Tuple:
+        """what train_precision adds to a training plan's key (as _wgrad_key: nothing for fp32, whose key stays what it always was)"""
+        return () if self._train_dtype == "fp32" else (("train", self._train_dtype),)
+
+    @staticmethod
+    def _key_train(k: Tuple) -> str:
+        """the forward / data-gradient precision of a training plan's key"""
+        return next((e[1] for e in k[7:-1] if isinstance(e, tuple) and e[0] == "train"), "fp32")
+
     def _wgrad_key(self) -> Tuple:
         """what the weight-gradient precision adds to a training plan's key, in front of its trailing fields (_plan_for reads those by
         position from the end and the leading ones by index): nothing for fp32, whose key stays what it always was"""
@@ -617,16 +644,17 @@ class ZSGNet(nn.Module):
             # shared-image training plan: exactly B image slots and Q queries.  One (B, Q) at a time: a new one, like a new trainable set,
             # drops the shared training plans of the old (activation buffers must not pile up)
             fz, fb, sb = self._frozen_key(), self._frozen_bn_key(), self._sync_bn_key()
-            key = (B, H, W, T, fz, fb, sb, ("shared", Q)) + self._wgrad_key() + (True,)
+            key = (B, H, W, T, fz, fb, sb, ("shared", Q)) + self._wgrad_key() + self._train_key() + (True,)
             if key not in self._plans:
                 for k in [k for k in self._plans if k[-1] and ((k[4], k[5], k[6]) != (fz, fb, sb) or self._key_wgrad(k) != self._wgrad_dtype
+                                                               or self._key_train(k) != self._train_dtype
                                                                or (self._key_shared(k) is not None and (k[0], self._key_shared(k)[1]) != (B, Q)))]:
                     old = self._plans.pop(k)
                     if old._prep_pending:
                         torch.cuda.current_stream().wait_event(old._prep_ev)
                 bn_names = list(self.bns)
                 self._plans[key] = _Plan(self, B, H, W, T, True, frozen={self._param_names[i] for i in fz},
-                                         frozen_bn={bn_names[i] for i in fb}, Q=Q, wgrad_dtype=self._wgrad_dtype)
+                                         frozen_bn={bn_names[i] for i in fb}, Q=Q, wgrad_dtype=self._wgrad_dtype, train_dtype=self._train_dtype)
             return self._plans[key]
         if Q is not None:
             # eval-only plan of Q queries over B (bucketed) images; the cache of these is bounded: least recently used first out
@@ -646,17 +674,19 @@ class ZSGNet(nn.Module):
                 self._plans[key] = _Plan(self, B, H, W, T, False, dtype=self._eval_dtype)
             return self._plans[key]
         fz, fb, sb = self._frozen_key(), self._frozen_bn_key(), self._sync_bn_key()
-        key = (B, H, W, T, fz, fb, sb) + self._wgrad_key() + (True,)
+        key = (B, H, W, T, fz, fb, sb) + self._wgrad_key() + self._train_key() + (True,)
         if key not in self._plans:
             # a new trainable set, frozen-BatchNorm set or synchronized-BatchNorm set: the training plans of the old one go (gradual
             # unfreezing must not pile up activation buffers)
-            for k in [k for k in self._plans if k[-1] and ((k[4], k[5], k[6]) != (fz, fb, sb) or self._key_wgrad(k) != self._wgrad_dtype)]:
+            for k in [k for k in self._plans if k[-1] and ((k[4], k[5], k[6]) != (fz, fb, sb) or self._key_wgrad(k) != self._wgrad_dtype
+                                                           or self._key_train(k) != self._train_dtype)]:
                 old = self._plans.pop(k)
                 if old._prep_pending:           # (its side-stream weight preparation may still be reading the weights)
                     torch.cuda.current_stream().wait_event(old._prep_ev)
             bn_names = list(self.bns)
             self._plans[key] = _Plan(self, B, H, W, T, True, frozen={self._param_names[i] for i in fz},
-                                     frozen_bn={bn_names[i] for i in fb}, sync_bn={bn_names[i] for i in sb}, wgrad_dtype=self._wgrad_dtype)
+                                     frozen_bn={bn_names[i] for i in fb}, sync_bn={bn_names[i] for i in sb}, wgrad_dtype=self._wgrad_dtype,
+                                     train_dtype=self._train_dtype)
         return self._plans[key]
 
     def _forward_shared(self, inp: Dict[str, Any]) -> Dict[str, Any]:
@@ -785,11 +815,22 @@ class _Plan:
     """Static lowering of ZSGNet for one (B, H, W, T, training) geometry."""
 
     def __init__(self, net: ZSGNet, B: int, H: int, W: int, T: int, training: bool, frozen=frozenset(), frozen_bn=frozenset(),
-                 sync_bn=frozenset(), Q: Optional[int] = None, dtype: str = "fp32", wgrad_dtype: str = "fp32"):
+                 sync_bn=frozenset(), Q: Optional[int] = None, dtype: str = "fp32", wgrad_dtype: str = "fp32", train_dtype: str = "fp32"):
         self.net, self.B, self.H, self.W, self.T, self.training = net, B, H, W, T, training
         # training plans only (ZSGNet.wgrad_precision): the weight gradients that go through wgrad() are lowered to zsg_conv_wgrad_bf16
         assert wgrad_dtype in WGRAD_DTYPES
         self.wgrad_bf16 = training and wgrad_dtype == "bf16"
+        # training plans only (ZSGNet.train_precision): the forward convolutions of the pyramid and the heads are lowered to
+        # zsg_conv_igemm_bf16 (their packed weights refreshed by ONE pack launch per forward, on the side stream with the other weight-only
+        # work: prep_u), their data gradients to zsg_conv_igemm_bf16_m (the packed transposed filters by one more pack launch in prep)
+        assert train_dtype in TRAIN_DTYPES
+        self.train_bf16 = training and train_dtype == "bf16_head"
+        self.dpack_jobs, self.dpack_blocks, self.dpack_jobs_dev, self._dpack = [], 0, None, {}
+        # every launch train_dtype = "bf16_head" put on bf16 MFMA, in lowering order: dict(kind "fwd" | "dgrad", what, idx (launch index in
+        # fwd / bwd), d (descriptor copy), src (src / dy), out (out / dx), add (Act | None), mask (Act | None), pname (weight), window
+        # ((wc0, C) of the weight's channels, forward; (row0, n) of its input channels, data gradient)).  No plan buffer is recycled, so
+        # after a step the operands still hold that step's values (the tests recompute each layer from them)
+        self._b16_log = []
         # eval plans only (ZSGNet.eval_precision): every convolution zsg_conv_igemm_bf16 supports is lowered to it; their weights are
         # packed to bf16 by ONE zsg_pack_w_bf16_batched launch per forward (behind the BatchNorm fold, whose output it reads)
         assert dtype in EVAL_DTYPES and not (training and dtype != "fp32")
@@ -890,6 +931,16 @@ class _Plan:
         if self.pack_jobs:
             blob = b"".join(_struct.pack("<qqiiiiiiii", *j) for j in self.pack_jobs)
             self.pack_jobs_dev = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(self.dev)
+            if training:
+                # train_dtype = "bf16_head": the weights change every step — ONE pack launch per forward with the other weight-only work
+                # on the side stream (prep_u: released behind the optimizer step's write of the weights by _rel_ev); the main stream waits
+                # for it in front of the first launch that reads an image, a side-stream reader is behind it in its own stream
+                self.prep_u.add(lib.zsg_pack_w_bf16_batched, self.pack_jobs_dev, len(self.pack_jobs), self.pack_blocks, what="pack bf16 weight images")
+                self._wait_idx = min(self._wait_idx, next(i for i, c in enumerate(self.fwd.calls) if c[0] is lib.zsg_conv_igemm_bf16))
+        for e in self._b16_log:          # (launch indices after the reordering of the programs: hoisting, _batch_wgrads)
+            prog = self.fwd if e["kind"] == "fwd" else self.bwd
+            call = e.pop("call")
+            e["idx"] = next(i for i, c in enumerate(prog.calls) if c is call)
 
     # ---- allocation helpers --------------------------------------------------------------------------------
     def _buf(self, n, dtype=torch.float32):
@@ -1057,17 +1108,7 @@ class _Plan:
                 return False
         elif not lib.zsg_conv_igemm_bf16_supported(_ct.byref(d)):
             return False
-        T, c8 = d.wR * d.wS, (d.C + 7) // 8 * 8
-        assert wc0 + d.C <= wC and w_src.numel() >= d.N * T * wC
-        wp = self._buf(d.N * T * c8, dtype=torch.int16)
-        job = (w_src.data_ptr(), wp.data_ptr(), d.N, T, wC, wc0, d.C, c8)
-        one = torch.frombuffer(bytearray(_struct.pack("<qqiiiiiiii", *job, 0, 0)), dtype=torch.uint8).to(self.dev)
-        nblk = (d.N * T * c8 // 8 + 255) // 256
-        check(lib.zsg_pack_w_bf16_batched(one.data_ptr(), 1, nblk, stream_ptr()), "pack_w_bf16")
-        torch.cuda.current_stream().synchronize()          # (`one` is freed on return)
-        self.pack_jobs.append(job + (self.pack_blocks, 0))
-        self.pack_blocks += nblk
-        self.pack_keep.append(w_src)
+        wp = self._fwd_image(d, w_src, wC, wc0)
         args = (src_buf, wp, out_buf, bias, add_src)
         if self.act16:
             self._tune("igemm", lib.zsg_conv_igemm_bf16_io, d, args + (io,), stream_ptr())
@@ -1075,6 +1116,47 @@ class _Plan:
             return True
         self._tune("igemm", lib.zsg_conv_igemm_bf16, d, args, stream_ptr())
         self.fwd.add(lib.zsg_conv_igemm_bf16, d, *args, what=what + "+bf16", lane=lane)
+        return True
+
+    def _pack_image(self, src_ptr: int, N: int, T: int, wC: int, wc0: int, C: int):
+        """A packed bf16 weight image uint16 [N][T][C8] of the channel window [wc0, wc0 + C) of the fp32 image [N][T][wC] at src_ptr,
+        filled once now so that the tuner times real data.  Returns (image, its zsg_pack_w_bf16_batched job without blk0, its blocks)."""
+        c8 = (C + 7) // 8 * 8
+        wp = self._buf(N * T * c8, dtype=torch.int16)
+        job = (src_ptr, wp.data_ptr(), N, T, wC, wc0, C, c8)
+        one = torch.frombuffer(bytearray(_struct.pack("<qqiiiiiiii", *job, 0, 0)), dtype=torch.uint8).to(self.dev)
+        nblk = (N * T * c8 // 8 + 255) // 256
+        check(lib.zsg_pack_w_bf16_batched(one.data_ptr(), 1, nblk, stream_ptr()), "pack_w_bf16")
+        torch.cuda.current_stream().synchronize()          # (`one` is freed on return)
+        return wp, job, nblk
+
+    def _fwd_image(self, d, w_src: torch.Tensor, wC: int, wc0: int) -> torch.Tensor:
+        """the packed image of a forward convolution's weight; its job joins the plan's one forward pack launch"""
+        T = d.wR * d.wS
+        assert wc0 + d.C <= wC and w_src.numel() >= d.N * T * wC
+        wp, job, nblk = self._pack_image(w_src.data_ptr(), d.N, T, wC, wc0, d.C)
+        self.pack_jobs.append(job + (self.pack_blocks, 0))
+        self.pack_blocks += nblk
+        self.pack_keep.append(w_src)
+        return wp
+
+    def _b16_eligible(self, lname: str) -> bool:
+        """train_dtype = "bf16_head" covers the layer: a convolution of the pyramid or of a head stack (never backbone.encoder.*)"""
+        return self.train_bf16 and lname.startswith(BF16_HEAD_PREFIXES)
+
+    def _bf16_train_fwd(self, lname: str, d, src: Act, w_src: torch.Tensor, wC: int, wc0: int, out: Act, bias, add: Optional[Act], what: str,
+                        lane: int = 0) -> bool:
+        """Lower the forward convolution `d` of layer `lname` to zsg_conv_igemm_bf16 when this is a bf16_head training plan, the layer
+        is covered and the library takes the descriptor (else False: the caller lowers the fp32 launch, Winograd candidates included).
+        The weight is the RAW parameter (training has no BatchNorm fold); activations stay fp32 in memory."""
+        if not self._b16_eligible(lname) or not lib.zsg_conv_igemm_bf16_supported(_ct.byref(d)):
+            return False
+        wp = self._fwd_image(d, w_src, wC, wc0)
+        args = (src.buf, wp, out.buf, bias, add.buf if add is not None else None)
+        self._tune("igemm", lib.zsg_conv_igemm_bf16, d, args, stream_ptr())
+        self.fwd.add(lib.zsg_conv_igemm_bf16, d, *args, what=what + "+bf16", lane=lane)
+        self._b16_log.append(dict(kind="fwd", what=what, idx=-1, call=self.fwd.calls[-1], d=type(d).from_buffer_copy(d), src=src, out=out,
+                                  add=add, mask=None, pname=lname + ".weight", window=(wc0, d.C)))
         return True
 
     def _wino_u(self, src_ptr: int, N: int, Cred: int, row_ld: int, tap_ld: int, flip: int):
@@ -1145,6 +1227,14 @@ class _Plan:
         wt = self.P(L.name + ".weight")
         if pend is not None:
             return self._conv_bnpre(L, src, out, d, wt, pend, bn_fuse)
+        if self._bf16_train_fwd(L.name, d, src, wt, L.cpad, 0, out, bias, None, L.name, lane=self._lane):
+            # (train_dtype = "bf16_head": the tape entry, needs_mask, requires_grad and the lane are the fp32 lowering's below)
+            assert bn_fuse is None, "a convolution in front of a BatchNorm is not a bf16_head layer"
+            out.bn_chunks, out.bn_inline, out.needs_mask, out.requires_grad = 0, None, relu, self._conv_rg(L, src)
+            completes = getattr(src, "bn_out", False) and not getattr(src, "_consumed", False)
+            src._consumed = True
+            self.tape.append(lambda: self._conv_bwd(L, src, out, completes_bn=completes))
+            return out
         if self._bf16_conv(d, rd.buf, wt, L.cpad, 0, out.buf, bias, None, L.name, lane=self._lane):
             # (an eval plan has no backward: the tape entry only keeps the callers' bookkeeping — _head_stack pops it — in step)
             out.bn_chunks, out.bn_inline, out.needs_mask, out.requires_grad = 0, None, relu, self._conv_rg(L, src)
@@ -1374,6 +1464,11 @@ class _Plan:
         self.wt_jobs_dev = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(self.dev)
         self.prep.add(lib.zsg_transpose_w_batched, self.net.store.flat, self.wt_arena, self.wt_jobs_dev, len(self.wt_jobs), tile0,
                       what="transpose all dgrad weight images")
+        if self.dpack_jobs:      # train_dtype = "bf16_head": the packed bf16 copies of the transposed images the bf16 data gradients read
+            blob = b"".join(_struct.pack("<qqiiiiiiii", *j) for j in self.dpack_jobs)
+            self.dpack_jobs_dev = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(self.dev)
+            self.prep.add(lib.zsg_pack_w_bf16_batched, self.dpack_jobs_dev, len(self.dpack_jobs), self.dpack_blocks,
+                          what="pack bf16 dgrad weight images")
         wj = self.wino_jobs["bwd"]
         if wj.jobs:          # rotated filter transforms of the Winograd data gradients, from the transposed images
             self.prep.add(lib.zsg_wino_weights, wj.finish(self.dev), len(wj.jobs), wj.blocks, what="wino dgrad filter transforms")
@@ -1446,6 +1541,26 @@ class _Plan:
             assert len(deltas) == 1 and src.ld == dx.ld, "ReLU mask needs one common offset between src and its gradient"
             mask = src.buf.data_ptr() + 4 * deltas.pop()
             self.bwd.keep.append(src.buf)
+        if self._b16_eligible(L.name) and not getattr(src, "bn_out", False) and lib.zsg_conv_igemm_bf16_m_supported(_ct.byref(d)):
+            # train_dtype = "bf16_head": the same launch on bf16 MFMA, on the packed copy of the transposed image (one more pack launch in
+            # prep, behind the transpose).  Not into a BatchNorm output (the laterals, P6): that data gradient completes the BatchNorm's
+            # dout and may be re-issued with its backward sums in the epilogue, which the bf16 entry does not have.  No Winograd
+            # candidates, no split-K (so no zero-fill beyond the one above)
+            key = (L.name, row0, n)
+            if key not in self._dpack:
+                self._dpack[key], job, nblk = self._pack_image(wt.data_ptr() + 4 * wt_off, n, L.k * L.k, cred, 0, cred)
+                self.dpack_jobs.append(job + (self.dpack_blocks, 0))
+                self.dpack_blocks += nblk
+            add = dx if dx.gfilled else None
+            args = (dy.buf, self._dpack[key], dx.buf, None, dx.buf if dx.gfilled else None, mask)
+            self._tune("igemm", lib.zsg_conv_igemm_bf16_m, d, args, stream_ptr())
+            self.bwd.add(lib.zsg_conv_igemm_bf16_m, d, *args, what="dgrad:" + L.name + "+bf16")
+            self._b16_log.append(dict(kind="dgrad", what="dgrad:" + L.name, idx=-1, call=self.bwd.calls[-1], d=type(d).from_buffer_copy(d),
+                                      src=dy, out=dx, add=add, mask=src if mask is not None else None, pname=L.name + ".weight",
+                                      window=(row0, n)))
+            dx.gfilled = True
+            dx.last_writer = None
+            return
         args = (dy.buf, wt[wt_off:], dx.buf, None, dx.buf if dx.gfilled else None, mask, None)
         wargs = None
         if wino_ok(L.k, L.stride, L.pad, L.dil) and wino_mode() != "0":
@@ -2373,7 +2488,8 @@ class _Plan:
             d0 = fwd_desc(Fp, Y, Cf, 256, 3, 1, 1, 1, wC=cp, wc0=0, relu=False)
             a0 = (Fp.buf, self.P(W0n), Y.buf, None, None, None, None)
             wargs = None
-            bf0 = self._bf16_conv(d0, Fp.buf, self.P(W0n), cp, 0, Y.buf, None, None, L0.name + ".feat")
+            bf0 = (self._bf16_conv(d0, Fp.buf, self.P(W0n), cp, 0, Y.buf, None, None, L0.name + ".feat")
+                   or self._bf16_train_fwd(L0.name, d0, Fp, self.P(W0n), cp, 0, Y, None, None, L0.name + ".feat"))
             if not bf0 and Fp.b16:           # (bf16_act and the bf16 entry refuses: the fp32 launch on a cast copy of the features)
                 a0 = (self._f32(Fp).buf,) + a0[1:]
             if not bf0 and wino_mode() != "0":
@@ -2417,7 +2533,8 @@ class _Plan:
             d0 = fwd_desc(Fp, h1, Cf, 256, 3, 1, 1, 1, wC=cp, wc0=0, relu=True)
             a0 = (Fp.buf, self.P(W0n), h1.buf, self.P(L0.name + ".bias"), lmap.buf if lmap is not None else None, None, None)
             wargs = None
-            bf0 = self._bf16_conv(d0, Fp.buf, self.P(W0n), cp, 0, h1.buf, a0[3], a0[4], L0.name)
+            bf0 = (self._bf16_conv(d0, Fp.buf, self.P(W0n), cp, 0, h1.buf, a0[3], a0[4], L0.name)
+                   or self._bf16_train_fwd(L0.name, d0, Fp, self.P(W0n), cp, 0, h1, a0[3], lmap, L0.name))
             finish0 = lambda: None
             if not bf0 and (Fp.b16 or h1.b16):      # (bf16_act and the bf16 entry refuses: the fp32 launch between casts)
                 f32_, h32, _, finish0 = self._via_f32(Fp, h1)
@@ -2618,7 +2735,7 @@ class _Plan:
         if not self.training and self.fold_jobs:       # the weights may have changed since the last eval forward: refold (one launch)
             check(lib.zsg_bn_fold(net.store.flat.data_ptr(), net._rm.data_ptr(), net._rv.data_ptr(), 1e-5, self.fold_jobs_dev.data_ptr(),
                                   len(self.fold_jobs), self.fold_rows, self.fold_arena.data_ptr(), stream_ptr()), "bn_fold")
-        if self.pack_jobs:       # bf16 eval plan: the packed weight images, from the parameters and the fold just made (one launch)
+        if self.pack_jobs and not self.training:       # bf16 eval plan: the packed weight images, from the parameters and the fold just made (one launch)
             check(lib.zsg_pack_w_bf16_batched(self.pack_jobs_dev.data_ptr(), len(self.pack_jobs), self.pack_blocks, stream_ptr()), "pack_w_bf16")
         if u8:
             check(lib.zsg_u8hwc_to_nhwc4(img.data_ptr(), n_img * self.H * self.W, self.fwd.calls[self.img_slot][1][5], stream_ptr()), "u8hwc_to_nhwc4")
@@ -2804,6 +2921,7 @@ def get_default_net(num_anchors=1, cfg=None):
     net = ZSGNet(kind, num_anchors, cfg=cfg, arch=arch)
     net.eval_precision(cfg["eval_dtype"] if "eval_dtype" in cfg else "fp32")          # (raises on anything but fp32 / bf16 / bf16_act)
     net.wgrad_precision(cfg["wgrad_dtype"] if "wgrad_dtype" in cfg else "fp32")       # (raises on anything but fp32 / bf16)
+    net.train_precision(cfg["train_dtype"] if "train_dtype" in cfg else "fp32")       # (raises on anything but fp32 / bf16_head)
     path = cfg["pretrained_path"] if "pretrained_path" in cfg else ""
     if path:
         n = load_pretrained_encoder(net, path)

@@ -219,7 +219,7 @@ SIDE_BATCH = int(os.environ.get("ZSG_SIDE_BATCH", "0"))
 
 
 _MAIN_CONVS = (lib.zsg_conv_igemm, lib.zsg_conv_wino, lib.zsg_conv_igemm_bnb, lib.zsg_conv_wino_bnb, lib.zsg_conv_igemm_bnstat,
-               lib.zsg_conv_wino_bnstat, lib.zsg_conv_igemm_bnb_tail, lib.zsg_conv_wino_bnb_tail)
+               lib.zsg_conv_wino_bnstat, lib.zsg_conv_igemm_bnb_tail, lib.zsg_conv_wino_bnb_tail, lib.zsg_conv_igemm_bf16_m)
 
 
 _SIDE = {}
@@ -850,8 +850,9 @@ def autotune_conv(kind: str, fn, d: ConvDesc, args: Sequence, stream: int, ws_by
         return 0
     _check_table_arch()
     io = fn is lib.zsg_conv_igemm_bf16_io         # (... add_src, io_flags): the storage formats are part of the key, through the name field
-    bf16 = io or fn is lib.zsg_conv_igemm_bf16    # (d, src, packed weights, out, bias, add_src): no mask operand
-    add_src, mask = (args[4], None if bf16 else args[5]) if kind == "igemm" else (None, None)
+    bf16m = fn is lib.zsg_conv_igemm_bf16_m       # (... add_src, mask_src): the training plans' forward / data-gradient entry
+    bf16 = io or bf16m or fn is lib.zsg_conv_igemm_bf16    # (d, src, packed weights, out, bias, add_src): no mask operand
+    add_src, mask = (args[4], args[5] if (bf16m or not bf16) else None) if kind == "igemm" else (None, None)
     key = _sig(kind, d, (add_src is not None, mask is not None, add_src is not None and add_src is args[2], split_penalty_ms > 0,
                          mode if wino_args is not None else "", deterministic(), "bf16" if bf16 else "fp32",
                          fn.__name__ + (":io%d" % args[5] if io else ""),
@@ -865,7 +866,7 @@ def autotune_conv(kind: str, fn, d: ConvDesc, args: Sequence, stream: int, ws_by
     rows = sum(d.B * d.seg[i].rows_y * d.seg[i].rows_x for i in range(d.nseg))
     cands = []
     if bf16:
-        # the bf16 eval entry: its tile hints are all there is (no split-K, stream-K, Winograd or streaming variants)
+        # the bf16 entries: their tile hints are all there is (no split-K, stream-K, Winograd or streaming variants)
         cands = [tile_hint(64, 64, 1), tile_hint(128, 64, 1)] + ([tile_hint(128, 128, 1)] if d.N > 64 else [])
     elif kind == "igemm":
         tiles = [(64, 64), (128, 64)] + ([(128, 128)] if d.N > 64 else [])
@@ -933,8 +934,13 @@ def autotune_conv(kind: str, fn, d: ConvDesc, args: Sequence, stream: int, ws_by
     def set_hint(h):
         d.tile_hint = h
 
+    # an accumulating launch (add_src is out: a data gradient adding to what is there, of either precision) is timed on the gradient
+    # buffer itself: the trials start from one saved state, put back when they are over
+    snap = args[2].clone() if (kind == "igemm" and isinstance(add_src, torch.Tensor) and add_src is args[2]) else None
     best = _pick_best(trials, set_hint, stream, lambda h: split_penalty_ms if (kind == "igemm" and ((h >> 16) & 0xff) > 1) else 0.0)
-    if os.environ.get("ZSG_TUNE_VERIFY") and fn in (lib.zsg_conv_igemm, lib.zsg_conv_wgrad):
+    if snap is not None:
+        args[2].copy_(snap)
+    if os.environ.get("ZSG_TUNE_VERIFY") and fn in (lib.zsg_conv_igemm, lib.zsg_conv_wgrad, lib.zsg_conv_igemm_bf16_m):
         _verify_candidates(kind, key, trials, set_hint, args[2], args[4] if kind == "igemm" else None, stream)
     d.tile_hint, d.use_wino = best & ~WINO_FLAG, bool(best & WINO_FLAG)
     _TUNE_CACHE[key] = best
