@@ -274,6 +274,33 @@ int zsg_pack_w_bf16_batched(const void* jobs_dev, int32_t njobs, int32_t total_b
 int zsg_conv_igemm_bf16_m(const zsg_conv_desc* d, const float* src, const uint16_t* wt_packed, float* out, const float* bias,
                           const float* add_src, const float* mask_src, void* stream);
 int32_t zsg_conv_igemm_bf16_m_supported(const zsg_conv_desc* d);
+/* ---------------------------------------------------------------------------------------------------------------
+ * Reduced-precision TRAINING forward of the ResNet encoder (enc_dtype = "bf16_fwd"; csrc/igemm_bf16.hip): the plain, bias-free
+ * convolution in front of a train-mode BatchNorm (fpn_resnet.py:86-97) on bf16 MFMA, with zsg_conv_igemm's fused BatchNorm statistics.
+ * zsg_conv_igemm_bf16_bn is zsg_conv_igemm_bf16 without bias, add_src and ReLU, plus the partial rows:
+ *       bn_partials[mt][0][n] = sum over the valid rows of M tile mt of v,   bn_partials[mt][1][n] = sum of v * v
+ *   v the fp32 value stored to out, mt the kernel's M-tile index counted across segments, the layout [m_tiles][2][N] with
+ *   m_tiles = sum over segments of ceil(B * rows_y * rows_x / BM) — zsg_conv_igemm's bn_partials, so zsg_bn_stats_from_partials,
+ *   zsg_bn_apply_from_partials and zsg_bn_sync_fwd_sums read it unchanged.
+ * Numerical contract of out: zsg_conv_igemm_bf16's, word for word (src rounded to bf16 by the loader, round-to-nearest-even; weights
+ * rounded once by zsg_pack_w_bf16_batched; exact products, fp32 accumulation in the fixed tap-major K order; no split-K, no stream-K):
+ * out is bit-equal to what zsg_conv_igemm_bf16 writes for the same descriptor, operands and hint (bias = add_src = NULL).
+ * Order of the sums (fp32, fixed, the same on every run): the output tile lies transposed in LDS; a thread owns 4 adjacent columns and
+ * the tile rows r, r + R, r + 2R, ... (R = 1024 / BN: 16 row groups at BN = 64, 8 at BN = 128), which it adds in ascending order
+ * (s += v; q = fma(v, v, q), invalid rows skipped); the R row-group sums of a column then meet in LDS and one thread adds them in
+ * ascending group order.  No atomics and nothing between workgroups: every (mt, n < N) element is written exactly once, by a 16-byte
+ * vector store; columns n >= N of a column tile that reaches past N are not written, nor is any row >= m_tiles.  No in-kernel
+ * finalize (no tickets), no bnpre loader, no BatchNorm-backward sums: those stay fp32 (zsg_conv_igemm_bnstat / _bnpre / _bnb).
+ * Not supported (-1, nothing launched, zsg_last_error names the argument): everything zsg_conv_igemm_bf16 refuses (merge_x,
+ * epi_flags, split-K / stream-K / variant hint bits); d->relu; N % 4 != 0; a descriptor or out pointer that does not take the 16-byte
+ * epilogue (out_ld, segment out_off / out_bstride multiples of 4, out 16-byte aligned); bn_partials NULL or not 16-byte aligned.
+ * zsg_conv_igemm_bf16_bn_supported: 1 when the DESCRIPTOR (and its tile_hint) is accepted, else 0 (the pointers are the entry's
+ * business).  zsg_conv_igemm_bf16_partial_rows: the rows of bn_partials the launch selected by d->tile_hint writes (hint 0: the tile
+ * the bf16 heuristic picks), or -1 where zsg_conv_igemm_bf16_bn_supported is 0. */
+int zsg_conv_igemm_bf16_bn(const zsg_conv_desc* d, const float* src, const uint16_t* wt_packed, float* out, float* bn_partials,
+                           void* stream);
+int32_t zsg_conv_igemm_bf16_bn_supported(const zsg_conv_desc* d);
+int32_t zsg_conv_igemm_bf16_partial_rows(const zsg_conv_desc* d);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * bf16 ACTIVATION STORAGE for inference (eval_dtype = "bf16_act"; csrc/igemm_bf16.hip, csrc/bf16_act.hip).  Everything "bf16" has;

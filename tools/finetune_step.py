@@ -35,6 +35,12 @@ fp32 plan, everything trainable.  Each variant also reports its weight-gradient 
 per-launch events over a few steps on one stream): wgrad_kernel / wino_wgrad_kernel / wgrad_bf16_kernel instantiations and
 wgrad_reduce_kernel, with launches and ms per step, TFLOP/s and algorithmic bytes per launch.
 
+    python tools/finetune_step.py --enc-bf16 [--train-bf16-head] [--wgrad-bf16] [--out profiles/enc_bf16_step.json]
+
+--enc-bf16 measures the encoder's forward convolutions on bf16 MFMA (ZSGNet.encoder_precision("bf16_fwd"): zsg_conv_igemm_bf16_bn) against
+the fp32 plan; with --train-bf16-head / --wgrad-bf16 four variants alternate: fp32, enc_bf16, those switches, those switches + enc_bf16.
+Each variant also reports its encoder forward convolutions launch by launch (serial replay) and the "stats:" launches beside them.
+
     python tools/finetune_step.py --train-bf16-head [--wgrad-bf16] [--out profiles/train_bf16_head_step.json]
 
 --train-bf16-head measures the forward convolutions and data gradients of the pyramid and the heads on bf16 MFMA
@@ -188,6 +194,30 @@ def head_class(v, nprof=3):
                 bwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "bwd"), 4), head_classes=cls)
 
 
+def enc_class(v, nprof=3):
+    """the encoder's forward convolutions of one variant (what enc_dtype = "bf16_fwd" replaces), from per-launch events as head_class
+    takes them: per launch the layer, the entry and the microseconds in serial replay; the "stats:" finalize launches of encoder
+    BatchNorms are counted and timed beside them (a bf16 launch has no in-kernel finalize)"""
+    net = v["net"]
+    plan = [p for k, p in net._plans.items() if k[-1]][0]
+    st = torch.cuda.current_stream().cuda_stream
+    acc = {}
+    for _ in range(nprof):
+        for i, (what, fname, ms) in enumerate(plan.fwd.profile(st)):
+            acc[(i, what, fname)] = acc.get((i, what, fname), 0.0) + ms / nprof
+    rows, stats_n, stats_ms, apply_ms = [], 0, 0.0, 0.0
+    for (i, what, fname), ms in sorted(acc.items()):
+        if what.startswith(mdl.BF16_ENC_PREFIX) and fname.startswith("zsg_conv"):
+            layer = what.split("+")[0]
+            rows.append([layer, fname, what[len(layer):], round(ms * 1e3, 1)])
+        elif what.startswith("stats:" + mdl.BF16_ENC_PREFIX):
+            stats_n, stats_ms = stats_n + 1, stats_ms + ms
+        elif what.startswith(mdl.BF16_ENC_PREFIX) and fname.startswith("zsg_bn_apply"):
+            apply_ms += ms
+    return dict(enc_fwd_conv_ms=round(sum(r[3] for r in rows) / 1e3, 4), enc_stats_launches=stats_n, enc_stats_ms=round(stats_ms, 4),
+                enc_bn_apply_ms=round(apply_ms, 4), fwd_program_ms=round(sum(acc.values()), 4), enc_fwd_rows=rows)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -201,6 +231,8 @@ def main():
     ap.add_argument("--ema", action="store_true")
     ap.add_argument("--wgrad-bf16", action="store_true")
     ap.add_argument("--train-bf16-head", action="store_true")
+    ap.add_argument("--enc-bf16", action="store_true", help="fp32 against enc_dtype = bf16_fwd; with --train-bf16-head / --wgrad-bf16 "
+                                                             "also those switches without and with the encoder's")
     ap.add_argument("--only", default="", help="comma-separated variant names to run (e.g. one variant under rocprofv3)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
@@ -219,7 +251,17 @@ def main():
     bt["h0"], bt["c0"] = torch.zeros(2, a.bs, 128), torch.zeros(2, a.bs, 128)
     sd = None
     runs = {}
-    if a.sync_bn:
+    enc_of = {}                              # variant -> cfg enc_dtype (default fp32)
+    if a.enc_bf16:
+        other = ("bf16" if a.wgrad_bf16 else "fp32", "bf16_head" if a.train_bf16_head else "fp32")
+        oname = next(k for k, v in TRAIN_VARIANTS.items() if v == other)
+        variants = {"fp32": ((), False, None, None, None, "fp32", "fp32"), "enc_bf16": ((), False, None, None, None, "fp32", "fp32")}
+        enc_of["enc_bf16"] = "bf16_fwd"
+        if oname != "fp32":
+            variants[oname] = ((), False, None, None, None) + other
+            variants["enc_bf16_" + oname] = ((), False, None, None, None) + other
+            enc_of["enc_bf16_" + oname] = "bf16_fwd"
+    elif a.sync_bn:
         variants = {k: ((), False, None, v, None, "fp32", "fp32") for k, v in SYNC_VARIANTS.items()}
     elif a.train_bf16_head:
         variants = {k: ((), False, None, None, None, v[0], v[1]) for k, v in TRAIN_VARIANTS.items() if a.wgrad_bf16 or v[0] == "fp32"}
@@ -237,7 +279,7 @@ def main():
         variants = {k: v for k, v in variants.items() if k in a.only.split(",")}
     for name, (prefixes, bn_frozen, clip, sync_bn, ema, wgrad_dtype, train_dtype) in variants.items():
         net = mdl.get_default_net(9, cfg)
-        net.wgrad_precision(wgrad_dtype).train_precision(train_dtype)
+        net.wgrad_precision(wgrad_dtype).train_precision(train_dtype).encoder_precision(enc_of.get(name, "fp32"))
         if sd is None:
             sd = {k: v.clone() for k, v in net.state_dict().items()}
         net.load_state_dict(sd)
@@ -312,7 +354,9 @@ def main():
         if v["clip"] is not None:
             res["variants"][name].update(clip=v["clip"][0], max_norm=v["clip"][1], last_grad_norm=round(float(v["norm"]), 6),
                                          engaged=float(v["norm"]) > v["clip"][1])
-        if a.train_bf16_head:
+        if a.enc_bf16:
+            res["variants"][name].update(enc_dtype=net._enc_dtype, train_dtype=net._train_dtype, wgrad_dtype=net._wgrad_dtype, **enc_class(v))
+        elif a.train_bf16_head:
             res["variants"][name].update(train_dtype=net._train_dtype, wgrad_dtype=net._wgrad_dtype, **head_class(v))
         elif a.wgrad_bf16:
             res["variants"][name].update(wgrad_dtype=net._wgrad_dtype, **wgrad_class(lambda: step(v)))

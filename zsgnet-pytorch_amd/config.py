@@ -51,6 +51,7 @@ DEFAULTS: Dict[str, Any] = {
     "eval_dtype": "fp32",           # "bf16": the convolutions of the EVAL forward (validation, only_val / only_test, Evaluator.predict, the many-phrases plan) run on bf16 MFMA with fp32 accumulation (zsg_conv_igemm_bf16; ZSGNet.eval_precision) — activations stay fp32 in memory, the stem, the LSTM and the language map stay fp32, training is untouched; "bf16_act": "bf16", and the activations between the stem's max-pool and the heads' last convolution are stored as bf16 (half the activation bytes of an eval plan; rounded once where stored, arithmetic in fp32; the outputs stay fp32); "fp32" = every plan as before
     "wgrad_dtype": "fp32",          # "bf16": the convolution weight gradients of the TRAINING backward run on bf16 MFMA with fp32 accumulation (zsg_conv_wgrad_bf16; ZSGNet.wgrad_precision) — src, dy and the gradients stay fp32 in memory, the forward, the data gradients, the stem and the small directly lowered weight gradients stay fp32
     "train_dtype": "fp32",          # "bf16_head": in TRAINING plans the forward convolutions and the data gradients of the pyramid (backbone.fpn.*) and the head stacks run on bf16 MFMA with fp32 accumulation (zsg_conv_igemm_bf16 / zsg_conv_igemm_bf16_m; ZSGNet.train_precision) — activations, weights and gradients stay fp32 in memory; the encoder, every BatchNorm-fused launch, the query encoder and the weight gradients (wgrad_dtype) are untouched
+    "enc_dtype": "fp32",            # "bf16_fwd": in TRAINING plans the forward convolutions of a ResNet encoder behind the stem (backbone.encoder.*) run on bf16 MFMA with fp32 accumulation and the fused BatchNorm statistics (zsg_conv_igemm_bf16_bn; ZSGNet.encoder_precision) — activations, weights and gradients stay fp32 in memory; the stem, the convolutions that apply a pending BatchNorm in their loader, the whole backward (fp32 data gradients, weight gradients as wgrad_dtype says) and the SSD-VGG encoder are untouched
     "atss_topk": 9,                 # ... candidates per pyramid level (1 .. 16)
     # configs/ds_info.json: where each dataset's images and csv files live (override with --ds_info.<name>.<key>=...)
     "ds_info": {name: {"data_dir": f"./data/{root}", "img_dir": f"./data/{imgs}",

@@ -107,6 +107,7 @@ struct BfParams {
     double alg_bytes;           // host only
     BfSegDev seg[ZSG_MAX_SEG];
     const float* mask_src;      // MK kernels only: fp32, indexed like out (behind the segments: the other kernels' argument offsets stay)
+    float* stats;               // BS kernels only: BatchNorm partials [m_tiles][2][N] of the stored values (behind everything, as mask_src)
 };
 
 // BM x BN block tile, 4 waves (2 x 2), each wave TM x TN MFMA tiles of 32x32.  Two blocks per CU (at most 256 registers per lane).
@@ -114,10 +115,15 @@ struct BfParams {
 // BF_SRC8 (with BF_SRC16): the two-halves loader.  A compile-time choice: a run-time branch around the loads made the compiler wait for
 // them where the paths join, i.e. in front of the MFMAs they are meant to fly under.
 // MK (with IO = 0): the epilogue's last term, out = v * (mask_src[same index] > 0) behind the ReLU — a data gradient into a ReLU's input.
+// BS (with IO = 0, no mask, the vectorised epilogue only): behind the output store the tile also writes its BatchNorm partial row,
+// stats[mt][0][n] = sum over the tile's valid rows of v, stats[mt][1][n] = sum of v * v, v the fp32 value stored — igemm.hip's bn_partials
+// layout.  Order: a thread owns 4 columns and the rows rr, rr + RPP, ... ascending (s += v; q = fma(v, v, q)); the RPP row groups are
+// combined through LDS in index order by one thread per column group.  No atomics, nothing between workgroups.
 #define BF_SRC8 8
-template <int BM, int BN, int IO, bool MK = false>
+template <int BM, int BN, int IO, bool MK = false, bool BS = false>
 __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
     static_assert(!MK || IO == 0, "the mask variant is built for fp32 storage only");
+    static_assert(!BS || (IO == 0 && !MK), "the BatchNorm-statistics variant is built for fp32 storage without a mask only");
     ZSG_SET_MAIN_PRIO();
     constexpr int WM = 2, WN = 2, NT = 256;
     constexpr int KG = BF_BK / 8;        // threads (8-channel groups) per tile row
@@ -311,6 +317,7 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
                     ct[row * LDC + wn * (BN / WN) + j * 32 + li] = acc[i][j][e];
                 }
         __syncthreads();
+        [[maybe_unused]] f32x4 bs_s = {0.f, 0.f, 0.f, 0.f}, bs_q = {0.f, 0.f, 0.f, 0.f};
         if (n < p.N) {
             f32x4 bv = {0.f, 0.f, 0.f, 0.f};
             if (p.bias) bv = *(const f32x4*)(p.bias + n);
@@ -335,6 +342,28 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
                 }
                 if constexpr (IO & BF_OUT16) *(u32x2*)((uint16_t*)p.out + o) = bf16_pack4(v);      // rounded once, here
                 else *(f32x4*)((float*)p.out + o) = v;
+                if constexpr (BS) {
+                    bs_s += v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) bs_q[e] = fmaf(v[e], v[e], bs_q[e]);
+                }
+            }
+        }
+        if constexpr (BS) {
+            // the RPP row groups of a column group meet in LDS (the transposed tile is dead behind the barrier; rowout lies behind it)
+            f32x4* red = (f32x4*)smem;                // [RPP][2][CG]
+            static_assert(RPP * 2 * CG * 16 <= 2 * (BM + BN) * LDR * 2, "the row-group sums must fit the K-loop staging area");
+            __syncthreads();
+            red[(rr * 2 + 0) * CG + cg] = bs_s;
+            red[(rr * 2 + 1) * CG + cg] = bs_q;
+            __syncthreads();
+            if (tid < 2 * CG) {
+                const int which = tid / CG, c = tid % CG;
+                const int nn = n0 + 4 * c;
+                f32x4 t = red[which * CG + c];
+#pragma unroll
+                for (int r = 1; r < RPP; ++r) t += red[(r * 2 + which) * CG + c];
+                if (nn < p.N) *(f32x4*)(p.stats + ((size_t)mt * 2 + which) * p.N + nn) = t;
             }
         }
     } else {
@@ -447,7 +476,32 @@ extern "C" int32_t zsg_conv_igemm_bf16_m_supported(const zsg_conv_desc* d) {
     return bf16_check(d, &bm, &bn) == nullptr ? 1 : 0;
 }
 
-template <int BM, int BN, int IO, bool MK = false>
+// What the fused BatchNorm statistics add to bf16_check (the descriptor's share; the pointers are the entry's business): a plain
+// convolution whose every operand layout takes the 16-byte epilogue.
+static const char* bf16_bn_check(const zsg_conv_desc* d) {
+    int bm = 0, bn = 0;
+    const char* why = bf16_check(d, &bm, &bn);
+    if (why) return why;
+    if (d->relu) return "relu (the statistics are those of a plain convolution in front of a BatchNorm)";
+    if ((d->N % 4) != 0) return "N must be a multiple of 4 (16-byte partial rows)";
+    if ((d->out_ld % 4) != 0) return "out_ld must be a multiple of 4 (the 16-byte epilogue)";
+    for (int s = 0; s < d->nseg; ++s)
+        if ((d->seg[s].out_off % 4) != 0 || (d->seg[s].out_bstride % 4) != 0) return "segment output not 16-byte aligned (the 16-byte epilogue)";
+    return nullptr;
+}
+
+extern "C" int32_t zsg_conv_igemm_bf16_bn_supported(const zsg_conv_desc* d) { return bf16_bn_check(d) == nullptr ? 1 : 0; }
+
+extern "C" int32_t zsg_conv_igemm_bf16_partial_rows(const zsg_conv_desc* d) {
+    if (bf16_bn_check(d) != nullptr) return -1;
+    int bm = 64, bn = 64;
+    (void)bf16_check(d, &bm, &bn);
+    int64_t tiles = 0;
+    for (int s = 0; s < d->nseg; ++s) tiles += cdiv((int64_t)d->B * d->seg[s].rows_y * d->seg[s].rows_x, bm);
+    return (int32_t)tiles;
+}
+
+template <int BM, int BN, int IO, bool MK = false, bool BS = false>
 static int launch_bf16(const BfParams& p, hipStream_t st, double flops, const char* kname) {
     const size_t lds = (size_t)2 * (BM + BN) * BF_LDR * sizeof(uint16_t) + BM * sizeof(int);
     static bool attr_done[ZSG_MAX_DEV] = {};      // per device; idempotent (a benign race sets it twice)
@@ -455,26 +509,33 @@ static int launch_bf16(const BfParams& p, hipStream_t st, double flops, const ch
     (void)hipGetDevice(&dev);
     ZSG_REQUIRE(dev >= 0 && dev < ZSG_MAX_DEV, "igemm_bf16: device %d", dev);
     if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN, IO, MK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN, IO, MK, BS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) ZSG_FAIL(-3, "igemm_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_done[dev] = true;
     }
     ZSG_PROF(kname, st, flops, p.alg_bytes);
-    ZSG_LAUNCH((igemm_bf16_kernel<BM, BN, IO, MK>), dim3(p.m_tiles * p.n_tiles), dim3(256), lds, st, p);
+    ZSG_LAUNCH((igemm_bf16_kernel<BM, BN, IO, MK, BS>), dim3(p.m_tiles * p.n_tiles), dim3(256), lds, st, p);
     ZSG_CHECK_LAUNCH("igemm_bf16");
     return 0;
 }
 
-template <int IO, bool MK = false>
+template <int IO, bool MK = false, bool BS = false>
 static int launch_bf16_tile(int BM, int BN, const BfParams& p, hipStream_t st, double fl, const char* n64, const char* n128x64, const char* n128) {
-    if (BM == 128 && BN == 128) return launch_bf16<128, 128, IO, MK>(p, st, fl, n128);
-    if (BM == 128 && BN == 64) return launch_bf16<128, 64, IO, MK>(p, st, fl, n128x64);
-    return launch_bf16<64, 64, IO, MK>(p, st, fl, n64);
+    if (BM == 128 && BN == 128) return launch_bf16<128, 128, IO, MK, BS>(p, st, fl, n128);
+    if (BM == 128 && BN == 64) return launch_bf16<128, 64, IO, MK, BS>(p, st, fl, n128x64);
+    return launch_bf16<64, 64, IO, MK, BS>(p, st, fl, n64);
 }
 
 static int conv_bf16_run(const char* who, const zsg_conv_desc* d, const void* src, const uint16_t* wt_packed, void* out, const float* bias,
-                         const void* add_src, int32_t io, void* stream, const float* mask_src = nullptr) {
+                         const void* add_src, int32_t io, void* stream, const float* mask_src = nullptr, float* bn_partials = nullptr,
+                         bool want_stats = false) {
     ZSG_REQUIRE(d && src && wt_packed && out, "%s: null argument", who);
+    if (want_stats) {
+        const char* why_bn = bf16_bn_check(d);
+        ZSG_REQUIRE(why_bn == nullptr, "%s: unsupported: %s", who, why_bn);
+        ZSG_REQUIRE(bn_partials && ((uintptr_t)bn_partials & 15) == 0, "%s: bn_partials null or not 16-byte aligned", who);
+        ZSG_REQUIRE(((uintptr_t)out & 15) == 0, "%s: out not 16-byte aligned (the BatchNorm statistics ride on the 16-byte epilogue)", who);
+    }
     ZSG_REQUIRE(!mask_src || io == 0, "%s: mask_src with io_flags %d (fp32 storage only)", who, io);
     ZSG_REQUIRE(((uintptr_t)mask_src & 3) == 0, "%s: mask_src not element-aligned", who);
     int BM = 64, BN = 64;
@@ -534,6 +595,13 @@ static int conv_bf16_run(const char* who, const zsg_conv_desc* d, const void* sr
                       - (s16 ? 2.0 * in_e : 0.0) - (o16 ? 2.0 * out_e : 0.0) - ((a16 && add_src) ? 2.0 * out_e : 0.0);
     }
     hipStream_t st = (hipStream_t)stream;
+    if (want_stats) {            // (the partial rows: 8 more bytes per tile row and output channel)
+        ZSG_REQUIRE(p.vec, "%s: out / descriptor do not qualify for the 16-byte epilogue", who);
+        p.stats = bn_partials;
+        p.alg_bytes += 8.0 * (double)p.m_tiles * d->N;
+        return launch_bf16_tile<0, false, true>(BM, BN, p, st, fl, "igemm_bf16_kernel<64, 64, 0, bn>", "igemm_bf16_kernel<128, 64, 0, bn>",
+                                                "igemm_bf16_kernel<128, 128, 0, bn>");
+    }
     if (mask_src) {              // (the mask reads 4 more bytes per output element)
         double out_e = 0;
         for (int s = 0; s < d->nseg; ++s) out_e += (double)d->B * d->seg[s].rows_y * d->seg[s].rows_x * d->N;
@@ -577,4 +645,9 @@ extern "C" int zsg_conv_igemm_bf16_m(const zsg_conv_desc* d, const float* src, c
 extern "C" int zsg_conv_igemm_bf16_io(const zsg_conv_desc* d, const void* src, const uint16_t* wt_packed, void* out, const float* bias,
                                       const void* add_src, int32_t io_flags, void* stream) {
     return conv_bf16_run("conv_igemm_bf16_io", d, src, wt_packed, out, bias, add_src, io_flags, stream);
+}
+
+extern "C" int zsg_conv_igemm_bf16_bn(const zsg_conv_desc* d, const float* src, const uint16_t* wt_packed, float* out, float* bn_partials,
+                                      void* stream) {
+    return conv_bf16_run("conv_igemm_bf16_bn", d, src, wt_packed, out, nullptr, nullptr, 0, stream, nullptr, bn_partials, true);
 }

@@ -281,6 +281,8 @@ class DistributedDataParallel(nn.Module):
             key += (("wgrad", self.module._wgrad_dtype),)    # (bf16 weight gradients are tuned under their own entries)
         if self.module.training and getattr(self.module, "_train_dtype", "fp32") != "fp32":
             key += (("train", self.module._train_dtype),)    # (so are the bf16 forward convolutions / data gradients of the pyramid and the heads)
+        if self.module.training and getattr(self.module, "_enc_dtype", "fp32") != "fp32":
+            key += (("enc", self.module._enc_dtype),)        # (and the encoder's bf16 forward convolutions)
         if key in self._tuned:
             return
         self._tuned.add(key)
@@ -319,6 +321,12 @@ class DistributedDataParallel(nn.Module):
         """ZSGNet.train_precision of the wrapped network ("fp32" | "bf16_head"): activations and gradients stay fp32 in memory, so buckets
         and collectives are unchanged"""
         self.module.train_precision(dtype)
+        return self
+
+    def encoder_precision(self, dtype: str = "fp32"):
+        """ZSGNet.encoder_precision of the wrapped network ("fp32" | "bf16_fwd"): activations and gradients stay fp32 in memory, so buckets
+        and collectives are unchanged (a synchronized BatchNorm reads the bf16 launch's partial rows as it reads the fp32 launch's)"""
+        self.module.encoder_precision(dtype)
         return self
 
     def close(self):

@@ -40,6 +40,8 @@ SSD_EXTRAS = [256, "S", 512, 128, "S", 256, 128, 256, 128, 256]                 
 WGRAD_DTYPES = ("fp32", "bf16")               # cfg wgrad_dtype / ZSGNet.wgrad_precision: operand precision of the training plans' convolution weight gradients
 EVAL_DTYPES = ("fp32", "bf16", "bf16_act")    # cfg eval_dtype / ZSGNet.eval_precision: operand precision of the eval plans' convolutions (+ bf16 activation storage)
 TRAIN_DTYPES = ("fp32", "bf16_head")         # cfg train_dtype / ZSGNet.train_precision: operand precision of the training plans' forward convolutions and data gradients ("bf16_head": the pyramid and the heads; "bf16" is left free for a whole-network version)
+ENC_DTYPES = ("fp32", "bf16_fwd")             # cfg enc_dtype / ZSGNet.encoder_precision: operand precision of the training plans' forward convolutions of a ResNet encoder behind the stem (the backward stays what wgrad_dtype / fp32 make it)
+BF16_ENC_PREFIX = "backbone.encoder."         # the layers enc_dtype = "bf16_fwd" covers (ResNet only; never the stem, never a convolution that applies a pending BatchNorm)
 BF16_HEAD_PREFIXES = ("backbone.fpn.", "att_reg_box.", "att_box.", "reg_box.")     # the layers train_dtype = "bf16_head" covers: no BatchNorm among them
 LSTM_DIMS = (32, 64, 128, 256)    # cfg lstm_dim: the widths csrc/lstm.hip instantiates zsg_lstm_fwd / zsg_lstm_bwd for
 
@@ -174,6 +176,7 @@ class ZSGNet(nn.Module):
         self._eval_dtype = "fp32"      # operand precision of the eval plans' convolutions (eval_precision)
         self._wgrad_dtype = "fp32"     # operand precision of the training plans' convolution weight gradients (wgrad_precision)
         self._train_dtype = "fp32"     # operand precision of the training plans' forward convolutions / data gradients (train_precision)
+        self._enc_dtype = "fp32"       # operand precision of the training plans' encoder forward convolutions (encoder_precision)
         LIVE_NETS.add(self)
 
     # ------------------------------------------------------------------------------------------------------
@@ -600,6 +603,36 @@ class ZSGNet(nn.Module):
         self._train_dtype = dtype
         return self
 
+    def encoder_precision(self, dtype: str = "fp32") -> "ZSGNet":
+        """Operand precision of the forward convolutions of the ENCODER in the TRAINING plans: "fp32" (default: what every plan lowered
+        before, launch for launch) or "bf16_fwd" — every forward convolution named backbone.encoder.* of a ResNet encoder (basic blocks and
+        bottlenecks, projection shortcuts included) runs on bf16 MFMA: in front of a live train-mode BatchNorm zsg_conv_igemm_bf16_bn,
+        whose epilogue writes the BatchNorm's partial rows as the fp32 launch does (fp32 activations rounded by the operand loader, the
+        weights packed by the forward's one pack launch, fp32 accumulation; include/zsg.h), in front of a frozen BatchNorm the plain
+        zsg_conv_igemm_bf16.  Not covered: the stem, and a convolution whose source carries a PENDING BatchNorm (it applies that
+        BatchNorm in its operand loader: zsg_conv_igemm_bnpre, fp32 with all its fusions).  The whole backward is the fp32 plan's
+        lowering — fp32 data gradients with their BatchNorm-backward epilogues, weight gradients as wgrad_precision says — and every
+        activation in memory stays fp32.  The SSD-VGG encoder is not covered: there the switch changes nothing.  Eval plans ignore the
+        switch.  Independent of train_precision, wgrad_precision and eval_precision.  The precision is part of a training plan's
+        identity: switching drops the training plans of the other precision."""
+        if dtype not in ENC_DTYPES:
+            raise ValueError(f"enc_dtype={dtype!r}: expected one of {', '.join(ENC_DTYPES)}")
+        self._enc_dtype = dtype
+        return self
+
+    def _enc_key(self) -> Tuple:
+        """what encoder_precision adds to a training plan's key (as _train_key: nothing for fp32, whose key stays what it always was)"""
+        return () if self._enc_dtype == "fp32" else (("enc", self._enc_dtype),)
+
+    @staticmethod
+    def _key_enc(k: Tuple) -> str:
+        """the encoder-forward precision of a training plan's key"""
+        return next((e[1] for e in k[7:-1] if isinstance(e, tuple) and e[0] == "enc"), "fp32")
+
+    def _enc_kw(self) -> Dict[str, str]:
+        """the _Plan keyword of the switch: none with the default, so that a plan of the default is constructed exactly as before"""
+        return {} if self._enc_dtype == "fp32" else {"enc_dtype": self._enc_dtype}
+
     def _train_key(self) -> Tuple:
         """what train_precision adds to a training plan's key (as _wgrad_key: nothing for fp32, whose key stays what it always was)"""
         return () if self._train_dtype == "fp32" else (("train", self._train_dtype),)
@@ -644,17 +677,18 @@ class ZSGNet(nn.Module):
             # shared-image training plan: exactly B image slots and Q queries.  One (B, Q) at a time: a new one, like a new trainable set,
             # drops the shared training plans of the old (activation buffers must not pile up)
             fz, fb, sb = self._frozen_key(), self._frozen_bn_key(), self._sync_bn_key()
-            key = (B, H, W, T, fz, fb, sb, ("shared", Q)) + self._wgrad_key() + self._train_key() + (True,)
+            key = (B, H, W, T, fz, fb, sb, ("shared", Q)) + self._wgrad_key() + self._train_key() + self._enc_key() + (True,)
             if key not in self._plans:
                 for k in [k for k in self._plans if k[-1] and ((k[4], k[5], k[6]) != (fz, fb, sb) or self._key_wgrad(k) != self._wgrad_dtype
-                                                               or self._key_train(k) != self._train_dtype
+                                                               or self._key_train(k) != self._train_dtype or self._key_enc(k) != self._enc_dtype
                                                                or (self._key_shared(k) is not None and (k[0], self._key_shared(k)[1]) != (B, Q)))]:
                     old = self._plans.pop(k)
                     if old._prep_pending:
                         torch.cuda.current_stream().wait_event(old._prep_ev)
                 bn_names = list(self.bns)
                 self._plans[key] = _Plan(self, B, H, W, T, True, frozen={self._param_names[i] for i in fz},
-                                         frozen_bn={bn_names[i] for i in fb}, Q=Q, wgrad_dtype=self._wgrad_dtype, train_dtype=self._train_dtype)
+                                         frozen_bn={bn_names[i] for i in fb}, Q=Q, wgrad_dtype=self._wgrad_dtype, train_dtype=self._train_dtype,
+                                         **self._enc_kw())
             return self._plans[key]
         if Q is not None:
             # eval-only plan of Q queries over B (bucketed) images; the cache of these is bounded: least recently used first out
@@ -674,19 +708,19 @@ class ZSGNet(nn.Module):
                 self._plans[key] = _Plan(self, B, H, W, T, False, dtype=self._eval_dtype)
             return self._plans[key]
         fz, fb, sb = self._frozen_key(), self._frozen_bn_key(), self._sync_bn_key()
-        key = (B, H, W, T, fz, fb, sb) + self._wgrad_key() + self._train_key() + (True,)
+        key = (B, H, W, T, fz, fb, sb) + self._wgrad_key() + self._train_key() + self._enc_key() + (True,)
         if key not in self._plans:
             # a new trainable set, frozen-BatchNorm set or synchronized-BatchNorm set: the training plans of the old one go (gradual
             # unfreezing must not pile up activation buffers)
             for k in [k for k in self._plans if k[-1] and ((k[4], k[5], k[6]) != (fz, fb, sb) or self._key_wgrad(k) != self._wgrad_dtype
-                                                           or self._key_train(k) != self._train_dtype)]:
+                                                           or self._key_train(k) != self._train_dtype or self._key_enc(k) != self._enc_dtype)]:
                 old = self._plans.pop(k)
                 if old._prep_pending:           # (its side-stream weight preparation may still be reading the weights)
                     torch.cuda.current_stream().wait_event(old._prep_ev)
             bn_names = list(self.bns)
             self._plans[key] = _Plan(self, B, H, W, T, True, frozen={self._param_names[i] for i in fz},
                                      frozen_bn={bn_names[i] for i in fb}, sync_bn={bn_names[i] for i in sb}, wgrad_dtype=self._wgrad_dtype,
-                                     train_dtype=self._train_dtype)
+                                     train_dtype=self._train_dtype, **self._enc_kw())
         return self._plans[key]
 
     def _forward_shared(self, inp: Dict[str, Any]) -> Dict[str, Any]:
@@ -815,7 +849,7 @@ class _Plan:
     """Static lowering of ZSGNet for one (B, H, W, T, training) geometry."""
 
     def __init__(self, net: ZSGNet, B: int, H: int, W: int, T: int, training: bool, frozen=frozenset(), frozen_bn=frozenset(),
-                 sync_bn=frozenset(), Q: Optional[int] = None, dtype: str = "fp32", wgrad_dtype: str = "fp32", train_dtype: str = "fp32"):
+                 sync_bn=frozenset(), Q: Optional[int] = None, dtype: str = "fp32", wgrad_dtype: str = "fp32", train_dtype: str = "fp32", enc_dtype: str = "fp32"):
         self.net, self.B, self.H, self.W, self.T, self.training = net, B, H, W, T, training
         # training plans only (ZSGNet.wgrad_precision): the weight gradients that go through wgrad() are lowered to zsg_conv_wgrad_bf16
         assert wgrad_dtype in WGRAD_DTYPES
@@ -826,6 +860,12 @@ class _Plan:
         assert train_dtype in TRAIN_DTYPES
         self.train_bf16 = training and train_dtype == "bf16_head"
         self.dpack_jobs, self.dpack_blocks, self.dpack_jobs_dev, self._dpack = [], 0, None, {}
+        # training plans only (ZSGNet.encoder_precision): the forward convolutions of a ResNet encoder behind the stem are lowered to
+        # zsg_conv_igemm_bf16_bn (fused BatchNorm partial rows) / zsg_conv_igemm_bf16 (frozen BatchNorm); their packed weights join the
+        # forward's one pack launch; the backward is the fp32 lowering's.  _b16_log entries of kind "enc_fwd" (see below) also hold
+        # bn (the BatchNorm's name), frozen and mean / invstd (the statistics buffers it normalises with), filled by bn()
+        assert enc_dtype in ENC_DTYPES
+        self.enc_bf16 = training and enc_dtype == "bf16_fwd" and net.backbone_kind == "retina"
         # every launch train_dtype = "bf16_head" put on bf16 MFMA, in lowering order: dict(kind "fwd" | "dgrad", what, idx (launch index in
         # fwd / bwd), d (descriptor copy), src (src / dy), out (out / dx), add (Act | None), mask (Act | None), pname (weight), window
         # ((wc0, C) of the weight's channels, forward; (row0, n) of its input channels, data gradient)).  No plan buffer is recycled, so
@@ -936,9 +976,10 @@ class _Plan:
                 # on the side stream (prep_u: released behind the optimizer step's write of the weights by _rel_ev); the main stream waits
                 # for it in front of the first launch that reads an image, a side-stream reader is behind it in its own stream
                 self.prep_u.add(lib.zsg_pack_w_bf16_batched, self.pack_jobs_dev, len(self.pack_jobs), self.pack_blocks, what="pack bf16 weight images")
-                self._wait_idx = min(self._wait_idx, next(i for i, c in enumerate(self.fwd.calls) if c[0] is lib.zsg_conv_igemm_bf16))
+                self._wait_idx = min(self._wait_idx, next(i for i, c in enumerate(self.fwd.calls)
+                                                          if c[0] in (lib.zsg_conv_igemm_bf16, lib.zsg_conv_igemm_bf16_bn)))
         for e in self._b16_log:          # (launch indices after the reordering of the programs: hoisting, _batch_wgrads)
-            prog = self.fwd if e["kind"] == "fwd" else self.bwd
+            prog = self.fwd if e["kind"] in ("fwd", "enc_fwd") else self.bwd
             call = e.pop("call")
             e["idx"] = next(i for i, c in enumerate(prog.calls) if c is call)
 
@@ -1141,8 +1182,55 @@ class _Plan:
         return wp
 
     def _b16_eligible(self, lname: str) -> bool:
-        """train_dtype = "bf16_head" covers the layer: a convolution of the pyramid or of a head stack (never backbone.encoder.*)"""
+        """train_dtype = "bf16_head" covers the layer, forward AND data gradient: a convolution of the pyramid or of a head stack (never
+        backbone.encoder.*)"""
         return self.train_bf16 and lname.startswith(BF16_HEAD_PREFIXES)
+
+    def _enc_eligible(self, L: ConvL) -> bool:
+        """enc_dtype = "bf16_fwd" covers the layer, FORWARD only (the data gradient asks _b16_eligible): an encoder convolution behind
+        the stem"""
+        return self.enc_bf16 and L.name.startswith(BF16_ENC_PREFIX) and not L.merge_x
+
+    def _enc_fwd(self, L: ConvL, d, src: Act, out: Act, wt: torch.Tensor, bias, relu: bool, bn_fuse: Optional[BnL]):
+        """Lower the forward convolution of a covered encoder layer on bf16 MFMA.  Returns (launched, partials): (False, None) where the
+        layer is not covered or the library refuses (the caller lowers fp32); (True, None) behind a plain zsg_conv_igemm_bf16 launch (no
+        batch statistics needed); (True, the partial-row buffer) behind a zsg_conv_igemm_bf16_bn launch, with out.bn_chunks set (the
+        caller continues with _conv_after).  Never raises: whatever does not fit falls back."""
+        no = (False, None)
+        if not self._enc_eligible(L):
+            return no
+        stats = bn_fuse is not None and not L.bias and not relu
+        if bn_fuse is not None and not stats:
+            return no                    # (a BatchNorm behind a bias or a ReLU: no such layer in a ResNet; fp32 serves it)
+        if stats:
+            rows = sum(src.B * d.seg[i].rows_y * d.seg[i].rows_x for i in range(d.nseg))
+            rows64 = sum((src.B * d.seg[i].rows_y * d.seg[i].rows_x + 63) // 64 for i in range(d.nseg))
+            if not lib.zsg_conv_igemm_bf16_bn_supported(_ct.byref(d)) or rows64 * 2 * L.cout * 4 > self.ws_bytes:
+                return no                # (statistics needed and no room / no kernel for them: the fp32 lowering)
+            wp = self._fwd_image(d, wt, L.cpad, 0)
+            partials = self._ws_now()    # (the tuner's trials write at most the BM = 64 rows)
+            # autotune_conv, NOT self._tune: this descriptor must stay out of _tunables — ops.refine_in_step switches tile hints in place,
+            # and another BM would leave out.bn_chunks (and the bn_inline / stats: choice made from it below) stale
+            autotune_conv("igemm", lib.zsg_conv_igemm_bf16_bn, d, (src.buf, wp, out.buf, partials), stream_ptr())
+            chunks = int(lib.zsg_conv_igemm_bf16_partial_rows(_ct.byref(d)))
+            assert 0 < chunks <= rows64 and rows > 0
+            out.bn_chunks = chunks
+            self.fwd.add(lib.zsg_conv_igemm_bf16_bn, d, src.buf, wp, out.buf, partials, what=L.name + "+bf16bn", lane=self._lane)
+            res = (True, partials)
+        else:
+            if not lib.zsg_conv_igemm_bf16_supported(_ct.byref(d)):
+                return no
+            wp = self._fwd_image(d, wt, L.cpad, 0)
+            args = (src.buf, wp, out.buf, bias, None)
+            self._tune("igemm", lib.zsg_conv_igemm_bf16, d, args, stream_ptr())
+            self.fwd.add(lib.zsg_conv_igemm_bf16, d, *args, what=L.name + "+bf16", lane=self._lane)
+            out.bn_chunks = 0
+            res = (True, None)
+        self._b16_log.append(dict(kind="enc_fwd", what=L.name, idx=-1, call=self.fwd.calls[-1], d=type(d).from_buffer_copy(d), src=src,
+                                  out=out, add=None, mask=None, pname=L.name + ".weight", window=(0, d.C),
+                                  bn=None, frozen=None, mean=None, invstd=None))
+        out._enc_log = self._b16_log[-1]
+        return res
 
     def _bf16_train_fwd(self, lname: str, d, src: Act, w_src: torch.Tensor, wC: int, wc0: int, out: Act, bias, add: Optional[Act], what: str,
                         lane: int = 0) -> bool:
@@ -1248,6 +1336,11 @@ class _Plan:
             finish()
             out.bn_chunks, out.bn_inline, out.needs_mask, out.requires_grad = 0, None, relu, o32.requires_grad
             return out
+        # enc_dtype = "bf16_fwd": a covered encoder convolution on bf16 MFMA; what follows the launch (the statistics branches, the tape
+        # entry: the fp32 lowering's backward) is _conv_after, shared with the fp32 launch below
+        launched, partials = self._enc_fwd(L, d, src, out, wt, bias, relu, bn_fuse)
+        if launched:
+            return self._conv_after(L, d, src, out, relu, bn_fuse, partials)
         wargs = None
         if wino_ok(L.k, L.stride, L.pad, L.dil) and not L.merge_x and wino_mode() != "0":
             U, job = self._wino_u(wt.data_ptr(), L.cout, L.cpad, L.k * L.k * L.cpad, L.cpad, 0)
@@ -1276,12 +1369,10 @@ class _Plan:
             self.prep_u.add(lib.zsg_memset_f32, out.buf[lv0.off:], out.B * lv0.bstride, 0.0, what="zero:" + L.name)
             pre_zero = out.buf
         tail_n = -1
-        sync = self.bn_synced(bn_fuse)
-        if partials is not None and not sync:
+        if partials is not None and not self.bn_synced(bn_fuse):
             # BatchNorm statistics FINALISED by the last-arriving tile of the convolution (csrc/bn_tail.h, round 5): no finalize launch, no
             # re-reduction in the apply pass, wherever the launch has <= 128 partial rows per column block (tail_n > 0)
             tail_n = int(lib.zsg_conv_bn_tail_tickets(_ct.byref(d), 1 if d.use_wino else 0))
-        out.bn_inline = None
         if tail_n > 0:
             # the convolution's last tile per column block finalises the statistics itself (mean / invstd / running statistics are ready
             # when the launch ends): the plain apply launch follows, nothing in between
@@ -1295,19 +1386,25 @@ class _Plan:
             self.fwd.add(fn, d, rd.buf, wt, out.buf, bias, pre_zero, None, partials, what=L.name, lane=self._lane)
         if pre_zero is not None:
             self._zero_calls.append(self.fwd.calls[-1])
-        if tail_n > 0:
+        return self._conv_after(L, d, src, out, relu, bn_fuse, None if tail_n > 0 else partials)
+
+    def _conv_after(self, L: ConvL, d, src: Act, out: Act, relu: bool, bn_fuse: Optional[BnL], partials) -> Act:
+        """What conv() lowers behind its launch.  partials: the rows (out.bn_chunks of them) the launch wrote for bn_fuse WITHOUT finalising
+        them, or None (no fused statistics, or finalised in the kernel).  Then the bookkeeping and the tape entry."""
+        out.bn_inline = None
+        if partials is None:
             pass
-        elif partials is not None and sync:
+        elif self.bn_synced(bn_fuse):
             # synchronized statistics from the partial rows, at once (the shared workspace is reused by the next launch)
             rows = sum(src.B * d.seg[i].rows_y * d.seg[i].rows_x for i in range(d.nseg))
             out.bn_mean, out.bn_invstd = self._buf(bn_fuse.c), self._buf(bn_fuse.c)
             self._sync_fwd_stats(bn_fuse, None, rows, partials, out.bn_chunks, out.bn_mean, out.bn_invstd, self._lane)
-        elif partials is not None and out.bn_chunks <= lib.zsg_bn_inline_max_chunks():
+        elif out.bn_chunks <= lib.zsg_bn_inline_max_chunks():
             # few partial rows: the BatchNorm apply launch (the very next launch on this stream: the workspace is still intact)
             # reduces them itself — no finalize launch
             out.bn_inline = partials
             out.bn_mean, out.bn_invstd = self._buf(bn_fuse.c), self._buf(bn_fuse.c)
-        elif partials is not None:         # finalize at once: the shared workspace is reused by the next launch
+        else:                              # finalize at once: the shared workspace is reused by the next launch
             Lb = bn_fuse
             rows = sum(src.B * d.seg[i].rows_y * d.seg[i].rows_x for i in range(d.nseg))
             out.bn_mean, out.bn_invstd = self._buf(Lb.c), self._buf(Lb.c)
@@ -1606,6 +1703,8 @@ class _Plan:
             mean, invstd = self._eval_stats(L)
         else:
             mean, invstd = (x.bn_mean, x.bn_invstd) if fused else (self._buf(L.c), self._buf(L.c))
+        if getattr(x, "_enc_log", None) is not None:       # (enc_dtype = "bf16_fwd": the statistics this convolution's output is normalised with)
+            x._enc_log.update(bn=L.name, frozen=frozen, mean=mean, invstd=invstd)
         rm, rv = net._rm[L.index:L.index + L.c], net._rv[L.index:L.index + L.c]
         self.ws_need = max(getattr(self, "ws_need", 0), lib.zsg_bn_workspace_bytes(rows, L.c))
         gam, bet = self.P(L.name + ".weight"), self.P(L.name + ".bias")
@@ -2922,6 +3021,7 @@ def get_default_net(num_anchors=1, cfg=None):
     net.eval_precision(cfg["eval_dtype"] if "eval_dtype" in cfg else "fp32")          # (raises on anything but fp32 / bf16 / bf16_act)
     net.wgrad_precision(cfg["wgrad_dtype"] if "wgrad_dtype" in cfg else "fp32")       # (raises on anything but fp32 / bf16)
     net.train_precision(cfg["train_dtype"] if "train_dtype" in cfg else "fp32")       # (raises on anything but fp32 / bf16_head)
+    net.encoder_precision(cfg["enc_dtype"] if "enc_dtype" in cfg else "fp32")         # (raises on anything but fp32 / bf16_fwd)
     path = cfg["pretrained_path"] if "pretrained_path" in cfg else ""
     if path:
         n = load_pretrained_encoder(net, path)

@@ -851,8 +851,9 @@ def autotune_conv(kind: str, fn, d: ConvDesc, args: Sequence, stream: int, ws_by
     _check_table_arch()
     io = fn is lib.zsg_conv_igemm_bf16_io         # (... add_src, io_flags): the storage formats are part of the key, through the name field
     bf16m = fn is lib.zsg_conv_igemm_bf16_m       # (... add_src, mask_src): the training plans' forward / data-gradient entry
-    bf16 = io or bf16m or fn is lib.zsg_conv_igemm_bf16    # (d, src, packed weights, out, bias, add_src): no mask operand
-    add_src, mask = (args[4], args[5] if (bf16m or not bf16) else None) if kind == "igemm" else (None, None)
+    bf16bn = fn is lib.zsg_conv_igemm_bf16_bn     # (d, src, packed weights, out, bn_partials): the encoder's training forward (enc_dtype)
+    bf16 = io or bf16m or bf16bn or fn is lib.zsg_conv_igemm_bf16    # (d, src, packed weights, out, bias, add_src): no mask operand
+    add_src, mask = (args[4], args[5] if (bf16m or not bf16) else None) if (kind == "igemm" and not bf16bn) else (None, None)
     key = _sig(kind, d, (add_src is not None, mask is not None, add_src is not None and add_src is args[2], split_penalty_ms > 0,
                          mode if wino_args is not None else "", deterministic(), "bf16" if bf16 else "fp32",
                          fn.__name__ + (":io%d" % args[5] if io else ""),
