@@ -269,7 +269,7 @@ int zsg_pack_w_bf16_batched(const void* jobs_dev, int32_t njobs, int32_t total_b
  * For a data gradient the weight operand is the packed image of the TRANSPOSED filter [n][wR*wS][cred] (zsg_transpose_w_batched, then
  * zsg_pack_w_bf16_batched with N = n, T = wR*wS, wC = C = cred): dy is rounded by the loader, the transposed weights by the packer.
  * Supported / not supported: zsg_conv_igemm_bf16's lists (one check, bf16_check); there is no bn_partials operand and no epi_flags:
- * a data gradient that carries a BatchNorm's backward sums stays fp32.
+ * a data gradient that carries a BatchNorm's backward sums stays fp32 or takes zsg_conv_igemm_bf16_bnb (below).
  * zsg_conv_igemm_bf16_m_supported: 1 when zsg_conv_igemm_bf16_m accepts the descriptor (and its tile_hint), else 0. */
 int zsg_conv_igemm_bf16_m(const zsg_conv_desc* d, const float* src, const uint16_t* wt_packed, float* out, const float* bias,
                           const float* add_src, const float* mask_src, void* stream);
@@ -301,6 +301,35 @@ int zsg_conv_igemm_bf16_bn(const zsg_conv_desc* d, const float* src, const uint1
                            void* stream);
 int32_t zsg_conv_igemm_bf16_bn_supported(const zsg_conv_desc* d);
 int32_t zsg_conv_igemm_bf16_partial_rows(const zsg_conv_desc* d);
+/* ---------------------------------------------------------------------------------------------------------------
+ * Reduced-precision TRAINING data gradient of the ResNet encoder (enc_bwd_dtype = "bf16"; csrc/igemm_bf16.hip): the data gradient that
+ * completes the dout of a train-mode (or frozen, or synchronized) BatchNorm, on bf16 MFMA, with zsg_conv_igemm_bnb's epilogue — the one
+ * bf16 entry that carries a BatchNorm's backward sums (every other bf16 entry still refuses epi_flags).
+ * Matrix part: zsg_conv_igemm_bf16's contract, word for word (src = dy rounded to bf16 by the loader, round-to-nearest-even; wt_packed
+ * the packed image of the TRANSPOSED filter as for zsg_conv_igemm_bf16_m; exact products, fp32 accumulation in the fixed tap-major K
+ * order; no split-K, no stream-K, no atomics: the same input gives the same bits on every run).
+ * Epilogue (o = the element's output offset; bn_x and bn_relu_mask are indexed with the OUTPUT offsets, as in zsg_conv_igemm_bnb):
+ *       v = acc [+ add_src[o]];   g[e] = bit e of bn_relu_mask[o >> 2] ? v[e] : 0   (4 bits per 16-byte group, as zsg_bn_apply writes
+ *       them; bn_relu_mask == NULL: all ones);   out[o] = (d->epi_flags & 1) ? g : v
+ *       partials[mt][0][n] = sum g,   partials[mt][1][n] = sum g * ((bn_x[o] - bn_mean[n]) * bn_invstd[n])   over the valid rows of M tile mt
+ *   layout [m_tiles][2][N], m_tiles counted exactly as zsg_conv_igemm_bf16_partial_rows counts it for the same descriptor WITHOUT the
+ *   epi_flags bit (that function keeps refusing epi_flags): zsg_bn_backward_from_partials, zsg_bn_frozen_backward and
+ *   zsg_bn_sync_bwd_sums read it unchanged.  add_src may alias out (a thread reads its elements before it writes them).
+ * Order of the sums (fp32, fixed, the same on every run; zsg_conv_igemm_bf16_bn's): the output tile lies transposed in LDS; a thread
+ * owns 4 adjacent columns and the tile rows r, r + R, r + 2R, ... (R = 1024 / BN), which it adds in ascending order (s += g;
+ * q += g * xhat with xhat = (x - mean) * invstd, invalid rows skipped); the R row-group sums of a column then meet in LDS and one thread
+ * adds them in ascending group order.  Every (mt, n < N) element is written exactly once, by a 16-byte store; columns n >= N of a column
+ * tile that reaches past N are not written, nor is any row >= m_tiles.  The thread's bn_x values, mask bits and add_src values are
+ * requested before the accumulators go through LDS.  No in-kernel finalize (no tickets): zsg_bn_backward_from_partials finalizes.
+ * Tiles served: 64x64, 128x64 and 128x128 (the last: 16 rows per thread, 237 vector registers, no scratch at two blocks per CU).
+ * Not supported (-1, nothing launched, zsg_last_error names the argument): everything zsg_conv_igemm_bf16 refuses except epi_flags bit 0
+ * (merge_x, split-K / stream-K / variant hint bits, ...); bits of epi_flags other than bit 0; d->relu; N % 4 != 0; a descriptor, out or
+ * add_src pointer that does not take the 16-byte epilogue; bn_x, bn_mean, bn_invstd or partials NULL or not 16-byte aligned.
+ * zsg_conv_igemm_bf16_bnb_supported: 1 when the DESCRIPTOR (and its tile_hint) is accepted, else 0. */
+int zsg_conv_igemm_bf16_bnb(const zsg_conv_desc* d, const float* src, const uint16_t* wt_packed, float* out, const float* add_src,
+                            const float* bn_x, const float* bn_mean, const float* bn_invstd, const uint8_t* bn_relu_mask, float* partials,
+                            void* stream);
+int32_t zsg_conv_igemm_bf16_bnb_supported(const zsg_conv_desc* d);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * bf16 ACTIVATION STORAGE for inference (eval_dtype = "bf16_act"; csrc/igemm_bf16.hip, csrc/bf16_act.hip).  Everything "bf16" has;

@@ -36,7 +36,12 @@ per-launch events over a few steps on one stream): wgrad_kernel / wino_wgrad_ker
 wgrad_reduce_kernel, with launches and ms per step, TFLOP/s and algorithmic bytes per launch.
 
     python tools/finetune_step.py --enc-bf16 [--train-bf16-head] [--wgrad-bf16] [--out profiles/enc_bf16_step.json]
+    python tools/finetune_step.py --enc-bwd-bf16 [--enc-bf16] [--train-bf16-head] [--wgrad-bf16] [--out profiles/enc_bwd_bf16_step.json]
 
+--enc-bwd-bf16 measures the encoder's data gradients on bf16 MFMA (ZSGNet.encoder_backward_precision("bf16"): zsg_conv_igemm_bf16_m /
+zsg_conv_igemm_bf16_bnb) against the fp32 plan; with the other three flags three variants alternate: fp32, those switches, those switches +
+the encoder's data gradients.  Each variant also reports its encoder data gradients launch by launch (serial replay) and the encoder's
+BatchNorm-backward launches by entry.
 --enc-bf16 measures the encoder's forward convolutions on bf16 MFMA (ZSGNet.encoder_precision("bf16_fwd"): zsg_conv_igemm_bf16_bn) against
 the fp32 plan; with --train-bf16-head / --wgrad-bf16 four variants alternate: fp32, enc_bf16, those switches, those switches + enc_bf16.
 Each variant also reports its encoder forward convolutions launch by launch (serial replay) and the "stats:" launches beside them.
@@ -218,6 +223,36 @@ def enc_class(v, nprof=3):
                 enc_bn_apply_ms=round(apply_ms, 4), fwd_program_ms=round(sum(acc.values()), 4), enc_fwd_rows=rows)
 
 
+def encb_class(v, nprof=3):
+    """the encoder's data gradients of one variant (what enc_bwd_dtype = "bf16" replaces) and the BatchNorm backward launches behind
+    them, from per-launch events of the backward program in serial replay: per launch the layer, the entry, its suffix and the
+    microseconds; the encoder's "bnbwd" launches by entry (a bf16 data gradient has no in-kernel finalize: zsg_bn_bwd_apply becomes
+    zsg_bn_backward_from_partials)"""
+    net = v["net"]
+    plan = [p for k, p in net._plans.items() if k[-1]][0]
+    st = torch.cuda.current_stream().cuda_stream
+    acc = {}
+    for _ in range(nprof):
+        for tag, prog in (("bwd-prep", plan.prep), ("bwd", plan.bwd)):
+            for i, (what, fname, ms) in enumerate(prog.profile(st)):
+                acc[(tag, i, what, fname)] = acc.get((tag, i, what, fname), 0.0) + ms / nprof
+    rows, bnb, pack_ms = [], {}, 0.0
+    for (tag, i, what, fname), ms in sorted(acc.items()):
+        if tag == "bwd-prep":
+            if fname == "zsg_pack_w_bf16_batched":
+                pack_ms += ms
+        elif what.startswith("dgrad:" + mdl.BF16_ENC_PREFIX):
+            layer = what.split("+")[0]
+            rows.append([layer[6:], fname, what[len(layer):], round(ms * 1e3, 1)])
+        elif what.startswith(("bnbwd:" + mdl.BF16_ENC_PREFIX, "bnbwd(frozen):" + mdl.BF16_ENC_PREFIX)):
+            e = bnb.setdefault(fname, dict(launches=0, ms_per_step=0.0))
+            e["launches"] += 1
+            e["ms_per_step"] = round(e["ms_per_step"] + ms, 4)
+    return dict(enc_dgrad_ms=round(sum(r[3] for r in rows) / 1e3, 4), enc_dgrad_in_kernel_finalize=sum(r[2].endswith("+fin") for r in rows),
+                enc_bnbwd=bnb, enc_bnbwd_ms=round(sum(e["ms_per_step"] for e in bnb.values()), 4), bwd_pack_ms=round(pack_ms, 4),
+                bwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "bwd"), 4), enc_dgrad_rows=rows)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -233,6 +268,8 @@ def main():
     ap.add_argument("--train-bf16-head", action="store_true")
     ap.add_argument("--enc-bf16", action="store_true", help="fp32 against enc_dtype = bf16_fwd; with --train-bf16-head / --wgrad-bf16 "
                                                              "also those switches without and with the encoder's")
+    ap.add_argument("--enc-bwd-bf16", action="store_true", help="fp32 against enc_bwd_dtype = bf16; with --enc-bf16 / --train-bf16-head / "
+                                                                 "--wgrad-bf16 also those switches without and with the encoder's data gradients")
     ap.add_argument("--only", default="", help="comma-separated variant names to run (e.g. one variant under rocprofv3)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
@@ -252,7 +289,21 @@ def main():
     sd = None
     runs = {}
     enc_of = {}                              # variant -> cfg enc_dtype (default fp32)
-    if a.enc_bf16:
+    encb_of = {}                             # variant -> cfg enc_bwd_dtype (default fp32)
+    if a.enc_bwd_bf16:
+        other = ("bf16" if a.wgrad_bf16 else "fp32", "bf16_head" if a.train_bf16_head else "fp32")
+        oname = "+".join(n for n, on in (("enc_bf16", a.enc_bf16), ("bf16_head", a.train_bf16_head), ("bf16_wgrad", a.wgrad_bf16)) if on)
+        variants = {"fp32": ((), False, None, None, None, "fp32", "fp32")}
+        if oname:
+            variants[oname] = ((), False, None, None, None) + other
+            variants[oname + "+encb_bf16"] = ((), False, None, None, None) + other
+            encb_of[oname + "+encb_bf16"] = "bf16"
+            if a.enc_bf16:
+                enc_of[oname] = enc_of[oname + "+encb_bf16"] = "bf16_fwd"
+        else:
+            variants["encb_bf16"] = ((), False, None, None, None, "fp32", "fp32")
+            encb_of["encb_bf16"] = "bf16"
+    elif a.enc_bf16:
         other = ("bf16" if a.wgrad_bf16 else "fp32", "bf16_head" if a.train_bf16_head else "fp32")
         oname = next(k for k, v in TRAIN_VARIANTS.items() if v == other)
         variants = {"fp32": ((), False, None, None, None, "fp32", "fp32"), "enc_bf16": ((), False, None, None, None, "fp32", "fp32")}
@@ -280,6 +331,7 @@ def main():
     for name, (prefixes, bn_frozen, clip, sync_bn, ema, wgrad_dtype, train_dtype) in variants.items():
         net = mdl.get_default_net(9, cfg)
         net.wgrad_precision(wgrad_dtype).train_precision(train_dtype).encoder_precision(enc_of.get(name, "fp32"))
+        net.encoder_backward_precision(encb_of.get(name, "fp32"))
         if sd is None:
             sd = {k: v.clone() for k, v in net.state_dict().items()}
         net.load_state_dict(sd)
@@ -354,7 +406,10 @@ def main():
         if v["clip"] is not None:
             res["variants"][name].update(clip=v["clip"][0], max_norm=v["clip"][1], last_grad_norm=round(float(v["norm"]), 6),
                                          engaged=float(v["norm"]) > v["clip"][1])
-        if a.enc_bf16:
+        if a.enc_bwd_bf16:
+            res["variants"][name].update(enc_bwd_dtype=net._enc_bwd_dtype, enc_dtype=net._enc_dtype, train_dtype=net._train_dtype,
+                                         wgrad_dtype=net._wgrad_dtype, **encb_class(v))
+        elif a.enc_bf16:
             res["variants"][name].update(enc_dtype=net._enc_dtype, train_dtype=net._train_dtype, wgrad_dtype=net._wgrad_dtype, **enc_class(v))
         elif a.train_bf16_head:
             res["variants"][name].update(train_dtype=net._train_dtype, wgrad_dtype=net._wgrad_dtype, **head_class(v))

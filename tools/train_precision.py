@@ -1,11 +1,12 @@
 """Developer tool (a report, not a test): what the reduced-precision TRAINING switches do to a short training run — bf16 weight gradients
 (cfg wgrad_dtype / ZSGNet.wgrad_precision("bf16")), the bf16 forward and data gradients of the pyramid and the heads (cfg train_dtype /
 ZSGNet.train_precision("bf16_head")), both, the bf16 forward of the ResNet encoder (cfg enc_dtype / ZSGNet.encoder_precision("bf16_fwd"):
---switch enc), or all three (--switch all).  N Adam steps on seeded synthetic batches, once in fp32 and once with the switch, from the
+--switch enc), the bf16 data gradients of the ResNet encoder (cfg enc_bwd_dtype / ZSGNet.encoder_backward_precision("bf16"): --switch encb),
+or all four (--switch all).  N Adam steps on seeded synthetic batches, once in fp32 and once with the switch, from the
 SAME initial weights and the same batches; prints both loss curves, the distance of the first step's gradients (same weights, same batch:
 the rounding's alone) and the relative L2 distance of the final weights.
 
-    python tools/train_precision.py [--switch wgrad|train|both|enc|all] [--steps 30] [--arch resnet50] [--size 300] [--bs 16] [--lr 1e-4] [--batches 4]
+    python tools/train_precision.py [--switch wgrad|train|both|enc|encb|all] [--steps 30] [--arch resnet50] [--size 300] [--bs 16] [--lr 1e-4] [--batches 4]
 
 ZSG_DETERMINISTIC=1 is set, so the fp32 run is reproducible and the distance is the bf16 rounding's alone."""
 import argparse
@@ -20,7 +21,7 @@ from zsgnet_pytorch_amd import config, loss, mdl, optim  # noqa: E402
 from zsgnet_pytorch_amd.synth import synthetic_batch  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--switch", default="wgrad", choices=("wgrad", "train", "both", "enc", "all"))
+ap.add_argument("--switch", default="wgrad", choices=("wgrad", "train", "both", "enc", "encb", "all"))
 ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--arch", default="resnet50")
 ap.add_argument("--size", type=int, default=300)
@@ -29,11 +30,12 @@ ap.add_argument("--lr", type=float, default=1e-4)
 ap.add_argument("--batches", type=int, default=4, help="distinct synthetic batches, visited round-robin")
 a = ap.parse_args()
 
-# (label, wgrad_dtype, train_dtype, enc_dtype) of the two runs
-ON = dict(wgrad=("bf16-wgrad", "bf16", "fp32", "fp32"), train=("bf16_head", "fp32", "bf16_head", "fp32"),
-          both=("bf16_head+bf16-wgrad", "bf16", "bf16_head", "fp32"), enc=("bf16_fwd-enc", "fp32", "fp32", "bf16_fwd"),
-          all=("bf16_fwd-enc+bf16_head+bf16-wgrad", "bf16", "bf16_head", "bf16_fwd"))[a.switch]
-RUNS = (("fp32", "fp32", "fp32", "fp32"), ON)
+# (label, wgrad_dtype, train_dtype, enc_dtype, enc_bwd_dtype) of the two runs
+ON = dict(wgrad=("bf16-wgrad", "bf16", "fp32", "fp32", "fp32"), train=("bf16_head", "fp32", "bf16_head", "fp32", "fp32"),
+          both=("bf16_head+bf16-wgrad", "bf16", "bf16_head", "fp32", "fp32"), enc=("bf16_fwd-enc", "fp32", "fp32", "bf16_fwd", "fp32"),
+          encb=("bf16-enc-dgrad", "fp32", "fp32", "fp32", "bf16"),
+          all=("bf16-enc-dgrad+bf16_fwd-enc+bf16_head+bf16-wgrad", "bf16", "bf16_head", "bf16_fwd", "bf16"))[a.switch]
+RUNS = (("fp32", "fp32", "fp32", "fp32", "fp32"), ON)
 
 torch.cuda.set_device(0)
 cfg = config.get_cfg(resnet_arch=a.arch, bs=a.bs, resize_img=[a.size, a.size])
@@ -46,13 +48,13 @@ for i in range(a.batches):
     batches.append(bt)
 sd, curves, final, g0, names, spans = None, {}, {}, {}, None, None
 w_init = None
-for label, wdt, tdt, edt in RUNS:
+for label, wdt, tdt, edt, bdt in RUNS:
     torch.manual_seed(1234)
     net = mdl.get_default_net(9, cfg)
     if sd is None:
         sd = {k: v.clone() for k, v in net.state_dict().items()}
     net.load_state_dict(sd)
-    net.to("cuda").train().wgrad_precision(wdt).train_precision(tdt).encoder_precision(edt)
+    net.to("cuda").train().wgrad_precision(wdt).train_precision(tdt).encoder_precision(edt).encoder_backward_precision(bdt)
     if w_init is None:
         w_init = net.store.flat.detach().double().cpu()
         names, spans = list(net._param_names), {n: (net.store.entries[n].offset, net.store.entries[n].size) for n in net._param_names}

@@ -78,6 +78,8 @@ SIGNATURES = {
     "zsg_conv_igemm_bf16_bn": (I32, [DP, P, P, P, P, P]),
     "zsg_conv_igemm_bf16_bn_supported": (I32, [DP]),
     "zsg_conv_igemm_bf16_partial_rows": (I32, [DP]),
+    "zsg_conv_igemm_bf16_bnb": (I32, [DP, P, P, P, P, P, P, P, P, P, P]),
+    "zsg_conv_igemm_bf16_bnb_supported": (I32, [DP]),
     "zsg_pack_w_bf16_batched": (I32, [P, I32, I32, P]),
     "zsg_conv_igemm_bf16_io": (I32, [DP, P, P, P, P, P, I32, P]),
     "zsg_conv_igemm_bf16_io_supported": (I32, [DP, I32]),

@@ -52,7 +52,8 @@ DEFAULTS: Dict[str, Any] = {
     "wgrad_dtype": "fp32",          # "bf16": the convolution weight gradients of the TRAINING backward run on bf16 MFMA with fp32 accumulation (zsg_conv_wgrad_bf16; ZSGNet.wgrad_precision) — src, dy and the gradients stay fp32 in memory, the forward, the data gradients, the stem and the small directly lowered weight gradients stay fp32
     "train_dtype": "fp32",          # "bf16_head": in TRAINING plans the forward convolutions and the data gradients of the pyramid (backbone.fpn.*) and the head stacks run on bf16 MFMA with fp32 accumulation (zsg_conv_igemm_bf16 / zsg_conv_igemm_bf16_m; ZSGNet.train_precision) — activations, weights and gradients stay fp32 in memory; the encoder, every BatchNorm-fused launch, the query encoder and the weight gradients (wgrad_dtype) are untouched
     "enc_dtype": "fp32",            # "bf16_fwd": in TRAINING plans the forward convolutions of a ResNet encoder behind the stem (backbone.encoder.*) run on bf16 MFMA with fp32 accumulation and the fused BatchNorm statistics (zsg_conv_igemm_bf16_bn; ZSGNet.encoder_precision) — activations, weights and gradients stay fp32 in memory; the stem, the convolutions that apply a pending BatchNorm in their loader, the whole backward (fp32 data gradients, weight gradients as wgrad_dtype says) and the SSD-VGG encoder are untouched
-    "atss_topk": 9,                 # ... candidates per pyramid level (1 .. 16)
+    "enc_bwd_dtype": "fp32",        # "bf16": in TRAINING plans the data gradients of a ResNet encoder behind the stem (backbone.encoder.*) run on bf16 MFMA with fp32 accumulation (zsg_conv_igemm_bf16_m; where one completes a BatchNorm's dout, zsg_conv_igemm_bf16_bnb with that BatchNorm's backward sums in its epilogue; ZSGNet.encoder_backward_precision) — activations, weights and gradients stay fp32 in memory; the forward, the stem, the pyramid's data gradients into C3-C5, the weight gradients (wgrad_dtype) and the SSD-VGG encoder are untouched; independent of enc_dtype
+    "atss_topk": 9,                # ... candidates per pyramid level (1 .. 16)
     # configs/ds_info.json: where each dataset's images and csv files live (override with --ds_info.<name>.<key>=...)
     "ds_info": {name: {"data_dir": f"./data/{root}", "img_dir": f"./data/{imgs}",
                        **{f"{s}_csv_file": f"./data/{csv}/csv_dir/{f}.csv" for s, f in (("trn", trn), ("val", "val"), ("test", "test"))}}

@@ -108,6 +108,7 @@ struct BfParams {
     BfSegDev seg[ZSG_MAX_SEG];
     const float* mask_src;      // MK kernels only: fp32, indexed like out (behind the segments: the other kernels' argument offsets stay)
     float* stats;               // BS kernels only: BatchNorm partials [m_tiles][2][N] of the stored values (behind everything, as mask_src)
+    BnbDev bnb;                 // BB kernels only: the BatchNorm whose backward sums go to stats instead (behind everything, as stats)
 };
 
 // BM x BN block tile, 4 waves (2 x 2), each wave TM x TN MFMA tiles of 32x32.  Two blocks per CU (at most 256 registers per lane).
@@ -119,11 +120,17 @@ struct BfParams {
 // stats[mt][0][n] = sum over the tile's valid rows of v, stats[mt][1][n] = sum of v * v, v the fp32 value stored — igemm.hip's bn_partials
 // layout.  Order: a thread owns 4 columns and the rows rr, rr + RPP, ... ascending (s += v; q = fma(v, v, q)); the RPP row groups are
 // combined through LDS in index order by one thread per column group.  No atomics, nothing between workgroups.
+// BB (with IO = 0, no mask, no BS, the vectorised epilogue only): igemm.hip's bnb epilogue — a data gradient that
+// completes the dout of a BatchNorm.  v = acc [+ add_src]; g = relu-bit ? v : 0 (bnb.mask, 4 bits per 16-byte group, NULL = all ones);
+// stored: v, or g with bnb.store_masked; stats[mt][0][n] = sum g, stats[mt][1][n] = sum g * ((bnb.x - mean) * invstd) over the tile's
+// valid rows, in the BS variant's order (s += g; q += g * xhat).  The thread's bnb.x values, bits and add_src values are requested
+// before the accumulators go through LDS, as in igemm.hip.
 #define BF_SRC8 8
-template <int BM, int BN, int IO, bool MK = false, bool BS = false>
+template <int BM, int BN, int IO, bool MK = false, bool BS = false, bool BB = false>
 __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
     static_assert(!MK || IO == 0, "the mask variant is built for fp32 storage only");
     static_assert(!BS || (IO == 0 && !MK), "the BatchNorm-statistics variant is built for fp32 storage without a mask only");
+    static_assert(!BB || (IO == 0 && !MK && !BS), "the BatchNorm-backward variant is built for fp32 storage without a mask or forward statistics only");
     ZSG_SET_MAIN_PRIO();
     constexpr int WM = 2, WN = 2, NT = 256;
     constexpr int KG = BF_BK / 8;        // threads (8-channel groups) per tile row
@@ -307,6 +314,21 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
         static_assert(BM % RPP == 0, "epilogue row passes");
         const int cg = tid % CG, rr = tid / CG;
         const int n = n0 + 4 * cg;
+        constexpr int NR = BB ? BM / RPP : 1;         // BB: rows per thread
+        [[maybe_unused]] f32x4 xpre[NR], apre[NR];
+        [[maybe_unused]] unsigned mpre[NR];
+        if constexpr (BB) {
+            // cold HBM reads: their latency hides behind the transposition (rows that are not stored read element 0)
+#pragma unroll
+            for (int i = 0; i < NR; ++i) {
+                const int ro = rowout[rr + RPP * i];
+                const bool ok = (ro >= 0) & (n < p.N);
+                const size_t o = ok ? (size_t)ro + n : 0;
+                xpre[i] = *(const f32x4*)(p.bnb.x + o);
+                mpre[i] = p.bnb.mask ? p.bnb.mask[o >> 2] : 0xfu;
+                if (p.add_src) apre[i] = *(const f32x4*)((const float*)p.add_src + o);
+            }
+        }
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -321,6 +343,23 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
         if (n < p.N) {
             f32x4 bv = {0.f, 0.f, 0.f, 0.f};
             if (p.bias) bv = *(const f32x4*)(p.bias + n);
+            if constexpr (BB) {                       // (bias / ReLU / float mask are excluded by the host for this variant)
+                const f32x4 mu = *(const f32x4*)(p.bnb.mean + n), is = *(const f32x4*)(p.bnb.invstd + n);
+#pragma unroll
+                for (int i = 0; i < NR; ++i) {
+                    const int row = rr + RPP * i;
+                    const int ro = rowout[row];
+                    if (ro < 0) continue;
+                    f32x4 v = *(const f32x4*)(ct + row * LDC + 4 * cg);
+                    if (p.add_src) v += apre[i];
+                    f32x4 gv = v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) gv[e] = ((mpre[i] >> e) & 1u) ? gv[e] : 0.f;
+                    *(f32x4*)((float*)p.out + (size_t)ro + n) = p.bnb.store_masked ? gv : v;
+                    bs_s += gv;
+                    bs_q += gv * ((xpre[i] - mu) * is);
+                }
+            } else
 #pragma unroll 4
             for (int row = rr; row < BM; row += RPP) {
                 const int ro = rowout[row];
@@ -349,7 +388,7 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const BfParams p) {
                 }
             }
         }
-        if constexpr (BS) {
+        if constexpr (BS || BB) {
             // the RPP row groups of a column group meet in LDS (the transposed tile is dead behind the barrier; rowout lies behind it)
             f32x4* red = (f32x4*)smem;                // [RPP][2][CG]
             static_assert(RPP * 2 * CG * 16 <= 2 * (BM + BN) * LDR * 2, "the row-group sums must fit the K-loop staging area");
@@ -492,6 +531,23 @@ static const char* bf16_bn_check(const zsg_conv_desc* d) {
 
 extern "C" int32_t zsg_conv_igemm_bf16_bn_supported(const zsg_conv_desc* d) { return bf16_bn_check(d) == nullptr ? 1 : 0; }
 
+// What the BatchNorm-backward epilogue changes in bf16_bn_check: bit 0 of epi_flags is its own (store the masked gradient).  All three
+// tiles are served (128x128: 16 rows per thread, 237 registers, no scratch at two blocks per CU).  plain: the descriptor without the bit.
+static const char* bf16_bnb_check(const zsg_conv_desc* d, zsg_conv_desc* plain) {
+    if (!d) return "null descriptor";
+    if (d->epi_flags & ~1) return "epi_flags bits other than bit 0 (store the masked gradient)";
+    *plain = *d;
+    plain->epi_flags = 0;
+    const char* why = bf16_bn_check(plain);
+    if (why) return why;
+    return nullptr;
+}
+
+extern "C" int32_t zsg_conv_igemm_bf16_bnb_supported(const zsg_conv_desc* d) {
+    zsg_conv_desc plain;
+    return bf16_bnb_check(d, &plain) == nullptr ? 1 : 0;
+}
+
 extern "C" int32_t zsg_conv_igemm_bf16_partial_rows(const zsg_conv_desc* d) {
     if (bf16_bn_check(d) != nullptr) return -1;
     int bm = 64, bn = 64;
@@ -501,7 +557,7 @@ extern "C" int32_t zsg_conv_igemm_bf16_partial_rows(const zsg_conv_desc* d) {
     return (int32_t)tiles;
 }
 
-template <int BM, int BN, int IO, bool MK = false, bool BS = false>
+template <int BM, int BN, int IO, bool MK = false, bool BS = false, bool BB = false>
 static int launch_bf16(const BfParams& p, hipStream_t st, double flops, const char* kname) {
     const size_t lds = (size_t)2 * (BM + BN) * BF_LDR * sizeof(uint16_t) + BM * sizeof(int);
     static bool attr_done[ZSG_MAX_DEV] = {};      // per device; idempotent (a benign race sets it twice)
@@ -509,12 +565,12 @@ static int launch_bf16(const BfParams& p, hipStream_t st, double flops, const ch
     (void)hipGetDevice(&dev);
     ZSG_REQUIRE(dev >= 0 && dev < ZSG_MAX_DEV, "igemm_bf16: device %d", dev);
     if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN, IO, MK, BS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)igemm_bf16_kernel<BM, BN, IO, MK, BS, BB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) ZSG_FAIL(-3, "igemm_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_done[dev] = true;
     }
     ZSG_PROF(kname, st, flops, p.alg_bytes);
-    ZSG_LAUNCH((igemm_bf16_kernel<BM, BN, IO, MK, BS>), dim3(p.m_tiles * p.n_tiles), dim3(256), lds, st, p);
+    ZSG_LAUNCH((igemm_bf16_kernel<BM, BN, IO, MK, BS, BB>), dim3(p.m_tiles * p.n_tiles), dim3(256), lds, st, p);
     ZSG_CHECK_LAUNCH("igemm_bf16");
     return 0;
 }
@@ -528,7 +584,7 @@ static int launch_bf16_tile(int BM, int BN, const BfParams& p, hipStream_t st, d
 
 static int conv_bf16_run(const char* who, const zsg_conv_desc* d, const void* src, const uint16_t* wt_packed, void* out, const float* bias,
                          const void* add_src, int32_t io, void* stream, const float* mask_src = nullptr, float* bn_partials = nullptr,
-                         bool want_stats = false) {
+                         bool want_stats = false, const BnbDev* bnb = nullptr) {
     ZSG_REQUIRE(d && src && wt_packed && out, "%s: null argument", who);
     if (want_stats) {
         const char* why_bn = bf16_bn_check(d);
@@ -596,9 +652,18 @@ static int conv_bf16_run(const char* who, const zsg_conv_desc* d, const void* sr
     }
     hipStream_t st = (hipStream_t)stream;
     if (want_stats) {            // (the partial rows: 8 more bytes per tile row and output channel)
-        ZSG_REQUIRE(p.vec, "%s: out / descriptor do not qualify for the 16-byte epilogue", who);
+        ZSG_REQUIRE(p.vec, "%s: out / add_src / descriptor do not qualify for the 16-byte epilogue", who);
         p.stats = bn_partials;
         p.alg_bytes += 8.0 * (double)p.m_tiles * d->N;
+        if (bnb) {               // (bn_x: 4 more bytes per output element)
+            p.bnb = *bnb;
+            double out_e = 0;
+            for (int s = 0; s < d->nseg; ++s) out_e += (double)d->B * d->seg[s].rows_y * d->seg[s].rows_x * d->N;
+            p.alg_bytes += 4.0 * out_e;
+            if (BM == 128 && BN == 128) return launch_bf16<128, 128, 0, false, false, true>(p, st, fl, "igemm_bf16_kernel<128, 128, 0, bnb>");
+            if (BM == 128) return launch_bf16<128, 64, 0, false, false, true>(p, st, fl, "igemm_bf16_kernel<128, 64, 0, bnb>");
+            return launch_bf16<64, 64, 0, false, false, true>(p, st, fl, "igemm_bf16_kernel<64, 64, 0, bnb>");
+        }
         return launch_bf16_tile<0, false, true>(BM, BN, p, st, fl, "igemm_bf16_kernel<64, 64, 0, bn>", "igemm_bf16_kernel<128, 64, 0, bn>",
                                                 "igemm_bf16_kernel<128, 128, 0, bn>");
     }
@@ -650,4 +715,18 @@ extern "C" int zsg_conv_igemm_bf16_io(const zsg_conv_desc* d, const void* src, c
 extern "C" int zsg_conv_igemm_bf16_bn(const zsg_conv_desc* d, const float* src, const uint16_t* wt_packed, float* out, float* bn_partials,
                                       void* stream) {
     return conv_bf16_run("conv_igemm_bf16_bn", d, src, wt_packed, out, nullptr, nullptr, 0, stream, nullptr, bn_partials, true);
+}
+
+extern "C" int zsg_conv_igemm_bf16_bnb(const zsg_conv_desc* d, const float* src, const uint16_t* wt_packed, float* out, const float* add_src,
+                                       const float* bn_x, const float* bn_mean, const float* bn_invstd, const uint8_t* bn_relu_mask,
+                                       float* partials, void* stream) {
+    static const char* who = "conv_igemm_bf16_bnb";
+    zsg_conv_desc plain;
+    const char* why = bf16_bnb_check(d, &plain);
+    ZSG_REQUIRE(why == nullptr, "%s: unsupported: %s", who, why);
+    ZSG_REQUIRE(bn_x && bn_mean && bn_invstd, "%s: bn_x / bn_mean / bn_invstd null", who);
+    ZSG_REQUIRE((((uintptr_t)bn_x | (uintptr_t)bn_mean | (uintptr_t)bn_invstd) & 15) == 0, "%s: bn_x / bn_mean / bn_invstd not 16-byte aligned", who);
+    ZSG_REQUIRE(partials && ((uintptr_t)partials & 15) == 0, "%s: partials null or not 16-byte aligned", who);
+    const BnbDev b = {bn_x, bn_mean, bn_invstd, bn_relu_mask, d->epi_flags & 1};
+    return conv_bf16_run(who, &plain, src, wt_packed, out, nullptr, add_src, 0, stream, nullptr, partials, true, &b);
 }

@@ -283,6 +283,8 @@ class DistributedDataParallel(nn.Module):
             key += (("train", self.module._train_dtype),)    # (so are the bf16 forward convolutions / data gradients of the pyramid and the heads)
         if self.module.training and getattr(self.module, "_enc_dtype", "fp32") != "fp32":
             key += (("enc", self.module._enc_dtype),)        # (and the encoder's bf16 forward convolutions)
+        if self.module.training and getattr(self.module, "_enc_bwd_dtype", "fp32") != "fp32":
+            key += (("encb", self.module._enc_bwd_dtype),)   # (and the encoder's bf16 data gradients)
         if key in self._tuned:
             return
         self._tuned.add(key)
@@ -327,6 +329,13 @@ class DistributedDataParallel(nn.Module):
         """ZSGNet.encoder_precision of the wrapped network ("fp32" | "bf16_fwd"): activations and gradients stay fp32 in memory, so buckets
         and collectives are unchanged (a synchronized BatchNorm reads the bf16 launch's partial rows as it reads the fp32 launch's)"""
         self.module.encoder_precision(dtype)
+        return self
+
+    def encoder_backward_precision(self, dtype: str = "fp32"):
+        """ZSGNet.encoder_backward_precision of the wrapped network ("fp32" | "bf16"): activations and gradients stay fp32 in memory, so
+        buckets and collectives are unchanged (a synchronized BatchNorm reads the bf16 data gradient's partial rows as it reads the fp32
+        launch's)"""
+        self.module.encoder_backward_precision(dtype)
         return self
 
     def close(self):

@@ -41,6 +41,7 @@ WGRAD_DTYPES = ("fp32", "bf16")               # cfg wgrad_dtype / ZSGNet.wgrad_p
 EVAL_DTYPES = ("fp32", "bf16", "bf16_act")    # cfg eval_dtype / ZSGNet.eval_precision: operand precision of the eval plans' convolutions (+ bf16 activation storage)
 TRAIN_DTYPES = ("fp32", "bf16_head")         # cfg train_dtype / ZSGNet.train_precision: operand precision of the training plans' forward convolutions and data gradients ("bf16_head": the pyramid and the heads; "bf16" is left free for a whole-network version)
 ENC_DTYPES = ("fp32", "bf16_fwd")             # cfg enc_dtype / ZSGNet.encoder_precision: operand precision of the training plans' forward convolutions of a ResNet encoder behind the stem (the backward stays what wgrad_dtype / fp32 make it)
+ENC_BWD_DTYPES = ("fp32", "bf16")             # cfg enc_bwd_dtype / ZSGNet.encoder_backward_precision: operand precision of the training plans' data gradients of a ResNet encoder behind the stem (independent of enc_dtype, which keeps its two values)
 BF16_ENC_PREFIX = "backbone.encoder."         # the layers enc_dtype = "bf16_fwd" covers (ResNet only; never the stem, never a convolution that applies a pending BatchNorm)
 BF16_HEAD_PREFIXES = ("backbone.fpn.", "att_reg_box.", "att_box.", "reg_box.")     # the layers train_dtype = "bf16_head" covers: no BatchNorm among them
 LSTM_DIMS = (32, 64, 128, 256)    # cfg lstm_dim: the widths csrc/lstm.hip instantiates zsg_lstm_fwd / zsg_lstm_bwd for
@@ -177,6 +178,7 @@ class ZSGNet(nn.Module):
         self._wgrad_dtype = "fp32"     # operand precision of the training plans' convolution weight gradients (wgrad_precision)
         self._train_dtype = "fp32"     # operand precision of the training plans' forward convolutions / data gradients (train_precision)
         self._enc_dtype = "fp32"       # operand precision of the training plans' encoder forward convolutions (encoder_precision)
+        self._enc_bwd_dtype = "fp32"   # operand precision of the training plans' encoder data gradients (encoder_backward_precision)
         LIVE_NETS.add(self)
 
     # ------------------------------------------------------------------------------------------------------
@@ -620,9 +622,32 @@ class ZSGNet(nn.Module):
         self._enc_dtype = dtype
         return self
 
+    def encoder_backward_precision(self, dtype: str = "fp32") -> "ZSGNet":
+        """Operand precision of the DATA GRADIENTS of the encoder in the TRAINING plans: "fp32" (default: what every plan lowered before,
+        launch for launch) or "bf16" — every data gradient of a convolution named backbone.encoder.* of a ResNet encoder (never the
+        stem's) that zsg_conv_igemm_bf16_m accepts runs on bf16 MFMA (dy rounded by the operand loader, the transposed filter packed by
+        one launch with the other weight-only work, fp32 accumulation, no Winograd, no split-K).  Where such a launch completes the
+        dout of a BatchNorm (live, frozen or synchronized) it is re-issued as zsg_conv_igemm_bf16_bnb, whose epilogue writes that
+        BatchNorm's backward partial rows as the fp32 launch does (include/zsg.h); there is no in-kernel finalize on this path:
+        zsg_bn_backward_from_partials reduces the rows.  The whole forward, the stem, the pyramid's data gradients into C3-C5, every
+        weight gradient (wgrad_precision decides those) and every activation in memory stay fp32.  The SSD-VGG encoder is not covered:
+        there the switch changes nothing.  Eval plans ignore the switch.  Independent of encoder_precision, train_precision,
+        wgrad_precision and eval_precision.  The precision is part of a training plan's identity: switching drops the training plans of
+        the other precision."""
+        if dtype not in ENC_BWD_DTYPES:
+            raise ValueError(f"enc_bwd_dtype={dtype!r}: expected one of {', '.join(ENC_BWD_DTYPES)}")
+        self._enc_bwd_dtype = dtype
+        return self
+
     def _enc_key(self) -> Tuple:
-        """what encoder_precision adds to a training plan's key (as _train_key: nothing for fp32, whose key stays what it always was)"""
-        return () if self._enc_dtype == "fp32" else (("enc", self._enc_dtype),)
+        """what encoder_precision and encoder_backward_precision add to a training plan's key (as _train_key: nothing for fp32, whose
+        key stays what it always was; ("encb", ...) stands behind ("enc", ...))"""
+        return (() if self._enc_dtype == "fp32" else (("enc", self._enc_dtype),)) + (() if self._enc_bwd_dtype == "fp32" else (("encb", self._enc_bwd_dtype),))
+
+    @staticmethod
+    def _key_encb(k: Tuple) -> str:
+        """the encoder data-gradient precision of a training plan's key"""
+        return next((e[1] for e in k[7:-1] if isinstance(e, tuple) and e[0] == "encb"), "fp32")
 
     @staticmethod
     def _key_enc(k: Tuple) -> str:
@@ -631,7 +656,10 @@ class ZSGNet(nn.Module):
 
     def _enc_kw(self) -> Dict[str, str]:
         """the _Plan keyword of the switch: none with the default, so that a plan of the default is constructed exactly as before"""
-        return {} if self._enc_dtype == "fp32" else {"enc_dtype": self._enc_dtype}
+        kw = {} if self._enc_dtype == "fp32" else {"enc_dtype": self._enc_dtype}
+        if self._enc_bwd_dtype != "fp32":
+            kw["enc_bwd_dtype"] = self._enc_bwd_dtype
+        return kw
 
     def _train_key(self) -> Tuple:
         """what train_precision adds to a training plan's key (as _wgrad_key: nothing for fp32, whose key stays what it always was)"""
@@ -680,7 +708,7 @@ class ZSGNet(nn.Module):
             key = (B, H, W, T, fz, fb, sb, ("shared", Q)) + self._wgrad_key() + self._train_key() + self._enc_key() + (True,)
             if key not in self._plans:
                 for k in [k for k in self._plans if k[-1] and ((k[4], k[5], k[6]) != (fz, fb, sb) or self._key_wgrad(k) != self._wgrad_dtype
-                                                               or self._key_train(k) != self._train_dtype or self._key_enc(k) != self._enc_dtype
+                                                               or self._key_train(k) != self._train_dtype or self._key_enc(k) != self._enc_dtype or self._key_encb(k) != self._enc_bwd_dtype
                                                                or (self._key_shared(k) is not None and (k[0], self._key_shared(k)[1]) != (B, Q)))]:
                     old = self._plans.pop(k)
                     if old._prep_pending:
@@ -713,7 +741,8 @@ class ZSGNet(nn.Module):
             # a new trainable set, frozen-BatchNorm set or synchronized-BatchNorm set: the training plans of the old one go (gradual
             # unfreezing must not pile up activation buffers)
             for k in [k for k in self._plans if k[-1] and ((k[4], k[5], k[6]) != (fz, fb, sb) or self._key_wgrad(k) != self._wgrad_dtype
-                                                           or self._key_train(k) != self._train_dtype or self._key_enc(k) != self._enc_dtype)]:
+                                                           or self._key_train(k) != self._train_dtype or self._key_enc(k) != self._enc_dtype
+                                                           or self._key_encb(k) != self._enc_bwd_dtype)]:
                 old = self._plans.pop(k)
                 if old._prep_pending:           # (its side-stream weight preparation may still be reading the weights)
                     torch.cuda.current_stream().wait_event(old._prep_ev)
@@ -849,7 +878,8 @@ class _Plan:
     """Static lowering of ZSGNet for one (B, H, W, T, training) geometry."""
 
     def __init__(self, net: ZSGNet, B: int, H: int, W: int, T: int, training: bool, frozen=frozenset(), frozen_bn=frozenset(),
-                 sync_bn=frozenset(), Q: Optional[int] = None, dtype: str = "fp32", wgrad_dtype: str = "fp32", train_dtype: str = "fp32", enc_dtype: str = "fp32"):
+                 sync_bn=frozenset(), Q: Optional[int] = None, dtype: str = "fp32", wgrad_dtype: str = "fp32", train_dtype: str = "fp32", enc_dtype: str = "fp32",
+                 enc_bwd_dtype: str = "fp32"):
         self.net, self.B, self.H, self.W, self.T, self.training = net, B, H, W, T, training
         # training plans only (ZSGNet.wgrad_precision): the weight gradients that go through wgrad() are lowered to zsg_conv_wgrad_bf16
         assert wgrad_dtype in WGRAD_DTYPES
@@ -866,6 +896,11 @@ class _Plan:
         # bn (the BatchNorm's name), frozen and mean / invstd (the statistics buffers it normalises with), filled by bn()
         assert enc_dtype in ENC_DTYPES
         self.enc_bf16 = training and enc_dtype == "bf16_fwd" and net.backbone_kind == "retina"
+        # enc_bwd_dtype = "bf16": the data gradients of the encoder behind the stem on bf16 MFMA (dgrad, _bnb_reissue); _b16_log entries of
+        # kind "enc_dgrad" hold d, src (dy), out (dx), add, window, pname and, where the launch was re-issued with a BatchNorm's backward
+        # sums, bn, x, mean, invstd, rmask, part, chunks and epi_flags
+        assert enc_bwd_dtype in ENC_BWD_DTYPES
+        self.encb_bf16 = training and enc_bwd_dtype == "bf16" and net.backbone_kind == "retina"
         # every launch train_dtype = "bf16_head" put on bf16 MFMA, in lowering order: dict(kind "fwd" | "dgrad", what, idx (launch index in
         # fwd / bwd), d (descriptor copy), src (src / dy), out (out / dx), add (Act | None), mask (Act | None), pname (weight), window
         # ((wc0, C) of the weight's channels, forward; (row0, n) of its input channels, data gradient)).  No plan buffer is recycled, so
@@ -1190,6 +1225,10 @@ class _Plan:
         """enc_dtype = "bf16_fwd" covers the layer, FORWARD only (the data gradient asks _b16_eligible): an encoder convolution behind
         the stem"""
         return self.enc_bf16 and L.name.startswith(BF16_ENC_PREFIX) and not L.merge_x
+
+    def _encb_eligible(self, L: ConvL) -> bool:
+        """enc_bwd_dtype = "bf16" covers the layer's DATA GRADIENT: an encoder convolution behind the stem"""
+        return self.encb_bf16 and L.name.startswith(BF16_ENC_PREFIX) and not L.merge_x
 
     def _enc_fwd(self, L: ConvL, d, src: Act, out: Act, wt: torch.Tensor, bias, relu: bool, bn_fuse: Optional[BnL]):
         """Lower the forward convolution of a covered encoder layer on bf16 MFMA.  Returns (launched, partials): (False, None) where the
@@ -1658,6 +1697,29 @@ class _Plan:
             dx.gfilled = True
             dx.last_writer = None
             return
+        if self._encb_eligible(L) and lib.zsg_conv_igemm_bf16_m_supported(_ct.byref(d)):
+            # enc_bwd_dtype = "bf16": the same launch on bf16 MFMA, on the packed copy of the transposed image (the one extra pack launch in
+            # prep that train_dtype has).  The strided (zero-filled) and the accumulating data gradients never carry a BatchNorm's sums; one
+            # that completes a BatchNorm's dout is re-issued by _bnb_reissue as zsg_conv_igemm_bf16_bnb.  No Winograd candidates, no split-K.
+            # autotune_conv, NOT self._tune: the partial-row count of the re-issued launch is baked into the BatchNorm backward behind it,
+            # so ops.refine_in_step must not move this descriptor's tile hint afterwards (as in _enc_fwd)
+            key = (L.name, row0, n)
+            if key not in self._dpack:
+                self._dpack[key], job, nblk = self._pack_image(wt.data_ptr() + 4 * wt_off, n, L.k * L.k, cred, 0, cred)
+                self.dpack_jobs.append(job + (self.dpack_blocks, 0))
+                self.dpack_blocks += nblk
+            add = dx if dx.gfilled else None
+            args = (dy.buf, self._dpack[key], dx.buf, None, dx.buf if dx.gfilled else None, mask)
+            autotune_conv("igemm", lib.zsg_conv_igemm_bf16_m, d, args, stream_ptr())
+            self.bwd.add(lib.zsg_conv_igemm_bf16_m, d, *args, what="dgrad:" + L.name + "+bf16")
+            self._b16_log.append(dict(kind="enc_dgrad", what="dgrad:" + L.name, idx=-1, call=self.bwd.calls[-1], d=type(d).from_buffer_copy(d),
+                                      src=dy, out=dx, add=add, mask=src if mask is not None else None, pname=L.name + ".weight",
+                                      window=(row0, n), bn=None))
+            dx.gfilled = True
+            covers_all = not d.zero_fill and mask is None and d.tile_hint and dx.ld == n and n % 4 == 0
+            # (the fifth field marks a bf16 launch: its _b16_log entry, which a re-issue completes)
+            dx.last_writer = (len(self.bwd.calls) - 1, d, args, "dgrad:" + L.name + "+bf16", self._b16_log[-1]) if covers_all else None
+            return
         args = (dy.buf, wt[wt_off:], dx.buf, None, dx.buf if dx.gfilled else None, mask, None)
         wargs = None
         if wino_ok(L.k, L.stride, L.pad, L.dil) and wino_mode() != "0":
@@ -1746,18 +1808,10 @@ class _Plan:
                 self._bn_sync_back(L, x, out, residual, relu, rmask, rows, mean, invstd, gam)
                 return
             dx = self.grad_of(x)
-            lw = getattr(out.grad, "last_writer", None)
-            fuse = (BNB_FUSE and lw is not None and lw[0] == len(self.bwd.calls) - 1 and self.bwd.lanes[lw[0]] == 0
-                    and len(out.grad.levels) == 1 and out.grad.levels[0].off == 0 and x.levels[0].off == 0 and out.grad.ld == L.c and x.ld == L.c)
-            if fuse:
-                # re-issue the data gradient that has just completed dout with the BatchNorm-backward sums in its epilogue
-                # (per-tile partial rows, reduced in a fixed order by the finalize launch: deterministic)
-                idx, d, a, what = lw
-                if d.use_wino:
-                    chunks = self._wino_chunks(d, x.B)
-                else:
-                    chunks = igemm_partial_rows(d)
-                fuse = chunks * 2 * L.c * 4 + 2 * L.c * 4 <= self.ws_bytes
+            # re-issue the data gradient that has just completed dout with the BatchNorm-backward sums in its epilogue
+            # (per-tile partial rows, reduced in a fixed order by the finalize launch: deterministic)
+            lw, chunks = self._bnb_chunks(L, x, out)
+            fuse = lw is not None
             g_out, bits = None, rmask
             if residual is not None and residual.requires_grad:
                 # Round 6: where the data gradient that completes dout carries this BatchNorm's backward sums anyway, it also STORES the
@@ -1777,22 +1831,17 @@ class _Plan:
                     rg.gfilled = True
             if fuse:
                 part = self.ws[2 * L.c:]              # (the first 2C floats of the workspace: the finalize launch's coefficients)
-                # a = (src, wt|U, out, bias=None, add_src, mask=None, partials=None)
-                assert a[3] is None and a[5] is None and a[6] is None
-                tail_n = int(lib.zsg_conv_bn_tail_tickets(_ct.byref(d), 1 if d.use_wino else 0))
+                tail_n = self._bnb_tail_tickets(lw)
                 if tail_n > 0:
                     # the data gradient's last tile per column block finalises the coefficients and d(gamma) / d(beta): the apply pass
                     # is all that is left of this BatchNorm's backward
-                    fn = lib.zsg_conv_wino_bnb_tail if d.use_wino else lib.zsg_conv_igemm_bnb_tail
                     tk = self._buf(tail_n, dtype=torch.int32)
                     coef = self._buf(2 * L.c)
-                    self.bwd.calls[idx] = (fn, marshal(fn, (d, a[0], a[1], a[2], a[4], x.buf, mean, invstd, rmask, part, tk, coef,
-                                                            self.G(L.name + ".weight"), self.G(L.name + ".bias"), 1), self.bwd.keep), what + "+bnb+fin")
+                    self._bnb_reissue(lw, L, x, mean, invstd, rmask, part, chunks, fin=(tk, coef, self.G(L.name + ".weight"), self.G(L.name + ".bias")))
                     self.bwd.add(lib.zsg_bn_bwd_apply, self.base(out.grad), bits, x.buf, rows, L.c, mean, invstd, gam, coef, dx.buf, g_out,
                                  what="bnbwd:" + L.name)
                 else:
-                    fn = lib.zsg_conv_wino_bnb if d.use_wino else lib.zsg_conv_igemm_bnb
-                    self.bwd.calls[idx] = (fn, marshal(fn, (d, a[0], a[1], a[2], a[4], x.buf, mean, invstd, rmask, part), self.bwd.keep), what + "+bnb")
+                    self._bnb_reissue(lw, L, x, mean, invstd, rmask, part, chunks)
                     self.bwd.add(lib.zsg_bn_backward_from_partials, self.base(out.grad), bits, x.buf, rows, L.c, mean, invstd, gam,
                                  dx.buf, g_out, self.G(L.name + ".weight"), self.G(L.name + ".bias"), 1, part, chunks, self.ws, self.ws_bytes,
                                  what="bnbwd:" + L.name)
@@ -1804,6 +1853,61 @@ class _Plan:
         self.tape.append(back)
         return out
 
+    def _bnb_chunks(self, L: BnL, x: Act, out: Act):
+        """(last_writer, partial rows) when the launch that has just completed out's gradient can be re-issued with this BatchNorm's
+        backward sums in its epilogue (_bnb_reissue) and its partial rows fit the workspace, else (None, 0): the BatchNorm then takes
+        its plain backward.  Never raises."""
+        lw = getattr(out.grad, "last_writer", None)
+        fuse = (BNB_FUSE and lw is not None and lw[0] == len(self.bwd.calls) - 1 and self.bwd.lanes[lw[0]] == 0
+                and len(out.grad.levels) == 1 and out.grad.levels[0].off == 0 and x.levels[0].off == 0 and out.grad.ld == L.c and x.ld == L.c)
+        if not fuse:
+            return None, 0
+        d = lw[1]
+        if len(lw) > 4:                  # a bf16 data gradient (enc_bwd_dtype): zsg_conv_igemm_bf16_bnb, or nothing
+            if not lib.zsg_conv_igemm_bf16_bnb_supported(_ct.byref(d)):
+                return None, 0
+            chunks = int(lib.zsg_conv_igemm_bf16_partial_rows(_ct.byref(d)))
+            if chunks <= 0:
+                return None, 0
+        elif d.use_wino:
+            chunks = self._wino_chunks(d, x.B)
+        else:
+            chunks = igemm_partial_rows(d)
+        if chunks * 2 * L.c * 4 + 2 * L.c * 4 > self.ws_bytes:
+            return None, 0
+        return lw, chunks
+
+    @staticmethod
+    def _bnb_tail_tickets(lw) -> int:
+        """tickets of the in-kernel finalize the re-issued launch can carry (0: none — every bf16 launch, which has no such form)"""
+        if len(lw) > 4:
+            return 0
+        return int(lib.zsg_conv_bn_tail_tickets(_ct.byref(lw[1]), 1 if lw[1].use_wino else 0))
+
+    def _bnb_reissue(self, lw, L: BnL, x: Act, mean, invstd, rmask, part, chunks: int, fin=None):
+        """Re-issue the data gradient lw, which has just completed the dout of BatchNorm L, with that BatchNorm's backward sums in its
+        epilogue: per-tile partial rows in `part`, reduced in a fixed order by the launch the caller adds behind it.  fin = (tickets,
+        coef, d(gamma), d(beta)): the fp32 launch whose last tile per column block also finalises the sums (never a bf16 launch)."""
+        idx, d, a, what = lw[:4]
+        if len(lw) > 4:
+            # a = (dy, packed transposed filter, out, bias=None, add_src, mask=None)
+            assert a[3] is None and a[5] is None and fin is None
+            fn = lib.zsg_conv_igemm_bf16_bnb
+            self.bwd.calls[idx] = (fn, marshal(fn, (d, a[0], a[1], a[2], a[4], x.buf, mean, invstd, rmask, part), self.bwd.keep), what + "+bnb")
+            lw[4].update(call=self.bwd.calls[idx], d=type(d).from_buffer_copy(d), bn=L.name, x=x, mean=mean, invstd=invstd, rmask=rmask,
+                         part=part, chunks=chunks, epi_flags=int(d.epi_flags))
+            return
+        # a = (src, wt|U, out, bias=None, add_src, mask=None, partials=None)
+        assert a[3] is None and a[5] is None and a[6] is None
+        if fin is not None:
+            tk, coef, dg, db = fin
+            fn = lib.zsg_conv_wino_bnb_tail if d.use_wino else lib.zsg_conv_igemm_bnb_tail
+            self.bwd.calls[idx] = (fn, marshal(fn, (d, a[0], a[1], a[2], a[4], x.buf, mean, invstd, rmask, part, tk, coef, dg, db, 1),
+                                               self.bwd.keep), what + "+bnb+fin")
+        else:
+            fn = lib.zsg_conv_wino_bnb if d.use_wino else lib.zsg_conv_igemm_bnb
+            self.bwd.calls[idx] = (fn, marshal(fn, (d, a[0], a[1], a[2], a[4], x.buf, mean, invstd, rmask, part), self.bwd.keep), what + "+bnb")
+
     def _bn_sync_back(self, L: BnL, x: Act, out: Act, residual: Optional[Act], relu: bool, rmask, rows: int, mean, invstd, gam):
         """Backward of a synchronized BatchNorm [+ residual] [+ ReLU] (torch's SyncBatchNorm): the rank-local (sum g, sum g * xhat) — from
         the epilogue of the data gradient that completed dout (zsg_conv_*_bnb, never the in-kernel finalize: the sums are not final
@@ -1811,13 +1915,8 @@ class _Plan:
         the forward's global N.  The residual gradient may alias dout exactly as in bn()'s back."""
         dx = self.grad_of(x)
         fs, bs = self._sync_bufs(L)
-        lw = getattr(out.grad, "last_writer", None)
-        fuse = (BNB_FUSE and lw is not None and lw[0] == len(self.bwd.calls) - 1 and self.bwd.lanes[lw[0]] == 0
-                and len(out.grad.levels) == 1 and out.grad.levels[0].off == 0 and x.levels[0].off == 0 and out.grad.ld == L.c and x.ld == L.c)
-        if fuse:
-            idx, d, a, what = lw
-            chunks = self._wino_chunks(d, x.B) if d.use_wino else igemm_partial_rows(d)
-            fuse = chunks * 2 * L.c * 4 + 2 * L.c * 4 <= self.ws_bytes
+        lw, chunks = self._bnb_chunks(L, x, out)
+        fuse = lw is not None
         g_out, bits = None, rmask
         if residual is not None and residual.requires_grad:
             alias = (fuse and relu and rmask is not None and residual.grad is None and len(residual.levels) == 1
@@ -1834,9 +1933,7 @@ class _Plan:
         dg, db = self.G(L.name + ".weight"), self.G(L.name + ".bias")
         if fuse:
             part = self.ws[2 * L.c:]
-            assert a[3] is None and a[5] is None and a[6] is None
-            fn = lib.zsg_conv_wino_bnb if d.use_wino else lib.zsg_conv_igemm_bnb
-            self.bwd.calls[idx] = (fn, marshal(fn, (d, a[0], a[1], a[2], a[4], x.buf, mean, invstd, rmask, part), self.bwd.keep), what + "+bnb")
+            self._bnb_reissue(lw, L, x, mean, invstd, rmask, part, chunks)
             self.bwd.add(lib.zsg_bn_sync_bwd_sums, None, None, None, rows, L.c, None, None, part, chunks, bs, dg, db, 1, None, 0,
                          what="bnsums:" + L.name)
         else:
@@ -1855,14 +1952,8 @@ class _Plan:
         dx = self.grad_of(x) if x.requires_grad else None
         dg = self.G(L.name + ".weight") if self.trains(L.name + ".weight") else None
         db = self.G(L.name + ".bias") if self.trains(L.name + ".bias") else None
-        lw = getattr(out.grad, "last_writer", None)
-        fuse = (BNB_FUSE and (dg is not None or db is not None) and lw is not None and lw[0] == len(self.bwd.calls) - 1
-                and self.bwd.lanes[lw[0]] == 0 and len(out.grad.levels) == 1 and out.grad.levels[0].off == 0 and x.levels[0].off == 0
-                and out.grad.ld == L.c and x.ld == L.c)
-        if fuse:
-            idx, d, a, what = lw
-            chunks = self._wino_chunks(d, x.B) if d.use_wino else igemm_partial_rows(d)
-            fuse = chunks * 2 * L.c * 4 + 2 * L.c * 4 <= self.ws_bytes
+        lw, chunks = self._bnb_chunks(L, x, out) if (dg is not None or db is not None) else (None, 0)
+        fuse = lw is not None
         g_out, bits = None, rmask
         if residual is not None and residual.requires_grad:
             alias = (fuse and relu and rmask is not None and residual.grad is None and len(residual.levels) == 1
@@ -1882,21 +1973,17 @@ class _Plan:
         path = "onepass" if (dg is not None or db is not None) else "scale"
         if fuse:
             part = self.ws[2 * L.c:]
-            assert a[3] is None and a[5] is None and a[6] is None
-            tail_n = int(lib.zsg_conv_bn_tail_tickets(_ct.byref(d), 1 if d.use_wino else 0))
+            tail_n = self._bnb_tail_tickets(lw)
             path = "bnb+fin" if tail_n > 0 else "bnb"
             if tail_n > 0:
                 # the data gradient's last tile per column block writes d(gamma) / d(beta) for the eval statistics: a pure scale is left
-                fn = lib.zsg_conv_wino_bnb_tail if d.use_wino else lib.zsg_conv_igemm_bnb_tail
                 tk, coef = self._buf(tail_n, dtype=torch.int32), self._buf(2 * L.c)
-                self.bwd.calls[idx] = (fn, marshal(fn, (d, a[0], a[1], a[2], a[4], x.buf, mean, invstd, rmask, part, tk, coef, dg, db, 1),
-                                                   self.bwd.keep), what + "+bnb+fin")
+                self._bnb_reissue(lw, L, x, mean, invstd, rmask, part, chunks, fin=(tk, coef, dg, db))
                 if dxb is not None or g_out is not None:
                     self.bwd.add(lib.zsg_bn_frozen_backward, dout, bits, None, rows, L.c, None, invstd, gam, dxb, g_out, None, None, 0,
                                  None, 0, None, 0, what=what_b)
             else:
-                fn = lib.zsg_conv_wino_bnb if d.use_wino else lib.zsg_conv_igemm_bnb
-                self.bwd.calls[idx] = (fn, marshal(fn, (d, a[0], a[1], a[2], a[4], x.buf, mean, invstd, rmask, part), self.bwd.keep), what + "+bnb")
+                self._bnb_reissue(lw, L, x, mean, invstd, rmask, part, chunks)
                 self.bwd.add(lib.zsg_bn_frozen_backward, dout, bits, x.buf, rows, L.c, mean, invstd, gam, dxb, g_out, dg, db, 1, part, chunks,
                              self.ws, self.ws_bytes, what=what_b)
         elif dxb is not None or g_out is not None or dg is not None or db is not None:
@@ -3022,6 +3109,7 @@ def get_default_net(num_anchors=1, cfg=None):
     net.wgrad_precision(cfg["wgrad_dtype"] if "wgrad_dtype" in cfg else "fp32")       # (raises on anything but fp32 / bf16)
     net.train_precision(cfg["train_dtype"] if "train_dtype" in cfg else "fp32")       # (raises on anything but fp32 / bf16_head)
     net.encoder_precision(cfg["enc_dtype"] if "enc_dtype" in cfg else "fp32")         # (raises on anything but fp32 / bf16_fwd)
+    net.encoder_backward_precision(cfg["enc_bwd_dtype"] if "enc_bwd_dtype" in cfg else "fp32")     # (raises on anything but fp32 / bf16)
     path = cfg["pretrained_path"] if "pretrained_path" in cfg else ""
     if path:
         n = load_pretrained_encoder(net, path)
