@@ -728,6 +728,28 @@ int zsg_loss_fwd_bwd_m(const float* out5, const float* annot, const float* ancho
 size_t zsg_match_atss_workspace_bytes(int32_t B, int32_t L);
 int zsg_match_atss(const float* annot, const float* anchors, const int32_t* level_off, int32_t L, int32_t B, int32_t A, int32_t topk,
                    uint8_t* pos_mask, double* thr, int32_t* cand, void* ws, size_t ws_bytes, void* stream);
+/* Task-aligned anchor assignment (TOOD's Task-Aligned Assigner, Feng et al. 2021) — ZSGLoss.forward with cfg matcher = "tal"; the mask
+ * goes to zsg_loss_fwd_bwd_m.  Unlike the fixed rule and ATSS it reads what the network predicts.  Per sample b: one annotation
+ * g = annot[b] (y1x1y2x2), the anchors a in create_anchors' flattened order, the network output out5[b][a] = (dy, dx, dh, dw, att).
+ *   s(a) = the fp32 sigmoid of att, 1 / (1 + expf(-att)): the score zsg_loss_fwd_bwd_q's quality term trains
+ *   p(a) = the decoded box (reg_params_to_bbox, anchors.py:182-197; the fp64 expressions of zsg_loss_fwd_bwd_iou)
+ *   u(a) = inter / (union + 1e-7) of p(a) with g, rounded to fp32: exactly the q of zsg_loss_fwd_bwd_q, here for EVERY anchor
+ *   inside(a) = g.y1 < acy < g.y2 and g.x1 < acx < g.x2, acy = (a.y1 + a.y2) / 2, acx likewise in fp32 (zsg_match_atss's centres)
+ *   t(a) = pow((double)s, alpha) * pow((double)u, beta) in fp64; NaN where any of the five values of the row is NaN or u(a) is NaN
+ *          (a decode that overflows to inf - inf; min / max inside u are C's fmin / fmax, as in zsg_loss_fwd_bwd_q)
+ *   a is a candidate iff inside(a) and t(a) > 0 (false for NaN: an anchor with a NaN in its row or in u is never a candidate)
+ *   selected: the min(topk, #candidates) candidates that come first when ordered by t descending, then by index ascending
+ * pos_mask [B][A] uint8: 1 at the selected anchors, else 0; every byte is written.  zsg_loss_fwd_bwd_m adds the sample's arg-max IoU
+ * anchor as for every mask, so every sample keeps a positive.  The mask is a constant of the backward: no gradient flows through the
+ * selection.  metric [B][A] double (may be null): t(a) where inside(a) (a NaN t stays NaN), -1.0 elsewhere; the selection can be redone
+ * from this array alone (candidates are its entries > 0).  ws: zsg_match_tal_workspace_bytes(B, A) bytes; it holds the fp64 keys when
+ * metric is null.  With metric given the keys are the metric, ws is neither read nor written and may be the same buffer as metric.
+ * Two launches, no atomics, no host synchronisation, the same bits on every run.
+ * Limits (else -1, nothing launched or written, zsg_last_error names the argument): 1 <= topk <= 32, B <= 512, alpha >= 0 and
+ * beta >= 0 and both finite, ws_bytes large enough, every pointer but metric non-null. */
+size_t zsg_match_tal_workspace_bytes(int32_t B, int32_t A);
+int zsg_match_tal(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, int32_t topk, float alpha,
+                  float beta, uint8_t* pos_mask, double* metric /* may be NULL */, void* ws, size_t ws_bytes, void* stream);
 
 /* Evaluator.forward, evaluator.py:48-117 (reg_params_to_bbox anchors.py:182-197): arg-max score anchor -> decode ->
  * IoU >= thr.  metrics[2] = (Acc, MaxPos); pred_boxes [B][4] pixels x1y1x2y2; pred_scores [B]; pred_idx [B] int32. */

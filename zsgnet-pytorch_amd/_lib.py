@@ -174,6 +174,8 @@ SIGNATURES = {
     "zsg_loss_fwd_bwd_m": (I32, [P, P, P, I32, I32, F32, F32, F32, F32, I32, F32, I32, F32, I32, P, P, P, P, P, P, SZ, P]),
     "zsg_match_atss_workspace_bytes": (SZ, [I32, I32]),
     "zsg_match_atss": (I32, [P, P, P, I32, I32, I32, I32, P, P, P, P, SZ, P]),
+    "zsg_match_tal_workspace_bytes": (SZ, [I32, I32]),
+    "zsg_match_tal": (I32, [P, P, P, I32, I32, I32, F32, F32, P, P, P, SZ, P]),
     "zsg_eval_workspace_bytes": (SZ, [I32]),
     "zsg_eval": (I32, [P, P, P, P, I32, I32, F32, P, P, P, P, P, P, P]),
     "zsg_eval_topk_workspace_bytes": (SZ, [I32, I32, I32, I32]),

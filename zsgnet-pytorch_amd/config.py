@@ -47,13 +47,16 @@ DEFAULTS: Dict[str, Any] = {
     "box_iou_loss": "none",         # "giou" / "diou": ZSGLoss adds lamb_iou * (that IoU loss of the decoded positive boxes) to the criterion and reports it as iou_ls (zsg_loss_fwd_bwd_iou); "none" = off
     "lamb_iou": 1.0,                # ... its weight (>= 0); lamb_reg = 0 with it trains on the IoU term alone
     "cls_quality": "none",          # "qfl" / "vfl": the att logit is trained towards the IoU of the anchor's decoded box with the annotation (Quality Focal / Varifocal loss, zsg_loss_fwd_bwd_q) and ZSGLoss also reports pos_iou; needs use_focal, no use_softmax, gamma >= 1; "none" = the reference's focal term
-    "matcher": "iou",               # which anchors are positive: "iou" = the reference's fixed rule (IoU > matching_threshold, or the arg-max anchor); "atss" = Adaptive Training Sample Selection on the device (zsg_match_atss + zsg_loss_fwd_bwd_m): per pyramid level the atss_topk anchors nearest the annotation's centre, of those the ones with IoU >= mean + std whose centre lies inside the annotation, and the arg-max anchor; needs use_multi, no use_softmax; matching_threshold is not read
+    "matcher": "iou",               # which anchors are positive: "iou" = the reference's fixed rule (IoU > matching_threshold, or the arg-max anchor); "atss" = Adaptive Training Sample Selection on the device (zsg_match_atss + zsg_loss_fwd_bwd_m): per pyramid level the atss_topk anchors nearest the annotation's centre, of those the ones with IoU >= mean + std whose centre lies inside the annotation, and the arg-max anchor; needs use_multi, no use_softmax; matching_threshold is not read; "tal" = task-aligned assignment from the network's own predictions (tal_topk / tal_alpha / tal_beta below)
     "eval_dtype": "fp32",           # "bf16": the convolutions of the EVAL forward (validation, only_val / only_test, Evaluator.predict, the many-phrases plan) run on bf16 MFMA with fp32 accumulation (zsg_conv_igemm_bf16; ZSGNet.eval_precision) — activations stay fp32 in memory, the stem, the LSTM and the language map stay fp32, training is untouched; "bf16_act": "bf16", and the activations between the stem's max-pool and the heads' last convolution are stored as bf16 (half the activation bytes of an eval plan; rounded once where stored, arithmetic in fp32; the outputs stay fp32); "fp32" = every plan as before
     "wgrad_dtype": "fp32",          # "bf16": the convolution weight gradients of the TRAINING backward run on bf16 MFMA with fp32 accumulation (zsg_conv_wgrad_bf16; ZSGNet.wgrad_precision) — src, dy and the gradients stay fp32 in memory, the forward, the data gradients, the stem and the small directly lowered weight gradients stay fp32
     "train_dtype": "fp32",          # "bf16_head": in TRAINING plans the forward convolutions and the data gradients of the pyramid (backbone.fpn.*) and the head stacks run on bf16 MFMA with fp32 accumulation (zsg_conv_igemm_bf16 / zsg_conv_igemm_bf16_m; ZSGNet.train_precision) — activations, weights and gradients stay fp32 in memory; the encoder, every BatchNorm-fused launch, the query encoder and the weight gradients (wgrad_dtype) are untouched
     "enc_dtype": "fp32",            # "bf16_fwd": in TRAINING plans the forward convolutions of a ResNet encoder behind the stem (backbone.encoder.*) run on bf16 MFMA with fp32 accumulation and the fused BatchNorm statistics (zsg_conv_igemm_bf16_bn; ZSGNet.encoder_precision) — activations, weights and gradients stay fp32 in memory; the stem, the convolutions that apply a pending BatchNorm in their loader, the whole backward (fp32 data gradients, weight gradients as wgrad_dtype says) and the SSD-VGG encoder are untouched
     "enc_bwd_dtype": "fp32",        # "bf16": in TRAINING plans the data gradients of a ResNet encoder behind the stem (backbone.encoder.*) run on bf16 MFMA with fp32 accumulation (zsg_conv_igemm_bf16_m; where one completes a BatchNorm's dout, zsg_conv_igemm_bf16_bnb with that BatchNorm's backward sums in its epilogue; ZSGNet.encoder_backward_precision) — activations, weights and gradients stay fp32 in memory; the forward, the stem, the pyramid's data gradients into C3-C5, the weight gradients (wgrad_dtype) and the SSD-VGG encoder are untouched; independent of enc_dtype
     "atss_topk": 9,                # ... candidates per pyramid level (1 .. 16)
+    "tal_topk": 13,                # matcher "tal" (task-aligned assignment, zsg_match_tal + zsg_loss_fwd_bwd_m): per annotation the tal_topk (1 .. 32) anchors with the largest sigmoid(att)^tal_alpha * IoU(decoded box, annotation)^tal_beta among those whose centre lies inside the annotation, and the arg-max anchor; reads the network's output, no gradient through the selection; needs use_multi, no use_softmax; matching_threshold and atss_topk are not read
+    "tal_alpha": 1.0,              # ... the exponent of the score (>= 0, finite)
+    "tal_beta": 6.0,               # ... the exponent of the IoU (>= 0, finite); 13 / 1 / 6 are TOOD's published values, not tuned here
     # configs/ds_info.json: where each dataset's images and csv files live (override with --ds_info.<name>.<key>=...)
     "ds_info": {name: {"data_dir": f"./data/{root}", "img_dir": f"./data/{imgs}",
                        **{f"{s}_csv_file": f"./data/{csv}/csv_dir/{f}.csv" for s, f in (("trn", trn), ("val", "val"), ("test", "test"))}}

@@ -680,9 +680,12 @@ __device__ __forceinline__ double decoded_iou(const float* __restrict__ o5, cons
     return inter / (uni + IOU_EPS);
 }
 
+// the fp32 score of an att logit: what the quality term trains towards q, and what zsg_match_tal ranks by
+__device__ __forceinline__ float att_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 // l and dl/dx of one anchor for cls_kind 1 / 2 (q = 0 at a negative anchor)
 __device__ __forceinline__ float quality_terms(float x, float q, bool pos, int cls_kind, float alpha, float gamma, float* dx) {
-    const float p = 1.0f / (1.0f + expf(-x));
+    const float p = att_sigmoid(x);
     const float bce = fmaxf(x, 0.f) - x * q + log1pf(expf(-fabsf(x)));
     if (cls_kind == 2 && pos) {
         *dx = q * (p - q);
@@ -1150,6 +1153,134 @@ extern "C" int zsg_match_atss(const float* annot, const float* anchors, const in
     ZSG_LAUNCH(atss_mask_kernel, dim3(cdiv(A, ATSS_TILE), B), dim3(256), 0, st, annot, anchors, A, L, (const AtssCand*)recs,
                        (const ArgMax*)lmax, pos_mask, thr, cand);
     ZSG_CHECK_LAUNCH("match_atss");
+    return 0;
+}
+
+// ---- task-aligned anchor assignment (zsg_match_tal): a positives mask from what the network predicts --------------------------------
+// TOOD's Task-Aligned Assigner (Feng et al. 2021) for one annotation g per sample.  Per anchor a with the row (dy, dx, dh, dw, att) of out5:
+//   s = att_sigmoid(att) (fp32, the score of the quality term);  u = (float)decoded_iou(row, a, g): the q of zsg_loss_fwd_bwd_q, here for
+//   EVERY anchor;  acy = (a.y1 + a.y2) / 2, acx likewise (fp32, zsg_match_atss's expressions);  inside = g.y1 < acy < g.y2 and g.x1 < acx < g.x2
+//   t = pow((double)s, alpha) * pow((double)u, beta) in fp64; NaN where any of the row's five values is NaN or u is NaN (a decode that
+//   overflows to inf - inf); said outright because pow(NaN, 0) is 1
+//   candidate: inside and t > 0 (false for NaN);  selected: the min(topk, #candidates) candidates first in the order (t descending, index ascending)
+// Two launches, no atomics, fixed orders: the same bits on every run.
+//   tal_key_kernel, (ranges of 256 anchors, B) blocks: key[b][a] = inside ? t : -1.0 (a candidate is exactly a key > 0) and 0 into EVERY
+//     byte of pos_mask.  The keys ARE the optional metric output: they are written into metric where it is given, else into ws.
+//   tal_select_kernel, one block per sample: up to topk block-wide arg-max rounds over the sample's keys, which stay in global memory (L2:
+//     A fp64 keys do not fit in LDS at A = 17460).  A thread keeps the best of its own keys that has not won; the winner's byte is set and
+//     only the thread that owned it reads its keys again, for its largest key behind that winner (no marks).  A round is latency: the
+//     fewer dependent L2 loads stand between two reductions, the shorter it is (the timings are in DESIGN section 7).
+#define TAL_MAX_K 32
+#define TAL_BATCH 8
+struct ArgMaxD {
+    double v;
+    int i;
+};
+__device__ __forceinline__ ArgMaxD argmax_merge_d(ArgMaxD x, ArgMaxD y) {   // larger value, then lower index; NaN never wins
+    const bool take = (y.v > x.v) || (y.v == x.v && y.i < x.i);
+    return take ? y : x;
+}
+__device__ ArgMaxD block_argmax_d(ArgMaxD m, ArgMaxD* sm) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ArgMaxD y;
+        y.v = __shfl_xor(m.v, o, 64);
+        y.i = __shfl_xor(m.i, o, 64);
+        m = argmax_merge_d(m, y);
+    }
+    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sm[wave] = m;
+    __syncthreads();
+    ArgMaxD r = sm[0];
+    for (int w = 1; w < nw; ++w) r = argmax_merge_d(r, sm[w]);
+    __syncthreads();
+    return r;
+}
+
+extern "C" size_t zsg_match_tal_workspace_bytes(int32_t B, int32_t A) {   // the fp64 keys [B][A] (where no metric output holds them)
+    if (B <= 0 || A <= 0) return 0;
+    return (size_t)B * (size_t)A * sizeof(double);
+}
+
+__global__ __launch_bounds__(256) void tal_key_kernel(const float* __restrict__ out5, const float* __restrict__ annot,
+                                                      const float* __restrict__ anchors, int A, double alpha, double beta,
+                                                      double* __restrict__ key, uint8_t* __restrict__ pos_mask) {
+    const int b = blockIdx.y, a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= A) return;
+    const f32x4 bx = *(const f32x4*)(annot + 4 * b);
+    const f32x4 an = *(const f32x4*)(anchors + 4 * a);
+    const size_t e = (size_t)b * A + a;
+    const float* o = out5 + e * 5;
+    const float acy = (an[0] + an[2]) / 2.f, acx = (an[1] + an[3]) / 2.f;
+    const bool inside = bx[0] < acy && acy < bx[2] && bx[1] < acx && acx < bx[3];
+    double t = -1.0;
+    if (inside) {
+        const float s = att_sigmoid(o[4]);
+        const float u = (float)decoded_iou(o, an, bx);
+        t = pow((double)s, alpha) * pow((double)u, beta);
+        if (o[0] != o[0] || o[1] != o[1] || o[2] != o[2] || o[3] != o[3] || o[4] != o[4] || u != u) t = __longlong_as_double(0x7ff8000000000000ll);
+    }
+    key[e] = t;
+    pos_mask[e] = 0;
+}
+
+__global__ __launch_bounds__(LS_THREADS) void tal_select_kernel(const double* __restrict__ key, int A, int topk,
+                                                                uint8_t* __restrict__ pos_mask) {
+    __shared__ ArgMaxD sm_a[LS_THREADS / 64];
+    const int b = blockIdx.x;
+    const double* k = key + (size_t)b * A;
+    // every thread holds the best of ITS keys (a = threadIdx.x + j LS_THREADS) that has not won yet; after a round only the winner's
+    // owner looks for its next one: the largest of its keys behind the winner in the order.  Every key (t, a) comes behind (+inf, -1).
+    double pt = INFINITY;
+    int pi = -1;
+    bool rescan = true;
+    ArgMaxD mine;
+    for (int r = 0; r < topk; ++r) {
+        if (rescan) {
+            mine.v = 0.0;                                // only keys > 0 are candidates (never NaN, never the -1.0 of an outside anchor)
+            mine.i = 0x7fffffff;
+            // TAL_BATCH independent loads in flight, then the compares in index order: the scan costs latencies, not bytes
+            for (int a0 = threadIdx.x; a0 < A; a0 += TAL_BATCH * LS_THREADS) {
+                double v[TAL_BATCH];
+#pragma unroll
+                for (int j = 0; j < TAL_BATCH; ++j) {
+                    const int a = a0 + j * LS_THREADS;
+                    v[j] = j * LS_THREADS < A - a0 ? k[a] : -1.0;      // (a < A, written so that a cannot wrap)
+                }
+#pragma unroll
+                for (int j = 0; j < TAL_BATCH; ++j) {
+                    const int a = a0 + j * LS_THREADS;
+                    if ((v[j] < pt || (v[j] == pt && a > pi)) && v[j] > mine.v) { mine.v = v[j]; mine.i = a; }
+                }
+            }
+        }
+        const ArgMaxD w = block_argmax_d(mine, sm_a);
+        if (w.i == 0x7fffffff) break;                    // the candidates are used up (block-uniform)
+        rescan = (w.i % LS_THREADS) == (int)threadIdx.x;
+        if (rescan) {
+            pt = w.v;
+            pi = w.i;
+            pos_mask[(size_t)b * A + w.i] = 1;
+        }
+    }
+}
+
+extern "C" int zsg_match_tal(const float* out5, const float* annot, const float* anchors, int32_t B, int32_t A, int32_t topk, float alpha,
+                             float beta, uint8_t* pos_mask, double* metric, void* ws, size_t ws_bytes, void* stream) {
+    ZSG_REQUIRE(out5 && annot && anchors && pos_mask && ws && B > 0 && A > 0, "match_tal: bad argument (a null pointer, B=%d or A=%d)", B, A);
+    ZSG_REQUIRE(topk >= 1 && topk <= TAL_MAX_K, "match_tal: topk=%d, expected 1..%d", topk, TAL_MAX_K);
+    ZSG_REQUIRE(B <= LS_MAX_B, "match_tal: B=%d exceeds %d", B, LS_MAX_B);
+    ZSG_REQUIRE(alpha >= 0.f && alpha <= 3.402823466e38f, "match_tal: alpha=%g, expected a finite value >= 0", (double)alpha);
+    ZSG_REQUIRE(beta >= 0.f && beta <= 3.402823466e38f, "match_tal: beta=%g, expected a finite value >= 0", (double)beta);
+    ZSG_REQUIRE(ws_bytes >= zsg_match_tal_workspace_bytes(B, A), "match_tal: ws_bytes=%zu, expected at least %zu", ws_bytes,
+                zsg_match_tal_workspace_bytes(B, A));
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("match_tal", st, 0, (double)B * A * (20 + 16 + 1 + 8 * (topk + 1)));
+    double* key = metric ? metric : (double*)ws;        // (with metric given ws is not touched: the caller may pass one buffer as both)
+    ZSG_LAUNCH(tal_key_kernel, dim3(cdiv(A, 256), B), dim3(256), 0, st, out5, annot, anchors, A, (double)alpha, (double)beta, key, pos_mask);
+    ZSG_LAUNCH(tal_select_kernel, dim3(B), dim3(LS_THREADS), 0, st, (const double*)key, A, topk, pos_mask);
+    ZSG_CHECK_LAUNCH("match_tal");
     return 0;
 }
 

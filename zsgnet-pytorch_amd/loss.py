@@ -53,7 +53,8 @@ class _LossFn(torch.autograd.Function):
         kind = mod.iou_kind                 # 0: the reference's criterion; 1 / 2: + lamb_iou * GIoU / DIoU loss (zsg_loss_fwd_bwd_iou)
         cls_kind = mod.cls_kind             # 0: the reference's classification term; 1 / 2: QFL / VFL on the IoU target (zsg_loss_fwd_bwd_q)
         atss = mod.matcher == "atss"        # the positives come from zsg_match_atss's mask (zsg_loss_fwd_bwd_m) instead of the fixed IoU rule
-        losses = torch.empty(5 if (cls_kind or atss) else (4 if kind else 3), device=dev)
+        tal = mod.matcher == "tal"          # ... from zsg_match_tal's mask: chosen from this forward's out5, a constant of the backward
+        losses = torch.empty(5 if (cls_kind or atss or tal) else (4 if kind else 3), device=dev)
         # Where d(loss)/d(out5) goes: straight into the incoming-gradient buffer of the network plan that produced out5 (ZSGNet.forward
         # attaches it), already scaled by 1 / world under data parallelism (the reducer SUMs) — the backward then needs no launch of
         # its own when the upstream gradient is the constant 1.  Only the FIRST loss applied to an output may take the buffer.
@@ -75,6 +76,13 @@ class _LossFn(torch.autograd.Function):
         wsb = lib.zsg_loss_workspace_bytes(B, A)
         ws = torch.empty((wsb + 7) // 8, dtype=torch.float64, device=dev)
         flags = (1 if mod.use_focal else 0) | (2 if mod.use_multi else 0) | (4 if mod.use_softmax else 0)
+        if tal:
+            mod.pos_mask = torch.empty((B, A), dtype=torch.uint8, device=dev)
+            mod.tal_metric = torch.empty((B, A), dtype=torch.float64, device=dev)
+            # (the keys the selection reads are the metric itself: with the metric asked for, the workspace is not touched and may be it)
+            check(lib.zsg_match_tal(out5.data_ptr(), annot.data_ptr(), mod.anchs.data_ptr(), B, A, int(mod.tal_topk), float(mod.tal_alpha),
+                                    float(mod.tal_beta), mod.pos_mask.data_ptr(), mod.tal_metric.data_ptr(), mod.tal_metric.data_ptr(),
+                                    lib.zsg_match_tal_workspace_bytes(B, A), stream_ptr()), "zsg_match_tal")
         if atss:
             assert mod.level_off is not None and int(mod.level_off[-1]) == A, "matcher='atss' needs the level table of these anchors (set_anchors)"
             L = mod.level_off.numel() - 1
@@ -85,6 +93,7 @@ class _LossFn(torch.autograd.Function):
             check(lib.zsg_match_atss(annot.data_ptr(), mod.anchs.data_ptr(), mod.level_off.data_ptr(), L, B, A, int(mod.atss_topk),
                                      mod.pos_mask.data_ptr(), mod.atss_thr.data_ptr(), None, mws.data_ptr(), mwsb, stream_ptr()),
                   "zsg_match_atss")
+        if atss or tal:
             check(lib.zsg_loss_fwd_bwd_m(out5.data_ptr(), annot.data_ptr(), mod.anchs.data_ptr(), B, A, mod.alpha, float(mod.gamma),
                                          float(mod.lamb_reg), float(mod.cfg["matching_threshold"]), flags, scale, kind,
                                          float(mod.lamb_iou), cls_kind, mod.pos_mask.data_ptr(), losses.data_ptr(), grad5.data_ptr(),
@@ -131,12 +140,16 @@ class ZSGLoss(nn.Module):
     cfg cls_quality = "qfl" / "vfl" trains the att logit towards the IoU of the anchor's decoded box with the annotation (Quality Focal /
     Varifocal loss in the place of the focal term) and adds the key 'pos_iou', the mean of that target over the positives (no gradient).
     cfg matcher = "atss" exchanges the fixed IoU rule for the positives with ATSS (zsg_match_atss, INTEGRATION.md "Anchor assignment");
-    the mask of the last call stays in .pos_mask [B, A] uint8 and the per-sample thresholds in .atss_thr [B] float64."""
+    the mask of the last call stays in .pos_mask [B, A] uint8 and the per-sample thresholds in .atss_thr [B] float64.
+    cfg matcher = "tal" exchanges it for the task-aligned assignment (zsg_match_tal on the forward's own output: the tal_topk anchors with the
+    largest sigmoid(att)^tal_alpha * IoU(decoded box, annotation)^tal_beta whose centre lies inside the annotation); the mask stays in
+    .pos_mask and the metric in .tal_metric [B, A] float64 (-1 where the centre lies outside)."""
 
     IOU_KINDS = {"none": 0, "giou": 1, "diou": 2}
     CLS_KINDS = {"none": 0, "qfl": 1, "vfl": 2}
-    MATCHERS = ("iou", "atss")
+    MATCHERS = ("iou", "atss", "tal")
     MAX_LEVELS, MAX_TOPK = 8, 16            # zsg_match_atss's limits
+    TAL_MAX_TOPK = 32                       # zsg_match_tal's limit
 
     def __init__(self, ratios, scales, cfg):
         super().__init__()
@@ -165,11 +178,19 @@ class ZSGLoss(nn.Module):
         self.matcher, self.atss_topk = cfg.get("matcher", "iou"), cfg.get("atss_topk", 9)
         if self.matcher not in self.MATCHERS:
             raise ValueError(f"matcher={self.matcher!r}: expected one of {sorted(self.MATCHERS)}")
-        if self.matcher == "atss":
+        self.tal_topk, self.tal_alpha, self.tal_beta = cfg.get("tal_topk", 13), cfg.get("tal_alpha", 1.0), cfg.get("tal_beta", 6.0)
+        if self.matcher in ("atss", "tal"):
             if not self.use_multi:
-                raise ValueError("matcher='atss' selects several positives per sample: use_multi must be True")
+                raise ValueError(f"matcher={self.matcher!r} selects several positives per sample: use_multi must be True")
             if self.use_softmax:
-                raise ValueError("matcher='atss' is defined on the sigmoid branch: use_softmax must be False")
+                raise ValueError(f"matcher={self.matcher!r} is defined on the sigmoid branch: use_softmax must be False")
+        if self.matcher == "tal":
+            if not (isinstance(self.tal_topk, int) and not isinstance(self.tal_topk, bool) and 1 <= self.tal_topk <= self.TAL_MAX_TOPK):
+                raise ValueError(f"tal_topk={self.tal_topk!r}: expected an integer in 1 .. {self.TAL_MAX_TOPK}")
+            for key, v in (("tal_alpha", self.tal_alpha), ("tal_beta", self.tal_beta)):
+                if not (isinstance(v, (int, float)) and not isinstance(v, bool) and 0 <= v < float("inf")):
+                    raise ValueError(f"{key}={v!r}: expected a finite number >= 0")
+        if self.matcher == "atss":
             if not (isinstance(self.atss_topk, int) and 1 <= self.atss_topk <= self.MAX_TOPK):
                 raise ValueError(f"atss_topk={self.atss_topk!r}: expected an integer in 1 .. {self.MAX_TOPK}")
         self.loss_keys = ["loss", "cls_ls", "box_ls"] + (["iou_ls"] if self.iou_kind else []) + (["pos_iou"] if self.cls_kind else [])
