@@ -585,6 +585,21 @@ int zsg_resize_u8_batched(const void* jobs_dev, int32_t njobs, int32_t C, int32_
  * runs only when do_cs != 0: pass 0 when every job has contrast == saturation == 1. */
 int zsg_augment_u8_batched(const void* jobs_dev, int32_t njobs, int32_t Ho, int32_t Wo, int32_t blocks_x, int32_t blocks_y,
                            void* gray_sums, int32_t do_cs, void* stream);
+/* The same three launches for windows that may leave the image (zoom-out: the outside is a fill colour) and for the horizontal flip,
+ * byte-identical to dat_loader.augment_host(..., flip, fill).  jobs = device array of
+ * {int64 img, tmp, out; int64 x_bounds, x_coef, y_bounds, y_coef; int32 ih, iw; int32 wx0, wy0, wh, ww; int32 x_ksize, y_ksize;
+ *  int32 blk0_x, blk0_y; int32 flags; uint32 fill; float brightness, contrast, saturation; int32 pad} (120 bytes): img = the address of
+ * the IMAGE's pixel (0, 0), ih / iw = its height and width (the row pitch is the width), wx0 / wy0 = the window's origin in image
+ * pixels (any sign), wh / ww = its sides (the tap tables are built for them), tmp = scratch [wh][Wo][3] (4-byte aligned), blk0_x /
+ * blk0_y = the first 256-pixel block of the job in launch 1 (wh * Wo pixels) / in launches 2 and 3, flags bit 0 = mirror left-right
+ * (applied last; launch 2 reads scratch column Wo - 1 - x for output column x), fill = r | g << 8 | b << 16.  Launch 1 takes a tap's
+ * source pixel from the image only when it lies inside [0, ih) x [0, iw) and `fill` otherwise, through the same integer sum: no window
+ * makes it read outside the image.  jobs_host (may be NULL): the same table in host memory; every record is then validated before
+ * anything is launched (addresses, image and window sides in 1..32768, wh * Wo <= 2^28, the origin within +-2^24, the first blocks equal
+ * to the running block sums and blocks_x / blocks_y to their totals).  gray_sums, do_cs, Ho * Wo <= 2^24: as zsg_augment_u8_batched.
+ * Returns -1 (nothing launched) for a bad argument or record. */
+int zsg_augment_geom_u8_batched(const void* jobs_dev, const void* jobs_host, int32_t njobs, int32_t Ho, int32_t Wo, int32_t blocks_x,
+                                int32_t blocks_y, void* gray_sums, int32_t do_cs, void* stream);
 /* Head input BackBone.concat_we (mdl.py:69-104) + head conv0 (mdl.py:216, 514 -> 256, 3x3 pad 1) without ever materialising
  * the concatenated tensor, and without its spatially-constant input channels: the language vector
  * is constant over the image and the grid channels do not depend on the batch index, so only the 256 feature channels

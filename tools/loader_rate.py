@@ -5,7 +5,11 @@ stream), zsg_resize_u8 + zsg_u8hwc_to_nhwc4 there.
 --aug adds two rows per worker count for the training augmentation (box-safe random crop + colour jitter, cfg aug_*): (c) on the GPU —
 the workers draw the crop and the factors, the raw image travels as in (b), zsg_augment_u8_batched crops, resizes and jitters — and
 (d) in the workers (dat_loader.augment_host: what the loader does without gpu_img_resize), uint8 300 x 300 uploaded.
-usage: python tools/loader_rate.py [--aug] [n_images] [workers ...]"""
+--flip P and / or --expand R (with --aug) add the same two rows with aug_flip = P / aug_expand_max = R on top (dat_loader.draw_augment_geom;
+on the GPU zsg_augment_geom_u8_batched whenever a job of the batch is flipped or its window leaves the image).  After the rows --aug
+prints the DEVICE time of the augmentation launches for one batch of 16 (the library's own HIP events around each entry point's
+launches, median of 20 calls), per configuration.
+usage: python tools/loader_rate.py [--aug [--flip P] [--expand R]] [n_images] [workers ...]"""
 import os
 import sys
 import tempfile
@@ -16,16 +20,26 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from zsgnet_pytorch_amd import dat_loader as D
-from zsgnet_pytorch_amd._lib import lib, check, stream_ptr
+from zsgnet_pytorch_amd._lib import lib, check, stream_ptr, ProfEntry
 
 
 AUG_CFG = {"aug_crop_min": 0.5, "aug_brightness": 0.4, "aug_contrast": 0.4, "aug_saturation": 0.4}
+FILL = (124, 116, 104)
+
+
+def draw(i, h, w, cfg):
+    """the augmentation of image i: (crop, jitter, flip), from a generator seeded by i"""
+    rng = np.random.RandomState(i)
+    x1, y1 = rng.uniform(0, w - 120), rng.uniform(0, h - 120)
+    return D.draw_augment_geom(rng, h, w, [[x1, y1, x1 + rng.uniform(20, 120), y1 + rng.uniform(20, 120)]], cfg)
 
 
 class Raw(torch.utils.data.Dataset):
-    def __init__(self, files, resize, aug=None):
-        """aug: None, "gpu" (the item carries the drawn crop / factors) or "host" (the worker applies them: augment_host)"""
-        self.files, self.resize, self.aug = files, resize, aug
+    def __init__(self, files, resize, aug=None, cfg=AUG_CFG):
+        """aug: None, "gpu" (the item carries the drawn crop / factors) or "host" (the worker applies them: augment_host); cfg: the aug_*
+        keys (AUG_CFG, or with aug_flip / aug_expand_max on top: the item then carries aug_geom too)"""
+        self.files, self.resize, self.aug, self.cfg = files, resize, aug, cfg
+        self.geom = cfg is not AUG_CFG
 
     def __len__(self):
         return len(self.files)
@@ -34,13 +48,13 @@ class Raw(torch.utils.data.Dataset):
         import PIL.Image
         img = PIL.Image.open(self.files[i]).convert("RGB")
         if self.aug:
-            rng = np.random.RandomState(i)
-            h, w = img.height, img.width
-            x1, y1 = rng.uniform(0, w - 120), rng.uniform(0, h - 120)
-            crop, jit = D.draw_augment(rng, h, w, [[x1, y1, x1 + rng.uniform(20, 120), y1 + rng.uniform(20, 120)]], AUG_CFG)
+            crop, jit, flip = draw(i, img.height, img.width, self.cfg)
             if self.aug == "host":
-                return torch.from_numpy(D.augment_host(np.asarray(img), crop, jit, (300, 300)))
-            return {"img": torch.from_numpy(np.asarray(img).copy()), "aug_crop": torch.tensor(crop, dtype=torch.int32), "aug_jitter": torch.from_numpy(jit)}
+                return torch.from_numpy(D.augment_host(np.asarray(img), crop, jit, (300, 300), flip=flip, fill=FILL if self.geom else None))
+            item = {"img": torch.from_numpy(np.asarray(img).copy()), "aug_crop": torch.tensor(crop, dtype=torch.int32), "aug_jitter": torch.from_numpy(jit)}
+            if self.geom:
+                item["aug_geom"] = torch.tensor([int(flip), *FILL], dtype=torch.int32)
+            return item
         if self.resize:                                             # the reference's item: resize + float conversion on the host
             img = img.resize((300, 300))
             return torch.from_numpy(np.asarray(img).transpose(2, 0, 1).astype(np.float64)).float().div_(255)
@@ -50,14 +64,58 @@ class Raw(torch.utils.data.Dataset):
 def collate_raw(b):
     if isinstance(b[0], dict):                                          # GPU augmentation: raw images + one crop / factor triple each
         out = dict(zip(("img", "img_hw"), D.flatten_raw([x["img"] for x in b])))
-        out["aug_crop"], out["aug_jitter"] = torch.stack([x["aug_crop"] for x in b]), torch.stack([x["aug_jitter"] for x in b])
+        for k in ("aug_crop", "aug_jitter", "aug_geom"):
+            if k in b[0]:
+                out[k] = torch.stack([x[k] for x in b])
         return out
     return dict(zip(("img", "img_hw"), D.flatten_raw(b)))
 
 
+def device_time(files, cfg, label, calls=20, warmup=5):
+    """one batch of 16 through GpuResizer.resize_flat: the device time between the first and the last launch of the entry point"""
+    import PIL.Image
+    imgs = [np.asarray(PIL.Image.open(f).convert("RGB")) for f in files[:16]]
+    draws = [draw(i, a.shape[0], a.shape[1], cfg) for i, a in enumerate(imgs)]
+    flat, hw = D.flatten_raw([torch.from_numpy(a.copy()) for a in imgs])
+    flat = flat.cuda()
+    geom = cfg is not AUG_CFG
+    kw = dict(crop=[d[0] for d in draws], jitter=np.stack([d[1] for d in draws]))
+    if geom:
+        kw.update(flip=[d[2] for d in draws], fill=FILL)
+    rz = D.GpuResizer((300, 300))
+    ents, ms = (ProfEntry * 16)(), {}
+    lib.zsg_prof_enable(1)
+    try:
+        for i in range(warmup + calls):
+            lib.zsg_prof_collect(ents, 16)                              # (drop earlier records)
+            rz.resize_flat(flat, hw, **kw)
+            n = lib.zsg_prof_collect(ents, 16)                          # (waits for the recorded events)
+            if i >= warmup:
+                for e in ents[:n]:
+                    ms.setdefault(e.name.decode(), []).append(e.ms)
+    finally:
+        lib.zsg_prof_enable(0)
+    rows = sum(d[0][3] - d[0][1] for d in draws)
+    for name, v in ms.items():
+        print(f"  device time, batch of 16  {label:34s} {name:18s} median {1e3 * np.median(v):7.1f} us  (min {1e3 * min(v):.1f}, max {1e3 * max(v):.1f}; "
+              f"{rows} window rows in launch 1, {sum(bool(d[2]) for d in draws)} flipped)")
+
+
 def main():
     import PIL.Image
-    argv = [a for a in sys.argv[1:] if a != "--aug"]
+    argv, geom_cfg = [], dict(AUG_CFG)
+    it = iter(sys.argv[1:])
+    for a in it:
+        if a == "--flip":
+            geom_cfg["aug_flip"] = float(next(it))
+        elif a == "--expand":
+            geom_cfg["aug_expand_max"] = float(next(it))
+        elif a != "--aug":
+            argv.append(a)
+    geom = len(geom_cfg) > len(AUG_CFG)
+    if geom and "--aug" not in sys.argv:
+        sys.exit("--flip / --expand need --aug")
+    D.aug_geom_params(geom_cfg)                                         # ValueError outside the keys' ranges
     n = int(argv[0]) if argv else 512
     workers = [int(a) for a in argv[1:]] or [1, 4, 16]
     rng = np.random.default_rng(0)
@@ -72,13 +130,17 @@ def main():
         files.append(f)
     files = (files * ((n + 63) // 64))[:n]
     print(f"{n} JPEGs (500x375 / 333x500), batch 16 -> 300x300; images per second")
+    geom_tag = " ".join(f"{k[4:]} {v:g}" for k, v in geom_cfg.items() if k not in AUG_CFG)
     for nw in workers:
         modes = ["host resize (reference path)", "GPU resize (zsg_resize_u8)"]
         if "--aug" in sys.argv:
             modes += ["GPU augment (zsg_augment_u8)", "host-worker augment (augment_host)"]
+        if geom:
+            modes += [f"GPU augment + {geom_tag}", f"host-worker augment + {geom_tag}"]
         for mode in modes:
             host = mode.startswith("host")
-            ds = Raw(files, resize=host, aug=("gpu" if mode.startswith("GPU augment") else "host" if mode.startswith("host-worker") else None))
+            ds = Raw(files, resize=host, aug=("gpu" if mode.startswith("GPU augment") else "host" if mode.startswith("host-worker") else None),
+                     cfg=geom_cfg if "+" in mode else AUG_CFG)
             dl = torch.utils.data.DataLoader(ds, batch_size=16, num_workers=nw, pin_memory=True, persistent_workers=False,
                                              collate_fn=(None if host else collate_raw))
             it = dl if host else D.DevicePrefetcher(dl, "cuda", resize_hw=(300, 300))      # (side-stream copies + resize, as the trainer's loader)
@@ -102,7 +164,11 @@ def main():
                     cnt += u8.shape[0]
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            print(f"  workers {nw:2d}  {mode:32s} {cnt / dt:8.1f} img/s  ({cnt / dt / nw:7.1f} per worker)")
+            print(f"  workers {nw:2d}  {mode:44s} {cnt / dt:8.1f} img/s  ({cnt / dt / nw:7.1f} per worker)")
+    if "--aug" in sys.argv:
+        device_time(files, AUG_CFG, "GPU augment")
+        if geom:
+            device_time(files, geom_cfg, f"GPU augment + {geom_tag}")
 
 
 if __name__ == "__main__":

@@ -44,6 +44,9 @@ DEFAULTS: Dict[str, Any] = {
     "aug_brightness": 0.0,          # > 0: training images get a brightness factor from U(max(0, 1 - v), 1 + v) (dat_loader.augment_host; on the GPU with gpu_img_resize); 0 = off
     "aug_contrast": 0.0,            # ... a contrast factor (blend with the image's mean gray value)
     "aug_saturation": 0.0,          # ... a saturation factor (blend with the pixel's gray value)
+    "aug_flip": 0.0,                # in [0, 1]: probability that a training image (one image slot in grouped batches) is mirrored left-right; its boxes are mirrored and the left / right words of its queries swapped (dat_loader.swap_left_right); 0 = off
+    "aug_expand_max": 1.0,          # > 1 (in [1, 4]): zoom-out — the image is placed on a canvas of r ~ U(1, aug_expand_max) times its sides before the window is drawn (dat_loader.draw_augment_geom); 1 = off
+    "aug_fill": [124, 116, 104],    # ... the canvas colour, RGB integers 0..255 (the ImageNet mean)
     "box_iou_loss": "none",         # "giou" / "diou": ZSGLoss adds lamb_iou * (that IoU loss of the decoded positive boxes) to the criterion and reports it as iou_ls (zsg_loss_fwd_bwd_iou); "none" = off
     "lamb_iou": 1.0,                # ... its weight (>= 0); lamb_reg = 0 with it trains on the IoU term alone
     "cls_quality": "none",          # "qfl" / "vfl": the att logit is trained towards the IoU of the anchor's decoded box with the annotation (Quality Focal / Varifocal loss, zsg_loss_fwd_bwd_q) and ZSGLoss also reports pos_iou; needs use_focal, no use_softmax, gamma >= 1; "none" = the reference's focal term

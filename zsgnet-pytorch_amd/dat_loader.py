@@ -155,8 +155,9 @@ def flatten_raw(imgs) -> Tuple[torch.Tensor, torch.Tensor]:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# training augmentation: box-safe random crop + colour jitter.  The host definition (exact to the byte); the HIP kernels of
-# csrc/aug.hip (zsg_augment_u8_batched, driven by GpuResizer.resize_flat) reproduce augment_host bit for bit.
+# training augmentation: box-safe random crop + colour jitter, zoom-out onto a filled canvas, phrase-aware horizontal flip.  The host
+# definition (exact to the byte); the HIP kernels of csrc/aug.hip (zsg_augment_u8_batched and, for flips and windows that leave the
+# image, zsg_augment_geom_u8_batched, driven by GpuResizer.resize_flat) reproduce augment_host bit for bit.
 # ---------------------------------------------------------------------------------------------------------------------
 AUG_KEYS = {"aug_crop_min": 1.0, "aug_brightness": 0.0, "aug_contrast": 0.0, "aug_saturation": 0.0}      # the defaults: off
 
@@ -172,8 +173,53 @@ def aug_params(cfg) -> Tuple[float, float, float, float]:
     return cmin, vb, vc, vs
 
 
+AUG_GEOM_KEYS = {"aug_flip": 0.0, "aug_expand_max": 1.0, "aug_fill": (124, 116, 104)}      # the defaults: off (aug_fill: the ImageNet mean)
+
+
+def aug_geom_params(cfg) -> Tuple[float, float, Tuple[int, int, int]]:
+    """aug_flip, aug_expand_max, aug_fill of cfg (a cfg without them = the defaults), validated: ValueError outside their ranges"""
+    pflip = float(cfg["aug_flip"]) if "aug_flip" in cfg else AUG_GEOM_KEYS["aug_flip"]
+    emax = float(cfg["aug_expand_max"]) if "aug_expand_max" in cfg else AUG_GEOM_KEYS["aug_expand_max"]
+    fill = cfg["aug_fill"] if "aug_fill" in cfg else AUG_GEOM_KEYS["aug_fill"]
+    if not (0.0 <= pflip <= 1.0):
+        raise ValueError(f"aug_flip = {pflip}: a probability, must lie in [0, 1]")
+    if not (1.0 <= emax <= 4.0):
+        raise ValueError(f"aug_expand_max = {emax}: must lie in [1, 4]")
+    return pflip, emax, _check_fill(fill, "aug_fill")
+
+
+def _check_fill(fill, name: str) -> Tuple[int, int, int]:
+    try:
+        vals = [v for v in fill]
+        ok = len(vals) == 3 and all(float(v) == int(v) and 0 <= int(v) <= 255 and not isinstance(v, bool) for v in vals)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{name} = {fill!r}: three integers 0..255 (RGB)")
+    return tuple(int(v) for v in vals)
+
+
 def aug_enabled(cfg) -> bool:
-    return aug_params(cfg) != tuple(AUG_KEYS.values())
+    pflip, emax, _ = aug_geom_params(cfg)
+    return aug_params(cfg) != tuple(AUG_KEYS.values()) or pflip > 0.0 or emax > 1.0
+
+
+def _draw_window(rng, h: int, w: int, boxes, cmin: float):
+    """the box-safe random window of an h x w area: cw, ch, x0, y0 in this order"""
+    cw = max(1, int(round(w * rng.uniform(cmin, 1.0))))
+    ch = max(1, int(round(h * rng.uniform(cmin, 1.0))))
+    b = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+    xs, ys = np.clip(b[:, [0, 2]], 0, w), np.clip(b[:, [1, 3]], 0, h)
+    X1, X2, Y1, Y2 = int(math.floor(xs.min())), int(math.ceil(xs.max())), int(math.floor(ys.min())), int(math.ceil(ys.max()))
+    cw, ch = min(w, max(cw, X2 - X1, 1)), min(h, max(ch, Y2 - Y1, 1))
+    x0 = int(rng.randint(max(0, X2 - cw), min(X1, w - cw) + 1))           # never empty: cw >= X2 - X1, X2 <= w, cw <= w
+    y0 = int(rng.randint(max(0, Y2 - ch), min(Y1, h - ch) + 1))
+    return x0, y0, x0 + cw, y0 + ch
+
+
+def _draw_factors(rng, vb: float, vc: float, vs: float) -> np.ndarray:
+    f = [np.float32(rng.uniform(max(0.0, 1.0 - v), 1.0 + v)) if v > 0 else np.float32(1.0) for v in (vb, vc, vs)]
+    return np.array(f, np.float32)
 
 
 def draw_augment(rng, h: int, w: int, boxes, cfg):
@@ -181,24 +227,60 @@ def draw_augment(rng, h: int, w: int, boxes, cfg):
     the aug_* keys are at their defaults, else (crop, jitter) with crop = (x0, y0, x0 + cw, y0 + ch) integers — inside the image and
     holding every box (clipped to the image) — and jitter = float32 (brightness, contrast, saturation) factors.  rng: numpy's
     uniform / randint interface (np.random, a RandomState).  Draw order: cw, ch, x0, y0, then the three factors; a part that is off
-    draws nothing."""
+    draws nothing.  (aug_flip / aug_expand_max are not read here: draw_augment_geom.)"""
     cmin, vb, vc, vs = aug_params(cfg)
     if (cmin, vb, vc, vs) == tuple(AUG_KEYS.values()):
         return None
     h, w = int(h), int(w)
-    crop = (0, 0, w, h)
+    crop = _draw_window(rng, h, w, boxes, cmin) if cmin < 1.0 else (0, 0, w, h)
+    return crop, _draw_factors(rng, vb, vc, vs)
+
+
+def draw_augment_geom(rng, h: int, w: int, boxes, cfg):
+    """draw_augment with the zoom-out and the flip: None when all seven aug_* keys are off, else (crop, jitter, flip).  Draw order — a part
+    that is off draws nothing, so with aug_flip = 0 and aug_expand_max = 1 this consumes exactly draw_augment's random numbers and
+    returns its (crop, jitter) plus False:
+      1. aug_expand_max > 1: r = uniform(1, aug_expand_max); the image lies on a canvas W = max(w, round(w r)), H = max(h, round(h r)) at
+         ox = randint(0, W - w + 1), oy = randint(0, H - h + 1);
+      2. aug_crop_min < 1: draw_augment's box-safe window (cw, ch, x0, y0) on the canvas, the boxes shifted by (ox, oy); else the window
+         is the whole canvas;
+      3. the brightness, contrast and saturation factors;
+      4. aug_flip > 0: flip = uniform() < aug_flip.
+    crop is in IMAGE coordinates, (x0 - ox, y0 - oy, x1 - ox, y1 - oy): integers that may be negative or beyond the image — what lies
+    outside is aug_fill (augment_host(..., fill=...))."""
+    cmin, vb, vc, vs = aug_params(cfg)
+    pflip, emax, _ = aug_geom_params(cfg)
+    if (cmin, vb, vc, vs) == tuple(AUG_KEYS.values()) and pflip <= 0.0 and emax <= 1.0:
+        return None
+    h, w = int(h), int(w)
+    W, H, ox, oy = w, h, 0, 0
+    if emax > 1.0:
+        r = rng.uniform(1.0, emax)
+        W, H = max(w, int(round(w * r))), max(h, int(round(h * r)))
+        ox, oy = int(rng.randint(0, W - w + 1)), int(rng.randint(0, H - h + 1))
     if cmin < 1.0:
-        cw = max(1, int(round(w * rng.uniform(cmin, 1.0))))
-        ch = max(1, int(round(h * rng.uniform(cmin, 1.0))))
-        b = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
-        xs, ys = np.clip(b[:, [0, 2]], 0, w), np.clip(b[:, [1, 3]], 0, h)
-        X1, X2, Y1, Y2 = int(math.floor(xs.min())), int(math.ceil(xs.max())), int(math.floor(ys.min())), int(math.ceil(ys.max()))
-        cw, ch = min(w, max(cw, X2 - X1, 1)), min(h, max(ch, Y2 - Y1, 1))
-        x0 = int(rng.randint(max(0, X2 - cw), min(X1, w - cw) + 1))           # never empty: cw >= X2 - X1, X2 <= w, cw <= w
-        y0 = int(rng.randint(max(0, Y2 - ch), min(Y1, h - ch) + 1))
-        crop = (x0, y0, x0 + cw, y0 + ch)
-    f = [np.float32(rng.uniform(max(0.0, 1.0 - v), 1.0 + v)) if v > 0 else np.float32(1.0) for v in (vb, vc, vs)]
-    return crop, np.array(f, np.float32)
+        b = np.asarray(boxes, dtype=np.float64).reshape(-1, 4) + np.array([ox, oy, ox, oy], np.float64)
+        x0, y0, x1, y1 = _draw_window(rng, H, W, b, cmin)
+    else:
+        x0, y0, x1, y1 = 0, 0, W, H
+    jitter = _draw_factors(rng, vb, vc, vs)
+    flip = bool(rng.uniform() < pflip) if pflip > 0.0 else False
+    return (x0 - ox, y0 - oy, x1 - ox, y1 - oy), jitter, flip
+
+
+_LR_WORDS = {"left": "right", "leftmost": "rightmost", "lefthand": "righthand"}
+_LR_WORDS.update({v: k for k, v in list(_LR_WORDS.items())})
+_LR_RE = re.compile(r"\b(" + "|".join(sorted(_LR_WORDS, key=len, reverse=True)) + r")\b", re.IGNORECASE)
+
+
+def swap_left_right(text: str) -> str:
+    """the query of a mirrored image: left <-> right, leftmost <-> rightmost, lefthand <-> righthand — whole words, any case, the token's
+    capitalisation style kept (Left -> Right, LEFT -> RIGHT); everything else ("bright", "leftover") is left alone"""
+    def sub(m):
+        tok = m.group(0)
+        new = _LR_WORDS[tok.lower()]
+        return new.upper() if tok.isupper() else (new.capitalize() if tok[0].isupper() else new)
+    return _LR_RE.sub(sub, text)
 
 
 def _resize_pass_host(src: np.ndarray, n_out: int) -> np.ndarray:
@@ -226,21 +308,35 @@ def _blend_host(x: np.ndarray, m, f: np.float32) -> np.ndarray:
     return np.trunc(np.clip(f * x + (np.float32(1.0) - f) * m, np.float32(0.0), np.float32(255.0)))
 
 
-def augment_host(img_u8_hwc: np.ndarray, crop, jitter, out_hw) -> np.ndarray:
+def augment_host(img_u8_hwc: np.ndarray, crop, jitter, out_hw, flip: bool = False, fill=None) -> np.ndarray:
     """THE definition of the training augmentation: uint8 [h, w, 3] -> uint8 [Ho, Wo, 3].
     1. Pillow's `img.crop(crop).resize((Wo, Ho))`: the tap tables of the crop's side lengths applied to the window (taps stop at the
-       window's edge, not the image's);
+       window's edge, not the image's).  fill = (r, g, b): the window may reach outside the image on any side (x0 < x1, y0 < y1, any
+       sign) — `canvas.crop(crop).resize((Wo, Ho))` with the image pasted on a `fill`-coloured canvas that covers the window: the same
+       two passes over the window's pixels, of which those outside the image are `fill`.  fill = None: a window that is not inside the
+       image is a ValueError;
     2. brightness: blend(x, 0, b);  3. contrast: blend(x, mean, c), mean = the exact integer sum of gray over the image after step 2,
        divided by Ho * Wo in double precision and rounded once to fp32;  4. saturation: blend(x, gray(pixel after step 3), s);
     with blend(x, m, f) = trunc(clamp(f * x + (1 - f) * m, 0, 255)) and gray = trunc((0.2989 r + 0.587 g) + 0.114 b), all in fp32 with
-    every product and sum rounded separately.  A factor of exactly 1 is the identity."""
+    every product and sum rounded separately.  A factor of exactly 1 is the identity.
+    5. flip: the result mirrored left-right, out[:, ::-1] — last (steps 2 and 4 are per pixel and the mean of step 3 is an exact
+       integer sum, so any earlier place gives the same bytes)."""
     Ho, Wo = int(out_hw[0]), int(out_hw[1])
     a = np.asarray(img_u8_hwc)
     assert a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3, "augment_host: uint8 [h, w, 3]"
     x0, y0, x1, y1 = (int(v) for v in crop)
-    if not (0 <= x0 < x1 <= a.shape[1] and 0 <= y0 < y1 <= a.shape[0]):
-        raise ValueError(f"augment_host: crop {(x0, y0, x1, y1)} is not inside the {a.shape[0]} x {a.shape[1]} image")
-    win = a[y0:y1, x0:x1]
+    if fill is None:
+        if not (0 <= x0 < x1 <= a.shape[1] and 0 <= y0 < y1 <= a.shape[0]):
+            raise ValueError(f"augment_host: crop {(x0, y0, x1, y1)} is not inside the {a.shape[0]} x {a.shape[1]} image")
+        win = a[y0:y1, x0:x1]
+    else:
+        if not (x0 < x1 and y0 < y1):
+            raise ValueError(f"augment_host: crop {(x0, y0, x1, y1)} is empty")
+        win = np.empty((y1 - y0, x1 - x0, 3), np.uint8)
+        win[:] = np.array(_check_fill(fill, "augment_host: fill"), np.uint8)
+        ix0, iy0, ix1, iy1 = max(x0, 0), max(y0, 0), min(x1, a.shape[1]), min(y1, a.shape[0])      # the window's part inside the image
+        if ix0 < ix1 and iy0 < iy1:
+            win[iy0 - y0:iy1 - y0, ix0 - x0:ix1 - x0] = a[iy0:iy1, ix0:ix1]
     win = _resize_pass_host(win.transpose(1, 0, 2), Wo).transpose(1, 0, 2)        # horizontal pass first, as Pillow
     p = _resize_pass_host(win, Ho).astype(np.float32)
     fb, fc, fs = (np.float32(v) for v in jitter)
@@ -248,7 +344,8 @@ def augment_host(img_u8_hwc: np.ndarray, crop, jitter, out_hw) -> np.ndarray:
     mean = np.float32(np.float64(int(_gray_host(p).astype(np.int64).sum())) / np.float64(Ho * Wo))
     p = _blend_host(p, mean, fc)
     p = _blend_host(p, _gray_host(p)[..., None], fs)
-    return p.astype(np.uint8)
+    out = p.astype(np.uint8)
+    return np.ascontiguousarray(out[:, ::-1]) if flip else out
 
 
 class GpuResizer:
@@ -263,6 +360,7 @@ class GpuResizer:
         self._tmp = None
         self._gray = None
         self._jobs_host = None
+        self.launches = {"augment_u8": 0, "augment_geom_u8": 0}      # calls of zsg_augment_u8_batched / zsg_augment_geom_u8_batched
         import PIL
         if tuple(int(v) for v in PIL.__version__.split(".")[:2]) < (7, 0):      # (Pillow < 7 resizes with NEAREST by default: the two paths would differ)
             raise RuntimeError("GpuResizer reproduces PIL.Image.resize's default filter of Pillow >= 7 (bicubic); found Pillow " + PIL.__version__)
@@ -305,28 +403,49 @@ class GpuResizer:
             self._tab[key] = (dev[off:off + 2 * n].view(n, 2), dev[off + 2 * n:off + (2 + ks) * n].view(n, ks), ks)
             off += (2 + ks) * n
 
-    def resize_flat(self, flat: torch.Tensor, hw, out: Optional[torch.Tensor] = None, crop=None, jitter=None) -> torch.Tensor:
+    def resize_flat(self, flat: torch.Tensor, hw, out: Optional[torch.Tensor] = None, crop=None, jitter=None, flip=None, fill=None) -> torch.Tensor:
         """flat: uint8 DEVICE tensor holding the raw images back to back; hw: [B, 2] (host) heights / widths.  Returns uint8 [B, Ho, Wo, 3].
         crop ([B, 4] host integers x0, y0, x1, y1 inside each image) and / or jitter ([B, 3] host float32 brightness, contrast,
         saturation factors): the training augmentation augment_host defines, on the GPU (zsg_augment_u8_batched) — each image's
-        window is resized instead of the whole image, then jittered; a missing one = the whole image / factors 1."""
+        window is resized instead of the whole image, then jittered; a missing one = the whole image / factors 1.
+        flip ([B] host booleans): the job's result is mirrored left-right.  fill ((r, g, b), or [B, 3], host integers 0..255): windows
+        may leave their images, what lies outside is that colour (without it such a window is a ValueError).  A batch with a flipped
+        job or a window not inside its image runs zsg_augment_geom_u8_batched, every other batch the kernels it always ran
+        (`self.launches` counts the calls of either entry)."""
         offs = self._offsets(hw)
-        if crop is None and jitter is None:
+        if crop is None and jitter is None and flip is None and fill is None:
             return self._run([(flat.data_ptr() + off, h, w) for off, h, w in offs], out, keep=flat)
         B = len(offs)
         crop = [[0, 0, w, h] for _, h, w in offs] if crop is None else (crop.tolist() if torch.is_tensor(crop) else [list(c) for c in crop])
         jit = np.ones((B, 3), np.float32) if jitter is None else np.asarray(jitter.cpu() if torch.is_tensor(jitter) else jitter, dtype=np.float32).reshape(-1, 3)
-        if len(crop) != B or jit.shape[0] != B:
-            raise ValueError(f"resize_flat: {B} images, {len(crop)} crops, {jit.shape[0]} jitter triples")
+        flips = [False] * B if flip is None else [bool(v) for v in (flip.tolist() if torch.is_tensor(flip) else flip)]
+        if len(crop) != B or jit.shape[0] != B or len(flips) != B:
+            raise ValueError(f"resize_flat: {B} images, {len(crop)} crops, {jit.shape[0]} jitter triples, {len(flips)} flips")
         if not np.isfinite(jit).all() or (jit < 0).any():
             raise ValueError("resize_flat: jitter factors must be finite and >= 0")
-        items = []
+        fills = None
+        if fill is not None:
+            f = np.asarray(fill.cpu() if torch.is_tensor(fill) else fill)
+            if f.ndim == 1:
+                f = np.broadcast_to(f, (B, f.shape[0]))
+            if f.shape != (B, 3):
+                raise ValueError(f"resize_flat: fill must be (r, g, b) or [{B}, 3]")
+            fills = [_check_fill(row.tolist(), "resize_flat: fill") for row in f]
+        items, geom = [], any(flips)
         for (off, h, w), c in zip(offs, crop):
             x0, y0, x1, y1 = (int(v) for v in c)
-            if not (0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h):          # checked HERE: the kernels read the window unchecked
+            inside = 0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h
+            if not inside and fills is None:                           # checked HERE: zsg_augment_u8_batched reads the window unchecked
                 raise ValueError(f"resize_flat: crop {(x0, y0, x1, y1)} is not inside the {h} x {w} image")
-            items.append((flat.data_ptr() + off + (y0 * w + x0) * 3, y1 - y0, x1 - x0, w))
-        return self._run_aug(items, jit, out)
+            if not (x0 < x1 and y0 < y1):
+                raise ValueError(f"resize_flat: crop {(x0, y0, x1, y1)} is empty")
+            geom = geom or not inside
+            items.append((flat.data_ptr() + off, h, w, x0, y0, x1, y1))
+        if geom:
+            return self._run_aug_geom(items, jit, flips, fills if fills is not None else [(0, 0, 0)] * B, out)
+        return self._run_aug([(ptr + (y0 * w + x0) * 3, y1 - y0, x1 - x0, w) for ptr, h, w, x0, y0, x1, y1 in items], jit, out)
+
+    MAX_GEOM_SIDE = 1 << 15     # zsg_augment_geom_u8_batched: image and window sides
 
     @staticmethod
     def _offsets(hw):
@@ -404,6 +523,43 @@ class GpuResizer:
         do_cs = int(bool((jit[:, 1:] != 1.0).any()))           # launch 3 (contrast, saturation) only when some job needs it
         check(lib.zsg_augment_u8_batched(jobs.data_ptr(), B, self.Ho, self.Wo, bx, by, self._gray.data_ptr(), do_cs, stream_ptr()),
               "zsg_augment_u8_batched")
+        self.launches["augment_u8"] += 1
+        return out
+
+    def _run_aug_geom(self, items, jit, flips, fills, out):
+        """items: (address of the image's pixel (0, 0), image height, width, window x0, y0, x1, y1) per image — the window may leave the
+        image; the 120-byte job record of zsg_augment_geom_u8_batched (include/zsg.h), which validates the table before it launches"""
+        import struct
+        from ._lib import check, lib, stream_ptr
+        B = len(items)
+        for _, h, w, x0, y0, x1, y1 in items:                  # (the C entry checks the same; here the message names the window)
+            if max(x1 - x0, y1 - y0, h, w) > self.MAX_GEOM_SIDE or max(abs(x0), abs(y0)) >= 1 << 24:
+                raise ValueError(f"resize_flat: crop {(x0, y0, x1, y1)} of the {h} x {w} image: sides up to {self.MAX_GEOM_SIDE} with fill / flip")
+        if out is None:
+            out = torch.empty(B, self.Ho, self.Wo, 3, dtype=torch.uint8, device=self.dev)
+        need = sum(((y1 - y0) * self.Wo * 3 + 3) // 4 * 4 for _, _, _, _, y0, _, y1 in items)
+        if self._tmp is None or self._tmp.numel() < need:
+            self._tmp = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        if self._gray is None or self._gray.numel() < B:
+            self._gray = torch.zeros(max(B, 64), dtype=torch.int32, device=self.dev)
+        blob, tmp_off, bx, by = b"", 0, 0, 0
+        per_out = self.Ho * self.Wo * 3
+        self._ensure_tables([(x1 - x0, self.Wo) for _, _, _, x0, _, x1, _ in items] + [(y1 - y0, self.Ho) for _, _, _, _, y0, _, y1 in items])
+        for i, (ptr, h, w, x0, y0, x1, y1) in enumerate(items):
+            wh, ww = y1 - y0, x1 - x0
+            tx, ty = self._tab[(ww, self.Wo)], self._tab[(wh, self.Ho)]
+            r, g, b = fills[i]
+            blob += struct.pack("<qqqqqqqiiiiiiiiiiiIfffi", ptr, self._tmp.data_ptr() + tmp_off, out.data_ptr() + i * per_out,
+                                tx[0].data_ptr(), tx[1].data_ptr(), ty[0].data_ptr(), ty[1].data_ptr(), h, w, x0, y0, wh, ww, tx[2], ty[2], bx, by,
+                                int(flips[i]), r | g << 8 | b << 16, float(jit[i, 0]), float(jit[i, 1]), float(jit[i, 2]), 0)
+            tmp_off += (wh * self.Wo * 3 + 3) // 4 * 4           # every job's scratch starts dword aligned
+            bx += (wh * self.Wo + 255) // 256
+            by += (self.Ho * self.Wo + 255) // 256
+        jobs = self._upload_jobs(blob, 120)
+        do_cs = int(bool((jit[:, 1:] != 1.0).any()))
+        check(lib.zsg_augment_geom_u8_batched(jobs.data_ptr(), blob, B, self.Ho, self.Wo, bx, by, self._gray.data_ptr(), do_cs, stream_ptr()),
+              "zsg_augment_geom_u8_batched")
+        self.launches["augment_geom_u8"] += 1
         return out
 
     def __call__(self, imgs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -428,7 +584,9 @@ class ImgQuDataset(Dataset):
         gpu_normalise = gpu_normalise or gpu_resize
         self.cfg, self.ds_name, self.split_type, self.gpu_normalise, self.gpu_resize = cfg, ds_name, split_type, gpu_normalise, gpu_resize
         self.embedder = embedder if embedder is not None else get_embedder(cfg)
-        self.augment = split_type == "train" and aug_enabled(cfg)      # training split only: draw_augment per item / per image slot
+        self.augment = split_type == "train" and aug_enabled(cfg)      # training split only: draw_augment_geom per item / per image slot
+        pflip, emax, fill = aug_geom_params(cfg)
+        self.aug_fill = fill if self.augment and (pflip > 0.0 or emax > 1.0) else None      # a new key is on: flips / windows that leave the image
         self.img_dir = Path(cfg["ds_info"][ds_name]["img_dir"])
         self.phrase_len = PHRASE_LEN
         df = pd.read_csv(csv_file)
@@ -443,17 +601,17 @@ class ImgQuDataset(Dataset):
 
     def load_image(self, idx: int, boxes=None):
         """the image of row idx as the batch carries it (decoded, resized unless gpu_resize) + its decoded height / width.
-        boxes (a training dataset with augmentation on): the pixel boxes the crop must keep — one draw_augment from np.random; a worker
-        that resizes applies it (augment_host), with gpu_resize the raw image travels and DevicePrefetcher applies it on the GPU.
-        Returns a fourth value then: the (crop, jitter) drawn."""
+        boxes (a training dataset with augmentation on): the pixel boxes the crop must keep — one draw_augment_geom from np.random; a
+        worker that resizes applies it (augment_host), with gpu_resize the raw image travels and DevicePrefetcher applies it on the GPU.
+        Returns a fourth value then: the (crop, jitter, flip) drawn."""
         import PIL.Image
         img = PIL.Image.open(self.img_dir / self.files[idx]).convert("RGB")
         h, w = img.height, img.width
         rs = self.cfg["resize_img"]
-        aug = draw_augment(np.random, h, w, boxes, self.cfg) if boxes is not None else None
+        aug = draw_augment_geom(np.random, h, w, boxes, self.cfg) if boxes is not None else None
         if not self.gpu_resize:
             if aug is not None:
-                img = augment_host(np.asarray(img), aug[0], aug[1], (rs[1], rs[0]))
+                img = augment_host(np.asarray(img), aug[0], aug[1], (rs[1], rs[0]), flip=aug[2], fill=self.aug_fill)
             else:
                 img = img.resize((rs[0], rs[1]))                  # PIL's default filter, as the reference (dat_loader.py:121)
         a = np.asarray(img)                                       # [H, W, 3] uint8
@@ -463,20 +621,26 @@ class ImgQuDataset(Dataset):
             img_t = torch.from_numpy(a.transpose(2, 0, 1).astype(np.float64)).float().div_(255)     # pil2tensor(...).float().div_(255)
         return (img_t, h, w) if boxes is None else (img_t, h, w, aug)
 
-    def query_item(self, idx: int, h: int, w: int, crop=None) -> Dict[str, torch.Tensor]:
+    def query_item(self, idx: int, h: int, w: int, crop=None, flip: bool = False) -> Dict[str, torch.Tensor]:
         """the per-query fields of row idx (everything but the image, whose decoded size h, w scales the box).  crop (x0, y0, x1, y1):
-        the image was cropped to that window — the box is given relative to it (unclipped) and img_size is the window's, so the
-        identities between annot, orig_annot and img_size the evaluator relies on keep holding."""
+        the image was cropped to that window (which may leave the image: zoom-out) — the box is given relative to it (unclipped) and
+        img_size is the window's, so the identities between annot, orig_annot and img_size the evaluator relies on keep holding.
+        flip: the window was mirrored left-right — so is the box, in window pixels (x1' = cw - x2, x2' = cw - x1), and the query's
+        direction words are swapped (swap_left_right) before it is embedded."""
         q = self.queries[idx]
         if isinstance(q, list):
             q = str(np.random.choice(q))                          # dat_loader.py:153-154
         q = q.replace("_", " ")
+        if flip:
+            q = swap_left_right(q)
         qvec, qlen = embed_query(self.embedder, q, self.phrase_len)
         x1, y1, x2, y2 = self.boxes[idx]
         if crop is not None:
             x0, y0 = int(crop[0]), int(crop[1])
             h, w = int(crop[3]) - y0, int(crop[2]) - x0
             x1, y1, x2, y2 = x1 - x0, y1 - y0, x2 - x0, y2 - y0
+        if flip:
+            x1, x2 = w - x2, w - x1
         target = 2 * np.array([y1 / h, x1 / w, y2 / h, x2 / w]) - 1          # y1x1y2x2 in [-1, 1] (anchors are row, column)
         return {"idxs": torch.tensor(idx).long(), "qvec": torch.from_numpy(qvec),
                 "qlens": torch.tensor(min(qlen, self.phrase_len)), "annot": torch.from_numpy(target).float(),
@@ -484,11 +648,13 @@ class ImgQuDataset(Dataset):
 
     def __getitem__(self, idx: int) -> Dict[str, torch.Tensor]:
         if self.augment:
-            img_t, h, w, (crop, jitter) = self.load_image(idx, [self.boxes[idx]])
+            img_t, h, w, (crop, jitter, flip) = self.load_image(idx, [self.boxes[idx]])
             item = {"img": img_t}
-            item.update(self.query_item(idx, h, w, crop))
+            item.update(self.query_item(idx, h, w, crop, flip))
             if self.gpu_resize:                                   # applied by DevicePrefetcher (GpuResizer.resize_flat), dropped there
                 item["aug_crop"], item["aug_jitter"] = torch.tensor(crop, dtype=torch.int32), torch.from_numpy(jitter)
+                if self.aug_fill is not None:                     # only with aug_flip / aug_expand_max on: (flip, fill r, g, b)
+                    item["aug_geom"] = torch.tensor([int(flip), *self.aug_fill], dtype=torch.int32)
             return item
         img_t, h, w = self.load_image(idx)
         item = {"img": img_t}
@@ -516,22 +682,25 @@ class ImgQuDataset(Dataset):
         """One batch of the grouped TRAINING loader (cfg group_trn_by_image): one image slot per chunk — the rows of a chunk share an image
         file, which is decoded (and resized) once, from the chunk's first row — even if two chunks of one file meet in a batch; the
         queries in chunk order.  Exactly len(chunks) slots, every one used (checked by the collater)."""
-        imgs, items, idx, crops, jitters = [], [], [], [], []
+        imgs, items, idx, crops, jitters, geoms = [], [], [], [], [], []
         for s, rows in enumerate(chunks):
             if len({self.files[r] for r in rows}) != 1:
                 raise ValueError(f"grouped_train_batch: chunk {s} mixes image files")
-            crop = None
+            crop, flip = None, False
             if self.augment:                                      # ONE draw per image slot, from the union of the chunk's boxes
-                img_t, h, w, (crop, jitter) = self.load_image(rows[0], [self.boxes[r] for r in rows])
+                img_t, h, w, (crop, jitter, flip) = self.load_image(rows[0], [self.boxes[r] for r in rows])
                 crops.append(crop)
                 jitters.append(jitter)
+                if self.aug_fill is not None:
+                    geoms.append([int(flip), *self.aug_fill])
             else:
                 img_t, h, w = self.load_image(rows[0])
             imgs.append(img_t)
-            for r in rows:
-                items.append(self.query_item(r, h, w, crop))
+            for r in rows:                                        # every query of the slot: the slot's window, mirrored and swapped alike
+                items.append(self.query_item(r, h, w, crop, flip))
                 idx.append(s)
-        return grouped_collater(items, imgs, idx, all_slots_used=True, aug=(crops, jitters) if self.augment and self.gpu_resize else None)
+        aug = ((crops, jitters, geoms) if geoms else (crops, jitters)) if self.augment and self.gpu_resize else None
+        return grouped_collater(items, imgs, idx, all_slots_used=True, aug=aug)
 
 
 def collater(batch: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
@@ -546,7 +715,7 @@ def collater(batch: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
             out["img"], out["img_hw"] = flatten_raw([b[k] for b in batch])
             continue
         t = torch.stack([b[k] for b in batch])
-        out[k] = t if ((k == "img" and t.dtype == torch.uint8) or k == "aug_crop") else t.float()       # (aug_crop: int32 pixel windows)
+        out[k] = t if ((k == "img" and t.dtype == torch.uint8) or k in ("aug_crop", "aug_geom")) else t.float()       # (aug_crop, aug_geom: int32)
     out["qvec"] = out["qvec"][:, :max_qlen]
     if "img_hw" in out:
         out["img_hw"] = out["img_hw"].int()
@@ -559,7 +728,8 @@ def grouped_collater(items: List[Dict[str, torch.Tensor]], imgs: List[torch.Tens
     This is where the index range is checked (on the host, once per batch): the forward reads img_idx on the device only.
     all_slots_used (training batches): every image slot must be named by some query — train-mode BatchNorm reduces over all slots.
     aug = (crops, jitters), one per image SLOT (gpu_resize training with augmentation): emitted as `aug_crop` int32 [slots, 4] and
-    `aug_jitter` float32 [slots, 3] alongside `img`."""
+    `aug_jitter` float32 [slots, 3] alongside `img`; a third member (aug_flip / aug_expand_max on) = (flip, fill r, g, b) per slot,
+    emitted as `aug_geom` int32 [slots, 4]."""
     if not imgs or len(img_idx) != len(items) or min(img_idx) < 0 or max(img_idx) >= len(imgs):
         raise ValueError(f"grouped_collater: img_idx out of range for {len(imgs)} images / {len(items)} queries")
     if all_slots_used and len(set(img_idx)) != len(imgs):
@@ -577,6 +747,10 @@ def grouped_collater(items: List[Dict[str, torch.Tensor]], imgs: List[torch.Tens
             raise ValueError(f"grouped_collater: {len(imgs)} image slots but {len(aug[0])} crops / {len(aug[1])} jitter triples")
         out["aug_crop"] = torch.tensor([list(c) for c in aug[0]], dtype=torch.int32)
         out["aug_jitter"] = torch.from_numpy(np.stack(aug[1]).astype(np.float32))
+        if len(aug) > 2:
+            if len(aug[2]) != len(imgs):
+                raise ValueError(f"grouped_collater: {len(imgs)} image slots but {len(aug[2])} flip / fill records")
+            out["aug_geom"] = torch.tensor([list(g) for g in aug[2]], dtype=torch.int32)
     return out
 
 
@@ -755,7 +929,7 @@ class DevicePrefetcher:
     """Wraps a loader of pinned host batches: the next batch is copied to the GPU on a side stream while the current one
     is being consumed (HIP copy engine overlaps the training step), and handed over with an event wait."""
 
-    _HOST_ONLY = ("img_hw", "aug_crop", "aug_jitter")        # fields the resizer consumes on the host: not part of the device batch
+    _HOST_ONLY = ("img_hw", "aug_crop", "aug_jitter", "aug_geom")        # fields the resizer consumes on the host: not part of the device batch
 
     def __init__(self, loader, device="cuda", resize_hw=None):
         """resize_hw = (H, W): batches whose "img" is raw uint8 HWC (a list of differently sized images, or a stack at another size)
@@ -788,7 +962,11 @@ class DevicePrefetcher:
                     raise RuntimeError("DevicePrefetcher: raw images of mixed sizes need resize_hw")
                 if self._resizer is None:
                     self._resizer = GpuResizer(self.resize_hw, self.device)
-                dev["img"] = self._resizer.resize_flat(dev["img"], hw, crop=crop, jitter=jitter)
+                geom = batch.get("aug_geom")                   # int32 [B, 4] = (flip, fill r, g, b): only with aug_flip / aug_expand_max on
+                if geom is not None:
+                    dev["img"] = self._resizer.resize_flat(dev["img"], hw, crop=crop, jitter=jitter, flip=geom[:, 0] != 0, fill=geom[:, 1:])
+                else:
+                    dev["img"] = self._resizer.resize_flat(dev["img"], hw, crop=crop, jitter=jitter)
             elif crop is not None:
                 raise RuntimeError("DevicePrefetcher: a batch with aug_crop / aug_jitter needs raw uint8 images and resize_hw")
             ev = torch.cuda.Event()
@@ -823,6 +1001,7 @@ def get_data(cfg, embedder=None, prefetch: Optional[bool] = None):
     ds_name = cfg["ds_to_use"]
     info = cfg["ds_info"][ds_name]
     aug_params(cfg)                                          # ValueError for an aug_* key outside its range
+    aug_geom_params(cfg)
     emb = embedder if embedder is not None else get_embedder(cfg)
     gpu = torch.cuda.is_available() and (cfg["gpu_img_normalise"] if "gpu_img_normalise" in cfg else True)
     prefetch = gpu if prefetch is None else prefetch

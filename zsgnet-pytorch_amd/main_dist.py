@@ -43,8 +43,8 @@ def learner_init(uid: str, cfg):
     if cfg["synthetic"]:
         from .dat_loader import aug_enabled
         if aug_enabled(cfg):                # (also a ValueError for an aug_* key outside its range)
-            raise ValueError("aug_crop_min / aug_brightness / aug_contrast / aug_saturation need synthetic=False: synthetic batches have "
-                             "no decoded image to crop")
+            raise ValueError("aug_crop_min / aug_brightness / aug_contrast / aug_saturation / aug_flip / aug_expand_max need synthetic=False: "
+                             "synthetic batches have no decoded image to crop")
         from .synth import get_data
         data = get_data(cfg, zdist.get_rank())
     else:                                   # CSV / image datasets of cfg.ds_to_use (dat_loader.py:233-257)
