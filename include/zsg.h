@@ -413,7 +413,9 @@ int zsg_transpose_w_batched(const float* src_base, float* dst_base, const void* 
 /* dst[r][0:dst_ld] = [ src[r*src_ld + 0:C] | 0 ... ] */
 int zsg_pad_rows(const float* src, int64_t rows, int32_t C, int32_t src_ld, float* dst, int32_t dst_ld, void* stream);
 
-/* out[g][c] (+)= sum_{r<rows} x[g*gstride + r*ld + c0 + c],  c < C   (bias gradients; per-image language-vector grads) */
+/* out[g][c] (+)= sum_{r<rows} x[g*gstride + r*ld + c0 + c],  c < C   (bias gradients; per-image language-vector grads).
+ * 16-byte loads when C, ld, c0, gstride are multiples of 4 and x is 16-byte aligned, else a scalar kernel; under
+ * zsg_set_deterministic one block per column group adds in a fixed order (the scalar form accumulates in fp64 there). */
 int zsg_colsum(const float* x, int32_t groups, int64_t gstride, int32_t rows, int32_t ld, int32_t c0, int32_t C,
                float* out, int32_t accumulate, void* stream);
 
@@ -533,7 +535,9 @@ int zsg_bn_sync_relu_maxpool_bwd_apply(const float* dout, const uint8_t* idx, co
 /* ---------------------------------------------------------------------------------------------------------------
  * Pooling / resampling / elementwise (NHWC, C % 4 == 0).
  * ------------------------------------------------------------------------------------------------------------- */
-/* nn.MaxPool2d(k, s, p, ceil_mode) — mdl.py:152 (3,2,1), ssd_vgg.py:122,124,132.  idx: uint8 window position. */
+/* nn.MaxPool2d(k, s, p, ceil_mode) — mdl.py:152 (3,2,1), ssd_vgg.py:122,124,132.  idx: uint8 window position r * k + q (k <= 15,
+ * both directions): the first maximum of the window, the last NaN if it holds one, its first in-bounds tap if every value is -inf
+ * (torch's rules: the backward gives the window's gradient to that element). */
 int zsg_maxpool_fwd(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k, int32_t s, int32_t p,
                     int32_t Ho, int32_t Wo, float* out, uint8_t* idx, void* stream);
 int zsg_maxpool_bwd(const float* dout, const uint8_t* idx, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,

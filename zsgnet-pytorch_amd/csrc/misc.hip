@@ -47,6 +47,7 @@ __global__ void maxpool_fwd_kernel(const float* __restrict__ x, int B, int H, in
         decomp4(i, total, C4, Wo, Ho, c4, wo, ho, b);
         f32x4 best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         int bi[4] = {0, 0, 0, 0};
+        bool seen = false;
         for (int r = 0; r < k; ++r) {
             const int hi = ho * s - p + r;
             if ((unsigned)hi >= (unsigned)H) continue;
@@ -54,6 +55,10 @@ __global__ void maxpool_fwd_kernel(const float* __restrict__ x, int B, int H, in
                 const int wi = wo * s - p + q;
                 if ((unsigned)wi >= (unsigned)W) continue;
                 const f32x4 v = *(const f32x4*)(x + (((int64_t)b * H + hi) * W + wi) * C4 * 4 + c4 * 4);
+                if (!seen) {                                   // the first in-bounds tap holds the index until a value beats -inf (torch rule:
+                    seen = true;                               // an all -inf window gives its gradient to that element, never to the padding)
+                    bi[0] = bi[1] = bi[2] = bi[3] = r * k + q;
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (v[e] > best[e] || v[e] != v[e]) {      // first maximum wins; NaN propagates (torch rule)
@@ -112,7 +117,7 @@ extern "C" int zsg_maxpool_fwd(const float* x, int32_t B, int32_t H, int32_t W, 
 
 extern "C" int zsg_maxpool_bwd(const float* dout, const uint8_t* idx, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k, int32_t s,
                                int32_t p, int32_t Ho, int32_t Wo, float* dx, void* stream) {
-    ZSG_REQUIRE(dout && idx && dx && (C % 4) == 0 && k > 0 && s > 0, "maxpool_bwd: bad argument");
+    ZSG_REQUIRE(dout && idx && dx && (C % 4) == 0 && k > 0 && k <= 15 && s > 0, "maxpool_bwd: bad argument");
     const int64_t n = (int64_t)B * H * W * (C / 4);
     hipStream_t st = (hipStream_t)stream;
     ZSG_PROF("maxpool_bwd", st, 0, ((double)B * H * W + (double)B * Ho * Wo * 1.25) * C * 4);
@@ -556,22 +561,25 @@ extern "C" int zsg_transpose_w_batched(const float* src_base, float* dst_base, c
 
 // ---- column sums ---------------------------------------------------------------------------------------------------------
 // grid (col blocks of 64, row splits, groups); block 256 = 64 columns x 4 row lanes; atomics merge the row splits.
+// ACC: float, or double for the deterministic single-block form: there one lane adds rows / 4 values in a row (7 760 for the head's bias
+// gradient), and an fp32 chain of that length missed the 1e-4 the split form keeps (measured 1e-3 absolute on sums of ~10).
+template <typename ACC>
 __global__ void colsum_kernel(const float* __restrict__ x, int64_t gstride, int rows, int ld, int c0, int C, float* __restrict__ out,
                               int rows_per_block) {
-    __shared__ float red[4][64];
+    __shared__ ACC red[4][64];
     const int col = blockIdx.x * 64 + (threadIdx.x & 63);
     const int rl = threadIdx.x >> 6;
     const int g = blockIdx.z;
     const int r_begin = blockIdx.y * rows_per_block;
     const int r_end = min(rows, r_begin + rows_per_block);
-    float s = 0.f;
+    ACC s = 0;
     if (col < C)
         for (int r = r_begin + rl; r < r_end; r += 4) s += x[g * gstride + (int64_t)r * ld + c0 + col];
     red[rl][threadIdx.x & 63] = s;
     __syncthreads();
     if (rl == 0 && col < C) {
         s = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        unsafeAtomicAdd(out + (int64_t)g * C + col, s);
+        unsafeAtomicAdd(out + (int64_t)g * C + col, (float)s);
     }
 }
 // 16-byte variant: a thread owns 4 consecutive columns; CL column lanes x (256/CL) row lanes; four independent loads
@@ -663,7 +671,10 @@ extern "C" int zsg_colsum(const float* x, int32_t groups, int64_t gstride, int32
     while (splits > 1 && (int64_t)splits * cb * groups > 2048) splits = (splits + 1) / 2;
     if (g_zsg_deterministic) splits = 1;
     const int rpb = cdiv(rows, splits);
-    ZSG_LAUNCH(colsum_kernel, dim3(cb, cdiv(rows, rpb), groups), dim3(256), 0, st, x, gstride, rows, ld, c0, C, out, rpb);
+    if (g_zsg_deterministic)
+        ZSG_LAUNCH(colsum_kernel<double>, dim3(cb, 1, groups), dim3(256), 0, st, x, gstride, rows, ld, c0, C, out, rpb);
+    else
+        ZSG_LAUNCH(colsum_kernel<float>, dim3(cb, cdiv(rows, rpb), groups), dim3(256), 0, st, x, gstride, rows, ld, c0, C, out, rpb);
     ZSG_CHECK_LAUNCH("colsum");
     return 0;
 }
