@@ -563,6 +563,22 @@ int zsg_nchw_to_nhwc4(const float* img, int32_t B, int32_t C, int32_t H, int32_t
 /* uint8 [pixels][3] (HWC, as PIL decodes) -> float [pixels][4] = (r,g,b)/255, 0 — `pil2tensor(img).float().div_(255)`
  * (dat_loader.py:26-33, 134) fused with the stem layout; IEEE division: equal to the host conversion bit for bit. */
 int zsg_u8hwc_to_nhwc4(const uint8_t* img, int64_t pixels, float* out, void* stream);
+/* Flip test-time augmentation (ZSGNet.eval_tta("flip"); csrc/tta.hip).
+ * Staging: img uint8 [B][H][W][3] (_u8) or fp32 [B][3][H][W] (_f32) -> out [2B][H][W][4], 16-byte aligned.  For pixel (b, y, x) the four
+ * floats zsg_u8hwc_to_nhwc4 / zsg_nchw_to_nhwc4 write for it go to row b at (y, x) and to row B + b at (y, W - 1 - x): rows 0..B-1 are
+ * the batch as given, rows B..2B-1 its mirror along W, bit for bit what the plain entries give on the flipped image.  Every input
+ * element is read once.  Returns -1 (nothing launched) for a null pointer, a non-positive size or a misaligned out. */
+int zsg_tta_flip_stage_u8(const uint8_t* img, int32_t B, int32_t H, int32_t W, float* out, void* stream);
+int zsg_tta_flip_stage_f32(const float* img, int32_t B, int32_t H, int32_t W, float* out, void* stream);
+/* Merge: out5_2b [2B][A][5] (ty, tx, th, tw, att per anchor; rows B..2B-1 from the mirrored images) -> out [B][A][5].  levels = HOST
+ * array int32 [L][4] of (first anchor, h, w, n) per pyramid level, anchor (y, x, k) of a level at first + (y * w + x) * n + k; its
+ * partner under the mirror is p = first + (y * w + (w - 1 - x)) * n + k.  With u = out5_2b[b][a], v = out5_2b[B + b][p]:
+ *   out[b][a] = 0.5f * (u0 + v0, u1 - v1, u2 + v2, u3 + v3, u4 + v4)
+ * one fp32 add / subtract and one multiply each (reproducible in numpy; NaN and infinities propagate as IEEE has it).  Fixed order,
+ * no atomics.  Returns -1 and launches nothing when a pointer is null, B or A is not positive, L is outside 1..ZSG_TTA_MAX_LEVELS, the
+ * levels do not tile [0, A) exactly in order, or out overlaps the input. */
+#define ZSG_TTA_MAX_LEVELS 8      /* as the loss kernels' level tables (zsg_match_atss) */
+int zsg_tta_flip_merge(const float* out5_2b, int32_t B, int32_t A, const int32_t* levels, int32_t L, float* out, void* stream);
 /* `img.resize((Wo, Ho))` of the reference loader (dat_loader.py:121: PIL.Image.resize, default filter = bicubic) for one uint8
  * [H][W][C] image, byte-identical to Pillow: its two fixed-point passes (horizontal into tmp [H][Wo][C], then vertical) with the
  * per-axis tap tables the HOST computes from the two axis lengths (bounds[o] = {first tap, tap count}, coef[o][ksize] 22-bit

@@ -4,7 +4,11 @@ images per batch; without --images the one-image-per-query path, as before.
 --topk K [--pre-nms N] [--queries Q]: the evaluator call alone, on a fixed [Q, 17460, 5] head output: eval_topk = 1 (zsg_eval only) against
 eval_topk = K in eval mode (zsg_eval + zsg_eval_topk), alternating; device events around groups of calls, the median per call of each, one
 JSON line (--json PATH also writes it to a file).
---dtype fp32|bf16|bf16_act: cfg eval_dtype of the network (the forward paths; --topk times no network)."""
+--dtype fp32|bf16|bf16_act: cfg eval_dtype of the network (the forward paths; --topk times no network).
+--tta flip: flip test-time augmentation (cfg eval_tta): the eval FORWARD of the same network at the same B = --queries, three ways,
+alternating — the plain batch, the plain batch at 2B, the TTA batch (2B rows in one forward + the staging and merge launches) — and the
+two new launches alone; device events around groups of calls, the median per call of each, one JSON line (--json PATH also writes it to
+a file).  Works with --dtype and --images / --queries.  The expectation to read it against: TTA ~ plain 2B + merge."""
 import argparse
 import json
 import os
@@ -19,7 +23,8 @@ ap.add_argument("--images", type=int, default=None, help="distinct images per ba
 ap.add_argument("--queries", type=int, default=16, help="queries per batch")
 ap.add_argument("--topk", type=int, default=None, help="time the evaluator call with and without the top-k launch (K boxes per query)")
 ap.add_argument("--pre-nms", type=int, default=128, help="with --topk: candidates per query that enter the NMS")
-ap.add_argument("--json", default=None, help="with --topk: also write the result line to this file")
+ap.add_argument("--tta", choices=("flip",), default=None, help="time the eval forward plain at B, plain at 2B and with eval_tta=flip at B, and the two TTA launches alone")
+ap.add_argument("--json", default=None, help="with --topk / --tta: also write the result line to this file")
 args = ap.parse_args()          # (before the heavy imports: --help and a bad value answer at once)
 
 import torch
@@ -71,6 +76,71 @@ if args.topk is not None:
     time_topk()
     sys.exit(0)
 net = mdl.get_default_net(9, cfg).to("cuda").eval()
+
+
+def time_tta():
+    from zsgnet_pytorch_amd._lib import check, lib, stream_ptr
+    groups, per_group = 21, 10
+    Bi = args.images
+
+    def batch(q, bi, seed):
+        b = synthetic_batch(q, 300, 300, seed=seed) if bi is None else synthetic_shared_batch(bi, q, 300, 300, seed=seed)
+        return {k: v.cuda() for k, v in b.items()}
+    b1, b2 = batch(Q, Bi, 1), batch(2 * Q, None if Bi is None else 2 * Bi, 2)
+    runs = {"plain_B": ("none", b1), "plain_2B": ("none", b2), "tta_B": ("flip", b1)}
+    ms = {k: [] for k in runs}
+    with torch.no_grad():
+        for g in range(groups + 3):                  # the first 3 groups are warm-up (they lower and tune the two plans)
+            for name, (mode, b) in runs.items():     # alternating: all three see the same clock state
+                net.eval_tta(mode)
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                for _ in range(per_group):
+                    net(b)
+                t1.record()
+                t1.synchronize()
+                if g >= 3:
+                    ms[name].append(t0.elapsed_time(t1) / per_group)
+        net.eval_tta("flip")
+        geo = net.plan_geometry(b1)                  # (B, H, W, T) or, for queries sharing images, (Bi, Q, H, W, T): the cached TTA plan
+        plan = net._plan_for(*geo) if Bi is None else net._plan_for(geo[0], geo[2], geo[3], geo[4], Q=geo[1])
+        A, lv = plan.A, plan._tta_levels()
+        n_img = Q if Bi is None else Bi
+        img = b1["img"].contiguous()
+        x0 = torch.empty(2 * n_img, 300, 300, 4, device="cuda")
+        o2, om = torch.randn(2 * Q, A, 5, device="cuda"), torch.empty(Q, A, 5, device="cuda")
+        alone = {"stage_f32": lambda: check(lib.zsg_tta_flip_stage_f32(img.data_ptr(), n_img, 300, 300, x0.data_ptr(), stream_ptr()), "stage"),
+                 "merge": lambda: check(lib.zsg_tta_flip_merge(o2.data_ptr(), Q, A, lv.ctypes.data, lv.shape[0], om.data_ptr(), stream_ptr()), "merge")}
+        us = {}
+        for name, fn in alone.items():
+            v = []
+            for g in range(groups + 3):
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                for _ in range(100):
+                    fn()
+                t1.record()
+                t1.synchronize()
+                if g >= 3:
+                    v.append(10.0 * t0.elapsed_time(t1))          # ms per 100 launches -> us per launch (back to back: includes the launch gap)
+            us[name] = sorted(v)[len(v) // 2]
+    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+    res = {"what": "eval forward, device events, median of %d groups of %d calls, ms per batch; launches alone back to back, us" % (groups, per_group),
+           "dtype": args.dtype, "B": Q, "images": Bi, "A": A,
+           **{k + "_ms": round(v, 4) for k, v in med.items()},
+           **{k + "_min_max_ms": [round(min(v), 4), round(max(v), 4)] for k, v in ms.items()},
+           "tta_over_plain_2B": round(med["tta_B"] / med["plain_2B"], 4), "tta_over_plain_B": round(med["tta_B"] / med["plain_B"], 4),
+           **{k + "_us": round(v, 2) for k, v in us.items()}}
+    line = json.dumps(res)
+    print(line)
+    if args.json:
+        with open(args.json, "w") as f:
+            f.write(line + "\n")
+
+
+if args.tta is not None:
+    time_tta()
+    sys.exit(0)
 if args.images is None:
     bt = synthetic_batch(Q, 300, 300, seed=1)
 else:

@@ -152,6 +152,9 @@ SIGNATURES = {
     "zsg_l2norm_bwd": (I32, [P, P, P, I64, I32, P, P]),
     "zsg_nchw_to_nhwc4": (I32, [P, I32, I32, I32, I32, P, P]),
     "zsg_u8hwc_to_nhwc4": (I32, [P, I64, P, P]),
+    "zsg_tta_flip_stage_u8": (I32, [P, I32, I32, I32, P, P]),
+    "zsg_tta_flip_stage_f32": (I32, [P, I32, I32, I32, P, P]),
+    "zsg_tta_flip_merge": (I32, [P, I32, I32, P, I32, P, P]),
     "zsg_resize_u8": (I32, [P, I32, I32, I32, P, P, I32, P, P, I32, I32, I32, P, P, P]),
     "zsg_resize_u8_batched": (I32, [P, I32, I32, I32, I32, I32, I32, P]),
     "zsg_augment_u8_batched": (I32, [P, I32, I32, I32, I32, I32, P, I32, P]),

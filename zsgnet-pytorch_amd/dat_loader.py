@@ -587,6 +587,10 @@ class ImgQuDataset(Dataset):
         self.augment = split_type == "train" and aug_enabled(cfg)      # training split only: draw_augment_geom per item / per image slot
         pflip, emax, fill = aug_geom_params(cfg)
         self.aug_fill = fill if self.augment and (pflip > 0.0 or emax > 1.0) else None      # a new key is on: flips / windows that leave the image
+        tta = cfg["eval_tta"] if "eval_tta" in cfg else "none"
+        if tta not in ("none", "flip"):
+            raise ValueError(f"eval_tta={tta!r}: expected one of none, flip")
+        self.tta_flip = split_type != "train" and tta == "flip"       # validation / test items also carry `qvec_flip` (ZSGNet.eval_tta)
         self.img_dir = Path(cfg["ds_info"][ds_name]["img_dir"])
         self.phrase_len = PHRASE_LEN
         df = pd.read_csv(csv_file)
@@ -634,6 +638,12 @@ class ImgQuDataset(Dataset):
         if flip:
             q = swap_left_right(q)
         qvec, qlen = embed_query(self.embedder, q, self.phrase_len)
+        extra = {}
+        if self.tta_flip:
+            # the query of the mirrored image (cfg eval_tta = "flip"): left <-> right word for word, so the token count cannot change
+            qvf, qlf = embed_query(self.embedder, swap_left_right(q), self.phrase_len)
+            assert qlf == qlen, f"swap_left_right changed the token count of {q!r}: {qlen} -> {qlf}"
+            extra["qvec_flip"] = torch.from_numpy(qvf)
         x1, y1, x2, y2 = self.boxes[idx]
         if crop is not None:
             x0, y0 = int(crop[0]), int(crop[1])
@@ -644,7 +654,7 @@ class ImgQuDataset(Dataset):
         target = 2 * np.array([y1 / h, x1 / w, y2 / h, x2 / w]) - 1          # y1x1y2x2 in [-1, 1] (anchors are row, column)
         return {"idxs": torch.tensor(idx).long(), "qvec": torch.from_numpy(qvec),
                 "qlens": torch.tensor(min(qlen, self.phrase_len)), "annot": torch.from_numpy(target).float(),
-                "orig_annot": torch.tensor([x1, y1, x2, y2]).float(), "img_size": torch.tensor([h, w])}
+                "orig_annot": torch.tensor([x1, y1, x2, y2]).float(), "img_size": torch.tensor([h, w]), **extra}
 
     def __getitem__(self, idx: int) -> Dict[str, torch.Tensor]:
         if self.augment:
@@ -705,7 +715,7 @@ class ImgQuDataset(Dataset):
 
 def collater(batch: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
     """dat_loader.py:187-196: every field stacked as float (uint8 images stay uint8: they become float on the GPU);
-    qvec cut to the longest query of the batch."""
+    qvec (and qvec_flip, the mirrored image's query of cfg eval_tta = "flip", where the items carry it) cut to the longest query of the batch."""
     max_qlen = int(max(int(b["qlens"]) for b in batch))
     out = {}
     for k in batch[0]:
@@ -717,6 +727,8 @@ def collater(batch: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
         t = torch.stack([b[k] for b in batch])
         out[k] = t if ((k == "img" and t.dtype == torch.uint8) or k in ("aug_crop", "aug_geom")) else t.float()       # (aug_crop, aug_geom: int32)
     out["qvec"] = out["qvec"][:, :max_qlen]
+    if "qvec_flip" in out:
+        out["qvec_flip"] = out["qvec_flip"][:, :max_qlen]
     if "img_hw" in out:
         out["img_hw"] = out["img_hw"].int()
     return out

@@ -314,6 +314,11 @@ class DistributedDataParallel(nn.Module):
         self.module.eval_precision(dtype)
         return self
 
+    def eval_tta(self, mode: str = "none"):
+        """ZSGNet.eval_tta of the wrapped network ("none" | "flip"): eval plans are per rank, nothing is communicated"""
+        self.module.eval_tta(mode)
+        return self
+
     def wgrad_precision(self, dtype: str = "fp32"):
         """ZSGNet.wgrad_precision of the wrapped network ("fp32" | "bf16"): the gradients stay fp32, so buckets and collectives are unchanged"""
         self.module.wgrad_precision(dtype)

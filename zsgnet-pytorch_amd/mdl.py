@@ -38,6 +38,7 @@ VGG_BASE = [64, 64, "M", 128, 128, "M", 256, 256, 256, "C", 512, 512, 512, "M", 
 SSD_EXTRAS = [256, "S", 512, 128, "S", 256, 128, 256, 128, 256]                                          # ssd_vgg.py:179-182
 
 WGRAD_DTYPES = ("fp32", "bf16")               # cfg wgrad_dtype / ZSGNet.wgrad_precision: operand precision of the training plans' convolution weight gradients
+EVAL_TTAS = ("none", "flip")                   # cfg eval_tta / ZSGNet.eval_tta: test-time augmentation of the eval forwards
 EVAL_DTYPES = ("fp32", "bf16", "bf16_act")    # cfg eval_dtype / ZSGNet.eval_precision: operand precision of the eval plans' convolutions (+ bf16 activation storage)
 TRAIN_DTYPES = ("fp32", "bf16_head")         # cfg train_dtype / ZSGNet.train_precision: operand precision of the training plans' forward convolutions and data gradients ("bf16_head": the pyramid and the heads; "bf16" is left free for a whole-network version)
 ENC_DTYPES = ("fp32", "bf16_fwd")             # cfg enc_dtype / ZSGNet.encoder_precision: operand precision of the training plans' forward convolutions of a ResNet encoder behind the stem (the backward stays what wgrad_dtype / fp32 make it)
@@ -175,6 +176,7 @@ class ZSGNet(nn.Module):
         self._sync_bn_conf = None      # (process group it was made for, force) of that group
         self.debug = False
         self._eval_dtype = "fp32"      # operand precision of the eval plans' convolutions (eval_precision)
+        self._eval_tta = "none"        # test-time augmentation of the eval forwards (eval_tta)
         self._wgrad_dtype = "fp32"     # operand precision of the training plans' convolution weight gradients (wgrad_precision)
         self._train_dtype = "fp32"     # operand precision of the training plans' forward convolutions / data gradients (train_precision)
         self._enc_dtype = "fp32"       # operand precision of the training plans' encoder forward convolutions (encoder_precision)
@@ -459,7 +461,8 @@ class ZSGNet(nn.Module):
         return self._pindex
 
     def plan_geometry(self, inp: Dict[str, Any]) -> Tuple[int, int, int, int]:
-        """(B, H, W, T_plan) of the launch plan forward(inp) will use (T is bucketed: see forward)"""
+        """(B, H, W, T_plan) of the launch plan forward(inp) will use (T is bucketed: see forward).  An eval forward with
+        eval_tta("flip") uses the plan of twice the rows (image slots and queries): the mirrored pass rides in the same forward."""
         img = inp["img"]
         if img.dtype == torch.uint8:
             B, H, W, _ = img.shape
@@ -467,15 +470,16 @@ class ZSGNet(nn.Module):
             B, _, H, W = img.shape
         T = inp["qvec"].shape[1]
         Tp = 20 if T <= 20 else (50 if T <= 50 else T)
+        m = 2 if self._tta_on() else 1          # (flip TTA: the mirrors behind the batch's own images, the mirrored queries behind its queries)
         if inp.get("img_idx") is not None:
             # queries sharing images: (Bi_plan, Q, H, W, T_plan), the image count bucketed as T is (bucket_images); the blind variants
             # gather the images into the plain plan of Q pairs.  A shared TRAINING plan has exactly the batch's image slots (train-mode
             # BatchNorm reduces across slots: no padding)
-            Q = inp["qvec"].shape[0]
+            Q = m * inp["qvec"].shape[0]
             if not (self.use_img and self.use_lang):
                 return Q, H, W, Tp
-            return (B if self.training else bucket_images(B, Q), Q, H, W, Tp)
-        return B, H, W, Tp
+            return (B if self.training else bucket_images(m * B, Q), Q, H, W, Tp)
+        return m * B, H, W, Tp
 
     def _frozen_key(self) -> Tuple[int, ...]:
         """flat-order indices of the parameters with requires_grad=False (the training plans are lowered for one trainable set)"""
@@ -577,6 +581,34 @@ class ZSGNet(nn.Module):
             raise ValueError(f"eval_dtype={dtype!r}: expected one of {', '.join(EVAL_DTYPES)}")
         self._eval_dtype = dtype
         return self
+
+    def eval_tta(self, mode: str = "none") -> "ZSGNet":
+        """Test-time augmentation of the EVAL forwards: "none" (default: one pass over the batch as given) or "flip" — the batch of B
+        queries runs as ONE eval forward of 2B rows: rows 0..B-1 as given, rows B..2B-1 with the image mirrored along W and the query
+        vectors of inp["qvec_flip"] (the embedding of dat_loader.swap_left_right(query); without that key the mirrored rows read
+        inp["qvec"]: an image-only flip), the same qlens and the same h0 | c0.  The two halves are merged per anchor in regression-parameter
+        space (anchor (y, x, k) of a level with anchor (y, w-1-x, k) of the mirrored row; tx changes sign; zsg_tta_flip_merge, include/zsg.h)
+        into a fresh [B, A, 5] output: the caller cannot tell it from a plain one by its shape.  tests/tta_ref.py is the definition.
+        Training-mode forwards ignore the switch.  The forward uses the plain eval plan of 2B rows (for a batch with img_idx: 2Bi image
+        slots, 2Q queries), so it composes with eval_precision and switching back and forth reuses plans."""
+        if mode not in EVAL_TTAS:
+            raise ValueError(f"eval_tta={mode!r}: expected one of {', '.join(EVAL_TTAS)}")
+        self._eval_tta = mode
+        return self
+
+    def _tta_on(self) -> bool:
+        return self._eval_tta == "flip" and not self.training
+
+    def _tta_inputs(self, inp: Dict[str, Any], h0, c0):
+        """(qvec, qlens, h0, c0) of the 2B rows of a flip-TTA forward: the mirrored rows behind the rows as given"""
+        qvec, qlens = inp["qvec"], inp["qlens"]
+        qf = inp.get("qvec_flip")
+        if qf is None:
+            qf = qvec
+        elif not isinstance(qf, torch.Tensor) or qf.shape != qvec.shape or qf.device != qvec.device or qf.dtype != qvec.dtype:
+            raise ValueError("qvec_flip must have the shape, dtype and device of qvec")
+        ql = qlens.reshape(-1)
+        return torch.cat([qvec, qf]), torch.cat([ql, ql]), torch.cat([h0, h0], dim=1), torch.cat([c0, c0], dim=1)
 
     def wgrad_precision(self, dtype: str = "fp32") -> "ZSGNet":
         """Operand precision of the convolution weight gradients of the TRAINING plans: "fp32" (default: what every plan lowered before,
@@ -773,12 +805,19 @@ class ZSGNet(nn.Module):
             sub = {k: v for k, v in inp.items() if k != "img_idx"}
             sub["img"] = img.index_select(0, idx.long())
             return self.forward(sub)
-        Bp, Q, H, W, Tp = self.plan_geometry(inp)
-        plan = self._plan_for(Bp, H, W, Tp, Q=Q)
+        tta = self._tta_on()
+        Bp, Qp, H, W, Tp = self.plan_geometry(inp)
+        plan = self._plan_for(Bp, H, W, Tp, Q=Qp)
         if "h0" in inp:
             h0, c0 = inp["h0"], inp["c0"]
         else:
             h0, c0 = self.lstm_init_hidden(Q)
+        plan.tta = tta
+        if tta:
+            # 2Bi image slots (the mirrors behind the originals) and 2Q queries; a mirrored query points at its image's mirror
+            qvec, qlens, h0, c0 = self._tta_inputs(inp, h0, c0)
+            idx = torch.cat([idx, idx + img.shape[0]])
+            inp = dict(inp, qlens=qlens)
         if self._anchor is None or self._anchor.device != img.device:
             self._anchor = torch.zeros(1, device=img.device, requires_grad=True)
         if train:
@@ -806,12 +845,16 @@ class ZSGNet(nn.Module):
         # The collater cuts qvec to the longest query of the batch (dat_loader.py:187-196), so T changes from batch to batch;
         # a launch plan (and its buffers) is built per geometry, so T is bucketed: the plan processes T_plan >= T tokens of
         # zero-padded input — the LSTM kernels stop at each query's own length, so the result does not depend on T_plan.
+        tta = self._tta_on()
         B, H, W, Tp = self.plan_geometry(inp)
         plan = self._plan_for(B, H, W, Tp)
         if "h0" in inp:
             h0, c0 = inp["h0"], inp["c0"]
         else:
-            h0, c0 = self.lstm_init_hidden(B)
+            h0, c0 = self.lstm_init_hidden(B // 2 if tta else B)
+        plan.tta = tta
+        if tta:
+            qvec, qlens, h0, c0 = self._tta_inputs(inp, h0, c0)
         # ONE differentiable input ties the custom Function into autograd: run_backward writes the parameter gradients
         # straight into the flat gradient buffer that every p.grad views, so autograd has nothing to accumulate per
         # parameter (161 AccumulateGrad nodes cost the host ~0.5 ms per step with the GPU idle at the end of backward)
@@ -881,6 +924,7 @@ class _Plan:
                  sync_bn=frozenset(), Q: Optional[int] = None, dtype: str = "fp32", wgrad_dtype: str = "fp32", train_dtype: str = "fp32", enc_dtype: str = "fp32",
                  enc_bwd_dtype: str = "fp32"):
         self.net, self.B, self.H, self.W, self.T, self.training = net, B, H, W, T, training
+        self.tta = False            # set per forward by ZSGNet.forward (eval_tta "flip", eval plans only): see run_forward
         # training plans only (ZSGNet.wgrad_precision): the weight gradients that go through wgrad() are lowered to zsg_conv_wgrad_bf16
         assert wgrad_dtype in WGRAD_DTYPES
         self.wgrad_bf16 = training and wgrad_dtype == "bf16"
@@ -2849,9 +2893,12 @@ class _Plan:
         net = self.net
         B = self.Q                               # the staged inputs and the output are per query
         n_img = self.B
+        tta = self.tta and not self.training     # flip TTA: img holds half the image rows, the staging launch writes the mirrors behind them
+        if tta and (B % 2 or (not self.shared and 2 * img.shape[0] != self.B)):
+            raise ValueError("flip TTA: img / qvec do not fit the plan's geometry (twice the batch's rows)")
         if self.shared:
             # the batch's own image count (<= the plan's slots; the slots behind it keep what they hold and no query points to them)
-            n_img = img.shape[0]
+            n_img = img.shape[0] * (2 if tta else 1)
             if img_idx is None or not 1 <= n_img <= self.B or qvec.shape[0] != B or (self.training and n_img != self.B):
                 raise ValueError("shared-image plan: img / qvec / img_idx do not fit the plan's geometry")
             self.in_idx.copy_(img_idx, non_blocking=True)          # (device to device: no host synchronisation)
@@ -2903,10 +2950,11 @@ class _Plan:
             else:
                 self.in_h0.view(nd, B, net.lstm_dim).copy_(h0, non_blocking=True)
                 self.in_c0.view(nd, B, net.lstm_dim).copy_(c0, non_blocking=True)
-        # patch the one dynamic pointer (the caller's image tensor)
+        # patch the one dynamic pointer (the caller's image tensor); a flip-TTA forward does not run that launch (img holds half its rows)
         fn, args, what = self.fwd.calls[self.img_slot]
         import ctypes as C_
-        self.fwd.calls[self.img_slot] = (fn, (C_.c_void_p(img.data_ptr()), C_.c_int32(n_img)) + args[2:], what)
+        if not tta:
+            self.fwd.calls[self.img_slot] = (fn, (C_.c_void_p(img.data_ptr()), C_.c_int32(n_img)) + args[2:], what)
         self._img_keepalive = img
         self.fwd_id += 1
         if self.training and self.frozen_bn:
@@ -2923,7 +2971,11 @@ class _Plan:
                                   len(self.fold_jobs), self.fold_rows, self.fold_arena.data_ptr(), stream_ptr()), "bn_fold")
         if self.pack_jobs and not self.training:       # bf16 eval plan: the packed weight images, from the parameters and the fold just made (one launch)
             check(lib.zsg_pack_w_bf16_batched(self.pack_jobs_dev.data_ptr(), len(self.pack_jobs), self.pack_blocks, stream_ptr()), "pack_w_bf16")
-        if u8:
+        if tta:
+            # the image conversion and its mirror in one launch: rows [0, n) as given, rows [n, 2n) mirrored along W
+            stage = lib.zsg_tta_flip_stage_u8 if u8 else lib.zsg_tta_flip_stage_f32
+            check(stage(img.data_ptr(), n_img // 2, self.H, self.W, self.fwd.calls[self.img_slot][1][5], stream_ptr()), "tta_flip_stage")
+        elif u8:
             check(lib.zsg_u8hwc_to_nhwc4(img.data_ptr(), n_img * self.H * self.W, self.fwd.calls[self.img_slot][1][5], stream_ptr()), "u8hwc_to_nhwc4")
         else:
             self.fwd.run(stream_ptr(), 0, 1)          # the one launch with a per-call pointer (the caller's image)
@@ -2966,9 +3018,28 @@ class _Plan:
                 pos = idx
             action()
         self.fwd.run(stream_ptr(), pos)
+        if tta:
+            # rows [B/2, B) are the mirrored pass: merged per anchor into the rows as given (zsg_tta_flip_merge), a fresh [B/2, A, 5]
+            src = out if out is not None else self.out5.buf
+            merged = torch.empty(B // 2, self.A, 5, device=src.device, dtype=torch.float32)
+            lv = self._tta_levels()
+            check(lib.zsg_tta_flip_merge(src.data_ptr(), B // 2, self.A, lv.ctypes.data, lv.shape[0], merged.data_ptr(), stream_ptr()),
+                  "tta_flip_merge")
+            return merged
         if out is not None:
             return out
         return self.out5.buf.view(B, self.A, 5).clone()
+
+    def _tta_levels(self) -> np.ndarray:
+        """the level table of zsg_tta_flip_merge, int32 [L][4] of (first anchor, h, w, anchors per cell): built once per plan"""
+        if getattr(self, "_tta_lv", None) is None:
+            n, rows, off = self.net.n_anchors, [], 0
+            for h, w in self.feat_sizes:
+                rows.append((off, h, w, n))
+                off += h * w * n
+            assert off == self.A, (off, self.A)
+            self._tta_lv = np.ascontiguousarray(rows, dtype=np.int32)
+        return self._tta_lv
 
     def _out_slots(self):
         """The pointer arguments of the forward program that hold the address of the [B, A, 5] output buffer (the last head convolution, or
@@ -3106,6 +3177,7 @@ def get_default_net(num_anchors=1, cfg=None):
     arch = cfg["resnet_arch"] if "resnet_arch" in cfg else "resnet50"
     net = ZSGNet(kind, num_anchors, cfg=cfg, arch=arch)
     net.eval_precision(cfg["eval_dtype"] if "eval_dtype" in cfg else "fp32")          # (raises on anything but fp32 / bf16 / bf16_act)
+    net.eval_tta(cfg["eval_tta"] if "eval_tta" in cfg else "none")                    # (raises on anything but none / flip)
     net.wgrad_precision(cfg["wgrad_dtype"] if "wgrad_dtype" in cfg else "fp32")       # (raises on anything but fp32 / bf16)
     net.train_precision(cfg["train_dtype"] if "train_dtype" in cfg else "fp32")       # (raises on anything but fp32 / bf16_head)
     net.encoder_precision(cfg["enc_dtype"] if "enc_dtype" in cfg else "fp32")         # (raises on anything but fp32 / bf16_fwd)
