@@ -434,7 +434,10 @@ int zsg_bn_stats_from_partials(const float* partials, int32_t chunks, int64_t ro
  * stem activation x [B][H][W][C] (the network's largest tensor): out [B][Ho][Wo][C] = maxpool(relu(bn(x))), idx = window position
  * of the first maximum (uint8, as zsg_maxpool_fwd).  The backward takes d(out): per-channel sums over the pooled gradient (the only
  * non-zero entries of the BatchNorm's grad_output), then dx per input pixel; dgamma / dbeta as zsg_bn_backward.
- * ws >= zsg_bn_workspace_bytes(B * Ho * Wo, C). */
+ * ws >= zsg_bn_workspace_bytes(B * Ho * Wo, C).
+ * The ReLU is fmaxf(bn(x), 0) (a NaN becomes 0, as zsg_relu_fwd) and runs BEFORE the pool: a NaN tap counts as 0 and does not
+ * propagate into the window's maximum; among equal values (zeros after the ReLU above all) the first in-bounds tap in (row, column)
+ * order wins.  In the backward a NaN position passes no gradient (relu(bn(x)) > 0 is false there). */
 int zsg_bn_relu_maxpool_fwd(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, const float* mean, const float* invstd,
                             const float* gamma, const float* beta, int32_t k, int32_t s, int32_t p, int32_t Ho, int32_t Wo, float* out,
                             uint8_t* idx, void* stream);
@@ -462,7 +465,9 @@ int zsg_bn_fold(const float* flat, const float* running_mean, const float* runni
 int zsg_bn_eval_stats(const float* running_mean, const float* running_var, int32_t C, float eps, float* mean,
                       float* invstd, void* stream);
 /* out = [relu]( (x-mean)*invstd*gamma + beta [+ residual] ).  relu_mask (optional, rows*C/4 bytes): bit e of byte i =
- * (element 4i+e > 0) — what zsg_bn_backward needs of the output, at 1/16 of its HBM traffic. */
+ * (element 4i+e > 0) — what zsg_bn_backward needs of the output, at 1/16 of its HBM traffic.  Bits 4-7 are 0; the mask is written
+ * only when relu != 0 (with relu == 0 a given buffer stays untouched).  relu: out = fmaxf(v, 0) (a NaN becomes 0, as zsg_relu_fwd) and
+ * its mask bit is 0; without relu a NaN stays.  zsg_bn_apply_from_partials follows the same rules. */
 int zsg_bn_apply(const float* x, int64_t rows, int32_t C, const float* mean, const float* invstd, const float* gamma,
                  const float* beta, const float* residual, int32_t relu, float* out, uint8_t* relu_mask, void* stream);
 /* g = dout * (out > 0), the mask taken from relu_mask if given, else from relu_out if given, else g = dout;  dgamma = sum g*xhat ; dbeta = sum g ;

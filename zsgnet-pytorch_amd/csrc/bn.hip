@@ -498,7 +498,9 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(const float* _
                 const f32x4 v = bn_pool_val(*(const f32x4*)(x + (((int64_t)b * H + hi) * W + wi) * C4 * 4 + c4 * 4), mu, sc, be);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (v[e] > best[e] || v[e] != v[e]) {      // first maximum wins; NaN propagates (torch rule)
+                    // first maximum wins.  bn_pool_val's fmaxf has already turned a NaN into 0 (the ReLU rule of zsg_relu_fwd), so
+                    // `v[e] != v[e]` never holds here: a NaN tap counts as 0 and does NOT propagate (torch's pool would carry it)
+                    if (v[e] > best[e] || v[e] != v[e]) {
                         best[e] = v[e];
                         bi[e] = r * k + q;
                     }
