@@ -625,6 +625,22 @@ int zsg_augment_u8_batched(const void* jobs_dev, int32_t njobs, int32_t Ho, int3
  * Returns -1 (nothing launched) for a bad argument or record. */
 int zsg_augment_geom_u8_batched(const void* jobs_dev, const void* jobs_host, int32_t njobs, int32_t Ho, int32_t Wo, int32_t blocks_x,
                                 int32_t blocks_y, void* gray_sums, int32_t do_cs, void* stream);
+/* Affine warp (rotation + shear about the image centre) and separable Gaussian blur of a finished uint8 batch, byte-identical to steps 6
+ * and 7 of dat_loader.augment_host(..., warp, blur) — integers only.  jobs = device array (8-byte aligned) of
+ * {int64 src, out; int32 m[6]; uint32 fill; int32 flags; int32 radius; int32 taps[17]; int32 pad[2]} (128 bytes): src / out = the
+ * addresses of the job's image [Ho][Wo][3] and of its result; flags bit 0 = warp: output pixel (x, y) samples the source at the 16.16
+ * position SU = m0 x + m1 y + m2, SV = m3 x + m4 y + m5 (64-bit sums: every int32 coefficient is valid) — ix = SU >> 16,
+ * fx = (SU >> 8) & 255, likewise iy, fy; the four taps (iy, ix) .. (iy + 1, ix + 1), each `fill` (r | g << 8 | b << 16) when outside
+ * [0, Ho) x [0, Wo); v = ((p00 (256 - fx) + p01 fx)(256 - fy) + (p10 (256 - fx) + p11 fx) fy + 32768) >> 16 per channel.  flags bit 1 =
+ * blur: along x, then along y, (sum_k taps[k + radius] p[clamp(i + k, 0, n - 1)] + 32768) >> 16 over k = -radius .. radius, radius in
+ * 0..8, taps >= 0 with sum 65536.  stages: bit 0 = some job warps, bit 1 = some job blurs; one launch for the warp, two for the blur,
+ * none for a stage no job has, and a job without a stage passes through it unchanged.  tmp: scratch of njobs slices of Ho * Wo * 3
+ * bytes rounded up to a multiple of 4 (4-byte aligned; needed with stages bit 1 only).  The sources are never written.  jobs_host (may
+ * be NULL): the same table in host memory; every record is then validated before anything is launched (addresses, flags within
+ * `stages`, radius, taps and their sum, fill < 2^24, sources / results / scratch in three disjoint address ranges).  Returns -1
+ * (nothing launched) for a bad argument or record; Ho, Wo in 1..32768. */
+int zsg_augment_warp_u8_batched(const void* jobs_dev, const void* jobs_host, int32_t njobs, int32_t Ho, int32_t Wo, void* tmp, int32_t stages,
+                                void* stream);
 /* Head input BackBone.concat_we (mdl.py:69-104) + head conv0 (mdl.py:216, 514 -> 256, 3x3 pad 1) without ever materialising
  * the concatenated tensor, and without its spatially-constant input channels: the language vector
  * is constant over the image and the grid channels do not depend on the batch index, so only the 256 feature channels

@@ -9,7 +9,10 @@ the workers draw the crop and the factors, the raw image travels as in (b), zsg_
 on the GPU zsg_augment_geom_u8_batched whenever a job of the batch is flipped or its window leaves the image).  After the rows --aug
 prints the DEVICE time of the augmentation launches for one batch of 16 (the library's own HIP events around each entry point's
 launches, median of 20 calls), per configuration.
-usage: python tools/loader_rate.py [--aug [--flip P] [--expand R]] [n_images] [workers ...]"""
+--rotate D / --shear D / --blur S (with --aug) likewise put aug_rotate / aug_shear / aug_blur on top (dat_loader.draw_augment_warp; on the
+GPU zsg_augment_warp_u8_batched after the other entry, whenever a job of the batch is warped or blurred: its device time is printed on a
+line of its own).
+usage: python tools/loader_rate.py [--aug [--flip P] [--expand R] [--rotate D] [--shear D] [--blur S]] [n_images] [workers ...]"""
 import os
 import sys
 import tempfile
@@ -28,18 +31,22 @@ FILL = (124, 116, 104)
 
 
 def draw(i, h, w, cfg):
-    """the augmentation of image i: (crop, jitter, flip), from a generator seeded by i"""
+    """the augmentation of image i: (crop, jitter, flip, six warp integers, sigma), from a generator seeded by i (with the warp / blur keys
+    off draw_augment_warp draws draw_augment_geom's numbers; then the identity and 0)"""
     rng = np.random.RandomState(i)
     x1, y1 = rng.uniform(0, w - 120), rng.uniform(0, h - 120)
-    return D.draw_augment_geom(rng, h, w, [[x1, y1, x1 + rng.uniform(20, 120), y1 + rng.uniform(20, 120)]], cfg)
+    crop, jit, flip, warp, sigma = D.draw_augment_warp(rng, h, w, [[x1, y1, x1 + rng.uniform(20, 120), y1 + rng.uniform(20, 120)]], cfg, (300, 300))
+    return crop, jit, flip, D.warp_matrix(*warp, (300, 300)) if warp is not None else D.WARP_IDENTITY, sigma or 0.0
 
 
 class Raw(torch.utils.data.Dataset):
     def __init__(self, files, resize, aug=None, cfg=AUG_CFG):
         """aug: None, "gpu" (the item carries the drawn crop / factors) or "host" (the worker applies them: augment_host); cfg: the aug_*
-        keys (AUG_CFG, or with aug_flip / aug_expand_max on top: the item then carries aug_geom too)"""
+        keys (AUG_CFG, or with aug_flip / aug_expand_max / aug_rotate / aug_shear / aug_blur on top: the item then carries aug_geom too, and
+        with one of the last three aug_warp and aug_blur)"""
         self.files, self.resize, self.aug, self.cfg = files, resize, aug, cfg
         self.geom = cfg is not AUG_CFG
+        self.warp = D.aug_warp_enabled(cfg)
 
     def __len__(self):
         return len(self.files)
@@ -48,12 +55,14 @@ class Raw(torch.utils.data.Dataset):
         import PIL.Image
         img = PIL.Image.open(self.files[i]).convert("RGB")
         if self.aug:
-            crop, jit, flip = draw(i, img.height, img.width, self.cfg)
+            crop, jit, flip, warp, sigma = draw(i, img.height, img.width, self.cfg)
             if self.aug == "host":
-                return torch.from_numpy(D.augment_host(np.asarray(img), crop, jit, (300, 300), flip=flip, fill=FILL if self.geom else None))
+                return torch.from_numpy(D.augment_host(np.asarray(img), crop, jit, (300, 300), flip=flip, fill=FILL if self.geom else None, warp=warp, blur=sigma))
             item = {"img": torch.from_numpy(np.asarray(img).copy()), "aug_crop": torch.tensor(crop, dtype=torch.int32), "aug_jitter": torch.from_numpy(jit)}
             if self.geom:
                 item["aug_geom"] = torch.tensor([int(flip), *FILL], dtype=torch.int32)
+            if self.warp:
+                item["aug_warp"], item["aug_blur"] = torch.tensor(warp, dtype=torch.int32), torch.tensor(sigma, dtype=torch.float32)
             return item
         if self.resize:                                             # the reference's item: resize + float conversion on the host
             img = img.resize((300, 300))
@@ -64,7 +73,7 @@ class Raw(torch.utils.data.Dataset):
 def collate_raw(b):
     if isinstance(b[0], dict):                                          # GPU augmentation: raw images + one crop / factor triple each
         out = dict(zip(("img", "img_hw"), D.flatten_raw([x["img"] for x in b])))
-        for k in ("aug_crop", "aug_jitter", "aug_geom"):
+        for k in ("aug_crop", "aug_jitter", "aug_geom", "aug_warp", "aug_blur"):
             if k in b[0]:
                 out[k] = torch.stack([x[k] for x in b])
         return out
@@ -82,6 +91,8 @@ def device_time(files, cfg, label, calls=20, warmup=5):
     kw = dict(crop=[d[0] for d in draws], jitter=np.stack([d[1] for d in draws]))
     if geom:
         kw.update(flip=[d[2] for d in draws], fill=FILL)
+    if D.aug_warp_enabled(cfg):
+        kw.update(warp=[d[3] for d in draws], blur=[d[4] for d in draws])
     rz = D.GpuResizer((300, 300))
     ents, ms = (ProfEntry * 16)(), {}
     lib.zsg_prof_enable(1)
@@ -98,7 +109,8 @@ def device_time(files, cfg, label, calls=20, warmup=5):
     rows = sum(d[0][3] - d[0][1] for d in draws)
     for name, v in ms.items():
         print(f"  device time, batch of 16  {label:34s} {name:18s} median {1e3 * np.median(v):7.1f} us  (min {1e3 * min(v):.1f}, max {1e3 * max(v):.1f}; "
-              f"{rows} window rows in launch 1, {sum(bool(d[2]) for d in draws)} flipped)")
+              f"{rows} window rows in launch 1, {sum(bool(d[2]) for d in draws)} flipped, {sum(d[3] != D.WARP_IDENTITY for d in draws)} warped, "
+              f"{sum(bool(d[4]) for d in draws)} blurred)")
 
 
 def main():
@@ -110,12 +122,15 @@ def main():
             geom_cfg["aug_flip"] = float(next(it))
         elif a == "--expand":
             geom_cfg["aug_expand_max"] = float(next(it))
+        elif a in ("--rotate", "--shear", "--blur"):
+            geom_cfg["aug_" + a[2:]] = float(next(it))
         elif a != "--aug":
             argv.append(a)
     geom = len(geom_cfg) > len(AUG_CFG)
     if geom and "--aug" not in sys.argv:
-        sys.exit("--flip / --expand need --aug")
+        sys.exit("--flip / --expand / --rotate / --shear / --blur need --aug")
     D.aug_geom_params(geom_cfg)                                         # ValueError outside the keys' ranges
+    D.aug_warp_params(geom_cfg)
     n = int(argv[0]) if argv else 512
     workers = [int(a) for a in argv[1:]] or [1, 4, 16]
     rng = np.random.default_rng(0)

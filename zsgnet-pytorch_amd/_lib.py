@@ -159,6 +159,7 @@ SIGNATURES = {
     "zsg_resize_u8_batched": (I32, [P, I32, I32, I32, I32, I32, I32, P]),
     "zsg_augment_u8_batched": (I32, [P, I32, I32, I32, I32, I32, P, I32, P]),
     "zsg_augment_geom_u8_batched": (I32, [P, P, I32, I32, I32, I32, I32, P, I32, P]),
+    "zsg_augment_warp_u8_batched": (I32, [P, P, I32, I32, I32, P, I32, P]),
     "zsg_interleave": (I32, [P, I64, I32, I32, P, I32, I32, I32, P]),
     "zsg_head_lang_map": (I32, [P, P, I32, I32, I32, I32, P, P]),
     "zsg_head_lang_map_packed": (I32, [P, P, I32, I32, P, I32, P, P]),

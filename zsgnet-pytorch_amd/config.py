@@ -46,7 +46,12 @@ DEFAULTS: Dict[str, Any] = {
     "aug_saturation": 0.0,          # ... a saturation factor (blend with the pixel's gray value)
     "aug_flip": 0.0,                # in [0, 1]: probability that a training image (one image slot in grouped batches) is mirrored left-right; its boxes are mirrored and the left / right words of its queries swapped (dat_loader.swap_left_right); 0 = off
     "aug_expand_max": 1.0,          # > 1 (in [1, 4]): zoom-out — the image is placed on a canvas of r ~ U(1, aug_expand_max) times its sides before the window is drawn (dat_loader.draw_augment_geom); 1 = off
-    "aug_fill": [124, 116, 104],    # ... the canvas colour, RGB integers 0..255 (the ImageNet mean)
+    "aug_fill": [124, 116, 104],    # ... the canvas colour, RGB integers 0..255 (the ImageNet mean); also the colour a warp (aug_rotate / aug_shear) brings in from outside the image
+    "aug_rotate": 0.0,              # > 0 (degrees, in [0, 30]): the resized training image is rotated about its centre by theta ~ U(-v, v) (dat_loader.warp_matrix, augment_host step 6; zsg_augment_warp_u8_batched with gpu_img_resize); the box becomes the clipped bounding box of its warped corners (dat_loader.warp_box); 0 = off
+    "aug_shear": 0.0,               # > 0 (degrees, in [0, 20]): ... and sheared along x by phi ~ U(-v, v), one warp M = R(theta) S(phi); 0 = off
+    "aug_warp_keep": 0.8,           # in (0, 1]: a drawn (theta, phi) is used only when every box of the item (of the image slot in grouped batches) keeps this fraction of its warped bounding box inside the image; else both are halved, at most four times, then the warp is dropped (dat_loader.settle_warp)
+    "aug_blur": 0.0,                # 0, or in [0.1, 2.5]: Gaussian blur of the training image with sigma ~ U(0.1, v) output pixels, radius min(8, ceil(3 sigma)) (dat_loader.blur_taps, augment_host step 7); 0 = off
+    "aug_blur_p": 0.5,              # ... applied when a uniform draw is below this probability (in [0, 1])
     "box_iou_loss": "none",         # "giou" / "diou": ZSGLoss adds lamb_iou * (that IoU loss of the decoded positive boxes) to the criterion and reports it as iou_ls (zsg_loss_fwd_bwd_iou); "none" = off
     "lamb_iou": 1.0,                # ... its weight (>= 0); lamb_reg = 0 with it trains on the IoU term alone
     "cls_quality": "none",          # "qfl" / "vfl": the att logit is trained towards the IoU of the anchor's decoded box with the annotation (Quality Focal / Varifocal loss, zsg_loss_fwd_bwd_q) and ZSGLoss also reports pos_iou; needs use_focal, no use_softmax, gamma >= 1; "none" = the reference's focal term

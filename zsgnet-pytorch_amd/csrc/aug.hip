@@ -376,3 +376,157 @@ extern "C" int zsg_augment_geom_u8_batched(const void* jobs_dev, const void* job
     ZSG_CHECK_LAUNCH("augment_geom_u8_batched");
     return 0;
 }
+
+// ---- affine warp and Gaussian blur of the finished batch: zsg_augment_warp_u8_batched ---------------------------------------------------
+// Steps 6 and 7 of dat_loader.augment_host, on the [Ho][Wo][3] result of either entry above.  No floating point: the host rounds the
+// inverse map to six 16.16 integers and the blur to at most 17 16-bit taps that sum to 65536; host and GPU evaluate the same integer
+// expressions.  Up to three launches — warp, blur along x, blur along y — of one thread per output pixel, 256 pixels per block; every
+// job has Ho * Wo pixels, so the running block sums are j * ceil(Ho * Wo / 256) and a block finds its job by one division.  A job
+// without a stage is copied through that stage; a launch no job needs is not made.  Buffers: warp src -> out; blur-x (src or out) ->
+// scratch; blur-y scratch -> out.  The source is only ever read.
+struct ZsgAugWarpJob {
+    int64_t src, out;                      // absolute device addresses: the image [Ho][Wo][3] to warp / blur, the result [Ho][Wo][3]
+    int32_t m[6];                          // a, b, c0, d, e, c1: source position of output pixel (x, y) in 16.16, SU = a x + b y + c0, SV = d x + e y + c1
+    uint32_t fill;                         // r | g << 8 | b << 16: the colour of a tap outside the image
+    int32_t flags;                         // bit 0: warp, bit 1: blur
+    int32_t radius;                        // blur radius r, 0..8: taps[0 .. 2r] weigh pixels i - r .. i + r (clamped to the image)
+    int32_t taps[17];
+    int32_t pad[2];
+};
+static_assert(sizeof(ZsgAugWarpJob) == 128, "ZsgAugWarpJob is packed by dat_loader.GpuResizer");
+
+#define AUG_WARP_MAX_R 8
+
+// the buffer a launch reads or writes: 0 = the job's source, 1 = the job's result, 2 = the job's slice of the scratch batch
+__device__ __forceinline__ uint8_t* aug_warp_buf(const ZsgAugWarpJob* jp, int sel, int j, uint8_t* tmp, int64_t tmp_stride) {
+    return sel == 0 ? (uint8_t*)jp->src : (sel == 1 ? (uint8_t*)jp->out : tmp + (int64_t)j * tmp_stride);
+}
+
+// STAGE 0: warp, 1: blur along x, 2: blur along y
+template <int STAGE>
+__global__ __launch_bounds__(AUG_PIX) void aug_warp_stage_kernel(const ZsgAugWarpJob* __restrict__ jobs, int Ho, int Wo, int bpj, int in_sel, int out_sel,
+                                                                 uint8_t* tmp, int64_t tmp_stride) {
+    __shared__ uint32_t stage[AUG_PIX * 3 / 4];
+    const int j = (int)blockIdx.x / bpj, lb = (int)blockIdx.x - j * bpj;
+    const ZsgAugWarpJob* jp = jobs + j;
+    const uint8_t* in = aug_warp_buf(jp, in_sel, j, tmp, tmp_stride);
+    uint8_t* out = aug_warp_buf(jp, out_sel, j, tmp, tmp_stride);
+    const int total = Ho * Wo;
+    const int nb = min(AUG_PIX, total - lb * AUG_PIX) * 3;
+    const int64_t boff = (int64_t)lb * AUG_PIX * 3;
+    if (!(jp->flags & (STAGE == 0 ? 1 : 2))) {       // (block-uniform) the job has no such stage: its bytes pass through
+        aug_load_block(in + boff, stage, nb);
+        __syncthreads();
+        aug_store_block(out + boff, stage, nb);
+        return;
+    }
+    const int i = lb * AUG_PIX + (int)threadIdx.x;
+    if (i < total) {
+        const int x = i % Wo, y = i / Wo;
+        int v0, v1, v2;
+        if (STAGE == 0) {
+            const int64_t SU = (int64_t)jp->m[0] * x + (int64_t)jp->m[1] * y + jp->m[2];      // 64 bits: exact for any int32 coefficients
+            const int64_t SV = (int64_t)jp->m[3] * x + (int64_t)jp->m[4] * y + jp->m[5];
+            const int fx = (int)((SU >> 8) & 255), fy = (int)((SV >> 8) & 255);
+            // [-2, side]: far outside stays outside for both taps of the axis, and the indices fit 32 bits
+            const int ix = (int)max(min(SU >> 16, (int64_t)Wo), (int64_t)-2), iy = (int)max(min(SV >> 16, (int64_t)Ho), (int64_t)-2);
+            const uint32_t fill = jp->fill;
+            int p[4][3];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int xx = ix + (t & 1), yy = iy + (t >> 1);
+                p[t][0] = (int)(fill & 255u);
+                p[t][1] = (int)((fill >> 8) & 255u);
+                p[t][2] = (int)((fill >> 16) & 255u);
+                if (xx >= 0 && xx < Wo && yy >= 0 && yy < Ho) {                             // the only reads of the image: inside it
+                    const uint8_t* q = in + ((int64_t)yy * Wo + xx) * 3;
+                    p[t][0] = q[0];
+                    p[t][1] = q[1];
+                    p[t][2] = q[2];
+                }
+            }
+            const int gx = 256 - fx, gy = 256 - fy;
+            v0 = ((p[0][0] * gx + p[1][0] * fx) * gy + (p[2][0] * gx + p[3][0] * fx) * fy + 32768) >> 16;
+            v1 = ((p[0][1] * gx + p[1][1] * fx) * gy + (p[2][1] * gx + p[3][1] * fx) * fy + 32768) >> 16;
+            v2 = ((p[0][2] * gx + p[1][2] * fx) * gy + (p[2][2] * gx + p[3][2] * fx) * fy + 32768) >> 16;
+        } else {
+            const int r = min(max(jp->radius, 0), AUG_WARP_MAX_R);
+            const int n = STAGE == 1 ? Wo : Ho, c = STAGE == 1 ? x : y;
+            int a0 = 32768, a1 = 32768, a2 = 32768;
+            for (int k = -r; k <= r; ++k) {
+                const int t = jp->taps[k + r];
+                const int cc = min(max(c + k, 0), n - 1);
+                const uint8_t* q = in + (STAGE == 1 ? (int64_t)y * Wo + cc : (int64_t)cc * Wo + x) * 3;
+                a0 += t * (int)q[0];
+                a1 += t * (int)q[1];
+                a2 += t * (int)q[2];
+            }
+            v0 = a0 >> 16;
+            v1 = a1 >> 16;
+            v2 = a2 >> 16;
+        }
+        uint8_t* s = (uint8_t*)stage + 3 * (int)threadIdx.x;
+        s[0] = (uint8_t)v0;
+        s[1] = (uint8_t)v1;
+        s[2] = (uint8_t)v2;
+    }
+    __syncthreads();
+    aug_store_block(out + boff, stage, nb);
+}
+
+// stages: bit 0 = some job warps, bit 1 = some job blurs (the launches made).  tmp: scratch of njobs slices of Ho * Wo * 3 bytes rounded
+// up to a multiple of 4, needed only with bit 1.  jobs_host (optional): the table as the caller packed it — every record is checked
+// before anything is launched: addresses present, flags within `stages`, a blur's radius in 0..8 with taps >= 0 that sum to 65536, fill
+// below 2^24, and the sources, the results and the scratch lying in three disjoint address ranges (no stage may write what another
+// block of its launch reads).  The map's sums are taken in 64 bits, so every int32 coefficient is valid.
+extern "C" int zsg_augment_warp_u8_batched(const void* jobs_dev, const void* jobs_host, int32_t njobs, int32_t Ho, int32_t Wo, void* tmp,
+                                           int32_t stages, void* stream) {
+    ZSG_REQUIRE(jobs_dev && (((uintptr_t)jobs_dev) & 7) == 0, "augment_warp_u8_batched: the job table is null or not 8-byte aligned");
+    ZSG_REQUIRE(njobs > 0 && Ho > 0 && Wo > 0 && Ho <= AUG_MAX_SIDE && Wo <= AUG_MAX_SIDE, "augment_warp_u8_batched: %d jobs of %d x %d (sides 1..%d)",
+                njobs, Ho, Wo, AUG_MAX_SIDE);
+    ZSG_REQUIRE(stages >= 1 && stages <= 3, "augment_warp_u8_batched: stages = %d (bit 0 warp, bit 1 blur; at least one)", stages);
+    ZSG_REQUIRE(!(stages & 2) || (tmp && (((uintptr_t)tmp) & 3) == 0), "augment_warp_u8_batched: a blur needs 4-byte aligned scratch");
+    const int64_t per = (int64_t)Ho * Wo * 3, tmp_stride = (per + 3) / 4 * 4;
+    const int64_t bpj = ((int64_t)Ho * Wo + AUG_PIX - 1) / AUG_PIX;
+    ZSG_REQUIRE(bpj * njobs <= 0x7fffffffLL, "augment_warp_u8_batched: %d jobs of %d x %d need too many blocks", njobs, Ho, Wo);
+    if (jobs_host) {
+        ZSG_REQUIRE((((uintptr_t)jobs_host) & 7) == 0, "augment_warp_u8_batched: the host table is not 8-byte aligned");
+        const ZsgAugWarpJob* h = (const ZsgAugWarpJob*)jobs_host;
+        int64_t s_lo = INT64_MAX, s_hi = INT64_MIN, o_lo = INT64_MAX, o_hi = INT64_MIN;
+        for (int32_t i = 0; i < njobs; ++i) {
+            const ZsgAugWarpJob& q = h[i];
+            ZSG_REQUIRE(q.src && q.out, "augment_warp_u8_batched: job %d: null address", i);
+            ZSG_REQUIRE(q.flags >= 0 && (q.flags & ~stages) == 0, "augment_warp_u8_batched: job %d: flags %d outside stages %d", i, q.flags, stages);
+            ZSG_REQUIRE(q.fill < (1u << 24), "augment_warp_u8_batched: job %d: fill", i);
+            if (q.flags & 2) {
+                ZSG_REQUIRE(q.radius >= 0 && q.radius <= AUG_WARP_MAX_R, "augment_warp_u8_batched: job %d: radius %d (0..%d)", i, q.radius, AUG_WARP_MAX_R);
+                int64_t sum = 0;
+                for (int k = 0; k <= 2 * q.radius; ++k) {
+                    ZSG_REQUIRE(q.taps[k] >= 0, "augment_warp_u8_batched: job %d: tap %d is negative", i, k);
+                    sum += q.taps[k];
+                }
+                ZSG_REQUIRE(sum == 65536, "augment_warp_u8_batched: job %d: the taps sum to %lld, not 65536", i, (long long)sum);
+            }
+            s_lo = q.src < s_lo ? q.src : s_lo;
+            s_hi = q.src + per > s_hi ? q.src + per : s_hi;
+            o_lo = q.out < o_lo ? q.out : o_lo;
+            o_hi = q.out + per > o_hi ? q.out + per : o_hi;
+        }
+        ZSG_REQUIRE(s_hi <= o_lo || o_hi <= s_lo, "augment_warp_u8_batched: the results overlap the sources");
+        if (stages & 2) {
+            const int64_t t_lo = (int64_t)(uintptr_t)tmp, t_hi = t_lo + tmp_stride * njobs;
+            ZSG_REQUIRE((t_hi <= o_lo || o_hi <= t_lo) && (t_hi <= s_lo || s_hi <= t_lo), "augment_warp_u8_batched: the scratch overlaps the sources or the results");
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    ZSG_PROF("augment_warp_u8", st, 0, 0);
+    const ZsgAugWarpJob* jobs = (const ZsgAugWarpJob*)jobs_dev;
+    const dim3 grid((unsigned)(bpj * njobs));
+    if (stages & 1) ZSG_LAUNCH(aug_warp_stage_kernel<0>, grid, dim3(AUG_PIX), 0, st, jobs, Ho, Wo, (int)bpj, 0, 1, (uint8_t*)tmp, tmp_stride);
+    if (stages & 2) {
+        ZSG_LAUNCH(aug_warp_stage_kernel<1>, grid, dim3(AUG_PIX), 0, st, jobs, Ho, Wo, (int)bpj, (stages & 1) ? 1 : 0, 2, (uint8_t*)tmp, tmp_stride);
+        ZSG_LAUNCH(aug_warp_stage_kernel<2>, grid, dim3(AUG_PIX), 0, st, jobs, Ho, Wo, (int)bpj, 2, 1, (uint8_t*)tmp, tmp_stride);
+    }
+    ZSG_CHECK_LAUNCH("augment_warp_u8_batched");
+    return 0;
+}

@@ -199,9 +199,34 @@ def _check_fill(fill, name: str) -> Tuple[int, int, int]:
     return tuple(int(v) for v in vals)
 
 
+AUG_WARP_KEYS = {"aug_rotate": 0.0, "aug_shear": 0.0, "aug_warp_keep": 0.8, "aug_blur": 0.0, "aug_blur_p": 0.5}      # the defaults: off
+
+
+def aug_warp_params(cfg) -> Tuple[float, float, float, float, float]:
+    """aug_rotate, aug_shear, aug_warp_keep, aug_blur, aug_blur_p of cfg (a cfg without them = the defaults), validated: ValueError
+    outside their ranges"""
+    rot, shear, keep, blur, blur_p = (float(cfg[k]) if k in cfg else d for k, d in AUG_WARP_KEYS.items())
+    if not (0.0 <= rot <= 30.0):
+        raise ValueError(f"aug_rotate = {rot}: degrees, must lie in [0, 30]")
+    if not (0.0 <= shear <= 20.0):
+        raise ValueError(f"aug_shear = {shear}: degrees, must lie in [0, 20]")
+    if not (0.0 < keep <= 1.0):
+        raise ValueError(f"aug_warp_keep = {keep}: must lie in (0, 1]")
+    if not (blur == 0.0 or BLUR_SIGMA_MIN <= blur <= 2.5):
+        raise ValueError(f"aug_blur = {blur}: 0 (off), or a sigma in [{BLUR_SIGMA_MIN}, 2.5] output pixels")
+    if not (0.0 <= blur_p <= 1.0):
+        raise ValueError(f"aug_blur_p = {blur_p}: a probability, must lie in [0, 1]")
+    return rot, shear, keep, blur, blur_p
+
+
+def aug_warp_enabled(cfg) -> bool:
+    rot, shear, _, blur, _ = aug_warp_params(cfg)
+    return rot > 0.0 or shear > 0.0 or blur > 0.0
+
+
 def aug_enabled(cfg) -> bool:
     pflip, emax, _ = aug_geom_params(cfg)
-    return aug_params(cfg) != tuple(AUG_KEYS.values()) or pflip > 0.0 or emax > 1.0
+    return aug_params(cfg) != tuple(AUG_KEYS.values()) or pflip > 0.0 or emax > 1.0 or aug_warp_enabled(cfg)
 
 
 def _draw_window(rng, h: int, w: int, boxes, cmin: float):
@@ -252,6 +277,11 @@ def draw_augment_geom(rng, h: int, w: int, boxes, cfg):
     pflip, emax, _ = aug_geom_params(cfg)
     if (cmin, vb, vc, vs) == tuple(AUG_KEYS.values()) and pflip <= 0.0 and emax <= 1.0:
         return None
+    return _draw_geom(rng, h, w, boxes, cmin, vb, vc, vs, pflip, emax)
+
+
+def _draw_geom(rng, h: int, w: int, boxes, cmin, vb, vc, vs, pflip, emax):
+    """steps 1-4 of draw_augment_geom, whatever is on"""
     h, w = int(h), int(w)
     W, H, ox, oy = w, h, 0, 0
     if emax > 1.0:
@@ -266,6 +296,141 @@ def draw_augment_geom(rng, h: int, w: int, boxes, cfg):
     jitter = _draw_factors(rng, vb, vc, vs)
     flip = bool(rng.uniform() < pflip) if pflip > 0.0 else False
     return (x0 - ox, y0 - oy, x1 - ox, y1 - oy), jitter, flip
+
+
+# ---- affine warp (rotation + shear about the centre of the OUTPUT) and Gaussian blur: steps 6 and 7 of augment_host ------------------
+WARP_IDENTITY = (65536, 0, 0, 0, 65536, 0)
+BLUR_SIGMA_MIN = 0.1
+BLUR_MAX_RADIUS = 8
+
+
+def _q16(v: float) -> int:
+    return int(math.floor(v * 65536.0 + 0.5))
+
+
+def _warp_forward(theta: float, shear: float):
+    """M = R(theta) S(shear), degrees: R = [[cos, -sin], [sin, cos]] (x right, y down: a positive theta turns the picture clockwise on
+    screen), S = [[1, tan], [0, 1]]; det M = 1"""
+    t, s = math.radians(theta), math.radians(shear)
+    c, sn, tn = math.cos(t), math.sin(t), math.tan(s)
+    return (c, c * tn - sn), (sn, sn * tn + c)
+
+
+def warp_matrix(theta: float, shear: float, out_hw) -> Tuple[int, int, int, int, int, int]:
+    """The six 16.16 integers (a, b, c0, d, e, c1) of the warp p' = c + M (p - c), c = (Wo / 2, Ho / 2), M = R(theta) S(shear): output
+    pixel (x, y) samples the source at SU = a x + b y + c0, SV = d x + e y + c1 — the inverse map through pixel centres,
+    u = Mi (x + 0.5 - cx) + cx - 0.5 — computed in float64 and rounded with q(v) = floor(v 65536 + 0.5)."""
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    (m00, m01), (m10, m11) = _warp_forward(theta, shear)
+    i00, i01, i10, i11 = m11, -m01, -m10, m00                                            # M^-1 (det M = 1)
+    cx, cy = Wo / 2.0, Ho / 2.0
+    c0 = cx - 0.5 + i00 * (0.5 - cx) + i01 * (0.5 - cy)
+    c1 = cy - 0.5 + i10 * (0.5 - cx) + i11 * (0.5 - cy)
+    return _q16(i00), _q16(i01), _q16(c0), _q16(i10), _q16(i11), _q16(c1)
+
+
+def warp_box(box, theta: float, shear: float, out_hw, win_hw, keep: Optional[float] = None):
+    """The box of a warped image.  box = (x1, y1, x2, y2) in WINDOW pixels (as query_item has it after crop and flip), win_hw = the window's
+    (height, width): scaled to output pixels, its four corners mapped forward with M, their bounding box clipped to [0, Wo] x [0, Ho] and
+    scaled back to window pixels.  keep: the draw is refused — None is returned — when the clipped bounding box has less than `keep`
+    of the unclipped one's area (keep = None: never refused)."""
+    Ho, Wo = float(out_hw[0]), float(out_hw[1])
+    ch, cw = float(win_hw[0]), float(win_hw[1])
+    sx, sy = Wo / cw, Ho / ch
+    (m00, m01), (m10, m11) = _warp_forward(theta, shear)
+    cx, cy = Wo / 2.0, Ho / 2.0
+    pts = [(float(box[i]) * sx - cx, float(box[j]) * sy - cy) for i in (0, 2) for j in (1, 3)]
+    xs, ys = [cx + m00 * x + m01 * y for x, y in pts], [cy + m10 * x + m11 * y for x, y in pts]
+    x1, y1, x2, y2 = min(xs), min(ys), max(xs), max(ys)
+    kx1, ky1 = min(max(x1, 0.0), Wo), min(max(y1, 0.0), Ho)
+    kx2, ky2 = max(min(x2, Wo), kx1), max(min(y2, Ho), ky1)
+    if keep is not None and (kx2 - kx1) * (ky2 - ky1) < keep * ((x2 - x1) * (y2 - y1)):
+        return None
+    return kx1 / sx, ky1 / sy, kx2 / sx, ky2 / sy
+
+
+def settle_warp(theta: float, shear: float, boxes, out_hw, win_hw, keep: float):
+    """The box rule: (theta, shear) is accepted when warp_box keeps every box; else both are halved and tested again, at most four
+    halvings; then the warp is dropped (None).  No random numbers."""
+    for _ in range(5):
+        if all(warp_box(b, theta, shear, out_hw, win_hw, keep) is not None for b in boxes):
+            return theta, shear
+        theta, shear = theta / 2.0, shear / 2.0
+    return None
+
+
+def blur_taps(sigma: float):
+    """(r, taps) of the separable Gaussian blur: r = min(8, ceil(3 sigma)), taps = int64 [2 r + 1], the float64 weights exp(-k^2 / 2 sigma^2)
+    normalised over k = -r .. r, rounded to 16 bits (floor(w 65536 + 0.5)), the centre tap adjusted so that they sum to exactly 65536"""
+    sigma = float(sigma)
+    if not (0.0 < sigma < math.inf):
+        raise ValueError(f"blur_taps: sigma = {sigma} must be positive")
+    r = min(BLUR_MAX_RADIUS, int(math.ceil(3.0 * sigma)))
+    w = np.exp(-(np.arange(-r, r + 1, dtype=np.float64) ** 2) / (2.0 * sigma * sigma))
+    w /= w.sum()
+    t = np.floor(w * 65536.0 + 0.5).astype(np.int64)
+    t[r] += 65536 - int(t.sum())
+    return r, t
+
+
+def warp_host(img: np.ndarray, m, fill) -> np.ndarray:
+    """step 6 of augment_host: uint8 [Ho, Wo, 3] warped by the six 16.16 integers m (warp_matrix), taps outside the image = fill"""
+    Ho, Wo = img.shape[:2]
+    a, b, c0, d, e, c1 = (np.int64(int(v)) for v in m)
+    y, x = np.mgrid[0:Ho, 0:Wo].astype(np.int64)
+    SU, SV = a * x + b * y + c0, d * x + e * y + c1
+    ix, iy = SU >> 16, SV >> 16
+    fx, fy = ((SU >> 8) & 255)[..., None], ((SV >> 8) & 255)[..., None]
+    fillv = np.array(_check_fill(fill, "warp_host: fill"), np.int64)
+
+    def tap(yy, xx):
+        ok = (xx >= 0) & (xx < Wo) & (yy >= 0) & (yy < Ho)
+        return np.where(ok[..., None], img[np.clip(yy, 0, Ho - 1), np.clip(xx, 0, Wo - 1)].astype(np.int64), fillv)
+    p00, p01, p10, p11 = tap(iy, ix), tap(iy, ix + 1), tap(iy + 1, ix), tap(iy + 1, ix + 1)
+    return (((p00 * (256 - fx) + p01 * fx) * (256 - fy) + (p10 * (256 - fx) + p11 * fx) * fy + 32768) >> 16).astype(np.uint8)
+
+
+def blur_host(img: np.ndarray, sigma: float) -> np.ndarray:
+    """step 7 of augment_host: blur_taps(sigma) along x, then along y, the index clamped to the image"""
+    r, t = blur_taps(sigma)
+    out = img
+    for axis in (1, 0):
+        n = out.shape[axis]
+        acc = np.full(out.shape, 32768, np.int64)
+        for k in range(-r, r + 1):
+            acc += t[k + r] * np.take(out, np.clip(np.arange(n) + k, 0, n - 1), axis=axis).astype(np.int64)
+        out = (acc >> 16).astype(np.uint8)
+    return out
+
+
+def draw_augment_warp(rng, h: int, w: int, boxes, cfg, out_hw):
+    """draw_augment_geom with the warp and the blur: None when every aug_* key is off, else (crop, jitter, flip, warp, sigma) — warp =
+    the settled (theta, shear) in degrees or None (keys off, or the draw dropped by the box rule), sigma = the blur's or None.  Draw
+    order: draw_augment_geom's steps 1-4, then
+      5. aug_rotate > 0: theta = uniform(-aug_rotate, aug_rotate);  6. aug_shear > 0: shear = uniform(-aug_shear, aug_shear);
+      7. aug_blur > 0: u = uniform(), sigma = uniform(0.1, aug_blur) rounded to float32 — both always drawn; the blur is applied when
+         u < aug_blur_p.
+    A part that is off draws nothing: with the new keys off this consumes exactly draw_augment_geom's random numbers.  The box rule
+    (settle_warp over all `boxes`, taken to window pixels and mirrored as query_item does) costs no random numbers."""
+    cmin, vb, vc, vs = aug_params(cfg)
+    pflip, emax, _ = aug_geom_params(cfg)
+    rot, shear, keep, blur, blur_p = aug_warp_params(cfg)
+    if (cmin, vb, vc, vs) == tuple(AUG_KEYS.values()) and pflip <= 0.0 and emax <= 1.0 and not (rot > 0.0 or shear > 0.0 or blur > 0.0):
+        return None
+    crop, jitter, flip = _draw_geom(rng, h, w, boxes, cmin, vb, vc, vs, pflip, emax)
+    warp = sigma = None
+    if rot > 0.0 or shear > 0.0:
+        theta = float(rng.uniform(-rot, rot)) if rot > 0.0 else 0.0
+        phi = float(rng.uniform(-shear, shear)) if shear > 0.0 else 0.0
+        x0, y0, x1, y1 = crop
+        b = np.asarray(boxes, dtype=np.float64).reshape(-1, 4) - np.array([x0, y0, x0, y0], np.float64)
+        if flip:
+            b[:, [0, 2]] = (x1 - x0) - b[:, [2, 0]]
+        warp = settle_warp(theta, phi, b.tolist(), out_hw, (y1 - y0, x1 - x0), keep)
+    if blur > 0.0:
+        u, s = rng.uniform(), rng.uniform(BLUR_SIGMA_MIN, blur)
+        sigma = float(np.float32(s)) if u < blur_p else None          # (float32: what the item's aug_blur field carries to the GPU path)
+    return crop, jitter, flip, warp, sigma
 
 
 _LR_WORDS = {"left": "right", "leftmost": "rightmost", "lefthand": "righthand"}
@@ -308,7 +473,7 @@ def _blend_host(x: np.ndarray, m, f: np.float32) -> np.ndarray:
     return np.trunc(np.clip(f * x + (np.float32(1.0) - f) * m, np.float32(0.0), np.float32(255.0)))
 
 
-def augment_host(img_u8_hwc: np.ndarray, crop, jitter, out_hw, flip: bool = False, fill=None) -> np.ndarray:
+def augment_host(img_u8_hwc: np.ndarray, crop, jitter, out_hw, flip: bool = False, fill=None, warp=None, blur: float = 0.0) -> np.ndarray:
     """THE definition of the training augmentation: uint8 [h, w, 3] -> uint8 [Ho, Wo, 3].
     1. Pillow's `img.crop(crop).resize((Wo, Ho))`: the tap tables of the crop's side lengths applied to the window (taps stop at the
        window's edge, not the image's).  fill = (r, g, b): the window may reach outside the image on any side (x0 < x1, y0 < y1, any
@@ -320,7 +485,13 @@ def augment_host(img_u8_hwc: np.ndarray, crop, jitter, out_hw, flip: bool = Fals
     with blend(x, m, f) = trunc(clamp(f * x + (1 - f) * m, 0, 255)) and gray = trunc((0.2989 r + 0.587 g) + 0.114 b), all in fp32 with
     every product and sum rounded separately.  A factor of exactly 1 is the identity.
     5. flip: the result mirrored left-right, out[:, ::-1] — last (steps 2 and 4 are per pixel and the mean of step 3 is an exact
-       integer sum, so any earlier place gives the same bytes)."""
+       integer sum, so any earlier place gives the same bytes).
+    6. warp = six 16.16 integers (warp_matrix; None or WARP_IDENTITY: nothing happens): the affine warp about the image centre, all in
+       integers — for output pixel (x, y): SU = a x + b y + c0, SV = d x + e y + c1 (exact), ix = SU >> 16, fx = (SU >> 8) & 255,
+       likewise iy, fy; the taps (iy, ix), (iy, ix + 1), (iy + 1, ix), (iy + 1, ix + 1) of the step-5 image, `fill` where a tap lies
+       outside it (a warp needs fill); v = ((p00 (256 - fx) + p01 fx)(256 - fy) + (p10 (256 - fx) + p11 fx) fy + 32768) >> 16.
+    7. blur = sigma in output pixels (0: nothing happens): blur_taps(sigma) along x, then along y, each pass
+       (sum_k t_k p[clamp(i + k, 0, n - 1)] + 32768) >> 16."""
     Ho, Wo = int(out_hw[0]), int(out_hw[1])
     a = np.asarray(img_u8_hwc)
     assert a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3, "augment_host: uint8 [h, w, 3]"
@@ -345,7 +516,14 @@ def augment_host(img_u8_hwc: np.ndarray, crop, jitter, out_hw, flip: bool = Fals
     p = _blend_host(p, mean, fc)
     p = _blend_host(p, _gray_host(p)[..., None], fs)
     out = p.astype(np.uint8)
-    return np.ascontiguousarray(out[:, ::-1]) if flip else out
+    out = np.ascontiguousarray(out[:, ::-1]) if flip else out
+    if warp is not None and tuple(int(v) for v in warp) != WARP_IDENTITY:
+        if fill is None:
+            raise ValueError("augment_host: a warp needs fill, the colour of the taps outside the image")
+        out = warp_host(out, warp, fill)
+    if blur:
+        out = blur_host(out, blur)
+    return out
 
 
 class GpuResizer:
@@ -361,6 +539,8 @@ class GpuResizer:
         self._gray = None
         self._jobs_host = None
         self.launches = {"augment_u8": 0, "augment_geom_u8": 0}      # calls of zsg_augment_u8_batched / zsg_augment_geom_u8_batched
+        self._warp_src = self._warp_tmp = None         # scratch batches of the warp / blur launches: allocated by the first batch that has one
+        self.warp_calls = 0                            # calls of zsg_augment_warp_u8_batched
         import PIL
         if tuple(int(v) for v in PIL.__version__.split(".")[:2]) < (7, 0):      # (Pillow < 7 resizes with NEAREST by default: the two paths would differ)
             raise RuntimeError("GpuResizer reproduces PIL.Image.resize's default filter of Pillow >= 7 (bicubic); found Pillow " + PIL.__version__)
@@ -403,8 +583,76 @@ class GpuResizer:
             self._tab[key] = (dev[off:off + 2 * n].view(n, 2), dev[off + 2 * n:off + (2 + ks) * n].view(n, ks), ks)
             off += (2 + ks) * n
 
-    def resize_flat(self, flat: torch.Tensor, hw, out: Optional[torch.Tensor] = None, crop=None, jitter=None, flip=None, fill=None) -> torch.Tensor:
-        """flat: uint8 DEVICE tensor holding the raw images back to back; hw: [B, 2] (host) heights / widths.  Returns uint8 [B, Ho, Wo, 3].
+    def resize_flat(self, flat: torch.Tensor, hw, out: Optional[torch.Tensor] = None, crop=None, jitter=None, flip=None, fill=None,
+                    warp=None, blur=None) -> torch.Tensor:
+        """resize_geom's batch, then steps 6 and 7 of augment_host on the GPU (zsg_augment_warp_u8_batched): warp = [B, 6] host integers
+        (warp_matrix; a WARP_IDENTITY row = that job is not warped; a warped job needs `fill`), blur = [B] host sigmas (0 = that job is not
+        blurred).  With a job to warp or blur the batch is resized into a scratch batch and the new launches write `out`; a batch
+        without one makes no new launch and allocates nothing new (`self.warp_calls` counts the calls of the new entry)."""
+        B = len(hw)
+        jobs = self._warp_jobs(B, warp, blur, fill)
+        if jobs is None:
+            return self.resize_geom(flat, hw, out, crop, jitter, flip, fill)
+        if self._warp_src is None or self._warp_src.shape[0] < B:
+            self._warp_src = torch.empty(B, self.Ho, self.Wo, 3, dtype=torch.uint8, device=self.dev)
+        src = self.resize_geom(flat, hw, self._warp_src[:B], crop, jitter, flip, fill)
+        if out is None:
+            out = torch.empty(B, self.Ho, self.Wo, 3, dtype=torch.uint8, device=self.dev)
+        return self._run_warp(src, out, jobs)
+
+    def _warp_jobs(self, B, warp, blur, fill):
+        """None when no job has a warp or a blur; else per job (six integers or None, (r, taps) or None, fill)"""
+        if warp is None and blur is None:
+            return None
+        wr = [None] * B if warp is None else [tuple(int(v) for v in row) for row in (warp.tolist() if torch.is_tensor(warp) else warp)]
+        sg = [0.0] * B if blur is None else [float(v) for v in (blur.tolist() if torch.is_tensor(blur) else blur)]
+        if len(wr) != B or len(sg) != B or any(m is not None and len(m) != 6 for m in wr):
+            raise ValueError(f"resize_flat: {B} images, warp must be [{B}, 6] and blur [{B}]")
+        wr = [None if m is None or m == WARP_IDENTITY else m for m in wr]
+        if any(m is not None and not all(-(1 << 31) <= v < 1 << 31 for v in m) for m in wr):
+            raise ValueError("resize_flat: warp coefficients must fit 32 bits")
+        if any(not (s == 0.0 or 0.0 < s < math.inf) for s in sg):
+            raise ValueError("resize_flat: blur sigmas must be 0 (off) or positive and finite")
+        if not any(m is not None for m in wr) and not any(sg):
+            return None
+        fills = [(0, 0, 0)] * B
+        if any(m is not None for m in wr):
+            if fill is None:
+                raise ValueError("resize_flat: a warp needs fill, the colour of the taps outside the image")
+            f = np.asarray(fill.cpu() if torch.is_tensor(fill) else fill)
+            f = np.broadcast_to(f, (B, f.shape[0])) if f.ndim == 1 else f
+            if f.shape != (B, 3):
+                raise ValueError(f"resize_flat: fill must be (r, g, b) or [{B}, 3]")
+            fills = [_check_fill(row.tolist(), "resize_flat: fill") for row in f]
+        return [(m, blur_taps(s) if s else None, fl) for m, s, fl in zip(wr, sg, fills)]
+
+    def _run_warp(self, src, out, jobs):
+        """src -> out through zsg_augment_warp_u8_batched; the 128-byte job record of include/zsg.h, validated by the entry before it launches"""
+        import struct
+        from ._lib import check, lib, stream_ptr
+        B, per = len(jobs), self.Ho * self.Wo * 3
+        if tuple(out.shape) != (B, self.Ho, self.Wo, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError(f"resize_flat: out must be a contiguous uint8 [{B}, {self.Ho}, {self.Wo}, 3]")
+        stages = int(any(m is not None for m, _, _ in jobs)) | 2 * int(any(t is not None for _, t, _ in jobs))
+        tmp_ptr = 0
+        if stages & 2:
+            need = B * ((per + 3) // 4 * 4)
+            if self._warp_tmp is None or self._warp_tmp.numel() < need:
+                self._warp_tmp = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            tmp_ptr = self._warp_tmp.data_ptr()
+        blob = b""
+        for i, (m, bt, (r, g, b)) in enumerate(jobs):
+            rad, taps = (bt[0], [int(v) for v in bt[1]]) if bt is not None else (0, [])
+            blob += struct.pack("<qq6iIii17i2i", src.data_ptr() + i * per, out.data_ptr() + i * per, *(m if m is not None else WARP_IDENTITY),
+                                r | g << 8 | b << 16, int(m is not None) | 2 * int(bt is not None), rad, *(taps + [0] * (17 - len(taps))), 0, 0)
+        table = self._upload_jobs(blob, 128)
+        check(lib.zsg_augment_warp_u8_batched(table.data_ptr(), blob, B, self.Ho, self.Wo, tmp_ptr, stages, stream_ptr()), "zsg_augment_warp_u8_batched")
+        self.warp_calls += 1
+        return out
+
+    def resize_geom(self, flat: torch.Tensor, hw, out: Optional[torch.Tensor] = None, crop=None, jitter=None, flip=None, fill=None) -> torch.Tensor:
+        """Steps 1-5 of augment_host (resize_flat without warp and blur is exactly this call).
+        flat: uint8 DEVICE tensor holding the raw images back to back; hw: [B, 2] (host) heights / widths.  Returns uint8 [B, Ho, Wo, 3].
         crop ([B, 4] host integers x0, y0, x1, y1 inside each image) and / or jitter ([B, 3] host float32 brightness, contrast,
         saturation factors): the training augmentation augment_host defines, on the GPU (zsg_augment_u8_batched) — each image's
         window is resized instead of the whole image, then jittered; a missing one = the whole image / factors 1.
@@ -586,7 +834,8 @@ class ImgQuDataset(Dataset):
         self.embedder = embedder if embedder is not None else get_embedder(cfg)
         self.augment = split_type == "train" and aug_enabled(cfg)      # training split only: draw_augment_geom per item / per image slot
         pflip, emax, fill = aug_geom_params(cfg)
-        self.aug_fill = fill if self.augment and (pflip > 0.0 or emax > 1.0) else None      # a new key is on: flips / windows that leave the image
+        self.aug_warp = self.augment and aug_warp_enabled(cfg)         # aug_rotate / aug_shear / aug_blur on: the items carry aug_warp and aug_blur
+        self.aug_fill = fill if self.augment and (pflip > 0.0 or emax > 1.0 or self.aug_warp) else None      # flips / windows that leave the image / warps
         tta = cfg["eval_tta"] if "eval_tta" in cfg else "none"
         if tta not in ("none", "flip"):
             raise ValueError(f"eval_tta={tta!r}: expected one of none, flip")
@@ -605,17 +854,18 @@ class ImgQuDataset(Dataset):
 
     def load_image(self, idx: int, boxes=None):
         """the image of row idx as the batch carries it (decoded, resized unless gpu_resize) + its decoded height / width.
-        boxes (a training dataset with augmentation on): the pixel boxes the crop must keep — one draw_augment_geom from np.random; a
+        boxes (a training dataset with augmentation on): the pixel boxes the crop must keep — one draw_augment_warp from np.random; a
         worker that resizes applies it (augment_host), with gpu_resize the raw image travels and DevicePrefetcher applies it on the GPU.
-        Returns a fourth value then: the (crop, jitter, flip) drawn."""
+        Returns a fourth value then: the (crop, jitter, flip, warp, sigma) drawn."""
         import PIL.Image
         img = PIL.Image.open(self.img_dir / self.files[idx]).convert("RGB")
         h, w = img.height, img.width
         rs = self.cfg["resize_img"]
-        aug = draw_augment_geom(np.random, h, w, boxes, self.cfg) if boxes is not None else None
+        aug = draw_augment_warp(np.random, h, w, boxes, self.cfg, (rs[1], rs[0])) if boxes is not None else None
         if not self.gpu_resize:
             if aug is not None:
-                img = augment_host(np.asarray(img), aug[0], aug[1], (rs[1], rs[0]), flip=aug[2], fill=self.aug_fill)
+                img = augment_host(np.asarray(img), aug[0], aug[1], (rs[1], rs[0]), flip=aug[2], fill=self.aug_fill,
+                                   warp=warp_matrix(*aug[3], (rs[1], rs[0])) if aug[3] is not None else None, blur=aug[4] or 0.0)
             else:
                 img = img.resize((rs[0], rs[1]))                  # PIL's default filter, as the reference (dat_loader.py:121)
         a = np.asarray(img)                                       # [H, W, 3] uint8
@@ -625,12 +875,14 @@ class ImgQuDataset(Dataset):
             img_t = torch.from_numpy(a.transpose(2, 0, 1).astype(np.float64)).float().div_(255)     # pil2tensor(...).float().div_(255)
         return (img_t, h, w) if boxes is None else (img_t, h, w, aug)
 
-    def query_item(self, idx: int, h: int, w: int, crop=None, flip: bool = False) -> Dict[str, torch.Tensor]:
+    def query_item(self, idx: int, h: int, w: int, crop=None, flip: bool = False, warp=None) -> Dict[str, torch.Tensor]:
         """the per-query fields of row idx (everything but the image, whose decoded size h, w scales the box).  crop (x0, y0, x1, y1):
         the image was cropped to that window (which may leave the image: zoom-out) — the box is given relative to it (unclipped) and
         img_size is the window's, so the identities between annot, orig_annot and img_size the evaluator relies on keep holding.
         flip: the window was mirrored left-right — so is the box, in window pixels (x1' = cw - x2, x2' = cw - x1), and the query's
-        direction words are swapped (swap_left_right) before it is embedded."""
+        direction words are swapped (swap_left_right) before it is embedded.
+        warp (theta, shear): the resized window was warped (augment_host step 6) — the box becomes warp_box's: the bounding box of its
+        warped corners, clipped to the window, in window pixels; img_size stays the window's."""
         q = self.queries[idx]
         if isinstance(q, list):
             q = str(np.random.choice(q))                          # dat_loader.py:153-154
@@ -651,6 +903,9 @@ class ImgQuDataset(Dataset):
             x1, y1, x2, y2 = x1 - x0, y1 - y0, x2 - x0, y2 - y0
         if flip:
             x1, x2 = w - x2, w - x1
+        if warp is not None:
+            rs = self.cfg["resize_img"]
+            x1, y1, x2, y2 = warp_box((x1, y1, x2, y2), warp[0], warp[1], (rs[1], rs[0]), (h, w))
         target = 2 * np.array([y1 / h, x1 / w, y2 / h, x2 / w]) - 1          # y1x1y2x2 in [-1, 1] (anchors are row, column)
         return {"idxs": torch.tensor(idx).long(), "qvec": torch.from_numpy(qvec),
                 "qlens": torch.tensor(min(qlen, self.phrase_len)), "annot": torch.from_numpy(target).float(),
@@ -658,18 +913,26 @@ class ImgQuDataset(Dataset):
 
     def __getitem__(self, idx: int) -> Dict[str, torch.Tensor]:
         if self.augment:
-            img_t, h, w, (crop, jitter, flip) = self.load_image(idx, [self.boxes[idx]])
+            img_t, h, w, (crop, jitter, flip, warp, sigma) = self.load_image(idx, [self.boxes[idx]])
             item = {"img": img_t}
-            item.update(self.query_item(idx, h, w, crop, flip))
+            item.update(self.query_item(idx, h, w, crop, flip, warp))
             if self.gpu_resize:                                   # applied by DevicePrefetcher (GpuResizer.resize_flat), dropped there
                 item["aug_crop"], item["aug_jitter"] = torch.tensor(crop, dtype=torch.int32), torch.from_numpy(jitter)
-                if self.aug_fill is not None:                     # only with aug_flip / aug_expand_max on: (flip, fill r, g, b)
+                if self.aug_fill is not None:                     # only with aug_flip / aug_expand_max / a warp key on: (flip, fill r, g, b)
                     item["aug_geom"] = torch.tensor([int(flip), *self.aug_fill], dtype=torch.int32)
+                if self.aug_warp:                                 # only with aug_rotate / aug_shear / aug_blur on
+                    item["aug_warp"], item["aug_blur"] = self._warp_fields(warp, sigma)
             return item
         img_t, h, w = self.load_image(idx)
         item = {"img": img_t}
         item.update(self.query_item(idx, h, w))
         return item
+
+    def _warp_fields(self, warp, sigma):
+        """(aug_warp int32 [6], aug_blur float32 scalar) of one drawn (theta, shear) / sigma: the identity and 0 where none applies"""
+        rs = self.cfg["resize_img"]
+        m = warp_matrix(warp[0], warp[1], (rs[1], rs[0])) if warp is not None else WARP_IDENTITY
+        return torch.tensor(m, dtype=torch.int32), torch.tensor(sigma or 0.0, dtype=torch.float32)
 
     def grouped_batch(self, rows: List[int]) -> Dict[str, torch.Tensor]:
         """One batch of the grouped validation loader (cfg group_val_by_image): every distinct image file among `rows` is decoded (and
@@ -692,24 +955,26 @@ class ImgQuDataset(Dataset):
         """One batch of the grouped TRAINING loader (cfg group_trn_by_image): one image slot per chunk — the rows of a chunk share an image
         file, which is decoded (and resized) once, from the chunk's first row — even if two chunks of one file meet in a batch; the
         queries in chunk order.  Exactly len(chunks) slots, every one used (checked by the collater)."""
-        imgs, items, idx, crops, jitters, geoms = [], [], [], [], [], []
+        imgs, items, idx, crops, jitters, geoms, warps = [], [], [], [], [], [], []
         for s, rows in enumerate(chunks):
             if len({self.files[r] for r in rows}) != 1:
                 raise ValueError(f"grouped_train_batch: chunk {s} mixes image files")
-            crop, flip = None, False
+            crop, flip, warp = None, False, None
             if self.augment:                                      # ONE draw per image slot, from the union of the chunk's boxes
-                img_t, h, w, (crop, jitter, flip) = self.load_image(rows[0], [self.boxes[r] for r in rows])
+                img_t, h, w, (crop, jitter, flip, warp, sigma) = self.load_image(rows[0], [self.boxes[r] for r in rows])
                 crops.append(crop)
                 jitters.append(jitter)
                 if self.aug_fill is not None:
                     geoms.append([int(flip), *self.aug_fill])
+                if self.aug_warp:
+                    warps.append(self._warp_fields(warp, sigma))
             else:
                 img_t, h, w = self.load_image(rows[0])
             imgs.append(img_t)
             for r in rows:                                        # every query of the slot: the slot's window, mirrored and swapped alike
-                items.append(self.query_item(r, h, w, crop, flip))
+                items.append(self.query_item(r, h, w, crop, flip, warp))
                 idx.append(s)
-        aug = ((crops, jitters, geoms) if geoms else (crops, jitters)) if self.augment and self.gpu_resize else None
+        aug = ((crops, jitters, geoms, warps) if warps else (crops, jitters, geoms) if geoms else (crops, jitters)) if self.augment and self.gpu_resize else None
         return grouped_collater(items, imgs, idx, all_slots_used=True, aug=aug)
 
 
@@ -725,7 +990,7 @@ def collater(batch: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
             out["img"], out["img_hw"] = flatten_raw([b[k] for b in batch])
             continue
         t = torch.stack([b[k] for b in batch])
-        out[k] = t if ((k == "img" and t.dtype == torch.uint8) or k in ("aug_crop", "aug_geom")) else t.float()       # (aug_crop, aug_geom: int32)
+        out[k] = t if ((k == "img" and t.dtype == torch.uint8) or k in ("aug_crop", "aug_geom", "aug_warp")) else t.float()       # (aug_crop, aug_geom, aug_warp: int32)
     out["qvec"] = out["qvec"][:, :max_qlen]
     if "qvec_flip" in out:
         out["qvec_flip"] = out["qvec_flip"][:, :max_qlen]
@@ -741,7 +1006,8 @@ def grouped_collater(items: List[Dict[str, torch.Tensor]], imgs: List[torch.Tens
     all_slots_used (training batches): every image slot must be named by some query — train-mode BatchNorm reduces over all slots.
     aug = (crops, jitters), one per image SLOT (gpu_resize training with augmentation): emitted as `aug_crop` int32 [slots, 4] and
     `aug_jitter` float32 [slots, 3] alongside `img`; a third member (aug_flip / aug_expand_max on) = (flip, fill r, g, b) per slot,
-    emitted as `aug_geom` int32 [slots, 4]."""
+    emitted as `aug_geom` int32 [slots, 4]; a fourth (aug_rotate / aug_shear / aug_blur on) = (six warp integers, sigma) tensors per slot,
+    emitted as `aug_warp` int32 [slots, 6] and `aug_blur` float32 [slots]."""
     if not imgs or len(img_idx) != len(items) or min(img_idx) < 0 or max(img_idx) >= len(imgs):
         raise ValueError(f"grouped_collater: img_idx out of range for {len(imgs)} images / {len(items)} queries")
     if all_slots_used and len(set(img_idx)) != len(imgs):
@@ -763,6 +1029,10 @@ def grouped_collater(items: List[Dict[str, torch.Tensor]], imgs: List[torch.Tens
             if len(aug[2]) != len(imgs):
                 raise ValueError(f"grouped_collater: {len(imgs)} image slots but {len(aug[2])} flip / fill records")
             out["aug_geom"] = torch.tensor([list(g) for g in aug[2]], dtype=torch.int32)
+        if len(aug) > 3:
+            if len(aug[3]) != len(imgs):
+                raise ValueError(f"grouped_collater: {len(imgs)} image slots but {len(aug[3])} warp / blur records")
+            out["aug_warp"], out["aug_blur"] = torch.stack([m for m, _ in aug[3]]), torch.stack([s for _, s in aug[3]])
     return out
 
 
@@ -941,7 +1211,7 @@ class DevicePrefetcher:
     """Wraps a loader of pinned host batches: the next batch is copied to the GPU on a side stream while the current one
     is being consumed (HIP copy engine overlaps the training step), and handed over with an event wait."""
 
-    _HOST_ONLY = ("img_hw", "aug_crop", "aug_jitter", "aug_geom")        # fields the resizer consumes on the host: not part of the device batch
+    _HOST_ONLY = ("img_hw", "aug_crop", "aug_jitter", "aug_geom", "aug_warp", "aug_blur")        # fields the resizer consumes on the host: not part of the device batch
 
     def __init__(self, loader, device="cuda", resize_hw=None):
         """resize_hw = (H, W): batches whose "img" is raw uint8 HWC (a list of differently sized images, or a stack at another size)
@@ -975,8 +1245,9 @@ class DevicePrefetcher:
                 if self._resizer is None:
                     self._resizer = GpuResizer(self.resize_hw, self.device)
                 geom = batch.get("aug_geom")                   # int32 [B, 4] = (flip, fill r, g, b): only with aug_flip / aug_expand_max on
-                if geom is not None:
-                    dev["img"] = self._resizer.resize_flat(dev["img"], hw, crop=crop, jitter=jitter, flip=geom[:, 0] != 0, fill=geom[:, 1:])
+                if geom is not None:               # (aug_warp / aug_blur: only with aug_rotate / aug_shear / aug_blur on, and then with aug_geom)
+                    dev["img"] = self._resizer.resize_flat(dev["img"], hw, crop=crop, jitter=jitter, flip=geom[:, 0] != 0, fill=geom[:, 1:],
+                                                           warp=batch.get("aug_warp"), blur=batch.get("aug_blur"))
                 else:
                     dev["img"] = self._resizer.resize_flat(dev["img"], hw, crop=crop, jitter=jitter)
             elif crop is not None:
@@ -1014,6 +1285,7 @@ def get_data(cfg, embedder=None, prefetch: Optional[bool] = None):
     info = cfg["ds_info"][ds_name]
     aug_params(cfg)                                          # ValueError for an aug_* key outside its range
     aug_geom_params(cfg)
+    aug_warp_params(cfg)
     emb = embedder if embedder is not None else get_embedder(cfg)
     gpu = torch.cuda.is_available() and (cfg["gpu_img_normalise"] if "gpu_img_normalise" in cfg else True)
     prefetch = gpu if prefetch is None else prefetch

@@ -43,7 +43,7 @@ def learner_init(uid: str, cfg):
     if cfg["synthetic"]:
         from .dat_loader import aug_enabled
         if aug_enabled(cfg):                # (also a ValueError for an aug_* key outside its range)
-            raise ValueError("aug_crop_min / aug_brightness / aug_contrast / aug_saturation / aug_flip / aug_expand_max need synthetic=False: "
+            raise ValueError("aug_crop_min / aug_brightness / aug_contrast / aug_saturation / aug_flip / aug_expand_max / aug_rotate / aug_shear / aug_blur need synthetic=False: "
                              "synthetic batches have no decoded image to crop")
         from .synth import get_data
         data = get_data(cfg, zdist.get_rank())
