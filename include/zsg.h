@@ -948,6 +948,43 @@ int zsg_optim_step_segments(int32_t algo, int32_t flags, float* p, const float* 
                             const zsg_adam_seg* segs, int32_t nseg, int32_t nchunks, const zsg_optim_group* groups, int32_t ngroups,
                             float grad_scale, int32_t* counters, int32_t* ticket, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Fused LAMB (You et al., "Large Batch Optimization for Deep Learning"; csrc/lamb.hip): Adam's moments, and every parameter tensor's
+ * update rescaled by its trust ratio.  For every listed segment (one parameter tensor w with gradient g * grad_scale, moments m, v, its
+ * group's lr, beta1, beta2, eps, weight_decay = wd and flag adapt, t = counters[counter] + 1):
+ *     m <- beta1 * m + (1 - beta1) * g          v <- beta2 * v + (1 - beta2) * g * g
+ *     u  = (m / bc1) / (sqrt(v / bc2) + eps) + wd * w          fp32, element-wise, every operation rounded on its own;
+ *                                                              bc = 1 - beta^t formed in fp64 and rounded once to fp32
+ *     Nw = sqrt(sum w^2)   Nu = sqrt(sum u^2)                  sums in fp64 over the segment, each result rounded to fp32
+ *     r  = Nw / Nu  if adapt and Nw > 0 and Nu > 0,  else 1    (adapt and a NaN in either norm: r = NaN — it propagates, in that segment only)
+ *     w <- w - (lr * r) * u
+ * No clamp on Nw, no global gradient pre-normalisation (zsg_grad_norm / zsg_grad_scale in front cover that).  Elements with w = g = 0 and
+ * zero moments (the parameter store's padding) have u = 0: they change neither norm and stay 0.
+ *
+ * Two launches over a DEVICE segment table exactly as zsg_adam_step_segments takes it (segs / nseg / nchunks; one 256-thread block per
+ * work chunk; 16-byte accesses plus a tail); nothing outside the listed ranges is read or written in p, m or v.  groups: a HOST table of
+ * ngroups <= ZSG_ADAM_MAX_GROUPS sets, passed by value; the same table to both launches.  counters / ticket as zsg_adam_step_segments:
+ * both launches compute with t = counters[counter] + 1, zsg_lamb_apply's last block advances every listed counter; ticket is 0 between
+ * launches and serves both.  HBM traffic 24 + 16 B per parameter (u is formed twice, from the same stored m, v with the same code: the
+ * same bits, never stored).
+ * zsg_lamb_moments: partials = device fp64 scratch of 2 * nchunks; ratio / norm_w / norm_u = device fp32 of nseg each, indexed by the
+ * segment's position in the table (r, Nw, Nu).  The block that arrives last reduces the chunks' sums per segment in an order fixed by the
+ * chunk index (zsg_grad_norm's hand-off): no float atomics, the same bits from run to run, whatever ZSG_DETERMINISTIC says.
+ * zsg_lamb_apply: ratio as zsg_lamb_moments wrote it, on the same stream behind it.
+ * A NULL required pointer (every pointer but stream is required), a misaligned buffer (p, g, m, v: 16 bytes; partials: 8), ngroups outside
+ * 1..ZSG_ADAM_MAX_GROUPS, nseg < 0 or nchunks < nseg: -1 before anything is launched (zsg_last_error names the argument).  nseg == 0: 0,
+ * no launch, nothing written, no counter moves.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct zsg_lamb_group {
+    float lr, beta1, beta2, eps, weight_decay;
+    int32_t adapt;          /* 0: r = 1 for the group's segments (biases, normalisation scales), their norms are still reported */
+} zsg_lamb_group;
+int zsg_lamb_moments(const float* p, const float* g, float* m, float* v, const zsg_adam_seg* segs, int32_t nseg, int32_t nchunks,
+                     const zsg_lamb_group* groups, int32_t ngroups, float grad_scale, const int32_t* counters, double* partials,
+                     int32_t* ticket, float* ratio, float* norm_w, float* norm_u, void* stream);
+int zsg_lamb_apply(float* p, const float* m, const float* v, const zsg_adam_seg* segs, int32_t nseg, int32_t nchunks,
+                   const zsg_lamb_group* groups, int32_t ngroups, const float* ratio, int32_t* counters, int32_t* ticket, void* stream);
+
 int zsg_memset_f32(float* p, int64_t n, float value, void* stream);
 
 /* Wave priority of the kernels of the step's dependent chain (convolutions forward / data gradient, BatchNorm passes, the small

@@ -55,6 +55,11 @@ class OptimGroup(C.Structure):
                 ("momentum", C.c_float), ("dampening", C.c_float), ("nesterov", C.c_int32)]
 
 
+class LambGroup(C.Structure):          # zsg_lamb_group
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("adapt", C.c_int32)]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -197,6 +202,8 @@ SIGNATURES = {
     "zsg_optim_step": (I32, [I32, I32, P, P, P, P, P, I64, C.POINTER(OptimGroup), F32, P, P]),
     "zsg_optim_step_ema": (I32, [I32, I32, P, P, P, P, P, I64, C.POINTER(OptimGroup), F32, P, P, F32, P]),
     "zsg_optim_step_segments": (I32, [I32, I32, P, P, P, P, P, P, I32, I32, C.POINTER(OptimGroup), I32, F32, P, P, P]),
+    "zsg_lamb_moments": (I32, [P, P, P, P, P, I32, I32, C.POINTER(LambGroup), I32, F32, P, P, P, P, P, P, P]),
+    "zsg_lamb_apply": (I32, [P, P, P, P, I32, I32, C.POINTER(LambGroup), I32, P, P, P, P]),
     "zsg_memset_f32": (I32, [P, I64, F32, P]),
     "zsg_set_stream_workspace": (I32, [P, P, SZ]),
     "zsg_set_main_priority": (I32, [I32]),

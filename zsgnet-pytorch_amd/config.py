@@ -8,7 +8,7 @@ from typing import Any, Dict
 DEFAULTS: Dict[str, Any] = {
     # configs/cfg.json:1-43
     "ds_to_use": "refclef", "bs": 16, "nw": 4, "bsv": 16, "nwv": 4, "lr": 1e-4, "devices": 0, "opt_fn": "Adam",
-    # opt_fn: "Adam" / "AdamW" / "SGD" (optim.make_opt_fn); opt_fn_params: the keys of all three, each rule takes its own (betas, eps, amsgrad:
+    # opt_fn: "Adam" / "AdamW" / "SGD" / "LAMB" (optim.make_opt_fn; LAMB: betas, eps, weight_decay, see lamb_adapt_1d below); opt_fn_params: the keys of all three, each rule takes its own (betas, eps, amsgrad:
     # Adam / AdamW; momentum, dampening, nesterov: SGD; weight_decay: all).  The reference has betas alone (cfg.json)
     "opt_fn_params": {"betas": [0.9, 0.99], "eps": 1e-8, "weight_decay": 0.0, "amsgrad": False, "momentum": 0.0, "dampening": 0.0,
                       "nesterov": False},
@@ -37,6 +37,8 @@ DEFAULTS: Dict[str, Any] = {
     "eval_topk": 1,                 # K > 1: in eval mode the evaluator also returns the K best NMS-filtered boxes per query and Acc@K (zsg_eval_topk)
     "eval_nms_thr": 0.5,            # ... a candidate is dropped when its IoU with a box already kept is > this
     "eval_pre_nms": 128,            # ... candidates per query (best scores first) that enter the NMS; K <= eval_pre_nms <= 512
+    "lamb_adapt_1d": False,         # opt_fn "LAMB" (the large-batch rule: optim.FusedLAMB; reads betas, eps, weight_decay of opt_fn_params): by default tensors of >= 2 dimensions get the trust ratio and the 1-D ones (biases, BatchNorm scales / shifts) plain Adam steps without weight decay (optim.lamb_param_groups); True = one adaptive group of everything
+    "warmup_iters": 0,              # W > 0: linear learning-rate warm-up — optimizer step k = 1..W runs at k / W of every group's base lr (the lr at prepare_optimizer), later steps leave the groups to the scheduler; a resume with load_opt continues from the checkpoint's num_it; 0 = off
     "ema_decay": 0.0,               # > 0: an exponential moving average of the weights, updated in every optimizer step (ema.ModelEma); 0 = off
     "ema_warmup": False,            # ... its decay ramps up as min(ema_decay, (1 + n) / (10 + n)) over the first updates
     "ema_eval": True,               # ... validation / testing (and with them the LR scheduler, best_met, the prediction files) use the average

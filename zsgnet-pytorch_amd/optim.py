@@ -19,15 +19,18 @@ clip_grad_norm_ is torch.nn.utils.clip_grad_norm_ over the same flat gradient bu
 through the segment table the segmented step uses, with no host round trip.
 
 A weight average (ema.ModelEma.attach) rides in the step: inside the single launch (zsg_adam_step_ema / zsg_optim_step_ema), or as one
-zsg_ema_update over the whole flat buffer behind the segmented step.  Which one follows from the path the step takes; nothing else selects it."""
+zsg_ema_update over the whole flat buffer behind the segmented step.  Which one follows from the path the step takes; nothing else selects it.
+
+FusedLAMB (cfg opt_fn "LAMB") is the large-batch rule: Adam's moments with every parameter tensor's update rescaled by its trust ratio
+|w| / |u| (zsg_lamb_moments + zsg_lamb_apply, always over the segment table: the rule needs the tensors' boundaries).  State m, v."""
 import ctypes as C
 import math
 
 import torch
 
 from . import mdl
-from ._lib import (ADAM_CHUNK, ADAM_MAX_GROUPS, OPT_ADAM, OPT_ADAMW, OPT_AMSGRAD, OPT_SGD, AdamGroup, AdamSeg, OptimGroup, check, lib,
-                   stream_ptr)
+from ._lib import (ADAM_CHUNK, ADAM_MAX_GROUPS, OPT_ADAM, OPT_ADAMW, OPT_AMSGRAD, OPT_SGD, AdamGroup, AdamSeg, LambGroup, OptimGroup, check,
+                   lib, stream_ptr)
 
 
 def segment_table(net, key):
@@ -52,7 +55,7 @@ class FusedOptimizer(torch.optim.Optimizer):
     updates and their segment table, the step counters (one while every step updates every parameter, one per parameter once a step
     leaves some out), the weight average's hook in step(), the checkpoint's frame.  A subclass names its rule (NAME, ALGO), the group
     keys it takes (HYPER), its state buffers (_buffers) and one hyperparameter set of the C ABI (_group)."""
-    NAME = None            # the rule's name in checkpoints and cfg opt_fn: 'Adam' / 'AdamW' / 'SGD'
+    NAME = None            # the rule's name in checkpoints and cfg opt_fn: 'Adam' / 'AdamW' / 'SGD' / 'LAMB'
     ALGO = None            # ZSG_OPT_*
     HYPER = ()             # group keys load_state_dict restores
 
@@ -356,19 +359,109 @@ class FusedSGD(FusedOptimizer):
                           1 if g["nesterov"] else 0)
 
 
-OPT_FNS = {"Adam": FusedAdam, "AdamW": FusedAdamW, "SGD": FusedSGD}          # cfg opt_fn
+class FusedLAMB(FusedOptimizer):
+    """LAMB (You et al., "Large Batch Optimization for Deep Learning"; the definition in include/zsg.h, "Fused LAMB"): Adam's moments,
+    and the update of every parameter tensor rescaled by its trust ratio |w| / |u|.  The rule needs the parameters' boundaries, so every
+    step takes the segmented path — two launches, zsg_lamb_moments and zsg_lamb_apply (csrc/lamb.hip), over the segment table of the
+    stepped parameters — and the step counts live in the per-parameter counters from the first step.  Group key `adapt` (default True):
+    False gives the group's tensors the ratio 1, i.e. Adam with a coupled weight decay (biases, normalisation scales).  Frozen
+    parameters, parameter groups, grad_scale, add_param_group and clip_grad_norm_ in front work as for the other rules; an attached
+    weight average updates through the segmented path's zsg_ema_update.  Under DDP the norms are taken from the reduced gradients
+    (run_backward returns behind reducer.wait()), in a fixed order: every rank computes the same ratios, bit for bit."""
+    NAME, ALGO, HYPER = "LAMB", None, ("lr", "betas", "eps", "weight_decay", "adapt")
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, adapt=True, grad_scale=1.0, params=None):
+        super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, adapt=adapt), grad_scale, params)
+        flat = self.net.store.flat
+        self.m = torch.zeros_like(flat)
+        self.v = torch.zeros_like(flat)
+        self._lamb_key = None          # the stepped set the scratch below was sized for
+        self._partials = self._stats = self._stepped_idx = None
+
+    def _buffers(self):
+        return dict(m=self.m, v=self.v)
+
+    def _group(self, g):
+        return LambGroup(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                         1 if g["adapt"] else 0)
+
+    def _stepped(self):
+        """never None: LAMB has no single-launch path"""
+        idx = self._index
+        return tuple(sorted((idx[id(p)], gi) for gi, g in enumerate(self.param_groups) for p in g["params"] if p.grad is not None))
+
+    def _launch_flat(self, g, ema, ema_w):
+        raise RuntimeError("FusedLAMB has no single-launch path")
+
+    def _launch_segments(self, nseg):
+        st, n, groups = self.net.store, len(self._index), self.param_groups
+        if self._lamb_key != self._seg_key:
+            # scratch of this stepped set: the chunks' fp64 partial sums [2 * nchunks] and [ratio | |w| | |u|] per segment
+            dev = st.flat.device
+            self._partials = torch.empty(2 * self._nchunks, dtype=torch.float64, device=dev)
+            self._stats = torch.ones(3, nseg, dtype=torch.float32, device=dev)
+            self._stepped_idx = torch.tensor([i for i, _ in self._seg_key], dtype=torch.int64, device=dev)
+            self._lamb_key = self._seg_key
+        gt = (LambGroup * len(groups))(*[self._group(g) for g in groups])
+        tab, cnt, ticket, stats = self._seg_tab.data_ptr(), self._pcount.data_ptr(), self._pcount[n:].data_ptr(), self._stats
+        check(lib.zsg_lamb_moments(st.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), tab, nseg, self._nchunks,
+                                   gt, len(groups), float(self.grad_scale), cnt, self._partials.data_ptr(), ticket, stats[0].data_ptr(),
+                                   stats[1].data_ptr(), stats[2].data_ptr(), stream_ptr()), "zsg_lamb_moments")
+        check(lib.zsg_lamb_apply(st.flat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), tab, nseg, self._nchunks, gt, len(groups),
+                                 stats[0].data_ptr(), cnt, ticket, stream_ptr()), "zsg_lamb_apply")
+
+    def _per_param(self, row, fill):
+        out = torch.full((len(self._index),), fill, dtype=torch.float32, device=self.net.store.flat.device)
+        if self._stats is not None and self._lamb_key == self._seg_key:
+            out[self._stepped_idx] = self._stats[row]
+        return out
+
+    def trust_ratios(self) -> torch.Tensor:
+        """the last step's trust ratio of every parameter, in flat order (1 for a parameter that step left out, and before the first
+        step): a device tensor, no host synchronisation"""
+        return self._per_param(0, 1.0)
+
+    def norms(self):
+        """(|w|, |u|) of the last step per parameter, in flat order (0 where trust_ratios() has its filler)"""
+        return self._per_param(1, 0.0), self._per_param(2, 0.0)
+
+
+OPT_FNS = {"Adam": FusedAdam, "AdamW": FusedAdamW, "SGD": FusedSGD, "LAMB": FusedLAMB}          # cfg opt_fn
 OPT_FN_PARAMS = dict(betas=[0.9, 0.99], eps=1e-8, weight_decay=0.0, amsgrad=False, momentum=0.0, dampening=0.0, nesterov=False)
+
+
+def lamb_param_groups(params, adapt_1d=False):
+    """The groups cfg opt_fn "LAMB" trains with when the trainer names no parameters: tensors of two or more dimensions (convolution,
+    linear, LSTM and embedding weights) get the trust ratio; one-dimensional ones (biases, BatchNorm scales and shifts) get adapt=False
+    and no weight decay — their norms say little about a sensible step (the usual LAMB / LARS exclusion).  adapt_1d (cfg lamb_adapt_1d):
+    one adaptive group of everything instead."""
+    params = list(params)
+    if adapt_1d:
+        return [dict(params=params)]
+    groups = [dict(params=[p for p in params if p.dim() >= 2]), dict(params=[p for p in params if p.dim() < 2], adapt=False, weight_decay=0.0)]
+    return [g for g in groups if g["params"]]
+
+
+def _make_lamb(model, lr=1e-3, params=None, grad_scale=1.0, adapt_1d=False, **hp):
+    if params is None:
+        net = model.module if hasattr(model, "module") else model
+        params = lamb_param_groups(net._ordered_params(), adapt_1d)
+    return FusedLAMB(model, lr=lr, params=params, grad_scale=grad_scale, **hp)
 
 
 def make_opt_fn(cfg):
     """The optimizer factory of cfg opt_fn / opt_fn_params (reference main_dist.py:50: partial(torch.optim.Adam, betas=(0.9, 0.99))): a
     callable (model, lr=..., params=...) as trainer.Learner expects.  Keys of opt_fn_params that the chosen rule does not have are
-    ignored, except that amsgrad or non-default betas with SGD are a ValueError (who sets them expects an effect)."""
+    ignored, except that amsgrad or non-default betas with SGD are a ValueError (who sets them expects an effect).  "LAMB" reads betas,
+    eps and weight_decay, and without params= builds lamb_param_groups (cfg lamb_adapt_1d)."""
     from functools import partial
     name = cfg["opt_fn"]
     if name not in OPT_FNS:
         raise ValueError(f"opt_fn {name!r} is not supported: one of {', '.join(OPT_FNS)}")
     hp = dict(OPT_FN_PARAMS, **cfg.get("opt_fn_params", {}))
+    if name == "LAMB":
+        return partial(_make_lamb, betas=tuple(float(b) for b in hp["betas"]), eps=float(hp["eps"]), weight_decay=float(hp["weight_decay"]),
+                       adapt_1d=bool(cfg.get("lamb_adapt_1d", False)))
     if name == "SGD":
         if hp["amsgrad"] or [float(b) for b in hp["betas"]] != OPT_FN_PARAMS["betas"]:
             raise ValueError("opt_fn SGD has no amsgrad and no betas (opt_fn_params.amsgrad / opt_fn_params.betas are set): choose Adam or "

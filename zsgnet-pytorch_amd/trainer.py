@@ -44,6 +44,9 @@ class Learner:
         self.predictions_dir.mkdir(parents=True, exist_ok=True)
         self.logger = logging.getLogger("zsg." + uid)
         self.optimizer, self.lr_scheduler = None, None
+        # cfg warmup_iters: every group's base lr (as prepare_optimizer found it), the lr the warm-up last set, and the iteration count
+        # at which this optimizer's trajectory began
+        self._base_lrs, self._warm_set, self._warm_start = None, None, 0
         self.ema = None               # cfg ema_decay > 0: the weight average (ema.ModelEma), built with the optimizer or a loaded checkpoint
         if cfg.get("freeze_bn", False):        # (kept across the mdl.train() of every epoch: ZSGNet.train re-applies it)
             getattr(mdl, "module", mdl).freeze_batchnorm()
@@ -62,11 +65,30 @@ class Learner:
             self.optimizer = self.opt_fn(self.mdl, lr=lr)
         else:
             self.optimizer = self.opt_fn(self.mdl, lr=lr, params=params)
+        self._base_lrs = [float(g["lr"]) for g in self.optimizer.param_groups]
+        self._warm_set, self._warm_start = [None] * len(self._base_lrs), self.num_it
         if self._ensure_ema() is not None:        # optimizer.step() updates the average from now on
             self.ema.attach(self.optimizer)
         if self.cfg["use_reduce_lr_plateau"]:     # reference steps it with val accuracy in the default mode='min'
             self.lr_scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, factor=self.cfg["reduce_factor"],
                                                                            patience=self.cfg["patience"])
+
+    def _warmup_lr(self):
+        """cfg warmup_iters = W > 0, called ahead of optimizer.step(): step k = 1..W of this optimizer's trajectory (num_it counts them; a
+        resume with load_opt continues the checkpoint's count) runs at k / W of every group's base lr; from step W + 1 on the groups are
+        left alone.  A scheduler that moves a group's lr during the warm-up (ReduceLROnPlateau) moves its base by the same factor."""
+        W = int(self.cfg.get("warmup_iters", 0))
+        k = self.num_it - self._warm_start
+        if W <= 0 or self._base_lrs is None or not 1 <= k <= W:
+            return
+        for i, g in enumerate(self.optimizer.param_groups):
+            if i == len(self._base_lrs):          # (a group added after prepare_optimizer)
+                self._base_lrs.append(float(g["lr"]))
+                self._warm_set.append(None)
+            last = self._warm_set[i]
+            if last is not None and last > 0 and g["lr"] != last:
+                self._base_lrs[i] *= g["lr"] / last
+            g["lr"] = self._warm_set[i] = self._base_lrs[i] * k / W
 
     def _ensure_ema(self):
         """the weight average of cfg ema_decay > 0 (None when off), created from the network's current weights on first use"""
@@ -112,6 +134,7 @@ class Learner:
             if self.optimizer is None:
                 self.prepare_optimizer(self.cfg["lr"])
             self.optimizer.load_state_dict(ckpt["optimizer_state_dict"])
+            self._warm_start = 0                  # the checkpoint's trajectory continues: num_it is its step count (cfg warmup_iters)
             if self.lr_scheduler is not None and ckpt.get("scheduler_state_dict"):
                 self.lr_scheduler.load_state_dict(ckpt["scheduler_state_dict"])
         return True
@@ -145,6 +168,7 @@ class Learner:
             out_loss["loss"].mean().backward()
             if clip > 0:
                 grad_norm = clip_grad_norm_(clip_params, clip)
+            self._warmup_lr()
             self.optimizer.step()
             metric = self.eval_fn(out, batch)
             n_img += batch["img"].shape[0]
