@@ -711,6 +711,49 @@ int zsg_lstm_bwd(const float* dwe, int32_t we_ld, int32_t we_off, const float* w
                  int32_t H, float* dgates, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Full-sequence query pooling (cfg lang_pool = final / mean / attn; csrc/lstm_seq.hip).
+ * With f_t the forward state after x_0..x_t and r_t the reverse state after x_{len-1}, .., x_t (len = clamp(lens[b], 0, T),
+ * each direction from row rank[b] of its h0 / c0 as above), o_t = [f_t | r_t] for t < len is nn.LSTM's padded output:
+ *   final  we = [f_{len-1} | r_0]  (nn.LSTM's h_n);   mean  we = (1/len) sum_{t<len} o_t;
+ *   attn   s_t = w . o_t,  alpha = softmax over t < len of s (max subtracted),  we = sum_t alpha_t o_t.
+ *
+ * zsg_lstm_seq_fwd: zsg_lstm_fwd with a walk direction and the state of every step as an output.  reverse = 1 walks
+ * t = len-1 .. 0.  hseq [B][T][hs_ld] (optional): h of the step that consumed token t, written to [hs_off, hs_off + H) of row
+ * (b, t) and exactly 0 there at t >= len — every element of the window is written, nothing outside it.  we (optional): the
+ * state after the walk's last step (the starting state at len = 0), window as zsg_lstm_fwd.  One of hseq / we is required.
+ * gates / cst / hprev are saved at TOKEN positions; hprev[t] is the state the step at t started from.  lens = NULL: all ones.
+ * H in {32, 64, 128, 256}, others return -1.  reverse = 0 with we alone computes zsg_lstm_fwd's bits.
+ *
+ * zsg_lstm_seq_bwd: BPTT in the walk's reverse order.  dwe (optional; gradient of the end state, window as zsg_lstm_bwd) starts dh,
+ * dhseq [B][T][hs_ld] (optional; window [hs_off, hs_off + H)) is added to dh at every step; one of the two is required.
+ * dgates [B][T][4H] at token positions, exactly 0 at t >= len; c_prev is cst at the walk's previous step, or c0.
+ * Weight gradients: zsg_conv_wgrad / zsg_colsum over the token-aligned rows, as for zsg_lstm_bwd.
+ *
+ * zsg_lang_pool_fwd: hseq [B][T][D] (dense; 0 at t >= len) -> we [B][D]; one workgroup per query.  mode ZSG_LANG_POOL_ATTN reads
+ * w [D] and writes alpha [B][T] (optional; 0 at t >= len); ZSG_LANG_POOL_MEAN takes w = alpha = NULL.  len = 0: we = 0.
+ * zsg_lang_pool_bwd: dalpha_t = dwe . o_t, ds_t = alpha_t (dalpha_t - sum_k alpha_k dalpha_k), dhseq_t = alpha_t dwe + ds_t w
+ * (mean: dhseq_t = dwe / len); dhseq [B][T][D] is written everywhere, 0 at t >= len; ds [B][T] (optional) likewise.
+ * zsg_lang_pool_wgrad: dw[d] (+)= sum_b sum_t ds[b][t] hseq[b][t][d]; per column 16 interleaved partial sums over the rows (b, t), each
+ * in ascending order, added in a fixed order.
+ * No float atomics in any of them: the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define ZSG_LANG_POOL_MEAN 0
+#define ZSG_LANG_POOL_ATTN 1
+int zsg_lstm_seq_fwd(const float* gin, const float* w_hh, const float* b_hh, const float* h0, const float* c0,
+                     const float* qlens_rank, const float* lens, int32_t B, int32_t T, int32_t H, int32_t reverse,
+                     float* gates, float* cst, float* hprev, float* hseq, int32_t hs_ld, int32_t hs_off, float* we,
+                     int32_t we_ld, int32_t we_off, void* stream);
+int zsg_lstm_seq_bwd(const float* dwe, int32_t we_ld, int32_t we_off, const float* dhseq, int32_t hs_ld, int32_t hs_off,
+                     const float* w_hh, const float* gates, const float* cst, const float* c0, const float* qlens_rank,
+                     const float* lens, int32_t B, int32_t T, int32_t H, int32_t reverse, float* dgates, void* stream);
+int zsg_lang_pool_fwd(const float* hseq, const float* lens, const float* w, int32_t mode, int32_t B, int32_t T, int32_t D,
+                      float* we, float* alpha, void* stream);
+int zsg_lang_pool_bwd(const float* dwe, const float* hseq, const float* lens, const float* w, const float* alpha,
+                      int32_t mode, int32_t B, int32_t T, int32_t D, float* dhseq, float* ds, void* stream);
+int zsg_lang_pool_wgrad(const float* ds, const float* hseq, int32_t B, int32_t T, int32_t D, float* dw, int32_t accumulate,
+                        void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Anchor matching + focal / smooth-L1 loss, forward and backward in one call — ZSGLoss.forward, loss.py:43-143
  * (IoU_values anchors.py:90-116, simple_match_anchors :153-165, bbox_to_reg_params :168-179).
  * out5: network output [B][A][5] = (dy,dx,dh,dw,att);  annot [B][4] y1x1y2x2;  anchors [A][4] fp32 tlbr.

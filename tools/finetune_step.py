@@ -55,6 +55,12 @@ four programs replayed on one stream (ops.Program.profile), the forward and data
 implicit-GEMM launches of the fp32 plan, the bf16 launches that replace them, the laterals' data gradients that stay fp32), the pack
 launches and the Winograd filter transforms.
 
+    python tools/finetune_step.py --lang-pool [--out profiles/lang_pool_step.json]
+
+--lang-pool measures cfg lang_pool, everything trainable: last (the reference's vector), final, mean and attn alternate.  Each variant also
+reports its query encoder launch by launch from per-launch events of the forward and backward programs replayed on one stream (every
+launch alone on the GPU): the side-stream (lane 1) time the encoder's launches add up to, forward and backward.
+
 host_enqueue_ms_per_step: host time to enqueue a step (starting from an idle GPU; equal
 to the GPU's ms_per_step when the host, not the GPU, sets the pace).  --only NAME[,NAME] runs the named variants alone (profiling).
 """
@@ -117,6 +123,31 @@ SYNC_VARIANTS = {
     "ddp_forced": False,
     "ddp_forced_sync_bn": True,
 }
+
+
+# cfg lang_pool of the variant's network
+POOL_VARIANTS = ("last", "final", "mean", "attn")
+# the query encoder's launches by their names in the plan (mdl._Plan._lower_lstm / _lower_lstm_seq)
+POOL_WHATS = ("gather_last", "lstm", "lang_pool", "wgrad:w_ih", "wgrad:w_hh", "bgrad:lstm.", "wgrad:lang_pool")
+
+
+def pool_class(v, nprof=3):
+    """the query encoder's launches of one variant from per-launch events, as head_class takes them: the forward and backward programs
+    replayed nprof times on one stream right after a step.  Per launch the name, the entry and the microseconds; the sums are the time
+    the encoder occupies lane 1 (the side stream) in the forward and in the backward"""
+    net = v["net"]
+    plan = [p for k, p in net._plans.items() if k[-1]][0]
+    st = torch.cuda.current_stream().cuda_stream
+    acc = {}
+    for _ in range(nprof):
+        for tag, prog in (("fwd", plan.fwd), ("bwd", plan.bwd)):
+            for i, (what, fname, ms) in enumerate(prog.profile(st)):
+                acc[(tag, i, what, fname)] = acc.get((tag, i, what, fname), 0.0) + ms / nprof
+    rows = [[tag, what, fname, round(ms * 1e3, 1)] for (tag, i, what, fname), ms in sorted(acc.items()) if what.startswith(POOL_WHATS)]
+    tot = lambda t: round(sum(r[3] for r in rows if r[0] == t) / 1e3, 4)
+    return dict(lang_pool=net.lang_pool_mode, encoder_fwd_ms=tot("fwd"), encoder_bwd_ms=tot("bwd"), encoder_launches=len(rows),
+                fwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "fwd"), 4),
+                bwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "bwd"), 4), encoder_rows=rows)
 
 
 WGRAD_KERNELS = ("wgrad_kernel", "wino_wgrad_kernel", "wgrad_bf16_kernel", "wgrad_reduce_kernel")
@@ -270,6 +301,7 @@ def main():
                                                              "also those switches without and with the encoder's")
     ap.add_argument("--enc-bwd-bf16", action="store_true", help="fp32 against enc_bwd_dtype = bf16; with --enc-bf16 / --train-bf16-head / "
                                                                  "--wgrad-bf16 also those switches without and with the encoder's data gradients")
+    ap.add_argument("--lang-pool", action="store_true", help="cfg lang_pool: last, final, mean and attn alternate")
     ap.add_argument("--only", default="", help="comma-separated variant names to run (e.g. one variant under rocprofv3)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
@@ -290,7 +322,11 @@ def main():
     runs = {}
     enc_of = {}                              # variant -> cfg enc_dtype (default fp32)
     encb_of = {}                             # variant -> cfg enc_bwd_dtype (default fp32)
-    if a.enc_bwd_bf16:
+    pool_of = {}                             # variant -> cfg lang_pool (default last)
+    if a.lang_pool:
+        variants = {k: ((), False, None, None, None, "fp32", "fp32") for k in POOL_VARIANTS}
+        pool_of = {k: k for k in POOL_VARIANTS}
+    elif a.enc_bwd_bf16:
         other = ("bf16" if a.wgrad_bf16 else "fp32", "bf16_head" if a.train_bf16_head else "fp32")
         oname = "+".join(n for n, on in (("enc_bf16", a.enc_bf16), ("bf16_head", a.train_bf16_head), ("bf16_wgrad", a.wgrad_bf16)) if on)
         variants = {"fp32": ((), False, None, None, None, "fp32", "fp32")}
@@ -329,12 +365,16 @@ def main():
     if a.only:
         variants = {k: v for k, v in variants.items() if k in a.only.split(",")}
     for name, (prefixes, bn_frozen, clip, sync_bn, ema, wgrad_dtype, train_dtype) in variants.items():
-        net = mdl.get_default_net(9, cfg)
+        net = mdl.get_default_net(9, config.get_cfg(lang_pool=pool_of[name]) if name in pool_of else cfg)
         net.wgrad_precision(wgrad_dtype).train_precision(train_dtype).encoder_precision(enc_of.get(name, "fp32"))
         net.encoder_backward_precision(encb_of.get(name, "fp32"))
         if sd is None:
             sd = {k: v.clone() for k, v in net.state_dict().items()}
-        net.load_state_dict(sd)
+        if "lang_pool.weight" in net.state_dict():      # (attn: a drawn scorer beside the shared weights, so the attention is not uniform)
+            g = torch.Generator().manual_seed(0)
+            net.load_state_dict(dict(sd, **{"lang_pool.weight": torch.randn(1, net.lstm_out_dim, generator=g) * 0.25}))
+        else:
+            net.load_state_dict(sd)
         net.to("cuda").train()
         for n, p in net.named_parameters():
             p.requires_grad_(not (prefixes and n.startswith(prefixes)))
@@ -406,7 +446,9 @@ def main():
         if v["clip"] is not None:
             res["variants"][name].update(clip=v["clip"][0], max_norm=v["clip"][1], last_grad_norm=round(float(v["norm"]), 6),
                                          engaged=float(v["norm"]) > v["clip"][1])
-        if a.enc_bwd_bf16:
+        if a.lang_pool:
+            res["variants"][name].update(**pool_class(v))
+        elif a.enc_bwd_bf16:
             res["variants"][name].update(enc_bwd_dtype=net._enc_bwd_dtype, enc_dtype=net._enc_dtype, train_dtype=net._train_dtype,
                                          wgrad_dtype=net._wgrad_dtype, **encb_class(v))
         elif a.enc_bf16:

@@ -177,6 +177,11 @@ SIGNATURES = {
     "zsg_lstm_gather_last": (I32, [P, P, I32, I32, I32, P, P]),
     "zsg_lstm_fwd": (I32, [P, P, P, P, P, P, P, I32, I32, I32, P, P, P, P, I32, I32, P]),
     "zsg_lstm_bwd": (I32, [P, I32, I32, P, P, P, P, P, P, I32, I32, I32, P, P]),
+    "zsg_lstm_seq_fwd": (I32, [P, P, P, P, P, P, P, I32, I32, I32, I32, P, P, P, P, I32, I32, P, I32, I32, P]),
+    "zsg_lstm_seq_bwd": (I32, [P, I32, I32, P, I32, I32, P, P, P, P, P, P, I32, I32, I32, I32, P, P]),
+    "zsg_lang_pool_fwd": (I32, [P, P, P, I32, I32, I32, I32, P, P, P]),
+    "zsg_lang_pool_bwd": (I32, [P, P, P, P, P, I32, I32, I32, I32, P, P, P]),
+    "zsg_lang_pool_wgrad": (I32, [P, P, I32, I32, I32, P, I32, P]),
     "zsg_loss_workspace_bytes": (SZ, [I32, I32]),
     "zsg_loss_fwd_bwd": (I32, [P, P, P, I32, I32, F32, F32, F32, F32, I32, F32, P, P, P, P, P, SZ, P]),
     "zsg_loss_fwd_bwd_iou": (I32, [P, P, P, I32, I32, F32, F32, F32, F32, I32, F32, I32, F32, P, P, P, P, P, SZ, P]),

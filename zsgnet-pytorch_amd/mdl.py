@@ -9,6 +9,8 @@ Reference behaviour mirrored here (file:line in /root/reference/code):
   * BackBone.concat_we mdl.py:69-104 (channel order [feat | language vector | grid y,x]).
   * shared 6-conv head mdl.py:235-244 + permute_correctly :246-254 (free here: NHWC output == [B, h*w*9, 5]).
   * BiLSTM query encoder apply_lstm mdl.py:296-336, random initial state lstm_init_hidden :279-294.
+    cfg lang_pool = final / mean / attn (not in the reference: its get_full_seq hook is unused) hands the head a vector of the whole
+    phrase instead of the last token's output; definitions in include/zsg.h, host twin tests/langpool_ref.py.
 
 Execution model: for a given input geometry the network is lowered ONCE into two static launch programs
 (forward, backward) over preallocated NHWC buffers (`ops.Program`); a step replays them on torch's current stream.
@@ -46,6 +48,7 @@ ENC_BWD_DTYPES = ("fp32", "bf16")             # cfg enc_bwd_dtype / ZSGNet.encod
 BF16_ENC_PREFIX = "backbone.encoder."         # the layers enc_dtype = "bf16_fwd" covers (ResNet only; never the stem, never a convolution that applies a pending BatchNorm)
 BF16_HEAD_PREFIXES = ("backbone.fpn.", "att_reg_box.", "att_box.", "reg_box.")     # the layers train_dtype = "bf16_head" covers: no BatchNorm among them
 LSTM_DIMS = (32, 64, 128, 256)    # cfg lstm_dim: the widths csrc/lstm.hip instantiates zsg_lstm_fwd / zsg_lstm_bwd for
+LANG_POOLS = ("last", "final", "mean", "attn")      # cfg lang_pool: the sentence vector the query encoder hands to the head (_lower_lstm)
 
 LIVE_NETS = weakref.WeakSet()      # every ZSGNet alive: optim.clip_grad_norm_ finds a parameter's flat store here
 
@@ -144,6 +147,12 @@ class ZSGNet(nn.Module):
             raise ValueError(f"emb_dim={self.emb_dim}: supported values are the positive multiples of 4 "
                              "(zero-pad the word vectors, e.g. GloVe-50 to 52)")
         self.lstm_out_dim = self.lstm_dim * (self.bid + 1)
+        # (fixed at construction: "attn" owns a parameter, lang_pool.weight, so the mode decides the state dict's keys)
+        self.lang_pool_mode = str(cfg["lang_pool"]) if "lang_pool" in cfg else "last"
+        if self.lang_pool_mode not in LANG_POOLS:
+            raise ValueError(f"lang_pool={self.lang_pool_mode!r}: supported values are {', '.join(LANG_POOLS)}")
+        if self.lang_pool_mode == "final" and not self.bid:
+            self.lang_pool_mode = "last"        # one direction: h_n IS the forward state at len - 1, the same program
         self.use_lang = bool(cfg["use_lang"])
         self.use_img = bool(cfg["use_img"])
         self.same_atb = bool(cfg["use_same_atb"])
@@ -307,6 +316,8 @@ class ZSGNet(nn.Module):
             self.store.add_mat("lstm.weight_hh_l0" + suf, H4, self.lstm_dim)
             self.store.add_vec("lstm.bias_ih_l0" + suf, H4)
             self.store.add_vec("lstm.bias_hh_l0" + suf, H4)
+        if self.lang_pool_mode == "attn":       # the attention scorer s_t = w . o_t (no bias: softmax is shift-invariant); last in the flat buffer
+            self.store.add_mat("lang_pool.weight", 1, self.lstm_out_dim)
 
     def _register(self):
         self._param_names = list(self.store.order)
@@ -369,6 +380,8 @@ class ZSGNet(nn.Module):
             elif name.startswith("lstm."):
                 bound = 1.0 / math.sqrt(self.lstm_dim)
                 p.copy_((torch.rand(e.shape, generator=g) * 2 - 1) * bound)
+            elif name == "lang_pool.weight":     # uniform attention: a fresh "attn" net computes "mean"
+                p.zero_()
             elif name.endswith(".bias") and name[:-5] in self.convs:
                 L = self.convs[name[:-5]]
                 bound = 1.0 / math.sqrt(L.cin * L.k * L.k)
@@ -2554,10 +2567,12 @@ class _Plan:
         return out
 
     def _lower_lstm(self) -> Act:
-        """mdl.py:296-336.  we [B, 2H] = [h_fwd(len-1) | reverse-cell(x[len-1])]"""
+        """mdl.py:296-336.  we [B, 2H] = [h_fwd(len-1) | reverse-cell(x[len-1])]  (cfg lang_pool = last; the other modes: _lower_lstm_seq)"""
         net, B, T = self.net, self.Q, self.T
         E, Hd = net.emb_dim, net.lstm_dim
         H4 = 4 * Hd
+        if net.lang_pool_mode != "last":
+            return self._lower_lstm_seq()
         we = self.act("we", B, 1, 1, net.lstm_out_dim)
         dirs = [("", 0)] + ([("_reverse", 1)] if net.bid else [])
         we.requires_grad = any(self.trains(f"lstm.{k}_l0{suf}") for suf, _ in dirs for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
@@ -2600,6 +2615,82 @@ class _Plan:
                         continue
                     self.bwd.add(lib.zsg_colsum, dg.buf, 1, 0, B * Tn, H4, 0, H4, self.G(bname + suf), 1, what="bgrad:" + bname + suf, lane=1)
             self.tape.append(back)
+        return we
+
+    def _lower_lstm_seq(self) -> Act:
+        """cfg lang_pool = final / mean / attn (csrc/lstm_seq.hip; definitions in include/zsg.h).  Both directions run over all T tokens:
+        the reverse direction's input projection has the forward direction's geometry (no gather_last), zsg_lstm_seq_fwd walks it from
+        x[len-1] down to x[0].  final: we [B, 2H] = [f_{len-1} | r_0], the two end states.  mean / attn: the directions write the padded
+        output o [B, T, 2H] and zsg_lang_pool_fwd reduces it over each query's valid tokens; on the tape the pool's backward comes first and
+        hands d(o) to the two BPTT sweeps.  Everything the steps save is token-aligned, so the weight / bias gradients are the GEMMs and
+        column sums of the `last` program over [B * T] rows.  All on the side stream (lane 1)."""
+        net, B, T = self.net, self.Q, self.T
+        E, Hd, D = net.emb_dim, net.lstm_dim, net.lstm_out_dim
+        H4 = 4 * Hd
+        mode = net.lang_pool_mode
+        pooled = mode in ("mean", "attn")
+        attn = mode == "attn"
+        pmode = 1 if attn else 0           # ZSG_LANG_POOL_ATTN / ZSG_LANG_POOL_MEAN
+        we = self.act("we", B, 1, 1, D)
+        dirs = [("", 0)] + ([("_reverse", 1)] if net.bid else [])
+
+        def dir_trains(suf):
+            return any(self.trains(f"lstm.{k}_l0{suf}") for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+        pw_trains = attn and self.trains("lang_pool.weight")
+        we.requires_grad = any(dir_trains(suf) for suf, _ in dirs) or pw_trains
+        x_all = Act(self.in_qvec, B, E, E, [Level(0, 1, T, T * E)], "qvec")
+        x_all.requires_grad = False
+        hseq = self._buf(B * T * D) if pooled else None
+        alpha = self._buf(B * T) if attn else None
+        pw = self.P("lang_pool.weight") if attn else None
+        lens = self.in_qlens
+        grads = {}                         # d(o) of the pool's backward, read by the two sweeps emitted behind it
+        for suf, di in dirs:
+            gin = self.act("gin" + suf, B, 1, T, H4)
+            d = fwd_desc(x_all, gin, E, H4, 1, 1, 0, 1, wC=E)
+            self.fwd.add(lib.zsg_conv_igemm, d, x_all.buf, self.P("lstm.weight_ih_l0" + suf), gin.buf, self.P("lstm.bias_ih_l0" + suf),
+                         None, None, None, what="lstm_in" + suf, lane=1)
+            gates, cst, hprev = self._buf(B * T * H4), self._buf(B * T * Hd), self._buf(B * T * Hd)
+            h0 = self.in_h0[di * B * Hd:(di + 1) * B * Hd]
+            c0 = self.in_c0[di * B * Hd:(di + 1) * B * Hd]
+            self.fwd.add(lib.zsg_lstm_seq_fwd, gin.buf, self.P("lstm.weight_hh_l0" + suf), self.P("lstm.bias_hh_l0" + suf), h0, c0,
+                         self.in_qlens, lens, B, T, Hd, di, gates, cst, hprev, hseq, D, di * Hd, None if pooled else we.buf, D, di * Hd,
+                         what="lstm_seq" + suf, lane=1)
+
+            def back(suf=suf, di=di, gates=gates, cst=cst, hprev=hprev, c0=c0):
+                if we.grad is None or not dir_trains(suf):
+                    return
+                dg = Act(self._buf(B * T * H4), B, H4, H4, [Level(0, 1, T, T * H4)], "dgates" + suf)
+                self.bwd.add(lib.zsg_lstm_seq_bwd, None if pooled else we.grad.buf, D, di * Hd, grads.get("dhseq"), D, di * Hd,
+                             self.P("lstm.weight_hh_l0" + suf), gates, cst, c0, self.in_qlens, lens, B, T, Hd, di, dg.buf,
+                             what="lstm_seq_bwd" + suf, lane=1)
+                if self.trains("lstm.weight_ih_l0" + suf):
+                    d_ih = fwd_desc(x_all, dg, E, H4, 1, 1, 0, 1, wC=E)
+                    self.bwd.add(lib.zsg_conv_wgrad, d_ih, x_all.buf, dg.buf, self.G("lstm.weight_ih_l0" + suf), 1, self.wg_ws, self.wg_ws_bytes,
+                                 what="wgrad:w_ih" + suf, lane=1)
+                if self.trains("lstm.weight_hh_l0" + suf):
+                    hp = Act(hprev, B, Hd, Hd, [Level(0, 1, T, T * Hd)], "hprev" + suf)
+                    d_hh = fwd_desc(hp, dg, Hd, H4, 1, 1, 0, 1, wC=Hd)
+                    self.bwd.add(lib.zsg_conv_wgrad, d_hh, hp.buf, dg.buf, self.G("lstm.weight_hh_l0" + suf), 1, self.wg_ws, self.wg_ws_bytes,
+                                 what="wgrad:w_hh" + suf, lane=1)
+                for bname in ("lstm.bias_ih_l0", "lstm.bias_hh_l0"):
+                    if not self.trains(bname + suf):
+                        continue
+                    self.bwd.add(lib.zsg_colsum, dg.buf, 1, 0, B * T, H4, 0, H4, self.G(bname + suf), 1, what="bgrad:" + bname + suf, lane=1)
+            self.tape.append(back)
+        if pooled:
+            self.fwd.add(lib.zsg_lang_pool_fwd, hseq, lens, pw, pmode, B, T, D, we.buf, alpha, what="lang_pool", lane=1)
+
+            def pool_back():               # (last on the tape: replayed ahead of the two sweeps)
+                if we.grad is None:
+                    return
+                grads["dhseq"] = self._buf(B * T * D)
+                ds = self._buf(B * T) if attn else None
+                self.bwd.add(lib.zsg_lang_pool_bwd, we.grad.buf, hseq, lens, pw, alpha, pmode, B, T, D, grads["dhseq"], ds,
+                             what="lang_pool_bwd", lane=1)
+                if pw_trains:
+                    self.bwd.add(lib.zsg_lang_pool_wgrad, ds, hseq, B, T, D, self.G("lang_pool.weight"), 1, what="wgrad:lang_pool", lane=1)
+            self.tape.append(pool_back)
         return we
 
     def _lower_head(self, feats: List[Act], we: Optional[Act]):
