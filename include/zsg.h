@@ -108,6 +108,36 @@ int zsg_conv_igemm(const zsg_conv_desc* d, const float* src, const float* wt, fl
  * by the epilogue so the following train-mode BatchNorm needs no extra pass over the activation
  * (m_tiles = sum over segments of ceil(rows / BM), BM = tile_hint & 0xff); finalize with zsg_bn_stats_from_partials. */
 
+/* Read / write contract of the fp32 entries (zsg_conv_igemm, zsg_conv_wino, zsg_conv_wgrad, zsg_conv_wgrad_wino[_batched]), held at
+ * zero tolerance by tests/test_gpu_conv_exact.py on integer data between NaN guards:
+ *   - a tap outside the image, a row beyond a segment's last, a channel beyond C (K tails of the 32- / 64-deep tiles, Winograd's
+ *     half chunk at C % 8 == 4) and a column beyond N contribute exactly +0;
+ *   - memory outside the operand extents is never read in a way that reaches a result, and nothing outside the addressed output
+ *     elements is written: pad lanes N..out_ld-1, gaps between images and levels, dw outside the [wc0, wc0+C) window and the wt_ld
+ *     slack keep their bits;
+ *   - elements INSIDE an operand's extent that the descriptor does not address (row padding C..src_ld-1, gaps, weight channels
+ *     outside the window) may be read only against an exact zero, so any finite value may stand there.  The data gradient's
+ *     descriptor reduces over C = dy.ld channels: there dy's pad lanes and the weight image's pad columns ARE operands and must be
+ *     zero (zsg_transpose_w writes those zeros).
+ * Refusals (-1, zsg_last_error says why, no output byte is touched) beyond the ones stated at the entries:
+ *   - zsg_conv_igemm tiles are 64x64, 128x64 and 128x128 (8-wave and 64-deep-K forms of each; a C that is no multiple of 64 takes the
+ *     64-deep tiles with a zero-filled tail); any other BM / BN field is refused.  A merge_x descriptor has the 64x64 and 128x64
+ *     kernels only: BM = 128 selects the latter, every other BM the former, the BN field and the 8-wave / 64-deep-K bits are ignored.
+ *   - stream-K exists for 64x64 (4-wave; 8-wave with 32- and 64-deep K), 128x64 (8-wave) and 128x128 (4- and 8-wave), and needs
+ *     16-byte addressable output rows (out_ld, N, the output offsets and strides multiples of 4, aligned pointers).
+ *   - BM = 32 (the streaming kernels): one dense 1x1 / stride-1 segment with C % 64 == 0 and N a multiple of the unit width whose
+ *     filter panel fits the LDS — or one merge_x segment with a 7x7 / 3x3 window and N = 64 —, 16-byte aligned operands, no split-K,
+ *     no stream-K; the merge_x form has no add_src / mask_src.
+ *   - bn_partials need a plain convolution: no bias, add_src or ReLU, split_k <= 1 (zsg_conv_wino: also 16-byte addressable rows).
+ *   - zsg_conv_wino: stream-K is the 32-tile x 64-channel four-group tile only, one segment, at most 256 tiles.
+ * zsg_conv_wgrad refuses no tile hint: a field it has no kernel for runs the nearest tile (dy rows that are not 16-byte addressable
+ * and image strides of 2^23 elements or more always take the 64x64 tile).
+ * Split-K and the epilogue (zsg_conv_igemm and zsg_conv_wino alike): the output is zeroed unless add_src aliases it, every K slice
+ * adds its term with an fp32 atomic, slice 0 also adds bias and a separate add_src, and mask_src multiplies EACH SLICE'S TERM, not what
+ * `out` already holds.  bias, a separate add_src and mask_src therefore give the documented epilogue; add_src aliasing out together
+ * with mask_src gives prev + (mask > 0) * sum, which is the documented (prev + sum) * (mask > 0) only where prev is zero wherever
+ * mask <= 0 — what the training plans hold in dx, every earlier writer having applied the same mask. */
+
 /* Weight gradient.  dw[n][(r*wS+s)*wC + wc0 + c] (+)= sum_rows dy[row][n] * src[gather(row, r, s)][c]
  * The descriptor is the FORWARD descriptor of the convolution (src = forward input, "out" geometry = dy); all
  * segments (pyramid levels of the shared head) are reduced in the one launch.  The pixel dimension is split over

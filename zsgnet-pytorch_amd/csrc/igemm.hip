@@ -921,6 +921,10 @@ static int conv_igemm_impl(const zsg_conv_desc* d, const float* src, const float
         p.tail.rows = rows;
     }
     hipStream_t st = (hipStream_t)stream;
+    // the tile must exist BEFORE anything is written (the split-K preparation below zeroes the output): a refused launch leaves every
+    // output byte as it was.  Every tile that exists has its 8-wave form; merge_x maps any tile field onto its two kernels.
+    if (!d->merge_x)
+        ZSG_REQUIRE((BM == 64 && BN == 64) || (BM == 128 && (BN == 64 || BN == 128)), "conv_igemm: unsupported tile %dx%d", BM, BN);
     if (splits > 1) {
         ZSG_REQUIRE(!d->relu && d->nseg == 1 && d->out_ld == d->N && d->seg[0].osy == 1 && d->seg[0].osx == 1 &&
                         d->seg[0].out_W == d->seg[0].rows_x && d->seg[0].out_bstride == (int64_t)d->seg[0].rows_y * d->seg[0].rows_x * d->N,

@@ -767,6 +767,14 @@ static int conv_wino_impl(const zsg_conv_desc* d, const float* src, const float*
         p.tail.rows = rows;
     }
     hipStream_t st = (hipStream_t)stream;
+    const bool sk = d->tile_hint && ((d->tile_hint >> 28) & 3);
+    if (sk) {      // checked BEFORE the split-K preparation zeroes the output: a refused launch leaves every output byte as it was
+        ZSG_REQUIRE(splits == 1 && p.vec && d->nseg == 1, "conv_wino: stream-K needs one segment, no split-K, 16-byte addressable output rows");
+        // (only the 32-tile x 64-channel, four-group tile: inside the pass loop the 64-tile kernels spill — 96 registers at the four-group
+        // tile's 128-register budget, 97 at the two-group tile's 256 — and a spilling instantiation is not shipped, tools/kernel_resources.py)
+        if (!(TB == 32 && BN == 64 && ((d->tile_hint >> 24) & 1)))
+            ZSG_FAIL(-1, "conv_wino: no stream-K variant for tile %dx%d (four position groups %d)", TB, BN, (int)((d->tile_hint >> 24) & 1));
+    }
     if (splits > 1) {
         ZSG_REQUIRE(!d->relu && d->nseg == 1 && d->out_ld == d->N && d->seg[0].out_bstride == (int64_t)d->seg[0].rows_y * d->seg[0].rows_x * d->N,
                     "conv_wino: split-K needs a single dense segment without ReLU");
@@ -776,14 +784,8 @@ static int conv_wino_impl(const zsg_conv_desc* d, const float* src, const float*
             if (e != hipSuccess) ZSG_FAIL(-3, "conv_wino: memset: %s", hipGetErrorString(e));
         }
     }
-    if (d->tile_hint && ((d->tile_hint >> 28) & 3)) {      // stream-K (one workgroup per CU whatever the field says: these tiles fill a CU's LDS)
-        ZSG_REQUIRE(splits == 1 && p.vec && d->nseg == 1, "conv_wino: stream-K needs one segment, no split-K, 16-byte addressable output rows");
-        const bool ps4 = (d->tile_hint >> 24) & 1;
-        // (only the 32-tile x 64-channel, four-group tile: inside the pass loop the 64-tile kernels spill — 96 registers at the four-group
-        // tile's 128-register budget, 97 at the two-group tile's 256 — and a spilling instantiation is not shipped, tools/kernel_resources.py)
-        if (TB == 32 && BN == 64 && ps4) return wino_launch_sk<1, 2, 4>(p, st, fl, "wino_kernel<1, 2, 4>");
-        ZSG_FAIL(-1, "conv_wino: no stream-K variant for tile %dx%d (four position groups %d)", TB, BN, (int)ps4);
-    }
+    if (sk)        // stream-K (one workgroup per CU whatever the field says: these tiles fill a CU's LDS)
+        return wino_launch_sk<1, 2, 4>(p, st, fl, "wino_kernel<1, 2, 4>");
     if ((d->tile_hint >> 24) & 1) {            // four position groups: twice the waves per SIMD
         if (TB == 64 && BN == 64) return wino_launch<2, 2, 4>(p, st, fl, "wino_kernel<2, 2, 4>");
         if (TB == 32 && BN == 64) return wino_launch<1, 2, 4>(p, st, fl, "wino_kernel<1, 2, 4>");
