@@ -899,6 +899,31 @@ size_t zsg_eval_topk_workspace_bytes(int32_t B, int32_t A, int32_t pre_n, int32_
 int zsg_eval_topk(const float* out5, const float* annot, const float* anchors, const float* img_size, int32_t B, int32_t A,
                   int32_t pre_n, int32_t K, float nms_thr, float acc_thr, float* topk_boxes, float* topk_scores,
                   int32_t* topk_idx, int32_t* topk_n, int32_t* hit_rank, float* acc_at, void* ws, void* stream);
+/* Score-weighted box voting over the NMS candidates (csrc/vote.hip; Evaluator with cfg eval_box_vote > 0; no counterpart in the
+ * reference; the host definition is tests/vote_ref.py).  Called after zsg_eval_topk on the SAME out5 / anchors / img_size / pre_n / K,
+ * with the topk_boxes / topk_scores / topk_idx / topk_n it produced; none of the four is written (topk_scores is not read either: the
+ * scores are the ranking's).  Scores, indices, count and row order of the kept rows stay: no re-sort, no second NMS.
+ * Candidates: exactly zsg_eval_topk's — the first min(pre_n, A) anchors ordered by (score descending, anchor index ascending), a NaN
+ * score below every number — decoded as there (y1x1y2x2 in [-1, 1], then pixels x1y1x2y2).  A candidate is VALID when its score is not
+ * NaN and its eight decoded coordinates (both forms) are finite.
+ * Members of the kept row r < topk_n[b], whose own candidate is the one of anchor topk_idx[b][r]: if that candidate is valid, itself and
+ * every other valid candidate c with IoU(box_r, box_c) >= vote_thr (the NMS's IoU: kept box first, the [-1, 1] coordinates, fp32 in
+ * loss.hip's operation order); if it is not valid (or topk_idx[b][r] is no candidate), nobody.
+ * voted[r][j] = (float)(sum_{c in M_r, in candidate order} (double)s_c (double)box_c[j] / sum (double)s_c), box_c in pixels, s_c the
+ * fp32 sigmoid score the ranking uses; with no member or a weight sum of 0 the row keeps topk_boxes[b][r].
+ * vote_boxes [B][K][4] pixels x1y1x2y2, rows past topk_n zero; vote_n [B][K] int32 member counts, 0 past topk_n.
+ * With annot: hit_rank [B] int32 = first row r whose voted box has IoU >= acc_thr with annot (zsg_eval_topk's rule, in its [-1, 1]
+ * coordinates: the voted box there is the same weighted mean of the candidates' y1x1y2x2 coordinates, the row's own decoded box where
+ * the row kept its box), K when none; acc_at [K] = mean over the batch of (hit_rank <= j).  annot, hit_rank and acc_at may be NULL
+ * (acc_at needs hit_rank, hit_rank needs annot).
+ * Three launches, one thread per kept row summing in candidate order: no atomics, no host synchronisation, the same bits on every run.
+ * Limits (else -1, nothing launched or written, zsg_last_error names the argument): zsg_eval_topk's 1 <= K <= 64, K <= pre_n <= 512,
+ * B <= 65535; 0 < vote_thr <= 1; ws 8-byte aligned with ws_bytes >= zsg_eval_vote_workspace_bytes(B, A, pre_n, K). */
+size_t zsg_eval_vote_workspace_bytes(int32_t B, int32_t A, int32_t pre_n, int32_t K);
+int zsg_eval_vote(const float* out5, const float* annot, const float* anchors, const float* img_size, int32_t B, int32_t A,
+                  int32_t pre_n, int32_t K, float vote_thr, float acc_thr, const float* topk_boxes, const float* topk_scores,
+                  const int32_t* topk_idx, const int32_t* topk_n, float* vote_boxes, int32_t* vote_n, int32_t* hit_rank, float* acc_at,
+                  void* ws, size_t ws_bytes, void* stream);
 /* IoU table [B][A] (tests / diagnostics) */
 int zsg_iou(const float* boxes, const float* anchors, int32_t B, int32_t A, float* iou, void* stream);
 

@@ -8,7 +8,12 @@ JSON line (--json PATH also writes it to a file).
 --tta flip: flip test-time augmentation (cfg eval_tta): the eval FORWARD of the same network at the same B = --queries, three ways,
 alternating — the plain batch, the plain batch at 2B, the TTA batch (2B rows in one forward + the staging and merge launches) — and the
 two new launches alone; device events around groups of calls, the median per call of each, one JSON line (--json PATH also writes it to
-a file).  Works with --dtype and --images / --queries.  The expectation to read it against: TTA ~ plain 2B + merge."""
+a file).  Works with --dtype and --images / --queries.  The expectation to read it against: TTA ~ plain 2B + merge.
+--scales 0.75,1.25 [--vote THR]: multi-scale test-time augmentation (cfg eval_scales) on a uint8 batch, alternating — the plain eval
+forward, the multi-scale forward, every pass alone (the plain forward on the resampled batch) — the resample launches alone, and the
+wall-clock time of the first multi-scale batch (the new geometries lower and tune there).  --vote THR (cfg eval_box_vote): the evaluator
+call on that forward's output with and without the vote, and zsg_eval_vote alone (with --topk K as its K, else 1).  Composes with --tta flip
+(every forward of the comparison then runs flip TTA), --dtype, --images / --queries.  One JSON line (--json PATH also writes it)."""
 import argparse
 import json
 import os
@@ -24,7 +29,9 @@ ap.add_argument("--queries", type=int, default=16, help="queries per batch")
 ap.add_argument("--topk", type=int, default=None, help="time the evaluator call with and without the top-k launch (K boxes per query)")
 ap.add_argument("--pre-nms", type=int, default=128, help="with --topk: candidates per query that enter the NMS")
 ap.add_argument("--tta", choices=("flip",), default=None, help="time the eval forward plain at B, plain at 2B and with eval_tta=flip at B, and the two TTA launches alone")
-ap.add_argument("--json", default=None, help="with --topk / --tta: also write the result line to this file")
+ap.add_argument("--scales", default=None, help="comma-separated eval_scales, e.g. 0.75,1.25: time the multi-scale eval forward against the plain one, pass by pass")
+ap.add_argument("--vote", type=float, default=None, help="eval_box_vote threshold: time the evaluator with and without the vote and zsg_eval_vote alone (on the --scales output when given)")
+ap.add_argument("--json", default=None, help="with --topk / --tta / --scales / --vote: also write the result line to this file")
 args = ap.parse_args()          # (before the heavy imports: --help and a bad value answer at once)
 
 import torch
@@ -72,10 +79,96 @@ def time_topk():
             f.write(line + "\n")
 
 
-if args.topk is not None:
+if args.topk is not None and args.scales is None and args.vote is None:
     time_topk()
     sys.exit(0)
 net = mdl.get_default_net(9, cfg).to("cuda").eval()
+
+
+def _median_groups(fns, groups, per_group, warm=3):
+    """{name: fn} -> {name: [ms per call of every group]}, the functions alternating group by group (all see the same clock state)"""
+    ms = {k: [] for k in fns}
+    for g in range(groups + warm):
+        for name, fn in fns.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(per_group):
+                fn()
+            t1.record()
+            t1.synchronize()
+            if g >= warm:
+                ms[name].append(t0.elapsed_time(t1) / per_group)
+    return ms
+
+
+def time_scales():
+    from zsgnet_pytorch_amd._lib import check, lib, stream_ptr
+    scales = [float(v) for v in args.scales.split(",")] if args.scales else []
+    K = args.topk or 1
+    Bi = args.images
+    b = synthetic_batch(Q, 300, 300, seed=1) if Bi is None else synthetic_shared_batch(Bi, Q, 300, 300, seed=1)
+    b["img"] = (b["img"].permute(0, 2, 3, 1) * 255).round().to(torch.uint8).contiguous()
+    b = {k: v.cuda() for k, v in b.items()}
+    net.eval_tta(args.tta or "none")
+    sizes = mdl.eval_scale_sizes(300, 300, scales)
+    res = {"what": "eval forward on a uint8 batch, device events, median ms per batch; launches alone back to back, us", "dtype": args.dtype,
+           "tta": args.tta or "none", "B": Q, "images": Bi, "scales": scales, "sizes": sizes}
+    with torch.no_grad():
+        net.eval_scales(())
+        net(b)
+        torch.cuda.synchronize()
+        net.eval_scales(scales)
+        t0 = time.perf_counter()
+        out = net(b)
+        torch.cuda.synchronize()
+        res["first_multi_scale_batch_s"] = round(time.perf_counter() - t0, 2)
+        if scales:
+            passes = {f"pass_{h}x{w}": dict(b, img=net._resample(b["img"], h, w).clone()) for h, w in sizes}
+
+            def plain(x):
+                net.eval_scales(())
+                net(x)
+
+            def multi():
+                net.eval_scales(scales)
+                net(b)
+            fns = {"plain": lambda: plain(b), "multi_scale": multi, **{k: (lambda x=x: plain(x)) for k, x in passes.items()}}
+            ms = _median_groups(fns, 15, 5)
+            med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+            res.update({k + "_ms": round(v, 4) for k, v in med.items()})
+            res.update({k + "_min_max_ms": [round(min(v), 4), round(max(v), 4)] for k, v in ms.items()})
+            res["multi_over_plain"] = round(med["multi_scale"] / med["plain"], 4)
+            res["sum_of_passes_ms"] = round(med["plain"] + sum(med[k] for k in passes), 4)
+            rs = _median_groups({f"resample_{h}x{w}": (lambda h=h, w=w: net._resample(b["img"], h, w)) for h, w in sizes}, 15, 100)
+            res.update({k + "_us": round(1e3 * sorted(v)[len(v) // 2], 2) for k, v in rs.items()})
+            net.eval_scales(scales)
+            out = net(b)
+        if args.vote is not None:
+            r, s = config.ratios_scales(cfg)
+            evs = {name: evaluator.get_default_eval(r, s, config.get_cfg(eval_topk=K, eval_pre_nms=args.pre_nms, eval_box_vote=v)).eval()
+                   for name, v in (("evaluator", 0.0), ("evaluator_vote", args.vote))}
+            ev = evs["evaluator_vote"]
+            em = ev(out, b)
+            o5, anchs = ev._out5_anchors(out)
+            A = o5.shape[1]
+            annot, sz = b["annot"].contiguous().float(), b["img_size"].contiguous().float()
+            tk = ev._topk(o5, anchs, annot, sz, K)
+            fns = {name: (lambda e=e: e(out, b)) for name, e in evs.items()}
+            fns["zsg_eval_vote"] = lambda: ev._vote(o5, anchs, annot, sz, K, tk)
+            ms = _median_groups(fns, 21, 25)
+            res.update({"A": A, "K": K, "pre_nms": args.pre_nms, "vote_thr": args.vote, "mean_members": round(float(em["vote_n"].float().mean()), 2)})
+            res.update({k + "_us": round(1e3 * sorted(v)[len(v) // 2], 2) for k, v in ms.items()})
+            res.update({k + "_min_max_us": [round(1e3 * min(v), 2), round(1e3 * max(v), 2)] for k, v in ms.items()})
+    line = json.dumps(res)
+    print(line)
+    if args.json:
+        with open(args.json, "w") as f:
+            f.write(line + "\n")
+
+
+if args.scales is not None or args.vote is not None:
+    time_scales()
+    sys.exit(0)
 
 
 def time_tta():

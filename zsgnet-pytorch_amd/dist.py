@@ -319,6 +319,11 @@ class DistributedDataParallel(nn.Module):
         self.module.eval_tta(mode)
         return self
 
+    def eval_scales(self, scales=()):
+        """ZSGNet.eval_scales of the wrapped network (extra eval passes at other resolutions): eval plans are per rank, nothing is communicated"""
+        self.module.eval_scales(scales)
+        return self
+
     def wgrad_precision(self, dtype: str = "fp32"):
         """ZSGNet.wgrad_precision of the wrapped network ("fp32" | "bf16"): the gradients stay fp32, so buckets and collectives are unchanged"""
         self.module.wgrad_precision(dtype)

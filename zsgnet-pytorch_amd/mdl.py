@@ -95,6 +95,34 @@ WG_BATCH = os.environ.get("ZSG_WG_BATCH", "1") != "0"      # identical-shape Win
 SHARED_PLANS_MAX = 12     # shared-image eval plans kept per network (least recently used goes first): two token buckets of a 32-query loader
 
 
+EVAL_SCALES_MAX = 4       # cfg eval_scales / ZSGNet.eval_scales: extra eval passes per batch
+EVAL_SCALE_RANGE = (0.5, 2.0)
+
+
+def check_eval_scales(scales) -> Tuple[float, ...]:
+    """cfg eval_scales as a tuple of floats; ValueError for anything but at most EVAL_SCALES_MAX finite numbers in EVAL_SCALE_RANGE"""
+    if isinstance(scales, (str, bytes)) or not isinstance(scales, (list, tuple)):
+        raise ValueError(f"eval_scales={scales!r}: expected a list of at most {EVAL_SCALES_MAX} numbers in [{EVAL_SCALE_RANGE[0]}, {EVAL_SCALE_RANGE[1]}]")
+    if len(scales) > EVAL_SCALES_MAX:
+        raise ValueError(f"eval_scales={list(scales)!r}: at most {EVAL_SCALES_MAX} entries")
+    for s in scales:
+        if isinstance(s, bool) or not isinstance(s, (int, float)) or not math.isfinite(s) or not EVAL_SCALE_RANGE[0] <= s <= EVAL_SCALE_RANGE[1]:
+            raise ValueError(f"eval_scales={list(scales)!r}: entry {s!r} is not a finite number in [{EVAL_SCALE_RANGE[0]}, {EVAL_SCALE_RANGE[1]}]")
+    return tuple(float(s) for s in scales)
+
+
+def eval_scale_sizes(H: int, W: int, scales) -> List[Tuple[int, int]]:
+    """The (height, width) of every extra pass of a multi-scale eval forward over an H x W batch: (round(s H), round(s W)) with halves
+    rounded up.  ValueError when two entries give one size or an entry gives the batch's own size (pass 0 already runs it)."""
+    sizes = [(int(math.floor(s * H + 0.5)), int(math.floor(s * W + 0.5))) for s in check_eval_scales(scales)]
+    for i, (s, hw) in enumerate(zip(scales, sizes)):
+        if hw == (H, W):
+            raise ValueError(f"eval_scales={list(scales)!r}: entry {s!r} rounds to the batch's own size {H} x {W}")
+        if hw in sizes[:i]:
+            raise ValueError(f"eval_scales={list(scales)!r}: entries {scales[sizes.index(hw)]!r} and {s!r} both round to {hw[0]} x {hw[1]}")
+    return sizes
+
+
 def bucket_images(Bi: int, Q: int) -> int:
     """Image-batch bucket of the shared-image eval plan: the smallest power of two >= Bi, capped at Q.  A grouped loader yields another
     number of distinct images in almost every batch and each plan geometry costs a set of activation buffers and a tuner run, so for a
@@ -186,6 +214,8 @@ class ZSGNet(nn.Module):
         self.debug = False
         self._eval_dtype = "fp32"      # operand precision of the eval plans' convolutions (eval_precision)
         self._eval_tta = "none"        # test-time augmentation of the eval forwards (eval_tta)
+        self._eval_scales = ()         # extra scales of the eval forwards (eval_scales)
+        self._ms_resize = {}           # (B, H, W, Hs, Ws) -> (GpuResizer of Hs x Ws, its uint8 output batch): the resampler of one extra pass
         self._wgrad_dtype = "fp32"     # operand precision of the training plans' convolution weight gradients (wgrad_precision)
         self._train_dtype = "fp32"     # operand precision of the training plans' forward convolutions / data gradients (train_precision)
         self._enc_dtype = "fp32"       # operand precision of the training plans' encoder forward convolutions (encoder_precision)
@@ -612,6 +642,55 @@ class ZSGNet(nn.Module):
     def _tta_on(self) -> bool:
         return self._eval_tta == "flip" and not self.training
 
+    def eval_scales(self, scales=()) -> "ZSGNet":
+        """Multi-scale test-time augmentation of the EVAL forwards: () (default: one pass) or up to four factors in [0.5, 2].  Pass 0 is
+        the batch as given, H x W; every entry s adds one pass over the batch resampled ON THE DEVICE to (round(s H), round(s W)) with
+        Pillow's bicubic (zsg_resize_u8_batched, byte-identical to PIL.Image.resize of the batch's own pixels — not of the raw file: for
+        real detail at the large scales set resize_img to the largest one).  Every pass is the plain eval forward of its geometry, with
+        the same queries and LSTM state and, under eval_tta("flip"), its own mirrored rows and merge.  The returned dict is pass 0's,
+        plus tta_att_bbx_out [B, sum A_s, 5] (the passes' outputs along the anchor axis, pass 0 first, a fresh tensor) and tta_feat_sizes
+        (a host list of one [(h, w), ...] per pass): anchors are normalised image coordinates, so the pooled output is one more head
+        output over the concatenated anchor tables (Evaluator reads the two keys).  Needs the uint8 [B, H, W, 3] batch.  Training-mode
+        forwards ignore the switch.  Sizes that collide (with each other or with H x W) are a ValueError at the forward."""
+        self._eval_scales = check_eval_scales(scales)
+        return self
+
+    def _forward_scales(self, inp: Dict[str, Any]) -> Dict[str, Any]:
+        """the eval forward under eval_scales: pass 0 on the batch as given, then one plain eval forward per extra size"""
+        img = inp["img"]
+        if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3:
+            raise ValueError("eval_scales needs the uint8 [B, H, W, 3] image batch (cfg gpu_img_normalise, the default); an fp32 NCHW img "
+                             "is not resampled")
+        B, H, W, _ = img.shape
+        sizes = eval_scale_sizes(H, W, self._eval_scales)
+        geo = self.plan_geometry(inp)
+        Q = geo[1] if len(geo) == 5 else None
+        plans = [self._plan_for(geo[0], H, W, geo[-1], Q=Q)]
+        for s, (Hs, Ws) in zip(self._eval_scales, sizes):      # every pass must lower before any pass runs
+            try:
+                plans.append(self._plan_for(geo[0], Hs, Ws, geo[-1], Q=Q))
+            except Exception as e:
+                raise ValueError(f"eval_scales: scale {s!r} ({Hs} x {Ws} from {H} x {W}) cannot be lowered: {e}") from e
+        img = img.contiguous()
+        res = dict(self._forward_one(inp))
+        outs = [res["att_bbx_out"].detach()]
+        for Hs, Ws in sizes:
+            outs.append(self._forward_one(dict(inp, img=self._resample(img, Hs, Ws)))["att_bbx_out"].detach())
+        res["tta_att_bbx_out"] = torch.cat(outs, dim=1)
+        res["tta_feat_sizes"] = [[(int(h), int(w)) for h, w in p.feat_sizes] for p in plans]
+        return res
+
+    def _resample(self, img: torch.Tensor, Hs: int, Ws: int) -> torch.Tensor:
+        """img uint8 [B, H, W, 3] on the device -> uint8 [B, Hs, Ws, 3], dat_loader.GpuResizer's two launches; one resizer and one output
+        batch per geometry, made by its first batch (imported here: the model does not need the loader to be imported)"""
+        B, H, W, _ = img.shape
+        key = (B, H, W, Hs, Ws)
+        if key not in self._ms_resize:
+            from .dat_loader import GpuResizer
+            self._ms_resize[key] = (GpuResizer((Hs, Ws), device=img.device), torch.empty(B, Hs, Ws, 3, dtype=torch.uint8, device=img.device))
+        rz, out = self._ms_resize[key]
+        return rz.resize_flat(img.view(-1), [(H, W)] * B, out=out)
+
     def _tta_inputs(self, inp: Dict[str, Any], h0, c0):
         """(qvec, qlens, h0, c0) of the 2B rows of a flip-TTA forward: the mirrored rows behind the rows as given"""
         qvec, qlens = inp["qvec"], inp["qlens"]
@@ -771,7 +850,8 @@ class ZSGNet(nn.Module):
                 self._plans[key] = self._plans.pop(key)         # (most recently used last)
             else:
                 old = [k for k in self._plans if len(k) in (7, 8) and k[5] == "shared"]      # (of every eval dtype: one bound)
-                for k in old[:max(0, len(old) + 1 - SHARED_PLANS_MAX)]:
+                # (a multi-scale set is one plan per pass: the bound grows with the passes, so that a set never evicts its own members)
+                for k in old[:max(0, len(old) + 1 - SHARED_PLANS_MAX * (1 + len(self._eval_scales)))]:
                     del self._plans[k]
                 self._plans[key] = _Plan(self, B, H, W, T, False, Q=Q, dtype=self._eval_dtype)
             return self._plans[key]
@@ -817,7 +897,7 @@ class ZSGNet(nn.Module):
             # blind variants: no image path or no phrase path to share; the plain plan on the gathered images (a device gather)
             sub = {k: v for k, v in inp.items() if k != "img_idx"}
             sub["img"] = img.index_select(0, idx.long())
-            return self.forward(sub)
+            return self._forward_one(sub)
         tta = self._tta_on()
         Bp, Qp, H, W, Tp = self.plan_geometry(inp)
         plan = self._plan_for(Bp, H, W, Tp, Q=Qp)
@@ -849,9 +929,16 @@ class ZSGNet(nn.Module):
 
     def forward(self, inp: Dict[str, Any]) -> Dict[str, Any]:
         require_gpu()
-        img, qvec, qlens = inp["img"], inp["qvec"], inp["qlens"]
+        img = inp["img"]
         if img.device.type != "cuda" or self.device.type != "cuda":
             raise RuntimeError("ZSGNet.forward needs the model and the batch on the MI355X (no CPU fallback)")
+        if self._eval_scales and not self.training:
+            return self._forward_scales(inp)
+        return self._forward_one(inp)
+
+    def _forward_one(self, inp: Dict[str, Any]) -> Dict[str, Any]:
+        """one forward of the batch as given (under eval_scales: one pass)"""
+        img, qvec, qlens = inp["img"], inp["qvec"], inp["qlens"]
         if inp.get("img_idx") is not None:
             return self._forward_shared(inp)
         # (img may be uint8 [B, H, W, 3] as PIL decodes (dat_loader gpu_normalise): /255 then happens on the GPU.)
@@ -3269,6 +3356,7 @@ def get_default_net(num_anchors=1, cfg=None):
     net = ZSGNet(kind, num_anchors, cfg=cfg, arch=arch)
     net.eval_precision(cfg["eval_dtype"] if "eval_dtype" in cfg else "fp32")          # (raises on anything but fp32 / bf16 / bf16_act)
     net.eval_tta(cfg["eval_tta"] if "eval_tta" in cfg else "none")                    # (raises on anything but none / flip)
+    net.eval_scales(cfg["eval_scales"] if "eval_scales" in cfg else ())               # (raises on more than 4 entries or one outside [0.5, 2])
     net.wgrad_precision(cfg["wgrad_dtype"] if "wgrad_dtype" in cfg else "fp32")       # (raises on anything but fp32 / bf16)
     net.train_precision(cfg["train_dtype"] if "train_dtype" in cfg else "fp32")       # (raises on anything but fp32 / bf16_head)
     net.encoder_precision(cfg["enc_dtype"] if "enc_dtype" in cfg else "fp32")         # (raises on anything but fp32 / bf16_fwd)
