@@ -709,6 +709,33 @@ int zsg_head_shared_conv0(const float* Y, const void* img_idx, int32_t idx_i64, 
  * run to run.  img_idx is read by the kernel.  N % 4 == 0, N <= 1024, Q <= 8192. */
 int zsg_head_shared_conv0_bwd(const float* dy, const void* img_idx, int32_t idx_i64, int32_t Bi, int32_t Q, int32_t nlev, const int32_t* hw, int32_t N,
                               float* dY, void* stream);
+/* FiLM language modulation of head conv0 (cfg lang_fuse = "film"; csrc/film.hip).  zsg_head_shared_conv0 with a per-query, per-channel
+ * scale on the feature accumulator:
+ *   h1[q][p][n] = relu( (1 + gamma[q][n]) * Y[img_idx[q]][p][n] + bias[n] + G[p][n] + sum_{tap valid at p} V[q][n*9 + tap] )
+ * Layouts, block order and the out-of-range rule (NaN rows, no access outside Y) are zsg_head_shared_conv0's; gamma [Q][N] fp32.
+ * img_idx == NULL is the identity (query q reads image q) and requires Bi == Q.  FIXED ORDER, each operation rounded on its own:
+ * s = 1.0f + gamma; t = s * Y; c = (taps row-major, summed from 0) + bias; h1 = relu((t + G) + c) (without G: relu(t + c)) — with
+ * gamma = 0 the output carries the bits of zsg_head_shared_conv0.  out_bf16 = 1: `out` is bf16 [same offsets], the fp32 result rounded
+ * once to nearest-even (zsg_head_shared_conv0_bf16's store).  N % 4 == 0, N <= 1024.
+ * HBM bytes: (Q + Bi) * P * N * 4 (bf16 out: Q * 2 + Bi * 4), P = sum of h_i * w_i. */
+int zsg_head_film_conv0(const float* Y, const void* img_idx, int32_t idx_i64, const float* bias, const float* G, const float* V, const float* gamma,
+                        int32_t Bi, int32_t Q, int32_t nlev, const int32_t* hw, int32_t N, void* out, int32_t out_bf16, void* stream);
+/* Its backward into the per-image accumulator (zsg_head_shared_conv0_bwd with each query's row scaled):
+ *   dY[i][p][n] = sum over q ascending with img_idx[q] == i of (1 + gamma[q][n]) * dy[q][p][n]
+ * plain fp32 (s = 1.0f + gamma; the product rounded, then added to the running sum, which starts at 0), no atomics, every element of
+ * dY WRITTEN (zeros for a slot no query points to; an out-of-range index contributes to no slot).  With gamma = 0 it has the bits of
+ * zsg_head_shared_conv0_bwd.  img_idx == NULL: identity, Bi == Q.  N % 4 == 0, N <= 1024, Q <= 8192.  HBM bytes: (Q + Bi) * P * N * 4. */
+int zsg_head_film_conv0_bwd(const float* dy, const void* img_idx, int32_t idx_i64, const float* gamma, int32_t Bi, int32_t Q, int32_t nlev,
+                            const int32_t* hw, int32_t N, float* dY, void* stream);
+/* The gradient of the scale:  dgamma[q][n] = sum_p dy[q][p][n] * Y[img_idx[q]][p][n]  over all levels.  Accumulated in fp64 in an order
+ * fixed by (P, N, Q) alone (per-query parts write fp64 partials [q][part][N] into ws, a finalize launch adds the parts in index order) and
+ * rounded to fp32 ONCE: |error| <= 2^-23 * sum_p |dy * Y|; no float atomics, the same bits on every run.  A query whose index lies
+ * outside [0, Bi) reads nothing and gets zeros.  dgamma_t (or NULL): the transposed copy [N][Q], written by the same finalize launch.
+ * ws: zsg_head_film_dgamma_ws_bytes(Q, nlev, hw, N) bytes (-1 for a bad argument), 8-byte aligned.  N % 4 == 0, N <= 1024.
+ * HBM bytes: about 2 * Q * P * N * 4 (dy once; Y once per query, from L2 for the later queries of an image) + the partials twice. */
+int64_t zsg_head_film_dgamma_ws_bytes(int32_t Q, int32_t nlev, const int32_t* hw, int32_t N);
+int zsg_head_film_dgamma(const float* dy, const float* Y, const void* img_idx, int32_t idx_i64, int32_t Bi, int32_t Q, int32_t nlev, const int32_t* hw,
+                         int32_t N, float* dgamma, float* dgamma_t, void* ws, int64_t ws_bytes, void* stream);
 int zsg_head_border_sums(const float* dy, int32_t B, int32_t h, int32_t w, int32_t N, float* Q /* [9][B][N], += */, void* stream);
 int zsg_head_border_finalize(const float* Q, int32_t B, int32_t N, float* S1, float* S2, float* bias_grad /* [N], += ; or NULL */,
                              void* stream);

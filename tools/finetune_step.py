@@ -61,6 +61,13 @@ launches and the Winograd filter transforms.
 reports its query encoder launch by launch from per-launch events of the forward and backward programs replayed on one stream (every
 launch alone on the GPU): the side-stream (lane 1) time the encoder's launches add up to, forward and backward.
 
+    python tools/finetune_step.py --lang-fuse film [--out profiles/film_step.json]
+
+--lang-fuse film measures cfg lang_fuse, everything trainable: concat (the reference's concatenation) and film alternate, film with drawn
+film weights (gamma of a few tenths).  Each variant also reports the launches of head conv0's fusion point (the language / scale
+launches, conv0's feature GEMM, the epilogue or film launch and their backward counterparts) from per-launch events of the forward and
+backward programs replayed on one stream (every launch alone on the GPU).
+
 host_enqueue_ms_per_step: host time to enqueue a step (starting from an idle GPU; equal
 to the GPU's ms_per_step when the host, not the GPU, sets the pace).  --only NAME[,NAME] runs the named variants alone (profiling).
 """
@@ -148,6 +155,29 @@ def pool_class(v, nprof=3):
     return dict(lang_pool=net.lang_pool_mode, encoder_fwd_ms=tot("fwd"), encoder_bwd_ms=tot("bwd"), encoder_launches=len(rows),
                 fwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "fwd"), 4),
                 bwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "bwd"), 4), encoder_rows=rows)
+
+
+# cfg lang_fuse of the variant's network
+FUSE_VARIANTS = ("concat", "film")
+# the launches of head conv0's fusion point by their names in the plan (mdl._Plan._head_stack)
+FUSE_WHATS = ("att_reg_box0.", "att_reg_box.0.0", "lmap", "dgamma:", "dwe", "wgrad:att_reg_box.film", "bsum", "zero:head.Q")
+
+
+def fuse_class(v, nprof=3):
+    """the launches of head conv0's fusion point of one variant, taken as pool_class takes the query encoder's"""
+    net = v["net"]
+    plan = [p for k, p in net._plans.items() if k[-1]][0]
+    st = torch.cuda.current_stream().cuda_stream
+    acc = {}
+    for _ in range(nprof):
+        for tag, prog in (("fwd", plan.fwd), ("bwd", plan.bwd)):
+            for i, (what, fname, ms) in enumerate(prog.profile(st)):
+                acc[(tag, i, what, fname)] = acc.get((tag, i, what, fname), 0.0) + ms / nprof
+    rows = [[tag, what, fname, round(ms * 1e3, 1)] for (tag, i, what, fname), ms in sorted(acc.items()) if any(k in what for k in FUSE_WHATS)]
+    tot = lambda t: round(sum(r[3] for r in rows if r[0] == t) / 1e3, 4)
+    return dict(lang_fuse=net.lang_fuse, fusion_fwd_ms=tot("fwd"), fusion_bwd_ms=tot("bwd"), fusion_launches=len(rows),
+                fwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "fwd"), 4),
+                bwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "bwd"), 4), fusion_rows=rows)
 
 
 WGRAD_KERNELS = ("wgrad_kernel", "wino_wgrad_kernel", "wgrad_bf16_kernel", "wgrad_reduce_kernel")
@@ -302,6 +332,7 @@ def main():
     ap.add_argument("--enc-bwd-bf16", action="store_true", help="fp32 against enc_bwd_dtype = bf16; with --enc-bf16 / --train-bf16-head / "
                                                                  "--wgrad-bf16 also those switches without and with the encoder's data gradients")
     ap.add_argument("--lang-pool", action="store_true", help="cfg lang_pool: last, final, mean and attn alternate")
+    ap.add_argument("--lang-fuse", default="", choices=("", "film"), help="cfg lang_fuse: concat and film alternate")
     ap.add_argument("--only", default="", help="comma-separated variant names to run (e.g. one variant under rocprofv3)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
@@ -323,7 +354,11 @@ def main():
     enc_of = {}                              # variant -> cfg enc_dtype (default fp32)
     encb_of = {}                             # variant -> cfg enc_bwd_dtype (default fp32)
     pool_of = {}                             # variant -> cfg lang_pool (default last)
-    if a.lang_pool:
+    fuse_of = {}                             # variant -> cfg lang_fuse (default concat)
+    if a.lang_fuse:
+        variants = {k: ((), False, None, None, None, "fp32", "fp32") for k in FUSE_VARIANTS}
+        fuse_of = {k: k for k in FUSE_VARIANTS}
+    elif a.lang_pool:
         variants = {k: ((), False, None, None, None, "fp32", "fp32") for k in POOL_VARIANTS}
         pool_of = {k: k for k in POOL_VARIANTS}
     elif a.enc_bwd_bf16:
@@ -365,7 +400,8 @@ def main():
     if a.only:
         variants = {k: v for k, v in variants.items() if k in a.only.split(",")}
     for name, (prefixes, bn_frozen, clip, sync_bn, ema, wgrad_dtype, train_dtype) in variants.items():
-        net = mdl.get_default_net(9, config.get_cfg(lang_pool=pool_of[name]) if name in pool_of else cfg)
+        vcfg = config.get_cfg(lang_pool=pool_of[name]) if name in pool_of else (config.get_cfg(lang_fuse=fuse_of[name]) if name in fuse_of else cfg)
+        net = mdl.get_default_net(9, vcfg)
         net.wgrad_precision(wgrad_dtype).train_precision(train_dtype).encoder_precision(enc_of.get(name, "fp32"))
         net.encoder_backward_precision(encb_of.get(name, "fp32"))
         if sd is None:
@@ -373,6 +409,9 @@ def main():
         if "lang_pool.weight" in net.state_dict():      # (attn: a drawn scorer beside the shared weights, so the attention is not uniform)
             g = torch.Generator().manual_seed(0)
             net.load_state_dict(dict(sd, **{"lang_pool.weight": torch.randn(1, net.lstm_out_dim, generator=g) * 0.25}))
+        elif net.lang_fuse == "film":                   # (drawn film weights beside the shared weights, so the scale is not 1)
+            g = torch.Generator().manual_seed(0)
+            net.load_state_dict(dict(sd, **{"att_reg_box.film.weight": torch.randn(256, net.lstm_out_dim, generator=g) * 0.05}))
         else:
             net.load_state_dict(sd)
         net.to("cuda").train()
@@ -446,7 +485,9 @@ def main():
         if v["clip"] is not None:
             res["variants"][name].update(clip=v["clip"][0], max_norm=v["clip"][1], last_grad_norm=round(float(v["norm"]), 6),
                                          engaged=float(v["norm"]) > v["clip"][1])
-        if a.lang_pool:
+        if a.lang_fuse:
+            res["variants"][name].update(**fuse_class(v))
+        elif a.lang_pool:
             res["variants"][name].update(**pool_class(v))
         elif a.enc_bwd_bf16:
             res["variants"][name].update(enc_bwd_dtype=net._enc_bwd_dtype, enc_dtype=net._enc_dtype, train_dtype=net._train_dtype,

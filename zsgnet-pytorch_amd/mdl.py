@@ -7,6 +7,8 @@ Reference behaviour mirrored here (file:line in /root/reference/code):
   * RetinaBackBone.encode_feats mdl.py:148-159 (ResNet stem + layer1..4, Bottleneck fpn_resnet.py:61-100,
     BasicBlock :26-58) and FPN_backbone.forward fpn_resnet.py:154-178.
   * BackBone.concat_we mdl.py:69-104 (channel order [feat | language vector | grid y,x]).
+    cfg lang_fuse = film (not in the reference) also scales conv0's feature part per query and channel by 1 + W_gamma . we
+    (csrc/film.hip; definition in include/zsg.h, host twin tests/film_ref.py).
   * shared 6-conv head mdl.py:235-244 + permute_correctly :246-254 (free here: NHWC output == [B, h*w*9, 5]).
   * BiLSTM query encoder apply_lstm mdl.py:296-336, random initial state lstm_init_hidden :279-294.
     cfg lang_pool = final / mean / attn (not in the reference: its get_full_seq hook is unused) hands the head a vector of the whole
@@ -49,6 +51,7 @@ BF16_ENC_PREFIX = "backbone.encoder."         # the layers enc_dtype = "bf16_fwd
 BF16_HEAD_PREFIXES = ("backbone.fpn.", "att_reg_box.", "att_box.", "reg_box.")     # the layers train_dtype = "bf16_head" covers: no BatchNorm among them
 LSTM_DIMS = (32, 64, 128, 256)    # cfg lstm_dim: the widths csrc/lstm.hip instantiates zsg_lstm_fwd / zsg_lstm_bwd for
 LANG_POOLS = ("last", "final", "mean", "attn")      # cfg lang_pool: the sentence vector the query encoder hands to the head (_lower_lstm)
+LANG_FUSES = ("concat", "film")                     # cfg lang_fuse: how that vector meets the image in the heads' conv0 (_head_stack)
 
 LIVE_NETS = weakref.WeakSet()      # every ZSGNet alive: optim.clip_grad_norm_ finds a parameter's flat store here
 
@@ -186,6 +189,12 @@ class ZSGNet(nn.Module):
         self.same_atb = bool(cfg["use_same_atb"])
         if backbone_kind not in ("retina", "ssd_vgg"):
             raise ValueError(f"mdl_to_use={backbone_kind!r}: expected 'retina' or 'ssd_vgg' (mdl.py:410-414)")
+        # (fixed at construction: "film" owns a parameter per head stack, <head>.film.weight, so the mode decides the state dict's keys)
+        self.lang_fuse = str(cfg["lang_fuse"]) if "lang_fuse" in cfg else "concat"
+        if self.lang_fuse not in LANG_FUSES:
+            raise ValueError(f"lang_fuse={self.lang_fuse!r}: supported values are {', '.join(LANG_FUSES)}")
+        if self.lang_fuse == "film" and not (self.use_lang and self.use_img):
+            raise ValueError("lang_fuse='film' scales the image features by a function of the phrase: it needs use_lang=True and use_img=True")
         self.do_norm = bool(cfg["do_norm"])
         # fpn_resnet.py:173 tests resize_img == [600,600]; ssd_vgg.py:98 tests resize_img[0] >= 600
         self.six_hundred = (list(cfg["resize_img"]) == [600, 600]) if backbone_kind == "retina" else (cfg["resize_img"][0] >= 600)
@@ -348,6 +357,9 @@ class ZSGNet(nn.Module):
             self.store.add_vec("lstm.bias_hh_l0" + suf, H4)
         if self.lang_pool_mode == "attn":       # the attention scorer s_t = w . o_t (no bias: softmax is shift-invariant); last in the flat buffer
             self.store.add_mat("lang_pool.weight", 1, self.lstm_out_dim)
+        if self.lang_fuse == "film":            # gamma = W_gamma . we per head stack; behind every other entry: no existing offset moves
+            for prefix, _ in heads:
+                self.store.add_mat(prefix + ".film.weight", 256, self.lstm_out_dim)
 
     def _register(self):
         self._param_names = list(self.store.order)
@@ -411,6 +423,8 @@ class ZSGNet(nn.Module):
                 bound = 1.0 / math.sqrt(self.lstm_dim)
                 p.copy_((torch.rand(e.shape, generator=g) * 2 - 1) * bound)
             elif name == "lang_pool.weight":     # uniform attention: a fresh "attn" net computes "mean"
+                p.zero_()
+            elif name.endswith(".film.weight"):  # gamma = 0: a fresh "film" net computes "concat"
                 p.zero_()
             elif name.endswith(".bias") and name[:-5] in self.convs:
                 L = self.convs[name[:-5]]
@@ -2875,7 +2889,15 @@ class _Plan:
         # mdl.py:363-375): only the features go through the big implicit GEMM; the rest enters as an additive map
         #   lmap[b][p][n] = G[p][n] + sum_{tap valid at p} V[b][n*9+tap],  V = W0[:, :, :, lang] . we[b],  G = conv(grid, W0[..., grid])
         lmap = None
-        if self.shared:
+        # cfg lang_fuse = "film": EVERY plan takes the shared plans' form — the feature GEMM leaves the raw accumulator Y and one launch
+        # (zsg_head_film_conv0) writes h1 = relu((1 + gamma[q]) * Y[img_idx[q]] + bias + G + taps of V[q]), gamma = W_gamma . we from one
+        # more 1x1 launch beside V's.  A plain plan passes no index (the identity, Bi == Q).  Y is kept for the backward (d(gamma) reads
+        # it; no plan buffer is recycled).  In a plain training plan V, gamma and G sit on the side stream and are hoisted behind the
+        # query encoder, as the language maps of a "concat" plan are.
+        film = net.lang_fuse == "film"
+        Wfn = prefix + ".film.weight"
+        gam = Y = None
+        if self.shared or film:
             # Queries sharing images: the feature GEMM runs once per IMAGE SLOT and leaves its raw accumulator Y (no bias, no ReLU, no
             # additive map); ONE zsg_head_shared_conv0 launch then writes every query's h1 = relu(Y[img_idx[q]] + bias + G + taps of V[q]),
             # which takes the place of the language map launch and of conv0's epilogue.  Nothing here reduces across image slots, so a
@@ -2884,14 +2906,24 @@ class _Plan:
             # upstream DOES reduce across slots, which is why such a plan has no padding slots.
             assert Cf
             V = G = None
+            side = 1 if (film and self.training and not self.shared) else 0
+            i0 = len(self.fwd.calls)
             if Cw:
                 V = self.act(prefix + ".V", B, 1, 1, 9 * 256, requires_grad=False)
                 dv = fwd_desc(we, V, Cw, 9 * 256, 1, 1, 0, 1, wC=cp, wt_ld=cp, wc0=Cf)
-                self.fwd.add(lib.zsg_conv_igemm, dv, we.buf, self.P(W0n), V.buf, None, None, None, None, what=prefix + "0.V", lane=2)
+                self.fwd.add(lib.zsg_conv_igemm, dv, we.buf, self.P(W0n), V.buf, None, None, None, None, what=prefix + "0.V", lane=(1 if side else 2))
+            if film:
+                gam = self.act(prefix + ".gamma", B, 1, 1, 256, requires_grad=False)
+                dgm = fwd_desc(we, gam, Cw, 256, 1, 1, 0, 1, wC=Cw)
+                self.fwd.add(lib.zsg_conv_igemm, dgm, we.buf, self.P(Wfn), gam.buf, None, None, None, None, what=prefix + "0.gamma",
+                             lane=(1 if side else 2))
             if Cg:
                 G = self.packed(prefix + ".G", 1, sizes, 256)
                 dg = fwd_desc(gridmap, G, 4, 256, 3, 1, 1, 1, wC=cp, wc0=Cf + Cw)
-                self.fwd.add(lib.zsg_conv_igemm, dg, gridmap.buf, self.P(W0n), G.buf, None, None, None, None, what=prefix + "0.G")
+                self.fwd.add(lib.zsg_conv_igemm, dg, gridmap.buf, self.P(W0n), G.buf, None, None, None, None, what=prefix + "0.G", lane=side)
+            if side:
+                self._hoist.append((i0, len(self.fwd.calls)))
+                self._join_side()
             Y = self.packed(prefix + ".Y", self.B, sizes, 256)
             d0 = fwd_desc(Fp, Y, Cf, 256, 3, 1, 1, 1, wC=cp, wc0=0, relu=False)
             a0 = (Fp.buf, self.P(W0n), Y.buf, None, None, None, None)
@@ -2911,8 +2943,12 @@ class _Plan:
                 else:
                     self.fwd.add(lib.zsg_conv_igemm, d0, *a0, what=L0.name + ".feat")
             hw = torch.tensor([v for hw_ in sizes for v in hw_], dtype=torch.int32)
-            self.fwd.add(lib.zsg_head_shared_conv0_bf16 if h1.b16 else lib.zsg_head_shared_conv0, Y.buf, self.in_idx, 1, self.P(L0.name + ".bias"), G.buf if G is not None else None,
-                         V.buf if V is not None else None, self.B, B, len(sizes), hw, 256, h1.buf, what=L0.name + ".shared")
+            if film:
+                self.fwd.add(lib.zsg_head_film_conv0, Y.buf, self.in_idx, 1, self.P(L0.name + ".bias"), G.buf if G is not None else None,
+                             V.buf if V is not None else None, gam.buf, self.B, B, len(sizes), hw, 256, h1.buf, int(h1.b16), what=L0.name + ".film")
+            else:
+                self.fwd.add(lib.zsg_head_shared_conv0_bf16 if h1.b16 else lib.zsg_head_shared_conv0, Y.buf, self.in_idx, 1, self.P(L0.name + ".bias"), G.buf if G is not None else None,
+                             V.buf if V is not None else None, self.B, B, len(sizes), hw, 256, h1.buf, what=L0.name + ".shared")
         elif Cw or Cg:
             # None of this depends on the image: in training it runs on the side stream right behind the query encoder (the
             # launches are moved there after lowering, see _hoist_language_maps) and conv0 joins.
@@ -2935,8 +2971,8 @@ class _Plan:
             if side:
                 self._hoist.append((i0, len(self.fwd.calls)))
                 self._join_side()
-        if self.shared:
-            pass                          # (h1 is written by zsg_head_shared_conv0 above)
+        if self.shared or film:
+            pass                          # (h1 is written by zsg_head_shared_conv0 / zsg_head_film_conv0 above)
         elif Cf:
             d0 = fwd_desc(Fp, h1, Cf, 256, 3, 1, 1, 1, wC=cp, wc0=0, relu=True)
             a0 = (Fp.buf, self.P(W0n), h1.buf, self.P(L0.name + ".bias"), lmap.buf if lmap is not None else None, None, None)
@@ -2967,7 +3003,8 @@ class _Plan:
         h1.needs_mask = True
         w0t, b0t = self.trains(W0n), self.trains(L0.name + ".bias")
         we_rg = bool(Cw) and we.requires_grad
-        h1.requires_grad = bool(Cf and Fp.requires_grad) or we_rg or w0t or b0t
+        wft = film and self.trains(Wfn)
+        h1.requires_grad = bool(Cf and Fp.requires_grad) or we_rg or w0t or b0t or wft
 
         def head0_back():
             dy = h1.grad
@@ -2978,7 +3015,14 @@ class _Plan:
                 self.bwd.add(lib.zsg_colsum, dy.buf, 1, 0, dy.rows(), 256, 0, 256, self.G(L0.name + ".bias"), 1, what="bgrad:" + L0.name, lane=1)
             if Cf:
                 dyf = dy                 # the gradient of conv0's feature GEMM output, at the batch of the features
-                if self.shared and (w0t or Fp.requires_grad):
+                if film and (w0t or Fp.requires_grad):
+                    # FiLM: d(Y)[i] = sum_{q: idx q == i} (1 + gamma[q]) * dy[q] — the segmented sum below with each query's row scaled
+                    # (a plain plan: the identity index, one query per slot)
+                    dyf = self.packed(prefix + ".dY", self.B, sizes, 256)
+                    hwb = torch.tensor([v for hw_ in sizes for v in hw_], dtype=torch.int32)
+                    self.bwd.add(lib.zsg_head_film_conv0_bwd, dy.buf, self.in_idx, 1, gam.buf, self.B, B, len(sizes), hwb, 256, dyf.buf,
+                                 what=L0.name + ".film_bwd")
+                elif self.shared and (w0t or Fp.requires_grad):
                     # queries sharing images: sum_q X[idx q]^T dy[q] = sum_i X[i]^T dY[i], so the feature columns of dW0 and d(Fp) take
                     # the segmented sum dY[i] = sum_{q: idx q == i} dy[q] (dy is already ReLU-masked) at batch self.B; img_idx is the
                     # forward's copy in in_idx, read by the kernel
@@ -3018,6 +3062,29 @@ class _Plan:
                     gwe = self.grad_of(we)
                     dwe = fwd_desc(Wrows, S2, Cw, B, 1, 1, 0, 1, wC=Cw, wt_ld=Cw)
                     self.bwd.add(lib.zsg_conv_wgrad, dwe, Wrows.buf, S, self.base(gwe), int(gwe.gfilled), hws, hws_bytes, what="dwe:" + prefix, lane=ln)
+                    gwe.gfilled = True
+            if film and (wft or we_rg):
+                # FiLM: d(gamma)[q][n] = sum_p dy[q][p][n] * Y[idx q][p][n] (fp64, fixed order; the forward's Y is still in place), then the
+                # two small GEMMs d(W_gamma) += d(gamma)^T . we and d(we) += d(gamma) . W_gamma through the entries of the launches above
+                hwg = torch.tensor([v for hw_ in sizes for v in hw_], dtype=torch.int32)
+                nws = int(lib.zsg_head_film_dgamma_ws_bytes(B, len(sizes), hwg.data_ptr(), 256))
+                assert nws > 0
+                gws = self._buf(nws // 8, dtype=torch.float64)
+                dgm_ = self.act(prefix + ".dgamma", B, 1, 1, 256, requires_grad=False)
+                dgt = Act(self._buf(256 * B), 1, B, B, [Level(0, 1, 256, 256 * B)], prefix + ".dgamma_t")
+                self.bwd.add(lib.zsg_head_film_dgamma, dy.buf, Y.buf, self.in_idx, 1, self.B, B, len(sizes), hwg, 256, dgm_.buf,
+                             dgt.buf if we_rg else None, gws, nws, what="dgamma:" + prefix, lane=ln)
+                if wft:
+                    dwf_ = fwd_desc(we, dgm_, Cw, 256, 1, 1, 0, 1, wC=Cw)
+                    self.bwd.add(lib.zsg_conv_wgrad, dwf_, we.buf, dgm_.buf, self.G(Wfn), 1, hws, hws_bytes, what="wgrad:" + prefix + ".film", lane=ln)
+                    self.grad_ready[Wfn] = len(self.bwd.calls)
+                if we_rg:
+                    entf = net.store.entries[Wfn]
+                    Wg = Act(net.store.flat, 1, Cw, Cw, [Level(entf.offset, 1, 256, 256 * Cw)], "head.Wgamma")
+                    gwe = self.grad_of(we)
+                    dwe2 = fwd_desc(Wg, dgt, Cw, B, 1, 1, 0, 1, wC=Cw, wt_ld=Cw)
+                    self.bwd.add(lib.zsg_conv_wgrad, dwe2, Wg.buf, dgt.buf, self.base(gwe), int(gwe.gfilled), hws, hws_bytes, what="dwe.film:" + prefix,
+                                 lane=ln)
                     gwe.gfilled = True
             if Cg and w0t:
                 dys = self.packed(prefix + ".dysum", 1, sizes, 256)
