@@ -736,6 +736,43 @@ int zsg_head_film_conv0_bwd(const float* dy, const void* img_idx, int32_t idx_i6
 int64_t zsg_head_film_dgamma_ws_bytes(int32_t Q, int32_t nlev, const int32_t* hw, int32_t N);
 int zsg_head_film_dgamma(const float* dy, const float* Y, const void* img_idx, int32_t idx_i64, int32_t Bi, int32_t Q, int32_t nlev, const int32_t* hw,
                          int32_t N, float* dgamma, float* dgamma_t, void* ws, int64_t ws_bytes, void* stream);
+/* Word-level attention modulation of head conv0 (cfg lang_fuse = "words"; csrc/words.hip).  zsg_head_film_conv0 with a scale that
+ * depends on the pixel: the raw accumulator row Y[img_idx[q]][p] is the attention query over the projected tokens of phrase q,
+ *   s_t = scale * sum_n Y[img_idx[q]][p][n] * Kw[q][t][n]   (t < len),   alpha = softmax over t < len of s (max subtracted),
+ *   gamma[n] = sum_t alpha_t * Vw[q][t][n],   h1[q][p][n] = relu( (1 + gamma[n]) * Y[..][n] + bias[n] + G[p][n] + taps of V[q] )
+ * Kw, Vw [Q][T][N] fp32; lens [Q] float as the collater makes it, len = clamp(lens[q], 0, T) (a NaN counts as 0); only rows t < len of
+ * Kw / Vw are ever read.  len = 0: alpha = 0, gamma = 0.  alpha (or NULL): [Q][P][T] packed like `out` (row (Q * p0_i + q * h_i w_i + px)
+ * of T floats), every element written, exact zeros at t >= len and for an out-of-range query.  Layouts, img_idx (int32 / int64 / NULL =
+ * identity, Bi == Q), the out-of-range rule (NaN rows, no access outside Y) and out_bf16 are zsg_head_film_conv0's.
+ * FIXED ORDER, each operation rounded on its own: tokens ascending everywhere; a dot product is summed per lane over the channels
+ * 4 (l + 64 k) + e (k, then e, ascending from 0) and across the 64 lanes by a 6-step xor butterfly (offsets 32 .. 1); the softmax sums
+ * exp(s_t - max) by the same butterfly and divides; gamma is summed from 0; then film's  s = 1.0f + gamma; t = s * Y;
+ * c = (taps row-major, summed from 0) + bias; h1 = relu((t + G) + c).  With Vw = 0 the output carries the bits of zsg_head_shared_conv0;
+ * with every len = 1 (alpha = 1 exactly) those of zsg_head_film_conv0 for gamma = Vw[:, 0].  N % 4 == 0, N <= 1024, 1 <= T <= 64.
+ * HBM bytes: (Q + Bi) * P * N * 4 (bf16 out: Q * 2 + Bi * 4) + Q * P * T * 4 for alpha + 2 * Q * T * N * 4; about 4 * len * N flops per
+ * pixel row (fp32 vector math). */
+int zsg_head_words_conv0(const float* Y, const void* img_idx, int32_t idx_i64, const float* bias, const float* G, const float* V, const float* Kw,
+                         const float* Vw, const float* lens, float scale, int32_t Bi, int32_t Q, int32_t T, int32_t nlev, const int32_t* hw, int32_t N,
+                         void* out, int32_t out_bf16, float* alpha, void* stream);
+/* Its backward.  dy [Q][P][N] is the ReLU-masked gradient of h1, alpha the forward's:
+ *   dgamma = dy * Y;   dalpha_t = dgamma . Vw_t;   ds_t = alpha_t (dalpha_t - sum_k alpha_k dalpha_k)
+ *   dYq[q][p]  = (1 + gamma) * dy + scale * sum_t ds_t Kw_t       (gamma recomputed from alpha and Vw in the forward's order;
+ *                                                                  s = 1.0f + gamma; a = s * dy; b = scale * sum; dYq = a + b)
+ *   dKw[q][t] = scale * sum_p ds_t(p) * Y[img_idx[q]][p]          dVw[q][t] = sum_p alpha_t(p) * dgamma(p)
+ * dYq [Q][P][N] packed like dy: one row per query, every element written (a shared-image plan folds it into the per-image accumulator
+ * with zsg_head_shared_conv0_bwd; with Vw = 0 it carries dy's values).  dKw / dVw [Q][T][N]: the sums over p run in fp64 (every term one
+ * fma of exact fp32 products) in an order fixed by (P, N, Q, T) alone — per-block partials in ws, then a finalize launch adds the parts in
+ * index order — and are rounded to fp32 ONCE (dKw after the fp64 product with scale): given the fp32 ds / alpha of the first launch,
+ * |error| <= 2^-23 * scale * sum_p |ds_t * Y|  resp.  2^-23 * sum_p |alpha_t * dy * Y|.  Rows t >= len are exact zeros; a query whose
+ * index lies outside [0, Bi) reads nothing and gets zeros everywhere.  No float atomics: the same bits on every run.  Each of dYq, dKw,
+ * dVw may be NULL (a frozen consumer), not all three; with dVw alone the per-pixel launch (dYq, ds) is not issued.  ws: zsg_head_words_bwd_ws_bytes(Q, T, nlev, hw, N) bytes (-1 for a bad argument),
+ * 16-byte aligned.  N % 4 == 0, N <= 1024, 1 <= T <= 64.
+ * HBM bytes: 3 * Q * P * N * 4 (dy, Y, dYq) + 2 * Q * P * T * 4 for the pixel launch; dy and Y once more per tile of 4 tokens below
+ * max len (from L2 where they fit) and the fp64 partials twice for dKw / dVw. */
+int64_t zsg_head_words_bwd_ws_bytes(int32_t Q, int32_t T, int32_t nlev, const int32_t* hw, int32_t N);
+int zsg_head_words_conv0_bwd(const float* dy, const float* Y, const void* img_idx, int32_t idx_i64, const float* Kw, const float* Vw, const float* alpha,
+                             const float* lens, float scale, int32_t Bi, int32_t Q, int32_t T, int32_t nlev, const int32_t* hw, int32_t N, float* dYq,
+                             float* dKw, float* dVw, void* ws, int64_t ws_bytes, void* stream);
 int zsg_head_border_sums(const float* dy, int32_t B, int32_t h, int32_t w, int32_t N, float* Q /* [9][B][N], += */, void* stream);
 int zsg_head_border_finalize(const float* Q, int32_t B, int32_t N, float* S1, float* S2, float* bias_grad /* [N], += ; or NULL */,
                              void* stream);

@@ -68,6 +68,12 @@ film weights (gamma of a few tenths).  Each variant also reports the launches of
 launches, conv0's feature GEMM, the epilogue or film launch and their backward counterparts) from per-launch events of the forward and
 backward programs replayed on one stream (every launch alone on the GPU).
 
+    python tools/finetune_step.py --lang-fuse concat,film,words [--out profiles/words_step.json]
+
+A comma-separated list names the modes to alternate (concat always runs).  words (word-level attention, drawn key / value weights) needs
+the BiLSTM's per-token output and so runs with lang_pool = final, the full-sequence program whose vector is closest to the default's; its
+difference to film therefore includes that encoder's (side-stream) cost.
+
 host_enqueue_ms_per_step: host time to enqueue a step (starting from an idle GPU; equal
 to the GPU's ms_per_step when the host, not the GPU, sets the pace).  --only NAME[,NAME] runs the named variants alone (profiling).
 """
@@ -158,9 +164,10 @@ def pool_class(v, nprof=3):
 
 
 # cfg lang_fuse of the variant's network
-FUSE_VARIANTS = ("concat", "film")
+FUSE_VARIANTS = ("concat", "film", "words")
 # the launches of head conv0's fusion point by their names in the plan (mdl._Plan._head_stack)
-FUSE_WHATS = ("att_reg_box0.", "att_reg_box.0.0", "lmap", "dgamma:", "dwe", "wgrad:att_reg_box.film", "bsum", "zero:head.Q")
+FUSE_WHATS = ("att_reg_box0.", "att_reg_box.0.0", "lmap", "dgamma:", "dwe", "wgrad:att_reg_box.film", "bsum", "zero:head.Q", "wgrad:att_reg_box.words", "dhseq.",
+              "transpose:att_reg_box")
 
 
 def fuse_class(v, nprof=3):
@@ -332,7 +339,7 @@ def main():
     ap.add_argument("--enc-bwd-bf16", action="store_true", help="fp32 against enc_bwd_dtype = bf16; with --enc-bf16 / --train-bf16-head / "
                                                                  "--wgrad-bf16 also those switches without and with the encoder's data gradients")
     ap.add_argument("--lang-pool", action="store_true", help="cfg lang_pool: last, final, mean and attn alternate")
-    ap.add_argument("--lang-fuse", default="", choices=("", "film"), help="cfg lang_fuse: concat and film alternate")
+    ap.add_argument("--lang-fuse", default="", help="cfg lang_fuse: concat and the named modes (film, words; comma-separated) alternate")
     ap.add_argument("--only", default="", help="comma-separated variant names to run (e.g. one variant under rocprofv3)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
@@ -356,8 +363,12 @@ def main():
     pool_of = {}                             # variant -> cfg lang_pool (default last)
     fuse_of = {}                             # variant -> cfg lang_fuse (default concat)
     if a.lang_fuse:
-        variants = {k: ((), False, None, None, None, "fp32", "fp32") for k in FUSE_VARIANTS}
-        fuse_of = {k: k for k in FUSE_VARIANTS}
+        asked = [m for m in a.lang_fuse.split(",") if m]
+        if [m for m in asked if m not in FUSE_VARIANTS]:
+            ap.error(f"--lang-fuse: expected a comma-separated list of {', '.join(FUSE_VARIANTS)}")
+        modes = [m for m in FUSE_VARIANTS if m == "concat" or m in asked]
+        variants = {k: ((), False, None, None, None, "fp32", "fp32") for k in modes}
+        fuse_of = {k: k for k in modes}
     elif a.lang_pool:
         variants = {k: ((), False, None, None, None, "fp32", "fp32") for k in POOL_VARIANTS}
         pool_of = {k: k for k in POOL_VARIANTS}
@@ -400,7 +411,7 @@ def main():
     if a.only:
         variants = {k: v for k, v in variants.items() if k in a.only.split(",")}
     for name, (prefixes, bn_frozen, clip, sync_bn, ema, wgrad_dtype, train_dtype) in variants.items():
-        vcfg = config.get_cfg(lang_pool=pool_of[name]) if name in pool_of else (config.get_cfg(lang_fuse=fuse_of[name]) if name in fuse_of else cfg)
+        vcfg = config.get_cfg(lang_pool=pool_of[name]) if name in pool_of else (config.get_cfg(lang_fuse=fuse_of[name], **({"lang_pool": "final"} if fuse_of[name] == "words" else {})) if name in fuse_of else cfg)
         net = mdl.get_default_net(9, vcfg)
         net.wgrad_precision(wgrad_dtype).train_precision(train_dtype).encoder_precision(enc_of.get(name, "fp32"))
         net.encoder_backward_precision(encb_of.get(name, "fp32"))
@@ -412,6 +423,10 @@ def main():
         elif net.lang_fuse == "film":                   # (drawn film weights beside the shared weights, so the scale is not 1)
             g = torch.Generator().manual_seed(0)
             net.load_state_dict(dict(sd, **{"att_reg_box.film.weight": torch.randn(256, net.lstm_out_dim, generator=g) * 0.05}))
+        elif net.lang_fuse == "words":                  # (drawn key / value weights: the attention is not uniform, the scale not 1)
+            g = torch.Generator().manual_seed(0)
+            net.load_state_dict(dict(sd, **{f"att_reg_box.words.{kv}.weight": torch.randn(256, net.lstm_out_dim, generator=g) * 0.05
+                                            for kv in ("key", "value")}))
         else:
             net.load_state_dict(sd)
         net.to("cuda").train()

@@ -9,6 +9,8 @@ Reference behaviour mirrored here (file:line in /root/reference/code):
   * BackBone.concat_we mdl.py:69-104 (channel order [feat | language vector | grid y,x]).
     cfg lang_fuse = film (not in the reference) also scales conv0's feature part per query and channel by 1 + W_gamma . we
     (csrc/film.hip; definition in include/zsg.h, host twin tests/film_ref.py).
+    cfg lang_fuse = words (not in the reference) makes that scale a function of the pixel: conv0's raw feature accumulator attends over
+    the BiLSTM's per-token output (csrc/words.hip; definition in include/zsg.h, host twin tests/words_ref.py).
   * shared 6-conv head mdl.py:235-244 + permute_correctly :246-254 (free here: NHWC output == [B, h*w*9, 5]).
   * BiLSTM query encoder apply_lstm mdl.py:296-336, random initial state lstm_init_hidden :279-294.
     cfg lang_pool = final / mean / attn (not in the reference: its get_full_seq hook is unused) hands the head a vector of the whole
@@ -51,7 +53,7 @@ BF16_ENC_PREFIX = "backbone.encoder."         # the layers enc_dtype = "bf16_fwd
 BF16_HEAD_PREFIXES = ("backbone.fpn.", "att_reg_box.", "att_box.", "reg_box.")     # the layers train_dtype = "bf16_head" covers: no BatchNorm among them
 LSTM_DIMS = (32, 64, 128, 256)    # cfg lstm_dim: the widths csrc/lstm.hip instantiates zsg_lstm_fwd / zsg_lstm_bwd for
 LANG_POOLS = ("last", "final", "mean", "attn")      # cfg lang_pool: the sentence vector the query encoder hands to the head (_lower_lstm)
-LANG_FUSES = ("concat", "film")                     # cfg lang_fuse: how that vector meets the image in the heads' conv0 (_head_stack)
+LANG_FUSES = ("concat", "film", "words")                   # cfg lang_fuse: how that vector meets the image in the heads' conv0 (_head_stack)
 
 LIVE_NETS = weakref.WeakSet()      # every ZSGNet alive: optim.clip_grad_norm_ finds a parameter's flat store here
 
@@ -182,8 +184,10 @@ class ZSGNet(nn.Module):
         self.lang_pool_mode = str(cfg["lang_pool"]) if "lang_pool" in cfg else "last"
         if self.lang_pool_mode not in LANG_POOLS:
             raise ValueError(f"lang_pool={self.lang_pool_mode!r}: supported values are {', '.join(LANG_POOLS)}")
-        if self.lang_pool_mode == "final" and not self.bid:
-            self.lang_pool_mode = "last"        # one direction: h_n IS the forward state at len - 1, the same program
+        if self.lang_pool_mode == "final" and not self.bid and not ("lang_fuse" in cfg and str(cfg["lang_fuse"]) == "words"):
+            # one direction: h_n IS the forward state at len - 1, the same program (lang_fuse = "words" keeps the sequence program: it reads
+            # the per-token output, which only that program writes; the vector is the same)
+            self.lang_pool_mode = "last"
         self.use_lang = bool(cfg["use_lang"])
         self.use_img = bool(cfg["use_img"])
         self.same_atb = bool(cfg["use_same_atb"])
@@ -195,6 +199,12 @@ class ZSGNet(nn.Module):
             raise ValueError(f"lang_fuse={self.lang_fuse!r}: supported values are {', '.join(LANG_FUSES)}")
         if self.lang_fuse == "film" and not (self.use_lang and self.use_img):
             raise ValueError("lang_fuse='film' scales the image features by a function of the phrase: it needs use_lang=True and use_img=True")
+        if self.lang_fuse == "words":
+            if not (self.use_lang and self.use_img):
+                raise ValueError("lang_fuse='words' lets every pixel attend over the phrase's words: it needs use_lang=True and use_img=True")
+            if self.lang_pool_mode == "last":
+                raise ValueError("lang_fuse='words' reads the BiLSTM's per-token output, which lang_pool='last' never forms (its reverse cell sees "
+                                 "one token): set lang_pool to 'final', 'mean' or 'attn'")
         self.do_norm = bool(cfg["do_norm"])
         # fpn_resnet.py:173 tests resize_img == [600,600]; ssd_vgg.py:98 tests resize_img[0] >= 600
         self.six_hundred = (list(cfg["resize_img"]) == [600, 600]) if backbone_kind == "retina" else (cfg["resize_img"][0] >= 600)
@@ -360,6 +370,10 @@ class ZSGNet(nn.Module):
         if self.lang_fuse == "film":            # gamma = W_gamma . we per head stack; behind every other entry: no existing offset moves
             for prefix, _ in heads:
                 self.store.add_mat(prefix + ".film.weight", 256, self.lstm_out_dim)
+        if self.lang_fuse == "words":           # Kw = W_key . o_t, Vw = W_value . o_t per head stack; behind every other entry, key then value
+            for prefix, _ in heads:
+                self.store.add_mat(prefix + ".words.key.weight", 256, self.lstm_out_dim)
+                self.store.add_mat(prefix + ".words.value.weight", 256, self.lstm_out_dim)
 
     def _register(self):
         self._param_names = list(self.store.order)
@@ -426,6 +440,11 @@ class ZSGNet(nn.Module):
                 p.zero_()
             elif name.endswith(".film.weight"):  # gamma = 0: a fresh "film" net computes "concat"
                 p.zero_()
+            elif name.endswith(".words.value.weight"):       # gamma = 0 whatever the attention: a fresh "words" net computes "concat"
+                p.zero_()
+            elif name.endswith(".words.key.weight"):         # (declared last: no existing net's draws change)
+                bound = 1.0 / math.sqrt(self.lstm_out_dim)
+                p.copy_((torch.rand(e.shape, generator=g) * 2 - 1) * bound)
             elif name.endswith(".bias") and name[:-5] in self.convs:
                 L = self.convs[name[:-5]]
                 bound = 1.0 / math.sqrt(L.cin * L.k * L.k)
@@ -2724,7 +2743,11 @@ class _Plan:
         x[len-1] down to x[0].  final: we [B, 2H] = [f_{len-1} | r_0], the two end states.  mean / attn: the directions write the padded
         output o [B, T, 2H] and zsg_lang_pool_fwd reduces it over each query's valid tokens; on the tape the pool's backward comes first and
         hands d(o) to the two BPTT sweeps.  Everything the steps save is token-aligned, so the weight / bias gradients are the GEMMs and
-        column sums of the `last` program over [B * T] rows.  All on the side stream (lane 1)."""
+        column sums of the `last` program over [B * T] rows.  All on the side stream (lane 1).
+        cfg lang_fuse = "words": o is written in every mode (final: beside the end states, by the same launches) and kept as self._hseq
+        for the heads' key / value projections; the heads leave their d(o) = dKw . W_key + dVw . W_value as deferred launches in
+        self._words_dhseq, which a tape entry replays BEHIND the pool's backward (that launch writes its d(o) everywhere; in final mode
+        the heads' is the only one) and ahead of the two sweeps, accumulating into the one buffer the sweeps read."""
         net, B, T = self.net, self.Q, self.T
         E, Hd, D = net.emb_dim, net.lstm_dim, net.lstm_out_dim
         H4 = 4 * Hd
@@ -2741,11 +2764,18 @@ class _Plan:
         we.requires_grad = any(dir_trains(suf) for suf, _ in dirs) or pw_trains
         x_all = Act(self.in_qvec, B, E, E, [Level(0, 1, T, T * E)], "qvec")
         x_all.requires_grad = False
-        hseq = self._buf(B * T * D) if pooled else None
+        words = net.lang_fuse == "words"
+        hseq = self._buf(B * T * D) if (pooled or words) else None
         alpha = self._buf(B * T) if attn else None
         pw = self.P("lang_pool.weight") if attn else None
         lens = self.in_qlens
         grads = {}                         # d(o) of the pool's backward, read by the two sweeps emitted behind it
+        if words:
+            if not 1 <= T <= 64:           # (zsg_head_words_conv0's contract: one lane of the wave per token)
+                raise ValueError(f"lang_fuse='words' attends over at most 64 token positions per query; this batch has qvec of {T}")
+            self._hseq = Act(hseq, B, D, D, [Level(0, 1, T, T * D)], "hseq")
+            self._hseq.requires_grad = any(dir_trains(suf) for suf, _ in dirs)      # (the heads form d(o) only when a direction trains)
+            self._words_dhseq = []         # emit(dst, filled) of every head stack, filled in by _head_stack's backward
         for suf, di in dirs:
             gin = self.act("gin" + suf, B, 1, T, H4)
             d = fwd_desc(x_all, gin, E, H4, 1, 1, 0, 1, wC=E)
@@ -2779,6 +2809,15 @@ class _Plan:
                         continue
                     self.bwd.add(lib.zsg_colsum, dg.buf, 1, 0, B * T, H4, 0, H4, self.G(bname + suf), 1, what="bgrad:" + bname + suf, lane=1)
             self.tape.append(back)
+        if words:
+            def words_back():              # (replayed behind pool_back, ahead of the two sweeps)
+                for emit in self._words_dhseq:
+                    if "dhseq" not in grads:
+                        grads["dhseq"] = self._buf(B * T * D)
+                        emit(grads["dhseq"], False)
+                    else:
+                        emit(grads["dhseq"], True)
+            self.tape.append(words_back)
         if pooled:
             self.fwd.add(lib.zsg_lang_pool_fwd, hseq, lens, pw, pmode, B, T, D, we.buf, alpha, what="lang_pool", lane=1)
 
@@ -2894,10 +2933,17 @@ class _Plan:
         # more 1x1 launch beside V's.  A plain plan passes no index (the identity, Bi == Q).  Y is kept for the backward (d(gamma) reads
         # it; no plan buffer is recycled).  In a plain training plan V, gamma and G sit on the side stream and are hoisted behind the
         # query encoder, as the language maps of a "concat" plan are.
+        # cfg lang_fuse = "words": film's form with a scale per PIXEL — Kw = W_key . o_t, Vw = W_value . o_t from two 1x1 launches over the
+        # [Q * T] rows of the BiLSTM's output (beside V on the side stream, hoisted with it), and zsg_head_words_conv0 in place of the film
+        # launch: every pixel's Y row attends over its phrase's tokens.  Training plans keep alpha [Q][P][T] and Y for the backward.
         film = net.lang_fuse == "film"
+        words = net.lang_fuse == "words"
+        mod = film or words
         Wfn = prefix + ".film.weight"
-        gam = Y = None
-        if self.shared or film:
+        Wkn, Wvn = prefix + ".words.key.weight", prefix + ".words.value.weight"
+        wscale = 1.0 / math.sqrt(256.0)
+        gam = Y = Kw = Vw = walpha = None
+        if self.shared or mod:
             # Queries sharing images: the feature GEMM runs once per IMAGE SLOT and leaves its raw accumulator Y (no bias, no ReLU, no
             # additive map); ONE zsg_head_shared_conv0 launch then writes every query's h1 = relu(Y[img_idx[q]] + bias + G + taps of V[q]),
             # which takes the place of the language map launch and of conv0's epilogue.  Nothing here reduces across image slots, so a
@@ -2906,7 +2952,7 @@ class _Plan:
             # upstream DOES reduce across slots, which is why such a plan has no padding slots.
             assert Cf
             V = G = None
-            side = 1 if (film and self.training and not self.shared) else 0
+            side = 1 if (mod and self.training and not self.shared) else 0
             i0 = len(self.fwd.calls)
             if Cw:
                 V = self.act(prefix + ".V", B, 1, 1, 9 * 256, requires_grad=False)
@@ -2917,6 +2963,16 @@ class _Plan:
                 dgm = fwd_desc(we, gam, Cw, 256, 1, 1, 0, 1, wC=Cw)
                 self.fwd.add(lib.zsg_conv_igemm, dgm, we.buf, self.P(Wfn), gam.buf, None, None, None, None, what=prefix + "0.gamma",
                              lane=(1 if side else 2))
+            if words:
+                hs = self._hseq
+                Dh = net.lstm_out_dim
+                Kw, Vw = (self.act(prefix + nm, B, 1, self.T, 256, requires_grad=False) for nm in (".Kw", ".Vw"))
+                for dst, wn, nm in ((Kw, Wkn, "0.Kw"), (Vw, Wvn, "0.Vw")):
+                    dkv = fwd_desc(hs, dst, Dh, 256, 1, 1, 0, 1, wC=Dh)
+                    self.fwd.add(lib.zsg_conv_igemm, dkv, hs.buf, self.P(wn), dst.buf, None, None, None, None, what=prefix + nm,
+                                 lane=(1 if side else 2))
+                if self.training:
+                    walpha = self._buf(B * sum(hh * ww for hh, ww in sizes) * self.T)
             if Cg:
                 G = self.packed(prefix + ".G", 1, sizes, 256)
                 dg = fwd_desc(gridmap, G, 4, 256, 3, 1, 1, 1, wC=cp, wc0=Cf + Cw)
@@ -2946,6 +3002,10 @@ class _Plan:
             if film:
                 self.fwd.add(lib.zsg_head_film_conv0, Y.buf, self.in_idx, 1, self.P(L0.name + ".bias"), G.buf if G is not None else None,
                              V.buf if V is not None else None, gam.buf, self.B, B, len(sizes), hw, 256, h1.buf, int(h1.b16), what=L0.name + ".film")
+            elif words:
+                self.fwd.add(lib.zsg_head_words_conv0, Y.buf, self.in_idx, 1, self.P(L0.name + ".bias"), G.buf if G is not None else None,
+                             V.buf if V is not None else None, Kw.buf, Vw.buf, self.in_qlens, wscale, self.B, B, self.T, len(sizes), hw, 256, h1.buf,
+                             int(h1.b16), walpha, what=L0.name + ".words")
             else:
                 self.fwd.add(lib.zsg_head_shared_conv0_bf16 if h1.b16 else lib.zsg_head_shared_conv0, Y.buf, self.in_idx, 1, self.P(L0.name + ".bias"), G.buf if G is not None else None,
                              V.buf if V is not None else None, self.B, B, len(sizes), hw, 256, h1.buf, what=L0.name + ".shared")
@@ -2971,8 +3031,8 @@ class _Plan:
             if side:
                 self._hoist.append((i0, len(self.fwd.calls)))
                 self._join_side()
-        if self.shared or film:
-            pass                          # (h1 is written by zsg_head_shared_conv0 / zsg_head_film_conv0 above)
+        if self.shared or mod:
+            pass                          # (h1 is written by zsg_head_shared_conv0 / zsg_head_film_conv0 / zsg_head_words_conv0 above)
         elif Cf:
             d0 = fwd_desc(Fp, h1, Cf, 256, 3, 1, 1, 1, wC=cp, wc0=0, relu=True)
             a0 = (Fp.buf, self.P(W0n), h1.buf, self.P(L0.name + ".bias"), lmap.buf if lmap is not None else None, None, None)
@@ -3004,7 +3064,9 @@ class _Plan:
         w0t, b0t = self.trains(W0n), self.trains(L0.name + ".bias")
         we_rg = bool(Cw) and we.requires_grad
         wft = film and self.trains(Wfn)
-        h1.requires_grad = bool(Cf and Fp.requires_grad) or we_rg or w0t or b0t or wft
+        wkt, wvt = words and self.trains(Wkn), words and self.trains(Wvn)
+        hs_rg = words and self._hseq.requires_grad
+        h1.requires_grad = bool(Cf and Fp.requires_grad) or we_rg or w0t or b0t or wft or wkt or wvt or hs_rg
 
         def head0_back():
             dy = h1.grad
@@ -3015,7 +3077,31 @@ class _Plan:
                 self.bwd.add(lib.zsg_colsum, dy.buf, 1, 0, dy.rows(), 256, 0, 256, self.G(L0.name + ".bias"), 1, what="bgrad:" + L0.name, lane=1)
             if Cf:
                 dyf = dy                 # the gradient of conv0's feature GEMM output, at the batch of the features
-                if film and (w0t or Fp.requires_grad):
+                dKw_ = dVw_ = None
+                if words and (w0t or Fp.requires_grad or wkt or wvt or hs_rg):
+                    # words: ONE call gives d(Y) per query, dYq = (1 + gamma) dy + c sum_t ds_t Kw_t, and the fp64 fixed-order sums
+                    # dKw / dVw over the pixels (the forward's Y and alpha are still in place); each output only where someone reads it.
+                    # Queries sharing images: the plain segmented sum of the shared plans folds dYq into the per-image accumulator.
+                    need_dy = w0t or Fp.requires_grad
+                    hwb = torch.tensor([v for hw_ in sizes for v in hw_], dtype=torch.int32)
+                    nws = int(lib.zsg_head_words_bwd_ws_bytes(B, self.T, len(sizes), hwb.data_ptr(), 256))
+                    assert nws > 0
+                    wws = self._buf((nws + 7) // 8, dtype=torch.float64)
+                    dYq = self.packed(prefix + ".dYq", B, sizes, 256) if need_dy else None
+                    if wkt or hs_rg:
+                        dKw_ = self.act(prefix + ".dKw", B, 1, self.T, 256, requires_grad=False)
+                    if wvt or hs_rg:
+                        dVw_ = self.act(prefix + ".dVw", B, 1, self.T, 256, requires_grad=False)
+                    self.bwd.add(lib.zsg_head_words_conv0_bwd, dy.buf, Y.buf, self.in_idx, 1, Kw.buf, Vw.buf, walpha, self.in_qlens, wscale, self.B, B,
+                                 self.T, len(sizes), hwb, 256, dYq.buf if need_dy else None, dKw_.buf if dKw_ is not None else None,
+                                 dVw_.buf if dVw_ is not None else None, wws, nws, what=L0.name + ".words_bwd")
+                    if need_dy and self.shared:
+                        dyf = self.packed(prefix + ".dY", self.B, sizes, 256)
+                        self.bwd.add(lib.zsg_head_shared_conv0_bwd, dYq.buf, self.in_idx, 1, self.B, B, len(sizes), hwb, 256, dyf.buf,
+                                     what=L0.name + ".shared_bwd")
+                    elif need_dy:
+                        dyf = dYq
+                elif film and (w0t or Fp.requires_grad):
                     # FiLM: d(Y)[i] = sum_{q: idx q == i} (1 + gamma[q]) * dy[q] — the segmented sum below with each query's row scaled
                     # (a plain plan: the identity index, one query per slot)
                     dyf = self.packed(prefix + ".dY", self.B, sizes, 256)
@@ -3086,6 +3172,28 @@ class _Plan:
                     self.bwd.add(lib.zsg_conv_wgrad, dwe2, Wg.buf, dgt.buf, self.base(gwe), int(gwe.gfilled), hws, hws_bytes, what="dwe.film:" + prefix,
                                  lane=ln)
                     gwe.gfilled = True
+            if words and (dKw_ is not None or dVw_ is not None):
+                # words: d(W_key) += dKw^T . o and d(W_value) += dVw^T . o over the [Q * T] token rows through the small-GEMM entry above;
+                # d(o) = dKw . W_key + dVw . W_value through the same entry on the transposed gradients [256][Q * T] — DEFERRED: the query
+                # encoder's tape replays these launches behind the pool's backward (_lower_lstm_seq), on its side stream
+                hs, Dh, QT = self._hseq, net.lstm_out_dim, B * self.T
+                for dkv_, wn, trn, nm in ((dKw_, Wkn, wkt, "key"), (dVw_, Wvn, wvt, "value")):
+                    if trn:
+                        dwk = fwd_desc(hs, dkv_, Dh, 256, 1, 1, 0, 1, wC=Dh)
+                        self.bwd.add(lib.zsg_conv_wgrad, dwk, hs.buf, dkv_.buf, self.G(wn), 1, hws, hws_bytes, what=f"wgrad:{prefix}.words.{nm}", lane=ln)
+                        self.grad_ready[wn] = len(self.bwd.calls)
+                if hs_rg:
+                    def emit_dhseq(dst, filled):
+                        for dkv_, wn, nm in ((dKw_, Wkn, "key"), (dVw_, Wvn, "value")):
+                            ent = net.store.entries[wn]
+                            Wm = Act(net.store.flat, 1, Dh, Dh, [Level(ent.offset, 1, 256, 256 * Dh)], "head.W" + nm)
+                            dt = Act(self._buf(256 * QT), 1, QT, QT, [Level(0, 1, 256, 256 * QT)], f"{prefix}.d{nm}_t")
+                            self.bwd.add(lib.zsg_transpose_w, dkv_.buf, dt.buf, QT, 1, 256, QT, what=f"transpose:{prefix}.d{nm}", lane=1)
+                            dho = fwd_desc(Wm, dt, Dh, QT, 1, 1, 0, 1, wC=Dh, wt_ld=Dh)
+                            self.bwd.add(lib.zsg_conv_wgrad, dho, Wm.buf, dt.buf, dst, int(filled), self.wg_ws, self.wg_ws_bytes,
+                                         what=f"dhseq.{nm}:{prefix}", lane=1)
+                            filled = True
+                    self._words_dhseq.append(emit_dhseq)
             if Cg and w0t:
                 dys = self.packed(prefix + ".dysum", 1, sizes, 256)
                 for i, (h, w) in enumerate(sizes):
