@@ -988,6 +988,35 @@ int zsg_eval_vote(const float* out5, const float* annot, const float* anchors, c
                   int32_t pre_n, int32_t K, float vote_thr, float acc_thr, const float* topk_boxes, const float* topk_scores,
                   const int32_t* topk_idx, const int32_t* topk_n, float* vote_boxes, int32_t* vote_n, int32_t* hit_rank, float* acc_at,
                   void* ws, size_t ws_bytes, void* stream);
+/* Soft-NMS selection of the K boxes per query (csrc/softnms.hip; Evaluator with cfg eval_nms = "soft_linear" / "soft_gauss"; Bodla et
+ * al., ICCV 2017; no counterpart in the reference; the host definition is tests/softnms_ref.py).  zsg_eval_topk with another selection
+ * rule: a picked box lowers the weights of its neighbours instead of deleting them, and selection goes on over the decayed weights.
+ * Candidates: exactly zsg_eval_topk's — the first nc = min(pre_n, A) anchors ordered by (fp32 sigmoid score descending, anchor index
+ * ascending), a NaN score below every number — decoded as there (y1x1y2x2 in [-1, 1], then pixels x1y1x2y2).  Candidate position c is
+ * its rank.
+ * Weights: fp64, w_c = (double)s_c at the start.  A candidate with a NaN score is never eligible after row 0.
+ * Row 0: unconditionally candidate 0, as under hard NMS: row 0 is bit-identical to zsg_eval_topk's row 0 and so to zsg_eval's
+ * pred_boxes / pred_scores / pred_idx (a query whose scores are all NaN: box and index of anchor 0 as there, the score NaN as in
+ * zsg_eval_topk).
+ * Rows r = 1 .. K-1: among the candidates not yet picked whose score is not NaN, the one with the largest w_c, ties to the smaller
+ * position; the rows end when there is none, or when that weight is < (double)min_score.
+ * Decay after picking m: for every unpicked candidate c, u = IoU(box_m, box_c) (the NMS's IoU: kept box first, the [-1, 1] coordinates,
+ * fp32 in loss.hip's operation order); method 1 (linear): if u > nms_thr (fp32 compare), w_c *= 1.0 - (double)u;  method 2 (gauss):
+ * if u == u, w_c *= exp(-((double)u * (double)u) / (double)sigma) with the fp64 exp (nms_thr is not read).  A NaN u never decays.
+ * Outputs: zsg_eval_topk's arrays — topk_boxes [B][K][4] pixels x1y1x2y2, topk_scores [B][K] = (float)w at pick time (row 0: the
+ * score itself), topk_idx [B][K] int32, topk_n [B] int32; rows past topk_n are boxes 0, score 0, index -1.  With annot: hit_rank [B] =
+ * first row r with IoU(box_r, annot) >= acc_thr, K when none; acc_at [K] = mean over the batch of (hit_rank <= j).  annot, hit_rank and
+ * acc_at may be NULL (acc_at needs hit_rank, hit_rank needs annot).
+ * Three launches (range sort, one 256-thread finishing block per query, the Acc@ mean): no atomics, no host synchronisation, the same
+ * bits on every run.
+ * Limits (else -1, nothing launched or written, zsg_last_error names the argument): 1 <= K <= 64, K <= pre_n <= 512, B <= 65535;
+ * method 1 or 2; 0 <= nms_thr <= 1; sigma > 0 and finite; 0 <= min_score < 1; ws 8-byte aligned with
+ * ws_bytes >= zsg_eval_topk_soft_workspace_bytes(B, A, pre_n, K). */
+size_t zsg_eval_topk_soft_workspace_bytes(int32_t B, int32_t A, int32_t pre_n, int32_t K);
+int zsg_eval_topk_soft(const float* out5, const float* annot, const float* anchors, const float* img_size, int32_t B, int32_t A,
+                       int32_t pre_n, int32_t K, float nms_thr, float acc_thr, int32_t method, float sigma, float min_score,
+                       float* topk_boxes, float* topk_scores, int32_t* topk_idx, int32_t* topk_n, int32_t* hit_rank, float* acc_at,
+                       void* ws, size_t ws_bytes, void* stream);
 /* IoU table [B][A] (tests / diagnostics) */
 int zsg_iou(const float* boxes, const float* anchors, int32_t B, int32_t A, float* iou, void* stream);
 

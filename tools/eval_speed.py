@@ -3,7 +3,8 @@
 images per batch; without --images the one-image-per-query path, as before.
 --topk K [--pre-nms N] [--queries Q]: the evaluator call alone, on a fixed [Q, 17460, 5] head output: eval_topk = 1 (zsg_eval only) against
 eval_topk = K in eval mode (zsg_eval + zsg_eval_topk), alternating; device events around groups of calls, the median per call of each, one
-JSON line (--json PATH also writes it to a file).
+JSON line (--json PATH also writes it to a file).  --nms soft_linear|soft_gauss (one or both): the same call with cfg eval_nms set
+(zsg_eval + zsg_eval_topk_soft) joins the alternation, `<name>_us` per rule.
 --dtype fp32|bf16|bf16_act: cfg eval_dtype of the network (the forward paths; --topk times no network).
 --tta flip: flip test-time augmentation (cfg eval_tta): the eval FORWARD of the same network at the same B = --queries, three ways,
 alternating — the plain batch, the plain batch at 2B, the TTA batch (2B rows in one forward + the staging and merge launches) — and the
@@ -28,6 +29,8 @@ ap.add_argument("--images", type=int, default=None, help="distinct images per ba
 ap.add_argument("--queries", type=int, default=16, help="queries per batch")
 ap.add_argument("--topk", type=int, default=None, help="time the evaluator call with and without the top-k launch (K boxes per query)")
 ap.add_argument("--pre-nms", type=int, default=128, help="with --topk: candidates per query that enter the NMS")
+ap.add_argument("--nms", nargs="+", choices=("soft_linear", "soft_gauss"), default=[],
+                help="with --topk: also time the evaluator call with eval_nms set to these Soft-NMS rules")
 ap.add_argument("--tta", choices=("flip",), default=None, help="time the eval forward plain at B, plain at 2B and with eval_tta=flip at B, and the two TTA launches alone")
 ap.add_argument("--scales", default=None, help="comma-separated eval_scales, e.g. 0.75,1.25: time the multi-scale eval forward against the plain one, pass by pass")
 ap.add_argument("--vote", type=float, default=None, help="eval_box_vote threshold: time the evaluator with and without the vote and zsg_eval_vote alone (on the --scales output when given)")
@@ -53,12 +56,12 @@ def time_topk():
     out = dict(att_bbx_out=out5, feat_sizes=torch.tensor(O.feat_sizes_for(300, 300)), num_f_out=torch.tensor([6]))
     inp = {k: bt[k].cuda() for k in ("annot", "img_size", "idxs")}
     evs = {}
-    for name, k in (("plain", 1), ("topk", args.topk)):
-        c = config.get_cfg(eval_topk=k, eval_pre_nms=args.pre_nms)
+    for name, k, nms in [("plain", 1, "hard"), ("topk", args.topk, "hard")] + [(m, args.topk, m) for m in args.nms]:
+        c = config.get_cfg(eval_topk=k, eval_pre_nms=args.pre_nms, eval_nms=nms)
         evs[name] = evaluator.get_default_eval(*config.ratios_scales(c), c).eval()
     ms = {name: [] for name in evs}
     for g in range(groups + 3):                      # the first 3 groups are warm-up
-        for name, e in evs.items():                  # alternating: both see the same clock state
+        for name, e in evs.items():                  # alternating: all see the same clock state
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
             for _ in range(per_group):
@@ -72,6 +75,13 @@ def time_topk():
            "K": args.topk, "pre_nms": args.pre_nms, "plain_us": round(1e3 * med["plain"], 2), "topk_us": round(1e3 * med["topk"], 2),
            "ratio": round(med["topk"] / med["plain"], 3), "plain_min_max_us": [round(1e3 * min(ms["plain"]), 2), round(1e3 * max(ms["plain"]), 2)],
            "topk_min_max_us": [round(1e3 * min(ms["topk"]), 2), round(1e3 * max(ms["topk"]), 2)]}
+    for m in args.nms:
+        c = evs[m].cfg
+        res.update({m + "_us": round(1e3 * med[m], 2), m + "_over_topk": round(med[m] / med["topk"], 3),
+                    m + "_min_max_us": [round(1e3 * min(ms[m]), 2), round(1e3 * max(ms[m]), 2)],
+                    m + "_mean_rows": round(float(evs[m](out, inp)["topk_n"].float().mean()), 2)})
+    if args.nms:
+        res.update({"nms_thr": c["eval_nms_thr"], "soft_sigma": c["eval_soft_sigma"], "soft_min_score": c["eval_soft_min_score"]})
     line = json.dumps(res)
     print(line)
     if args.json:

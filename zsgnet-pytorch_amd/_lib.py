@@ -204,6 +204,8 @@ SIGNATURES = {
     "zsg_eval_topk": (I32, [P, P, P, P, I32, I32, I32, I32, F32, F32, P, P, P, P, P, P, P, P]),
     "zsg_eval_vote_workspace_bytes": (SZ, [I32, I32, I32, I32]),
     "zsg_eval_vote": (I32, [P, P, P, P, I32, I32, I32, I32, F32, F32, P, P, P, P, P, P, P, P, P, SZ, P]),
+    "zsg_eval_topk_soft_workspace_bytes": (SZ, [I32, I32, I32, I32]),
+    "zsg_eval_topk_soft": (I32, [P, P, P, P, I32, I32, I32, I32, F32, F32, I32, F32, F32, P, P, P, P, P, P, P, SZ, P]),
     "zsg_iou": (I32, [P, P, I32, I32, P, P]),
     "zsg_adam_step": (I32, [P, P, P, P, I64, F32, F32, F32, F32, F32, F32, P, P]),
     "zsg_adam_step_range": (I32, [P, P, P, P, I64, F32, F32, F32, F32, F32, F32, P, I32, P]),

@@ -64,6 +64,9 @@ DEFAULTS: Dict[str, Any] = {
     "eval_tta": "none",             # "flip": every EVAL forward (validation, only_val / only_test, EMA validation, Evaluator.predict, the many-phrases plan) also runs the batch mirrored left-right — the image mirrored on the GPU, the left / right words of the query swapped by the loader (`qvec_flip`, dat_loader.swap_left_right) — as rows B..2B-1 of ONE eval forward of 2B rows, and the two predictions are averaged per anchor in regression-parameter space (tx changes sign; zsg_tta_flip_stage_* / zsg_tta_flip_merge; ZSGNet.eval_tta); the output keeps its [B, A, 5] shape; training is untouched; "none" = every plan as before
     "eval_scales": [],              # e.g. [0.75, 1.25]: multi-scale test-time augmentation — every EVAL forward also runs the batch resampled on the GPU (Pillow bicubic of the batch's own H x W pixels, zsg_resize_u8_batched) to (round(s H), round(s W)) for every entry s, each pass the plain eval plan of its geometry (with its own mirrored rows under eval_tta = "flip"); the output dict is pass 0's plus `tta_att_bbx_out` [B, sum A_s, 5] and `tta_feat_sizes`, which the evaluator scores over the concatenated anchor tables (arg-max / top-k NMS over all scales; ZSGNet.eval_scales); at most 4 entries in [0.5, 2], none rounding to the base size or to another entry's; needs the uint8 batch of gpu_img_normalise; training is untouched; [] = every plan as before
     "eval_box_vote": 0.0,           # in (0, 1]: in eval mode the evaluator replaces every kept box (eval_topk rows, K = 1 included) by the score-weighted mean of the eval_pre_nms candidates whose IoU with it is >= this (zsg_eval_vote, tests/vote_ref.py): Acc / Acc@K / pred_boxes / topk_boxes are the voted boxes', pred_boxes_raw keeps the arg-max box; scores, order and count stay; 0 = off
+    "eval_nms": "hard",             # how the evaluator picks the eval_topk rows (and the rows eval_box_vote refines): "hard" = greedy NMS at eval_nms_thr (zsg_eval_topk); "soft_linear" / "soft_gauss" = Soft-NMS (Bodla et al. 2017; zsg_eval_topk_soft, tests/softnms_ref.py): a picked box multiplies the score of every other candidate by 1 - IoU where IoU > eval_nms_thr (linear) or by exp(-IoU^2 / eval_soft_sigma) (gauss), selection goes on over the decayed scores, topk_scores are the decayed scores; row 0 stays the arg-max box
+    "eval_soft_sigma": 0.5,         # ... the Gaussian decay's sigma (> 0, finite); read by "soft_gauss" only
+    "eval_soft_min_score": 0.001,   # ... the score floor of both soft rules, in [0, 1): the rows end at the first decayed score below it (topk_n < K)
     "wgrad_dtype": "fp32",          # "bf16": the convolution weight gradients of the TRAINING backward run on bf16 MFMA with fp32 accumulation (zsg_conv_wgrad_bf16; ZSGNet.wgrad_precision) — src, dy and the gradients stay fp32 in memory, the forward, the data gradients, the stem and the small directly lowered weight gradients stay fp32
     "train_dtype": "fp32",          # "bf16_head": in TRAINING plans the forward convolutions and the data gradients of the pyramid (backbone.fpn.*) and the head stacks run on bf16 MFMA with fp32 accumulation (zsg_conv_igemm_bf16 / zsg_conv_igemm_bf16_m; ZSGNet.train_precision) — activations, weights and gradients stay fp32 in memory; the encoder, every BatchNorm-fused launch, the query encoder and the weight gradients (wgrad_dtype) are untouched
     "enc_dtype": "fp32",            # "bf16_fwd": in TRAINING plans the forward convolutions of a ResNet encoder behind the stem (backbone.encoder.*) run on bf16 MFMA with fp32 accumulation and the fused BatchNorm statistics (zsg_conv_igemm_bf16_bn; ZSGNet.encoder_precision) — activations, weights and gradients stay fp32 in memory; the stem, the convolutions that apply a pending BatchNorm in their loader, the whole backward (fp32 data gradients, weight gradients as wgrad_dtype says) and the SSD-VGG encoder are untouched

@@ -7,7 +7,11 @@ greedy NMS at eval_nms_thr over the eval_pre_nms best candidates (csrc/loss.hip:
 A multi-scale eval forward (ZSGNet.eval_scales) hands over `tta_att_bbx_out` [B, sum A_s, 5] and `tta_feat_sizes`: the same two entries
 then run on that tensor against the passes' anchor tables back to back — the arg-max is the best box over all scales, the NMS removes
 the object found at several of them.  cfg eval_box_vote = t in (0, 1] (eval mode only): every kept box becomes the score-weighted
-mean of the candidates whose IoU with it is >= t (csrc/vote.hip: zsg_eval_vote; tests/vote_ref.py is the definition)."""
+mean of the candidates whose IoU with it is >= t (csrc/vote.hip: zsg_eval_vote; tests/vote_ref.py is the definition).
+
+cfg eval_nms = "soft_linear" / "soft_gauss": the K rows are picked by Soft-NMS instead of the greedy NMS (csrc/softnms.hip:
+zsg_eval_topk_soft; tests/softnms_ref.py is the definition) — a picked box decays the scores of its neighbours, topk_scores are the
+decayed scores, the rows end at eval_soft_min_score; everything downstream (voting included) reads the rows as it reads the hard ones."""
 from functools import partial
 from typing import Dict
 
@@ -33,6 +37,8 @@ class Evaluator(nn.Module):
         self.nms_thr = float(cfg.get("eval_nms_thr", 0.5))
         self.pre_nms = int(cfg.get("eval_pre_nms", 128))
         self.box_vote = check_box_vote(cfg.get("eval_box_vote", 0.0))
+        self.nms, self.soft_sigma, self.soft_min_score = check_nms(cfg.get("eval_nms", "hard"), cfg.get("eval_soft_sigma", 0.5),
+                                                                   cfg.get("eval_soft_min_score", 0.001))
         self._tta_anchs = {}                               # the per-pass size lists of a multi-scale output -> its concatenated anchor table
         if self.topk > 1:                                  # met_keys[0] stays Acc: checkpoint gating / the LR scheduler read it
             self.met_keys = self.met_keys + [f"Acc@{self.topk}"]
@@ -57,7 +63,7 @@ class Evaluator(nn.Module):
         return out["tta_att_bbx_out"].detach().contiguous(), self._tta_anchs[key]
 
     def _topk(self, out5, anchs, annot, img_size, K) -> Dict[str, torch.Tensor]:
-        """one zsg_eval_topk call; annot None: boxes only (no hit_rank / Acc@K)"""
+        """one zsg_eval_topk call (zsg_eval_topk_soft under eval_nms soft_*); annot None: boxes only (no hit_rank / Acc@K)"""
         B, A, _ = out5.shape
         dev = out5.device
         boxes = torch.empty(B, K, 4, device=dev)
@@ -66,12 +72,22 @@ class Evaluator(nn.Module):
         n = torch.empty(B, dtype=torch.int32, device=dev)
         hit = torch.empty(B, dtype=torch.int32, device=dev) if annot is not None else None
         acc = torch.empty(K, device=dev) if annot is not None else None
-        ws = torch.empty((int(lib.zsg_eval_topk_workspace_bytes(B, A, self.pre_nms, K)) + 7) // 8, dtype=torch.int64, device=dev)
-        check(lib.zsg_eval_topk(out5.data_ptr(), annot.data_ptr() if annot is not None else None, anchs.data_ptr(),
-                                img_size.data_ptr(), B, A, self.pre_nms, K, self.nms_thr, float(self.acc_iou_threshold),
-                                boxes.data_ptr(), scores.data_ptr(), self.topk_idx.data_ptr(), n.data_ptr(),
-                                hit.data_ptr() if hit is not None else None, acc.data_ptr() if acc is not None else None,
-                                ws.data_ptr(), stream_ptr()), "zsg_eval_topk")
+        if self.nms != "hard":
+            nb = int(lib.zsg_eval_topk_soft_workspace_bytes(B, A, self.pre_nms, K))
+            ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
+            check(lib.zsg_eval_topk_soft(out5.data_ptr(), annot.data_ptr() if annot is not None else None, anchs.data_ptr(),
+                                         img_size.data_ptr(), B, A, self.pre_nms, K, self.nms_thr, float(self.acc_iou_threshold),
+                                         SOFT_METHODS[self.nms], self.soft_sigma, self.soft_min_score, boxes.data_ptr(),
+                                         scores.data_ptr(), self.topk_idx.data_ptr(), n.data_ptr(),
+                                         hit.data_ptr() if hit is not None else None, acc.data_ptr() if acc is not None else None,
+                                         ws.data_ptr(), nb, stream_ptr()), "zsg_eval_topk_soft")
+        else:
+            ws = torch.empty((int(lib.zsg_eval_topk_workspace_bytes(B, A, self.pre_nms, K)) + 7) // 8, dtype=torch.int64, device=dev)
+            check(lib.zsg_eval_topk(out5.data_ptr(), annot.data_ptr() if annot is not None else None, anchs.data_ptr(),
+                                    img_size.data_ptr(), B, A, self.pre_nms, K, self.nms_thr, float(self.acc_iou_threshold),
+                                    boxes.data_ptr(), scores.data_ptr(), self.topk_idx.data_ptr(), n.data_ptr(),
+                                    hit.data_ptr() if hit is not None else None, acc.data_ptr() if acc is not None else None,
+                                    ws.data_ptr(), stream_ptr()), "zsg_eval_topk")
         res = {"topk_boxes": boxes, "topk_scores": scores, "topk_n": n}
         if annot is not None:
             self.acc_at = acc
@@ -150,6 +166,20 @@ def check_box_vote(v) -> float:
     if isinstance(v, bool) or not isinstance(v, (int, float)) or not (v == 0 or 0 < v <= 1):
         raise ValueError(f"eval_box_vote={v!r}: expected 0 (off) or an IoU threshold in (0, 1]")
     return float(v)
+
+
+SOFT_METHODS = {"soft_linear": 1, "soft_gauss": 2}      # zsg_eval_topk_soft's method argument
+
+
+def check_nms(nms, sigma, min_score):
+    """cfg eval_nms / eval_soft_sigma / eval_soft_min_score -> (nms, sigma, min_score); ValueError for anything zsg_eval_topk_soft refuses"""
+    if not isinstance(nms, str) or (nms != "hard" and nms not in SOFT_METHODS):
+        raise ValueError(f"eval_nms={nms!r}: expected 'hard', 'soft_linear' or 'soft_gauss'")
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not (0 < sigma < float("inf")):
+        raise ValueError(f"eval_soft_sigma={sigma!r}: expected a finite number > 0")
+    if isinstance(min_score, bool) or not isinstance(min_score, (int, float)) or not (0 <= min_score < 1):
+        raise ValueError(f"eval_soft_min_score={min_score!r}: expected a number in [0, 1)")
+    return nms, float(sigma), float(min_score)
 
 
 def get_default_eval(ratios, scales, cfg):
