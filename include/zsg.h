@@ -219,7 +219,10 @@ int32_t zsg_conv_igemm_partial_rows(const zsg_conv_desc* d);
  * when that launch cannot finalise in-kernel (no hint, the streaming 1x1 kernel, split_k > 1, merge_x, or more than 128 partial rows
  * per column block) — the caller then keeps the separate finalize.  is_wino != 0: the hint is zsg_conv_wino's.
  * tickets must be ZERO at entry and are zero again when the launch ends (the caller allocates them zeroed once; one set per call
- * site, never shared between launches that may be in flight together). */
+ * site, never shared between launches that may be in flight together).  The entries below that finalise in-kernel refuse (-1, nothing
+ * written) every launch for which this function says -1 — a descriptor without a tile hint included: the heuristic's tile may have more
+ * column blocks than any ticket buffer the caller could have sized.  tests/test_gpu_conv_bn_exact.py holds these entries, zsg_conv_*_bnb
+ * and zsg_conv_igemm_bnpre to exact integer references between guards. */
 int32_t zsg_conv_bn_tail_tickets(const zsg_conv_desc* d, int32_t is_wino);
 /* The 1x1 / stride-1 convolution that consumes a train-mode BatchNorm + residual + ReLU — the next bottleneck's conv1 behind bn3
  * (fpn_resnet.py:86-100: `out = relu(bn3(conv3(..)) + residual)` ... `conv1(out)`) — applies that BatchNorm in its operand loader

@@ -16,7 +16,7 @@ every output byte untouched and set zsg_last_error.  Nothing is skipped silently
 
 Not covered: an out-of-range read whose value never reaches a result is not detected by guards; rounding on non-integer data stays
 with the Gaussian-data tests (test_gpu_ops.py, test_gpu_wino.py, test_gpu_streamk.py); the BatchNorm-fused siblings (_bnb, _bnpre,
-_bnstat, _tail) keep their own files.
+_bnstat, _tail) are held to the same method by tests/test_gpu_conv_bn_exact.py.
 
 Split-K and the accumulate + mask epilogue (include/zsg.h): every K slice adds its own masked term to what `out` holds, so the launch
 computes prev + mask * sum, which is the documented (prev + sum) * mask exactly when prev is zero wherever mask <= 0 — what the

@@ -911,6 +911,9 @@ static int conv_igemm_impl(const zsg_conv_desc* d, const float* src, const float
         ZSG_REQUIRE(splits == 1 && !bias && !add_src && !d->relu, "conv_igemm: BN-statistics fusion needs a plain (bias-free, unsplit) convolution");
     }
     if (tail) {
+        // (zsg_conv_bn_tail_tickets sizes the ticket words from the hint's column blocks and says -1 without one: the heuristic's tile
+        // may have more column blocks than any ticket buffer the caller could have sized)
+        ZSG_REQUIRE(d->tile_hint, "conv_igemm: in-kernel BatchNorm finalize needs a tile hint (zsg_conv_bn_tail_tickets says so)");
         ZSG_REQUIRE(tail->tickets && bn_partials && splits == 1 && p.vec && !d->merge_x && p.m_tiles <= BN_TAIL_MAX_ROWS,
                     "conv_igemm: in-kernel BatchNorm finalize needs fused partials, the vectorised epilogue and at most %d row tiles (%d)",
                     BN_TAIL_MAX_ROWS, p.m_tiles);

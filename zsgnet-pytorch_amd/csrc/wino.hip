@@ -757,6 +757,7 @@ static int conv_wino_impl(const zsg_conv_desc* d, const float* src, const float*
         ZSG_REQUIRE(splits == 1 && !bias && !add_src && !d->relu && p.vec, "conv_wino: BN-statistics fusion needs a plain (bias-free, unsplit, 16-byte addressable) convolution");
     }
     if (tail) {
+        ZSG_REQUIRE(d->tile_hint, "conv_wino: in-kernel BatchNorm finalize needs a tile hint (zsg_conv_bn_tail_tickets says so)");
         ZSG_REQUIRE(tail->tickets && bn_partials && splits == 1 && p.vec && !mask_src && p.m_blocks <= BN_TAIL_MAX_ROWS,
                     "conv_wino: in-kernel BatchNorm finalize needs fused partials, the vectorised epilogue and at most %d row blocks (%d)",
                     BN_TAIL_MAX_ROWS, p.m_blocks);
