@@ -776,6 +776,48 @@ int64_t zsg_head_words_bwd_ws_bytes(int32_t Q, int32_t T, int32_t nlev, const in
 int zsg_head_words_conv0_bwd(const float* dy, const float* Y, const void* img_idx, int32_t idx_i64, const float* Kw, const float* Vw, const float* alpha,
                              const float* lens, float scale, int32_t Bi, int32_t Q, int32_t T, int32_t nlev, const int32_t* hw, int32_t N, float* dYq,
                              float* dKw, float* dVw, void* ws, int64_t ws_bytes, void* stream);
+/* Global-context block of the head towers (cfg head_ctx = "gc"; csrc/gcblock.hip; GCNet, Cao et al. 2019).  Per query q and pyramid level
+ * l, over the rows x_p (p < P = h_l * w_l) of the post-ReLU h1, N = 256, M = N / 4 = 64:
+ *   s_p = key . x_p;   alpha = softmax_p(s) (max subtracted);   c = sum_p alpha_p x_p
+ *   u = W1 c + b1;     uh = (u - mean u) / sqrt(var u + 1e-5) (biased variance over M);   r = relu(lnw * uh + lnb)
+ *   t = W2 r + b2;     y_p = x_p + t
+ * x, y [level][Q][P_l][N] fp32, the packed head layout of zsg_head_film_conv0's output (hw: nlev (h, w) pairs); key [N], W1 [M][N],
+ * b1 / lnw / lnb [M], W2 [N][M], b2 [N].  All arithmetic is fp32.  With W2 = 0 and b2 = 0, t = 0 and y carries x's values.
+ * Training saves s [level][Q][P_l] (the logits, packed like the rows of x) and stat [level][Q][ZSG_GC_STAT_LD]: the (q, l)'s softmax
+ * max and denominator, var u, 1 / sqrt(var u + 1e-5), c, uh and r at the ZSG_GC_STAT_* offsets; eval passes s = stat = NULL and saves nothing.
+ * Three launches (chunk partials of 64 rows; combine + MLP per (q, l); the add); no float atomics, no hand-offs between blocks; every
+ * sum's order is fixed by (Q, hw): the same bits on every run.  ws: zsg_head_gc_fwd_ws_bytes(Q, nlev, hw, N) bytes, 16-byte aligned.
+ * Refused with -1 and the argument's name, nothing launched: a NULL pointer, N != 256, nlev outside [1, ZSG_MAX_SEG], Q < 1, an empty
+ * level, a short workspace, x / y / key / W1 / W2 / ws off 16-byte alignment.
+ * HBM bytes: 3 * Q * P * N * 4 (x twice — the second read of a 64-row chunk comes from registers, the add's from memory — and y). */
+#define ZSG_GC_STAT_MAX 0
+#define ZSG_GC_STAT_DEN 1
+#define ZSG_GC_STAT_VAR 2
+#define ZSG_GC_STAT_RSTD 3
+#define ZSG_GC_STAT_C 4        /* [256] */
+#define ZSG_GC_STAT_UHAT 260   /* [64] */
+#define ZSG_GC_STAT_R 324      /* [64] */
+#define ZSG_GC_STAT_LD 388
+int64_t zsg_head_gc_fwd_ws_bytes(int32_t Q, int32_t nlev, const int32_t* hw, int32_t N);
+int zsg_head_gc_fwd(const float* x, const float* key, const float* W1, const float* b1, const float* lnw, const float* lnb, const float* W2,
+                    const float* b2, int32_t Q, int32_t nlev, const int32_t* hw, int32_t N, float* y, float* s, float* stat, void* ws,
+                    int64_t ws_bytes, void* stream);
+/* Its backward, g = dL/dy [level][Q][P_l][N], s / stat the forward's:
+ *   dt = sum_p g_p;  db2 = dt;  dW2 = dt r^T;  dr = W2^T dt;  dv = dr * [r > 0];  dlnw = dv * uh;  dlnb = dv;  duh = dv * lnw
+ *   du = (duh - mean duh - uh * mean(duh * uh)) / sqrt(var u + 1e-5);  db1 = du;  dW1 = du c^T;  dc = W1^T du
+ *   a_p = dc . x_p;  abar = sum_p alpha_p a_p;  ds_p = alpha_p (a_p - abar);  dx_p = g_p + alpha_p dc + ds_p key;  dkey = sum_p ds_p x_p
+ * dx is the gradient of the post-ReLU x (the caller applies the ReLU mask).  With W2 = 0: dc = 0, every a_p and ds_p is 0 and dx
+ * carries g's values.  The seven parameter gradients are summed over every (q, l): the column sums of g run in fp64, the chain
+ * dt -> dc -> ds in fp32 per (q, l), and the final sums over (q, l) (dkey: over the 64-row chunk partials of sum ds_p x_p) are fp64 fmas
+ * of exact fp32 products in index order, rounded to fp32 ONCE; accumulate != 0 adds that value to the output (the flat gradient
+ * buffer's convention), 0 stores it.  Any of dx and the seven gradients may be NULL (a frozen parameter, nothing in front of x), not
+ * all eight; without dx and dkey the two per-row launches are not issued.  Up to five launches, no float atomics, no hand-offs between
+ * blocks, the same bits on every run.  ws: zsg_head_gc_bwd_ws_bytes(Q, nlev, hw, N) bytes, 16-byte aligned.  Refusals as the forward's.
+ * HBM bytes: Q * P * N * 4 * (g for the column sums + x for a_p + g and dx + x for dkey). */
+int64_t zsg_head_gc_bwd_ws_bytes(int32_t Q, int32_t nlev, const int32_t* hw, int32_t N);
+int zsg_head_gc_bwd(const float* g, const float* x, const float* s, const float* stat, const float* key, const float* W1, const float* lnw,
+                    const float* W2, int32_t Q, int32_t nlev, const int32_t* hw, int32_t N, float* dx, float* dkey, float* dW1, float* db1,
+                    float* dlnw, float* dlnb, float* dW2, float* db2, int32_t accumulate, void* ws, int64_t ws_bytes, void* stream);
 int zsg_head_border_sums(const float* dy, int32_t B, int32_t h, int32_t w, int32_t N, float* Q /* [9][B][N], += */, void* stream);
 int zsg_head_border_finalize(const float* Q, int32_t B, int32_t N, float* S1, float* S2, float* bias_grad /* [N], += ; or NULL */,
                              void* stream);

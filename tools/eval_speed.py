@@ -6,6 +6,8 @@ eval_topk = K in eval mode (zsg_eval + zsg_eval_topk), alternating; device event
 JSON line (--json PATH also writes it to a file).  --nms soft_linear|soft_gauss (one or both): the same call with cfg eval_nms set
 (zsg_eval + zsg_eval_topk_soft) joins the alternation, `<name>_us` per rule.
 --dtype fp32|bf16|bf16_act: cfg eval_dtype of the network (the forward paths; --topk times no network).
+--head-ctx none|gc: cfg head_ctx of the network (gc: the global-context block behind the heads' conv0, with drawn weights and a non-zero
+last layer); composes with every forward path above.
 --tta flip: flip test-time augmentation (cfg eval_tta): the eval FORWARD of the same network at the same B = --queries, three ways,
 alternating — the plain batch, the plain batch at 2B, the TTA batch (2B rows in one forward + the staging and merge launches) — and the
 two new launches alone; device events around groups of calls, the median per call of each, one JSON line (--json PATH also writes it to
@@ -24,6 +26,7 @@ import time
 ap = argparse.ArgumentParser()
 ap.add_argument("--dtype", choices=("fp32", "bf16", "bf16_act"), default="fp32",
                 help="eval_dtype: operand precision of the eval plan's convolutions (bf16_act: bf16 activation storage as well)")
+ap.add_argument("--head-ctx", choices=("none", "gc"), default="none", help="head_ctx: the global-context block of the head towers")
 ap.add_argument("--per-kernel", action="store_true", help="also print the per-launch device times of one forward and the plan's bytes")
 ap.add_argument("--images", type=int, default=None, help="distinct images per batch (shared-image plan); default: one image per query")
 ap.add_argument("--queries", type=int, default=16, help="queries per batch")
@@ -44,7 +47,7 @@ from zsgnet_pytorch_amd import config, evaluator, loss, mdl
 from zsgnet_pytorch_amd.synth import synthetic_batch, synthetic_shared_batch
 
 Q = args.queries
-cfg = config.get_cfg(eval_dtype=args.dtype)
+cfg = config.get_cfg(eval_dtype=args.dtype, head_ctx=args.head_ctx)
 
 
 def time_topk():
@@ -92,7 +95,12 @@ def time_topk():
 if args.topk is not None and args.scales is None and args.vote is None:
     time_topk()
     sys.exit(0)
-net = mdl.get_default_net(9, cfg).to("cuda").eval()
+net = mdl.get_default_net(9, cfg)
+if args.head_ctx == "gc":           # (drawn gc tensors: the fresh net's zero last layer would time the same launches on t = 0)
+    g_ = torch.Generator().manual_seed(0)
+    net.load_state_dict({k: (torch.randn(v.shape, generator=g_) * 0.05 + (1.0 if k.endswith("ln.weight") else 0.0)) for k, v in net.state_dict().items()
+                         if ".gc." in k}, strict=False)
+net = net.to("cuda").eval()
 
 
 def _median_groups(fns, groups, per_group, warm=3):

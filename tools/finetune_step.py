@@ -74,6 +74,11 @@ A comma-separated list names the modes to alternate (concat always runs).  words
 the BiLSTM's per-token output and so runs with lang_pool = final, the full-sequence program whose vector is closest to the default's; its
 difference to film therefore includes that encoder's (side-stream) cost.
 
+    python tools/finetune_step.py --head-ctx none,gc [--out profiles/head_ctx_step.json]
+
+cfg head_ctx: none and gc (the global-context block behind the heads' conv0, drawn weights with a non-zero last layer) alternate; each
+variant also reports the block's launches (the gc forward and backward calls and the ReLU-mask commit of d(h1)) from the serial replay.
+
 host_enqueue_ms_per_step: host time to enqueue a step (starting from an idle GPU; equal
 to the GPU's ms_per_step when the host, not the GPU, sets the pace).  --only NAME[,NAME] runs the named variants alone (profiling).
 """
@@ -185,6 +190,29 @@ def fuse_class(v, nprof=3):
     return dict(lang_fuse=net.lang_fuse, fusion_fwd_ms=tot("fwd"), fusion_bwd_ms=tot("bwd"), fusion_launches=len(rows),
                 fwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "fwd"), 4),
                 bwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "bwd"), 4), fusion_rows=rows)
+
+
+# cfg head_ctx of the variant's network
+CTX_VARIANTS = ("none", "gc")
+# the block's launches by their names in the plan (mdl._Plan._head_gc)
+CTX_WHATS = (".gc", "mask+acc:att_reg_box.h1", "cast f32<-att_reg_box.h1", "cast bf16<-att_reg_box.h1g")
+
+
+def ctx_class(v, nprof=3):
+    """the launches of the heads' global-context block of one variant, taken as pool_class takes the query encoder's"""
+    net = v["net"]
+    plan = [p for k, p in net._plans.items() if k[-1]][0]
+    st = torch.cuda.current_stream().cuda_stream
+    acc = {}
+    for _ in range(nprof):
+        for tag, prog in (("fwd", plan.fwd), ("bwd", plan.bwd)):
+            for i, (what, fname, ms) in enumerate(prog.profile(st)):
+                acc[(tag, i, what, fname)] = acc.get((tag, i, what, fname), 0.0) + ms / nprof
+    rows = [[tag, what, fname, round(ms * 1e3, 1)] for (tag, i, what, fname), ms in sorted(acc.items()) if any(k in what for k in CTX_WHATS)]
+    tot = lambda t: round(sum(r[3] for r in rows if r[0] == t) / 1e3, 4)
+    return dict(head_ctx=net.head_ctx, ctx_fwd_ms=tot("fwd"), ctx_bwd_ms=tot("bwd"), ctx_launches=len(rows),
+                fwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "fwd"), 4),
+                bwd_program_ms=round(sum(ms for (tag, *_), ms in acc.items() if tag == "bwd"), 4), ctx_rows=rows)
 
 
 WGRAD_KERNELS = ("wgrad_kernel", "wino_wgrad_kernel", "wgrad_bf16_kernel", "wgrad_reduce_kernel")
@@ -340,8 +368,14 @@ def main():
                                                                  "--wgrad-bf16 also those switches without and with the encoder's data gradients")
     ap.add_argument("--lang-pool", action="store_true", help="cfg lang_pool: last, final, mean and attn alternate")
     ap.add_argument("--lang-fuse", default="", help="cfg lang_fuse: concat and the named modes (film, words; comma-separated) alternate")
+    ap.add_argument("--head-ctx", default="", help="cfg head_ctx: the named modes (none, gc; comma-separated) alternate")
     ap.add_argument("--only", default="", help="comma-separated variant names to run (e.g. one variant under rocprofv3)")
     a = ap.parse_args()
+    modes = [f for f, on in (("--head-ctx", a.head_ctx), ("--lang-fuse", a.lang_fuse), ("--lang-pool", a.lang_pool), ("--enc-bwd-bf16", a.enc_bwd_bf16),
+                             ("--enc-bf16", a.enc_bf16), ("--sync-bn", a.sync_bn), ("--train-bf16-head", a.train_bf16_head),
+                             ("--wgrad-bf16", a.wgrad_bf16), ("--ema", a.ema), ("--clip", a.clip), ("--frozen-bn", a.frozen_bn)) if on]
+    if a.head_ctx and len(modes) > 1:       # (the switches below it in the chain would be dropped without a word)
+        ap.error(f"--head-ctx chooses the variants on its own: it does not combine with {', '.join(modes[1:])}")
     torch.cuda.set_device(0)
     if a.sync_bn:
         import socket
@@ -362,7 +396,14 @@ def main():
     encb_of = {}                             # variant -> cfg enc_bwd_dtype (default fp32)
     pool_of = {}                             # variant -> cfg lang_pool (default last)
     fuse_of = {}                             # variant -> cfg lang_fuse (default concat)
-    if a.lang_fuse:
+    ctx_of = {}                              # variant -> cfg head_ctx (default none)
+    if a.head_ctx:
+        asked = [m for m in a.head_ctx.split(",") if m]
+        if not asked or [m for m in asked if m not in CTX_VARIANTS]:
+            ap.error(f"--head-ctx: expected a comma-separated list of {', '.join(CTX_VARIANTS)}")
+        variants = {k: ((), False, None, None, None, "fp32", "fp32") for k in CTX_VARIANTS if k in asked}
+        ctx_of = {k: k for k in variants}
+    elif a.lang_fuse:
         asked = [m for m in a.lang_fuse.split(",") if m]
         if [m for m in asked if m not in FUSE_VARIANTS]:
             ap.error(f"--lang-fuse: expected a comma-separated list of {', '.join(FUSE_VARIANTS)}")
@@ -411,15 +452,19 @@ def main():
     if a.only:
         variants = {k: v for k, v in variants.items() if k in a.only.split(",")}
     for name, (prefixes, bn_frozen, clip, sync_bn, ema, wgrad_dtype, train_dtype) in variants.items():
-        vcfg = config.get_cfg(lang_pool=pool_of[name]) if name in pool_of else (config.get_cfg(lang_fuse=fuse_of[name], **({"lang_pool": "final"} if fuse_of[name] == "words" else {})) if name in fuse_of else cfg)
+        vcfg = config.get_cfg(head_ctx=ctx_of[name]) if name in ctx_of else config.get_cfg(lang_pool=pool_of[name]) if name in pool_of else (config.get_cfg(lang_fuse=fuse_of[name], **({"lang_pool": "final"} if fuse_of[name] == "words" else {})) if name in fuse_of else cfg)
         net = mdl.get_default_net(9, vcfg)
         net.wgrad_precision(wgrad_dtype).train_precision(train_dtype).encoder_precision(enc_of.get(name, "fp32"))
         net.encoder_backward_precision(encb_of.get(name, "fp32"))
         if sd is None:
-            sd = {k: v.clone() for k, v in net.state_dict().items()}
+            sd = {k: v.clone() for k, v in net.state_dict().items() if ".gc." not in k}
         if "lang_pool.weight" in net.state_dict():      # (attn: a drawn scorer beside the shared weights, so the attention is not uniform)
             g = torch.Generator().manual_seed(0)
             net.load_state_dict(dict(sd, **{"lang_pool.weight": torch.randn(1, net.lstm_out_dim, generator=g) * 0.25}))
+        elif net.head_ctx == "gc":                      # (drawn gc tensors beside the shared weights: a non-zero last layer, so every launch works)
+            g = torch.Generator().manual_seed(0)
+            net.load_state_dict(dict(sd, **{k: torch.randn(v.shape, generator=g) * 0.05 + (1.0 if k.endswith("ln.weight") else 0.0)
+                                            for k, v in net.state_dict().items() if ".gc." in k}))
         elif net.lang_fuse == "film":                   # (drawn film weights beside the shared weights, so the scale is not 1)
             g = torch.Generator().manual_seed(0)
             net.load_state_dict(dict(sd, **{"att_reg_box.film.weight": torch.randn(256, net.lstm_out_dim, generator=g) * 0.05}))
@@ -500,7 +545,9 @@ def main():
         if v["clip"] is not None:
             res["variants"][name].update(clip=v["clip"][0], max_norm=v["clip"][1], last_grad_norm=round(float(v["norm"]), 6),
                                          engaged=float(v["norm"]) > v["clip"][1])
-        if a.lang_fuse:
+        if a.head_ctx:
+            res["variants"][name].update(**ctx_class(v))
+        elif a.lang_fuse:
             res["variants"][name].update(**fuse_class(v))
         elif a.lang_pool:
             res["variants"][name].update(**pool_class(v))

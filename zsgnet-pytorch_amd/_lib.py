@@ -177,6 +177,10 @@ SIGNATURES = {
     "zsg_head_words_conv0": (I32, [P, P, I32, P, P, P, P, P, P, F32, I32, I32, I32, I32, P, I32, P, I32, P, P]),
     "zsg_head_words_bwd_ws_bytes": (I64, [I32, I32, I32, P, I32]),
     "zsg_head_words_conv0_bwd": (I32, [P, P, P, I32, P, P, P, P, F32, I32, I32, I32, I32, P, I32, P, P, P, P, I64, P]),
+    "zsg_head_gc_fwd_ws_bytes": (I64, [I32, I32, P, I32]),
+    "zsg_head_gc_fwd": (I32, [P, P, P, P, P, P, P, P, I32, I32, P, I32, P, P, P, P, I64, P]),
+    "zsg_head_gc_bwd_ws_bytes": (I64, [I32, I32, P, I32]),
+    "zsg_head_gc_bwd": (I32, [P, P, P, P, P, P, P, P, I32, I32, P, I32, P, P, P, P, P, P, P, P, I32, P, I64, P]),
     "zsg_stage_inputs": (I32, [P, I32, I32, I32, I32, P, P, I32, P, P, I32, P, P, I32, P]),
     "zsg_head_border_sums": (I32, [P, I32, I32, I32, I32, P, P]),
     "zsg_head_border_finalize": (I32, [P, I32, I32, P, P, P, P]),

@@ -40,6 +40,7 @@ DEFAULTS: Dict[str, Any] = {
     "lamb_adapt_1d": False,         # opt_fn "LAMB" (the large-batch rule: optim.FusedLAMB; reads betas, eps, weight_decay of opt_fn_params): by default tensors of >= 2 dimensions get the trust ratio and the 1-D ones (biases, BatchNorm scales / shifts) plain Adam steps without weight decay (optim.lamb_param_groups); True = one adaptive group of everything
     "lang_pool": "last",            # the query encoder's sentence vector, fixed at construction (ZSGNet.__init__): "last" = the reference's [h_fwd(len-1) | reverse cell on x[len-1]] (mdl.py:296-336); "final" = nn.LSTM's h_n [f_{len-1} | r_0] (the reverse direction reads the whole phrase); "mean" = the mean of the padded BiLSTM output over the valid tokens; "attn" = its softmax(w . o_t)-weighted sum with the extra parameter lang_pool.weight [1, lstm_out_dim] (zero-initialised: starts as "mean"); csrc/lstm_seq.hip
     "lang_fuse": "concat",          # how the sentence vector meets the image in the heads' first convolution, fixed at construction (ZSGNet.__init__): "concat" = the reference's concatenation (a purely additive effect: the vector is constant over the image); "film" = it also scales the convolution's feature part per query and channel, h1 = relu((1 + gamma) * conv(F, W0[:, :Cf]) + conv([lang | grid], W0[:, Cf:]) + bias) with gamma = W_gamma . we and one extra parameter per head stack, <head>.film.weight [256, lstm_out_dim] (zero-initialised: starts as "concat"); needs use_lang and use_img; csrc/film.hip; "words" = the scale becomes a function of the pixel: conv0's raw feature accumulator Y attends over the BiLSTM's per-token output o_t, alpha = softmax_t(Y[p] . W_key o_t / 16), gamma[p] = sum_t alpha_t W_value o_t, with two extra parameters per head stack, <head>.words.key.weight / <head>.words.value.weight [256, lstm_out_dim] (value zero-initialised: starts as "concat"); needs use_lang, use_img and lang_pool final / mean / attn; csrc/words.hip
+    "head_ctx": "none",             # a global-context block behind the heads' first convolution, fixed at construction (ZSGNet.__init__): "none" = the reference's towers (an anchor sees a 13 x 13 cell window); "gc" (GCNet, Cao et al. 2019) = per query and pyramid level one attention-pooled vector of h1, c = sum_p softmax_p(k . x_p) x_p, through a bottleneck MLP (256 -> 64, LayerNorm, ReLU, 64 -> 256) and added to every pixel of h1, with seven extra parameters per head stack, <head>.gc.{key.weight, fc1.weight, fc1.bias, ln.weight, ln.bias, fc2.weight, fc2.bias} (fc2 zero-initialised: starts as "none"); csrc/gcblock.hip
     "warmup_iters": 0,              # W > 0: linear learning-rate warm-up — optimizer step k = 1..W runs at k / W of every group's base lr (the lr at prepare_optimizer), later steps leave the groups to the scheduler; a resume with load_opt continues from the checkpoint's num_it; 0 = off
     "ema_decay": 0.0,               # > 0: an exponential moving average of the weights, updated in every optimizer step (ema.ModelEma); 0 = off
     "ema_warmup": False,            # ... its decay ramps up as min(ema_decay, (1 + n) / (10 + n)) over the first updates

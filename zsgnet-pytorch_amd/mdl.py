@@ -54,6 +54,9 @@ BF16_HEAD_PREFIXES = ("backbone.fpn.", "att_reg_box.", "att_box.", "reg_box.")  
 LSTM_DIMS = (32, 64, 128, 256)    # cfg lstm_dim: the widths csrc/lstm.hip instantiates zsg_lstm_fwd / zsg_lstm_bwd for
 LANG_POOLS = ("last", "final", "mean", "attn")      # cfg lang_pool: the sentence vector the query encoder hands to the head (_lower_lstm)
 LANG_FUSES = ("concat", "film", "words")                   # cfg lang_fuse: how that vector meets the image in the heads' conv0 (_head_stack)
+HEAD_CTXS = ("none", "gc")                          # cfg head_ctx: a global-context block behind the heads' conv0 (_head_stack, csrc/gcblock.hip)
+GC_STAT_LD = 388                                    # floats zsg_head_gc_fwd saves per (query, level): ZSG_GC_STAT_LD of include/zsg.h
+GC_SUFFIXES = (".gc.key.weight", ".gc.fc1.weight", ".gc.fc1.bias", ".gc.ln.weight", ".gc.ln.bias", ".gc.fc2.weight", ".gc.fc2.bias")
 
 LIVE_NETS = weakref.WeakSet()      # every ZSGNet alive: optim.clip_grad_norm_ finds a parameter's flat store here
 
@@ -205,6 +208,10 @@ class ZSGNet(nn.Module):
             if self.lang_pool_mode == "last":
                 raise ValueError("lang_fuse='words' reads the BiLSTM's per-token output, which lang_pool='last' never forms (its reverse cell sees "
                                  "one token): set lang_pool to 'final', 'mean' or 'attn'")
+        # (fixed at construction: "gc" owns seven parameters per head stack, so the mode decides the state dict's keys)
+        self.head_ctx = str(cfg["head_ctx"]) if "head_ctx" in cfg else "none"
+        if self.head_ctx not in HEAD_CTXS:
+            raise ValueError(f"head_ctx={self.head_ctx!r}: supported values are {', '.join(HEAD_CTXS)}")
         self.do_norm = bool(cfg["do_norm"])
         # fpn_resnet.py:173 tests resize_img == [600,600]; ssd_vgg.py:98 tests resize_img[0] >= 600
         self.six_hundred = (list(cfg["resize_img"]) == [600, 600]) if backbone_kind == "retina" else (cfg["resize_img"][0] >= 600)
@@ -374,6 +381,15 @@ class ZSGNet(nn.Module):
             for prefix, _ in heads:
                 self.store.add_mat(prefix + ".words.key.weight", 256, self.lstm_out_dim)
                 self.store.add_mat(prefix + ".words.value.weight", 256, self.lstm_out_dim)
+        if self.head_ctx == "gc":               # the global-context block behind conv0 (N = 256, M = 64); behind every other entry
+            for prefix, _ in heads:
+                self.store.add_mat(prefix + ".gc.key.weight", 1, 256)
+                self.store.add_mat(prefix + ".gc.fc1.weight", 64, 256)
+                self.store.add_vec(prefix + ".gc.fc1.bias", 64)
+                self.store.add_vec(prefix + ".gc.ln.weight", 64)
+                self.store.add_vec(prefix + ".gc.ln.bias", 64)
+                self.store.add_mat(prefix + ".gc.fc2.weight", 256, 64)
+                self.store.add_vec(prefix + ".gc.fc2.bias", 256)
 
     def _register(self):
         self._param_names = list(self.store.order)
@@ -445,6 +461,12 @@ class ZSGNet(nn.Module):
             elif name.endswith(".words.key.weight"):         # (declared last: no existing net's draws change)
                 bound = 1.0 / math.sqrt(self.lstm_out_dim)
                 p.copy_((torch.rand(e.shape, generator=g) * 2 - 1) * bound)
+            elif name.endswith((".gc.key.weight", ".gc.fc1.weight", ".gc.fc1.bias")):      # U(+-1/sqrt(N)) (declared last: no existing net's draws change)
+                p.copy_((torch.rand(e.shape, generator=g) * 2 - 1) * (1.0 / math.sqrt(256.0)))
+            elif name.endswith((".gc.fc2.weight", ".gc.fc2.bias", ".gc.ln.bias")):        # t = 0: a fresh "gc" net computes "none"
+                p.zero_()
+            elif name.endswith(".gc.ln.weight"):
+                p.fill_(1.0)
             elif name.endswith(".bias") and name[:-5] in self.convs:
                 L = self.convs[name[:-5]]
                 bound = 1.0 / math.sqrt(L.cin * L.k * L.k)
@@ -3203,7 +3225,7 @@ class _Plan:
             if w0t:
                 self.grad_ready[W0n] = len(self.bwd.calls)
         self.tape.append(head0_back)
-        hs = [h1]
+        hs = [self._head_gc(prefix, h1) if net.head_ctx == "gc" else h1]
         for i in range(1, 5):
             nxt = self.packed(f"{prefix}.h{i + 1}", B, sizes, 256, dtype=self.adt)
             self.conv(C[f"{prefix}.{i}.0"], hs[-1], relu=True, out=nxt)      # backward via the tape
@@ -3240,6 +3262,54 @@ class _Plan:
             if h5.requires_grad:
                 self.dgrad(L5, g5p, h5, n=256)
         self.tape.append(head5_back)
+
+    def _head_gc(self, prefix: str, h1: Act) -> Act:
+        """cfg head_ctx = "gc": the global-context block between h1 and `prefix`.1.0 (csrc/gcblock.hip; definition in include/zsg.h, host
+        twin tests/gc_ref.py).  Per query and level, y_p = x_p + W2 relu(LN(W1 sum_p softmax_p(k . x_p) x_p + b1)) + b2 over the rows
+        of the post-ReLU h1, whatever wrote it (plain, shared-image, film, words, image- or language-blind): ONE zsg_head_gc_fwd call
+        (three launches) writes y, which takes h1's place as conv1's input.  fp32 under every dtype switch: a bf16_act eval plan casts
+        around it (_via_f32).  A training plan keeps the logits and the per-(q, l) statistics; ONE zsg_head_gc_bwd call gives d(h1) —
+        through h1's ReLU mask (_grad_sink / _grad_commit) — and the gradients of the parameters that train; it is left out when
+        neither h1 nor any of the seven needs a gradient (then conv1 forms no d(y))."""
+        B, sizes = self.Q, self.feat_sizes
+        names = [prefix + suf for suf in GC_SUFFIXES]
+        nlev, rows = len(sizes), B * sum(hh * ww for hh, ww in sizes)
+        hw = torch.tensor([v for hw_ in sizes for v in hw_], dtype=torch.int32)
+        y = self.packed(prefix + ".h1g", B, sizes, 256, dtype=self.adt)
+        x32, y32, _, finish = self._via_f32(h1, y)
+        nws = int(lib.zsg_head_gc_fwd_ws_bytes(B, nlev, hw.data_ptr(), 256))
+        assert nws > 0
+        ws = self._buf((nws + 3) // 4)
+        s = self._buf(rows) if self.training else None
+        stat = self._buf(B * nlev * GC_STAT_LD) if self.training else None
+        self.fwd.add(lib.zsg_head_gc_fwd, x32.buf, *[self.P(n) for n in names], B, nlev, hw, 256, y32.buf, s, stat, ws, nws, what=prefix + ".gc")
+        finish()
+        trains = [self.trains(n) for n in names]
+        y.needs_mask = False
+        y.requires_grad = h1.requires_grad or any(trains)
+        if not self.training:
+            return y
+        Pk, Pw1, _, Plw, _, Pw2, _ = [self.P(n) for n in names]
+
+        def gc_back():
+            g = y.grad
+            if g is None:
+                return
+            gh, tmp = self._grad_sink(h1) if h1.requires_grad else (None, None)
+            dx = None if gh is None else (tmp if tmp is not None else gh)
+            nwb = int(lib.zsg_head_gc_bwd_ws_bytes(B, nlev, hw.data_ptr(), 256))
+            assert nwb > 0
+            wsb = self._buf((nwb + 7) // 8, dtype=torch.float64)
+            grads = [self.G(n) if t else None for n, t in zip(names, trains)]
+            self.bwd.add(lib.zsg_head_gc_bwd, g.buf, h1.buf, s, stat, Pk, Pw1, Plw, Pw2, B, nlev, hw, 256, dx.buf if dx is not None else None, *grads, 1,
+                         wsb, nwb, what=prefix + ".gc_bwd")
+            for n, t in zip(names, trains):
+                if t:
+                    self.grad_ready[n] = len(self.bwd.calls)
+            if gh is not None:
+                self._grad_commit(h1, gh, tmp)
+        self.tape.append(gc_back)
+        return y
 
     # ---- execution -------------------------------------------------------------------------------------------------------
     def run_forward(self, img, qvec, qlens, h0, c0, img_idx=None) -> torch.Tensor:
